@@ -3,12 +3,18 @@
 GPU, device-resident, q16 = 17592182243329 (the 44-bit prime 17592169062401 of the reference cannot host
 n = 2^16: SURVEY.md F5) — plus config 3 (rank-4 Module-LWE matrix–vector commitment, 1024 witness vectors).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One step = one forward pass + one inverse pass over the rank's 4096 polynomials (8192 transforms).  Ranks are
 independent (weak scaling, no data-path collective — SURVEY.md §8(e)); the only communication is the barrier and
 the MAX-reduction of the elapsed time.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the
+benchmark measures and checks: the CPU oracle baseline and checker, per-direction HIP-event timings and the roofline,
+the u64 flavour, config 3, the quotient pipeline, whole commitments, the flat host entry points and config 4 (the
+`roofline`, `extra` and `cpu_baseline` fields of the line).  --dump-outputs DIR writes what the last timed step
+computed for a fixed, seeded sample of rank 0's polynomials as float64 .npy files (residues < 2^45 are exact).
 """
 import argparse
 import json
@@ -40,7 +46,32 @@ def parse():
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--cpu-polys", type=int, default=8192, help="CPU baseline sample: polynomials transformed fwd+inv on one core (~10 s)")
     ap.add_argument("--check-polys", type=int, default=64, help="forward outputs compared word for word with the CPU oracle (outside the timed region)")
+    ap.add_argument("--full", action="store_true", help="also run every secondary measurement and check (see the module docstring); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's outputs (sampled) to DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_ROWS = 32              # polynomials in the dumped sample: 2 arrays x 32 x 2^16 float64 = 32 MiB
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, ctx, polys, stream):
+    """What the timed path hands its caller, for a fixed, seeded sample of the batch: `ntt_forward` = forward_device's output of the
+    sampled polynomials in the last step (recomputed after timing from the same inputs: the transform is exact, so the words are
+    those of the step), `ntt_forward_inverse` = the array after the last step's inverse_device.  float64 holds every residue exactly."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    count = polys.shape[0]
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(count, size=min(DUMP_ROWS, count), replace=False))
+    idx = torch.from_numpy(rows.astype(np.int64)).to(polys.device)
+    after_step = polys.index_select(0, idx)
+    fwd = after_step.clone()
+    ctx.forward_device(fwd.data_ptr(), len(rows), stream)
+    torch.cuda.synchronize()
+    as_f64 = lambda t: t.cpu().numpy().view(np.uint64).astype(np.float64)
+    np.save(os.path.join(out_dir, "ntt_forward.npy"), as_f64(fwd))
+    np.save(os.path.join(out_dir, "ntt_forward_inverse.npy"), as_f64(after_step))
+    np.save(os.path.join(out_dir, "sample_rows.npy"), rows.astype(np.float64))
 
 
 def do_verify_long(fctx, lib, d_rows, d_msgs, msg_len, count, d_res, stream):
@@ -206,14 +237,15 @@ def main():
     polys = torch.empty((args.polys, N), dtype=torch.int64, device="cuda")
     assert lib.lsr_fill_splitmix_device(polys.data_ptr(), args.polys, N, seed_base, Q16, stream) == 0
     torch.cuda.synchronize()
-    reference_copy = polys[:8].clone()
-    # checker sample (outside the timed region): forward outputs of the first polynomials, compared with the CPU oracle below
-    n_check = min(args.check_polys, args.polys)
-    ctx.forward_device(polys.data_ptr(), n_check, stream)
-    torch.cuda.synchronize()
-    gpu_forward_sample = polys[:n_check].cpu().numpy().view(np.uint64).copy()
-    ctx.inverse_device(polys.data_ptr(), n_check, stream)
-    torch.cuda.synchronize()
+    if args.full:
+        reference_copy = polys[:8].clone()
+        # checker sample (outside the timed region): forward outputs of the first polynomials, compared with the CPU oracle below
+        n_check = min(args.check_polys, args.polys)
+        ctx.forward_device(polys.data_ptr(), n_check, stream)
+        torch.cuda.synchronize()
+        gpu_forward_sample = polys[:n_check].cpu().numpy().view(np.uint64).copy()
+        ctx.inverse_device(polys.data_ptr(), n_check, stream)
+        torch.cuda.synchronize()
 
     def barrier():
         torch.cuda.synchronize()
@@ -237,7 +269,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=reduce_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    verified = bool(torch.equal(polys[:8], reference_copy))        # fwd∘inv identity survived every step
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, polys, stream)
 
     # per-direction device time with HIP events on the launch stream (roofline figure)
     def event_time(fn, reps):
@@ -249,30 +282,32 @@ def main():
         torch.cuda.synchronize()
         return float(np.median([a.elapsed_time(b) for a, b in evs])) * 1e-3
 
-    reps = max(5, min(args.steps, 20))
-    t_fwd = event_time(lambda: ctx.forward_device(polys.data_ptr(), args.polys, stream), reps)
-    t_inv = event_time(lambda: ctx.inverse_device(polys.data_ptr(), args.polys, stream), reps)
-    fwd_rate, inv_rate = args.polys / t_fwd, args.polys / t_inv
+    if args.full:
+        verified = bool(torch.equal(polys[:8], reference_copy))        # fwd∘inv identity survived every step
+        reps = max(5, min(args.steps, 20))
+        t_fwd = event_time(lambda: ctx.forward_device(polys.data_ptr(), args.polys, stream), reps)
+        t_inv = event_time(lambda: ctx.inverse_device(polys.data_ptr(), args.polys, stream), reps)
+        fwd_rate, inv_rate = args.polys / t_fwd, args.polys / t_inv
 
-    extra = {"fwd_ntt_per_s": fwd_rate, "inv_ntt_per_s": inv_rate, "fwd_ms_per_batch": t_fwd * 1e3, "inv_ms_per_batch": t_inv * 1e3,
-             "verified_roundtrip": verified,
-             "arith": ("u64 residues mod q; products by exact FP64-FMA Barrett (q < 2^45, DESIGN.md §4), canonical u64 in and out"
-                       if ctx.uses_f64 else "u64 Harvey/Shoup lazy butterflies")}
-    # the reference's own algorithm (SEAL Harvey butterflies, Shoup products on u64) on the GPU, same array, for comparison
-    lib.lsr_set_arith_mode(1)
-    ctx_u64 = pkg.NttContext(Q16, N, device=local)
-    lib.lsr_set_arith_mode(0)
-    ctx_u64.forward_device(polys.data_ptr(), args.polys, stream)
-    t_fwd_u64 = event_time(lambda: ctx_u64.forward_device(polys.data_ptr(), args.polys, stream), max(3, reps // 2))
-    extra["u64_flavour_fwd_ntt_per_s"] = args.polys / t_fwd_u64
-    extra["u64_flavour_roofline_frac"] = args.polys / t_fwd_u64 * NTT_BYTES / (HBM_PEAK_GBS * 1e9)
-    ctx_u64.close()
+        extra = {"fwd_ntt_per_s": fwd_rate, "inv_ntt_per_s": inv_rate, "fwd_ms_per_batch": t_fwd * 1e3, "inv_ms_per_batch": t_inv * 1e3,
+                 "verified_roundtrip": verified,
+                 "arith": ("u64 residues mod q; products by exact FP64-FMA Barrett (q < 2^45, DESIGN.md §4), canonical u64 in and out"
+                           if ctx.uses_f64 else "u64 Harvey/Shoup lazy butterflies")}
+        # the reference's own algorithm (SEAL Harvey butterflies, Shoup products on u64) on the GPU, same array, for comparison
+        lib.lsr_set_arith_mode(1)
+        ctx_u64 = pkg.NttContext(Q16, N, device=local)
+        lib.lsr_set_arith_mode(0)
+        ctx_u64.forward_device(polys.data_ptr(), args.polys, stream)
+        t_fwd_u64 = event_time(lambda: ctx_u64.forward_device(polys.data_ptr(), args.polys, stream), max(3, reps // 2))
+        extra["u64_flavour_fwd_ntt_per_s"] = args.polys / t_fwd_u64
+        extra["u64_flavour_roofline_frac"] = args.polys / t_fwd_u64 * NTT_BYTES / (HBM_PEAK_GBS * 1e9)
+        ctx_u64.close()
 
     # ---- config 3: rank-k Module-LWE matrix–vector commitment u = INTT(A^T NTT(r)) + e1 ----
     commit_check = None
     commit_roofline = None
     del polys
-    if not args.no_commit:
+    if args.full and not args.no_commit:
         torch.cuda.empty_cache()
         k = args.rank
         lctx = pkg.LweContext(pkg.Params(q=Q16, n=N, k=k, sigma=3.19), key_seed=0xC0DE + 1, device=local)
@@ -354,7 +389,7 @@ def main():
         del r, e1, u, r_work
 
     # ---- "next" row: NTT-path quotient polynomials, 4096 instances of m = 4096 constraints ----
-    if not args.no_quotient:
+    if args.full and not args.no_quotient:
         torch.cuda.empty_cache()
         qm, qb = 4096, 4096
         plan = pkg.QuotientPlan(qm, device=local)
@@ -381,7 +416,7 @@ def main():
     #      lwe_commit / lwe_verify_opening for a batch (cpp-core/src/commitment.cpp:138-164,200-232) at the reference's parameters
     #      (n = 4096, k = 2: one launch, one workgroup per commitment) and at config 3's shape (n = 2^16, k = 4: sampled inside the
     #      strided rounds).  Algorithmic bytes per commitment = the wire row ((k + 1) n + 5 words), written once / read once. ----
-    if not args.no_commit and rank == 0:
+    if args.full and not args.no_commit and rank == 0:
         torch.cuda.empty_cache()
         full = {}
         for label, fq, fn_, fk, fb in (("n4096_k2", 17592169062401, 4096, 2, 16384), ("n65536_k4", Q16, N, 4, 1024)):
@@ -448,7 +483,7 @@ def main():
 
     # ---- complete commitments at the reference's parameters (n = 4096, k = 2), PCIe included: host-visible throughput of the
     #      additive flat entry points (never the headline value) ----
-    if not args.no_commit and rank == 0:
+    if args.full and not args.no_commit and rank == 0:
         torch.cuda.empty_cache()
         rctx = pkg.LweContext(pkg.Params(q=17592186044417, n=4096, k=2, sigma=3.19), key_seed=0xC0DE + 2, device=local)
         nb = 2048
@@ -535,7 +570,7 @@ def main():
             tctx.close()
         return result
 
-    if not args.no_commit:
+    if args.full and not args.no_commit:
         torch.cuda.empty_cache()
         cpu_barrier()                 # the other ranks wait on the CPU (gloo), their GPUs idle, while rank 0 drives every device
         if rank == 0:
@@ -546,11 +581,8 @@ def main():
         cpu_barrier()
 
     if rank == 0:
-        ntt_pmc, ntt_pmc_note = pmc_profile("r*_roofline_inputs.json")
-        extra["provenance"] = provenance_module().provenance()
         transforms = 2 * args.polys * args.steps * world
         value = transforms / elapsed
-        achieved = fwd_rate * NTT_BYTES / 1e9
         line = {
             "metric": "degree-2^16 NTTs/sec (forward+inverse, batched, device-resident)",
             "value": value, "unit": "NTT/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -559,21 +591,25 @@ def main():
             "data": "synthetic" + (" (REHEARSAL: all ranks on device 0, gloo)" if rehearsal else ""),
             "config": {"workload": "config2: batched forward+inverse negacyclic NTT, n=2^16, 4096 polys/GPU, q=17592182243329 (44-bit)",
                        "polys_per_gpu": args.polys, "ring_degree": N, "modulus": Q16, "parallelism": f"independent batches x{world}, no collectives"},
+        }
+        if args.full:
+            ntt_pmc, ntt_pmc_note = pmc_profile("r*_roofline_inputs.json")
+            extra["provenance"] = provenance_module().provenance()
+            achieved = fwd_rate * NTT_BYTES / 1e9
             # achieved = ALGORITHMIC bytes (1 MiB per transform) / measured time of one forward batch launch sequence
             # (8 chunks x {ntt_strided_round<4>, ntt_tile_forward<12>}); traffic = PMC bytes of the same sequence.
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": ((ntt_pmc or {}).get("forward_bytes_per_transform") or 0) * args.polys or None,
-                         "traffic_source": ntt_pmc_note,
-                         "algorithmic_bytes": NTT_BYTES * args.polys, "launch_ms": t_fwd * 1e3,
-                         "kernel": "forward NTT batch = ntt_strided_round<ArithF64,4> + ntt_tile_forward<ArithF64,12> per 512-poly chunk",
-                         # what two passes over the array can reach on this part: every residue crosses the L2 <-> memory fabric
-                         # twice (32 B where the algorithm counts 16); the measured pure-movement floor of that pattern is
-                         # 1.27-1.31 ms per 4096 polynomials (profiles/r02_ubench_move2.txt, r01_ubench_pack.txt)
-                         "ceiling_frac": 4096 * NTT_BYTES / 1.272e-3 / (HBM_PEAK_GBS * 1e9),
-                         "ceiling_source": "profiles/r02_ubench_move2.txt (two-pass data movement alone: 1.272 ms per 4096 polynomials)"},
-            "extra": extra,
-        }
-        if not args.no_cpu and world == 1:      # reported at N = 1 only
+            line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                                "traffic": ((ntt_pmc or {}).get("forward_bytes_per_transform") or 0) * args.polys or None,
+                                "traffic_source": ntt_pmc_note,
+                                "algorithmic_bytes": NTT_BYTES * args.polys, "launch_ms": t_fwd * 1e3,
+                                "kernel": "forward NTT batch = ntt_strided_round<ArithF64,4> + ntt_tile_forward<ArithF64,12> per 512-poly chunk",
+                                # what two passes over the array can reach on this part: every residue crosses the L2 <-> memory fabric
+                                # twice (32 B where the algorithm counts 16); the measured pure-movement floor of that pattern is
+                                # 1.27-1.31 ms per 4096 polynomials (profiles/r02_ubench_move2.txt, r01_ubench_pack.txt)
+                                "ceiling_frac": 4096 * NTT_BYTES / 1.272e-3 / (HBM_PEAK_GBS * 1e9),
+                                "ceiling_source": "profiles/r02_ubench_move2.txt (two-pass data movement alone: 1.272 ms per 4096 polynomials)"}
+            line["extra"] = extra
+        if args.full and not args.no_cpu and world == 1:      # reported at N = 1 only
             line["cpu_baseline"] = cpu_baseline(args.cpu_polys, gpu_forward_sample, seed_base, commit_check)
         print(json.dumps(line), flush=True)
     if use_dist:

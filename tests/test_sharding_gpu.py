@@ -214,7 +214,7 @@ def test_bench_with_two_ranks_prints_one_line(tmp_path):
         env.pop(name, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--polys", "256", "--commits", "64"]
+           "--polys", "256", "--commits", "64", "--full"]
     done = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert done.returncode == 0, done.stderr[-2000:]
     lines = [ln for ln in done.stdout.splitlines() if ln.strip()]

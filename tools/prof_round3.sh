@@ -10,9 +10,9 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/r03p
 rm -rf $out && mkdir -p $out
-python3 bench.py > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+python3 bench.py --full > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
 echo "bench done"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --no-cpu > $out/bench_under_rocprof.json 2> $out/stats.log
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --no-cpu > $out/bench_under_rocprof.json 2> $out/stats.log
 cp $(ls $out/stats/*/*kernel_stats.csv | head -1) $out/bench_kernel_stats.csv && rm -rf $out/stats
 echo "kernel stats done"
 export J=256
