@@ -51,6 +51,30 @@ int lsr_ntt_inverse_batch_device(const NttContext* ctx, uint64_t* d_polys, size_
 int lsr_ntt_mul_pointwise_device(const NttContext* ctx, uint64_t* d_result, const uint64_t* d_a,
                                  const uint64_t* d_b, size_t count, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: batched ring multiply ---------------- */
+/* c_j = a_j * b_j in the ring of the context: Z_q[X]/(X^n + 1) for ntt_context_create / lsr_ntt_context_create_on contexts,
+ * Z_q[X]/(X^n - 1) for lsr_cyclic_ntt_context_create contexts.  Natural coefficient order in and out, inputs in [0,q),
+ * outputs canonical.  a, c: [batch][n]; b: [b_rows][n] with b_rows == batch (one b per product) or b_rows == 1 (the same b
+ * for every product).  c may alias a or b exactly (partial overlap: undefined).  batch == 0: no-op, 0.  0 / -1.
+ * NULL context or buffer, b_rows not in {1, batch}, no visible device: -1 and lsr_last_error, before any device work.
+ * One fused pass per product at n <= 4096; four passes per chunk of the batch above.
+ *
+ * lsr_ntt_ring_mul_batch: host buffers, staged through bounded device chunks; returns when c is complete.
+ * lsr_ntt_ring_mul_batch_device: device buffers on the context's device, asynchronous on `stream` (enqueues only).
+ *
+ * Workspace, ordering and graph capture.  n > 4096, and b_rows == 1 with batch > 1, use a workspace owned by the context.  Its
+ * size depends on n alone; the first call that needs it allocates it, it is never resized and is freed by ntt_context_free.
+ *   - Calls on one context are ordered: each call's work starts on the device after the previous call's work has finished, whatever
+ *     streams they were issued on (an event recorded by every call).  Calls may come from several host threads.
+ *   - Capture into a HIP graph (stream capture on `stream`): allowed once the workspace exists, i.e. after one eager call of a kind that
+ *     needs it.  A call that would have to allocate it while `stream` is capturing returns -1.  A captured call is not bracketed by
+ *     the ordering event: the caller orders graph launches against other ring multiplies on the same context.
+ *   - ntt_context_free and lsr_ntt_ring_mul_batch wait for ring multiplies still pending on the context. */
+int lsr_ntt_ring_mul_batch(const NttContext* ctx, uint64_t* c, const uint64_t* a, const uint64_t* b,
+                           size_t batch, size_t b_rows) LSR_NOEXCEPT;
+int lsr_ntt_ring_mul_batch_device(const NttContext* ctx, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b,
+                                  size_t batch, size_t b_rows, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

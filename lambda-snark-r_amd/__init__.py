@@ -37,6 +37,22 @@ def _u64_array(values, name="array"):
     return arr
 
 
+def _ring_mul(lib, handle, n, a, b):
+    """c = a * b in the context's ring (host arrays): a is [n] or [batch, n]; b is [n] (one b for every product) or [batch, n]."""
+    a2 = np.ascontiguousarray(_u64_array(a).reshape(-1, n))
+    b2 = np.ascontiguousarray(_u64_array(b).reshape(-1, n))
+    batch, b_rows = a2.shape[0], b2.shape[0]
+    out = np.empty_like(a2)
+    if lib.lsr_ntt_ring_mul_batch(handle, out.ctypes.data, a2.ctypes.data, b2.ctypes.data, batch, b_rows) != 0:
+        raise CoreError("lsr_ntt_ring_mul_batch failed: " + _abi.last_error())
+    return out.reshape(np.shape(a)) if np.ndim(a) == 1 else out
+
+
+def _ring_mul_device(lib, handle, d_c, d_a, d_b, batch, b_rows, stream):
+    if lib.lsr_ntt_ring_mul_batch_device(handle, d_c, d_a, d_b, batch, b_rows, stream) != 0:
+        raise CoreError("lsr_ntt_ring_mul_batch_device failed: " + _abi.last_error())
+
+
 class NttContext:
     """RAII handle over ``NttContext*`` (cpp-core/include/lambda_snark/ntt.h:25-41)."""
 
@@ -116,6 +132,15 @@ class NttContext:
     def mul_pointwise_device(self, dres, da, db, count, stream=0):
         if self._lib.lsr_ntt_mul_pointwise_device(self._h, dres, da, db, count, stream) != 0:
             raise CoreError("lsr_ntt_mul_pointwise_device failed: " + _abi.last_error())
+
+    # --- ring multiply in Z_q[X]/(X^n + 1) ---
+    def ring_mul(self, a, b):
+        """a * b mod (X^n + 1, q): a is [n] or [batch, n], b is [n] (shared by every product) or [batch, n]; numpy in and out."""
+        return _ring_mul(self._lib, self._h, self.n, a, b)
+
+    def ring_mul_device(self, d_c, d_a, d_b, batch, b_rows, stream=0):
+        """Device buffers [batch][n] (b: [b_rows][n], b_rows 1 or batch), asynchronous on `stream`."""
+        _ring_mul_device(self._lib, self._h, d_c, d_a, d_b, batch, b_rows, stream)
 
 
 class Params:
@@ -509,6 +534,13 @@ class CyclicNtt:
 
     def inverse(self, evals):
         return self._run(self._lib.lsr_cyclic_ntt_inverse_batch, evals)
+
+    def ring_mul(self, a, b):
+        """Cyclic convolution a * b mod (X^n - 1, modulus); shapes as NttContext.ring_mul."""
+        return _ring_mul(self._lib, self._h, self.n, a, b)
+
+    def ring_mul_device(self, d_c, d_a, d_b, batch, b_rows, stream=0):
+        _ring_mul_device(self._lib, self._h, d_c, d_a, d_b, batch, b_rows, stream)
 
     def close(self):
         if self._h:

@@ -9,6 +9,7 @@
 
 #include "lambda_snark/batch.h"
 #include "lambda_snark/ntt.h"
+#include "lsr_flavour.hpp"
 #include "lsr_ntt_kernels.hpp"
 #include "lsr_runtime.hpp"
 
@@ -203,6 +204,11 @@ void destroy_ntt_context(NttContext* ctx) {
     if (!ctx) return;
     try {
         DeviceGuard guard(ctx->device);
+        if (ctx->ring_event) {                      // a ring multiply still in flight may be using ring_scratch
+            (void)hipEventSynchronize(ctx->ring_event);
+            (void)hipEventDestroy(ctx->ring_event);
+        }
+        ctx->ring_scratch.release();
         if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
         ctx->staging.release();
         ctx->fwd_f64.release();
@@ -219,24 +225,6 @@ void destroy_ntt_context(NttContext* ctx) {
 // ------------------------------------------------------------------------------------------------
 // dispatch
 // ------------------------------------------------------------------------------------------------
-template <class A> struct Flavour;
-template <> struct Flavour<ArithF64> {
-    static const double* fwd(const NttContext& c) { return c.fwd_f64.ptr; }
-    static const double* inv(const NttContext& c) { return c.inv_f64.ptr; }
-    static RoundConsts<ArithF64> consts(const NttContext& c) { return {c.n_inv_f64, c.w_last_scaled_f64}; }
-};
-template <> struct Flavour<ArithU64> {
-    static const ShoupOperand* fwd(const NttContext& c) { return c.fwd_u64.ptr; }
-    static const ShoupOperand* inv(const NttContext& c) { return c.inv_u64.ptr; }
-    static RoundConsts<ArithU64> consts(const NttContext& c) { return {c.n_inv_u64, c.w_last_scaled_u64}; }
-};
-
-template <> struct Flavour<ArithGold> {
-    static const uint64_t* fwd(const NttContext& c) { return c.fwd_gold.ptr; }
-    static const uint64_t* inv(const NttContext& c) { return c.inv_gold.ptr; }
-    static RoundConsts<ArithGold> consts(const NttContext& c) { return {c.n_inv_gold, c.w_last_scaled_gold}; }
-};
-
 template <class A, int LT, bool RAW_IN, bool RAW_OUT>
 static void tile_fwd(const NttContext& c, uint64_t* d, size_t total, hipStream_t s, const uint64_t* src = nullptr) {
     const unsigned grid = static_cast<unsigned>((total + kTile - 1) / kTile);
@@ -339,7 +327,7 @@ static void small_inverse(const NttContext& c, uint64_t* d, size_t total, hipStr
     }
 }
 
-static size_t ntt_chunk_bytes() {
+size_t ntt_chunk_bytes() {
     static const size_t bytes = [] {
         if (const char* e = std::getenv("LAMBDA_SNARK_NTT_CHUNK_MIB")) {
             const long v = std::atol(e);
@@ -450,6 +438,24 @@ void launch_top_round_inverse(const NttContext& c, uint64_t* data, size_t polys,
     if (!c.use_f64 || c.logn <= kTileLog) throw std::runtime_error("top-round launch: FP64 flavour, n > 4096 only");
     const int r_top = std::max(c.logn - kTileLog, 4);
     strided<ArithF64, true, true, false>(c, data, polys << c.logn, c.logn - r_top, r_top, s, add);
+    LSR_HIP(hipGetLastError());
+}
+
+// The strided round of an n > 4096 transform in any flavour (the outer passes of the ring multiply, lsr_ring_mul.hip): forward reads
+// canonical `src` and writes raw elements to `d` (may alias); inverse turns raw elements of `d` into canonical residues in place.
+void launch_strided_round(const NttContext& c, uint64_t* d, const uint64_t* src, size_t polys, bool inverse, hipStream_t s) {
+    if (c.logn <= kTileLog) throw std::runtime_error("strided round: n > 4096 only");
+    const int r_top = std::max(c.logn - kTileLog, 4), lo = c.logn - r_top;
+    const size_t total = polys << c.logn;
+    if (inverse) {
+        if (c.gold) strided<ArithGold, true, true, false>(c, d, total, lo, r_top, s);
+        else if (c.use_f64) strided<ArithF64, true, true, false>(c, d, total, lo, r_top, s);
+        else strided<ArithU64, true, true, false>(c, d, total, lo, r_top, s);
+    } else {
+        if (c.gold) strided<ArithGold, false, false, true>(c, d, total, lo, r_top, s, src);
+        else if (c.use_f64) strided<ArithF64, false, false, true>(c, d, total, lo, r_top, s, src);
+        else strided<ArithU64, false, false, true>(c, d, total, lo, r_top, s, src);
+    }
     LSR_HIP(hipGetLastError());
 }
 

@@ -469,6 +469,158 @@ __global__ void __launch_bounds__(kThreads) ntt_tile_inverse(uint64_t* __restric
     tile_inverse_body<A, LT, RAW_IN, RAW_OUT, PRE>(data, total, p, tw, cs, add, pre, blockIdx.x);
 }
 
+// ---- ring multiply c = a b in the tile (lsr_ring_mul.hip) --------------------------------------------
+// One workgroup: forward rounds of its tile of a, forward rounds of the same tile of b, the product in registers, inverse rounds,
+// store.  The last forward round and the first inverse round share the mapping TileRound<LT, NR-1>, so a-hat (16 registers) and
+// b-hat meet in registers and the product feeds the inverse without an LDS round trip.
+// MID: the middle pass of an n > 4096 product — a and b hold raw elements left by the strided forward rounds, c receives raw
+// elements for the strided inverse round (c may be a: in place).  BHAT: b is the transform of ONE polynomial ([n] words, canonical,
+// the order launch_ntt writes), read at the last-round positions instead of transformed.
+// Product at the boundary (flavour-specific): inputs are forward-round outputs, the result must meet the inverse
+// rounds' input contract (F64: |x| <= 2 q; U64: [0, 2q); Gold: canonical).
+template <class A> __device__ __forceinline__ typename A::elem ring_product(typename A::elem x, typename A::elem y, const ModParams& p);
+template <> __device__ __forceinline__ double ring_product<ArithF64>(double x, double y, const ModParams& p) {
+    // |x|, |y| < 16 q (17 CT stages, each adding < 0.875 q); one canonical operand and |x| < 2^50 make the product exact, |r| <= 0.875 q
+    return mulmod_f64(x, canonical_f64(y, p.qd, p.inv_qd), p.qd, p.inv_qd);
+}
+template <> __device__ __forceinline__ uint64_t ring_product<ArithU64>(uint64_t x, uint64_t y, const ModParams& p) {
+    return mulmod_barrett128(x, y, p);   // lazy [0, 4q) operands: the Barrett product takes any 64-bit pair, canonical out
+}
+template <> __device__ __forceinline__ uint64_t ring_product<ArithGold>(uint64_t x, uint64_t y, const ModParams&) {
+    return gold_mul(x, y);               // lazy 64-bit representatives: the 128-bit reduction takes any pair, canonical out
+}
+
+// Forward rounds of one tile operand, left in v at the last round's mapping (no LDS store after the last round).  Round I uses the
+// twiddle slot w[(S + I) & 1]; PRELOADED: round 0's twiddles are already in w[S].  `after` fills w[(S + NR) & 1] while the last round
+// computes (the next phase's first twiddles).
+template <class A, int LT, bool RAW, int S, bool PRELOADED, class After>
+__device__ __forceinline__ void ring_forward_tile(typename A::elem (&v)[kRegs], typename A::twid (&w)[2][kRoundTwiddles], uint64_t* lds, rsrc_t from,
+                                                  rsrc_t table, uint32_t block_pos, uint32_t nmask, const ModParams& p, After&& after) {
+    constexpr int NR = TileRound<LT, 0>::kCount;
+    const uint32_t t = threadIdx.x;
+    {
+        constexpr int LO = TileRound<LT, 0>::LO, R = TileRound<LT, 0>::R;
+        const uint32_t base = lane_base<LO, R>(t);
+        uint64_t raw[kRegs];
+#pragma unroll
+        for (int k = 0; k < kRegs; ++k) raw[k] = buf_load64<RAW ? 0 : kAuxStream>(from, base * 8u, reg_offset<LO, R>(k) * 8u);
+        if constexpr (!PRELOADED) load_round_twiddles<A, LO, R, false, false>(w[S & 1], base, block_pos, nmask, p.logn, table);
+#pragma unroll
+        for (int k = 0; k < kRegs; ++k) v[k] = RAW ? elem_from_bits<A>(raw[k]) : A::load(raw[k], p);
+    }
+    static_for<0, NR>([&](auto ic) {
+        constexpr int I = decltype(ic)::value;
+        constexpr int LO = TileRound<LT, I>::LO, R = TileRound<LT, I>::R;
+        if constexpr (I + 1 < NR) {
+            constexpr int LO1 = TileRound<LT, I + 1>::LO, R1 = TileRound<LT, I + 1>::R;
+            load_round_twiddles<A, LO1, R1, false, false>(w[(S + I + 1) & 1], lane_base<LO1, R1>(t), block_pos, nmask, p.logn, table);
+        } else {
+            after(w[(S + NR) & 1]);
+        }
+        forward_round<A, LO, R, I == 0 && !RAW && (LO + R == LT)>(v, w[(S + I) & 1], p);
+        if constexpr (I + 1 < NR) {
+            uint64_t* const row = lds + lds_slot(lane_base<LO, R>(t));
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) row[lds_slot(reg_offset<LO, R>(k))] = elem_bits<A>(v[k]);
+            __syncthreads();
+            constexpr int LO1 = TileRound<LT, I + 1>::LO, R1 = TileRound<LT, I + 1>::R;
+            const uint64_t* const row1 = lds + lds_slot(lane_base<LO1, R1>(t));
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) v[k] = elem_from_bits<A>(row1[lds_slot(reg_offset<LO1, R1>(k))]);
+        }
+    });
+}
+
+template <class A, int LT, bool MID, bool BHAT>
+__global__ void __launch_bounds__(kThreads) ntt_tile_ring_mul(uint64_t* c, const uint64_t* a, const uint64_t* b, size_t total, ModParams p,
+                                                                const typename A::twid* __restrict__ fwd, const typename A::twid* __restrict__ inv,
+                                                                RoundConsts<A> cs) {
+    // (no __restrict__ on c, a, b: c may alias either; every load of the tile precedes the first store)
+    __shared__ uint64_t lds[kLdsWords];
+    using elem = typename A::elem;
+    using twid = typename A::twid;
+    constexpr int NR = TileRound<LT, 0>::kCount;
+    constexpr int LOL = TileRound<LT, NR - 1>::LO, RL = TileRound<LT, NR - 1>::R;    // the shared last-forward / first-inverse mapping
+    const uint32_t t = threadIdx.x;
+    const size_t tile_base = (size_t)blockIdx.x * kTile;
+    const uint32_t nmask = (1u << p.logn) - 1u;
+    const uint32_t block_pos = (uint32_t)(tile_base & nmask);
+    const size_t left = total - tile_base;
+    const uint32_t tile_bytes = left >= kTile ? kTile * 8u : (uint32_t)left * 8u;
+    const rsrc_t out = make_rsrc(c + tile_base, tile_bytes);
+    const rsrc_t ra = make_rsrc(a + tile_base, tile_bytes);
+    const rsrc_t ftab = make_rsrc(fwd, (uint32_t)sizeof(twid) << p.logn);
+    const rsrc_t itab = make_rsrc(inv, (uint32_t)sizeof(twid) << p.logn);
+    const uint32_t lbase = lane_base<LOL, RL>(t);
+    // first inverse round's twiddles; SKIP_TOP when that round is also the transform's last stage
+    auto inverse_first = [&](twid (&slot)[kRoundTwiddles]) {
+        load_round_twiddles<A, LOL, RL, true, (NR == 1) && !MID>(slot, lbase, block_pos, nmask, p.logn, itab);
+    };
+    elem v[kRegs];
+    twid w[2][kRoundTwiddles];
+    constexpr int S1 = BHAT ? NR & 1 : 0;   // twiddle slot of the first inverse round: (S + NR) & 1 of the last forward transform
+
+    if constexpr (BHAT) {
+        ring_forward_tile<A, LT, MID, 0, false>(v, w, lds, ra, ftab, block_pos, nmask, p, inverse_first);
+        // b-hat at this lane's last-round positions within the polynomial (one polynomial's transform: stays L2-resident)
+        const rsrc_t rb = make_rsrc(b, 8u << p.logn);
+        constexpr uint32_t kMask = MID ? 0xFFFFFFFFu : (1u << LT) - 1u;          // n <= 4096: the tile holds 4096 / n polynomials
+        const uint32_t lane_off = MID ? block_pos + lbase : (lbase & kMask);
+#pragma unroll
+        for (int k = 0; k < kRegs; ++k) v[k] = ring_product<A>(v[k], A::load(buf_load64(rb, lane_off * 8u, (reg_offset<LOL, RL>(k) & kMask) * 8u), p), p);
+    } else {
+        elem ah[kRegs];
+        // a's last round prefetches b's first-round twiddles (round 0 of the same table) into the free slot
+        ring_forward_tile<A, LT, MID, 0, false>(v, w, lds, ra, ftab, block_pos, nmask, p, [&](twid (&slot)[kRoundTwiddles]) {
+            constexpr int LO0 = TileRound<LT, 0>::LO, R0 = TileRound<LT, 0>::R;
+            load_round_twiddles<A, LO0, R0, false, false>(slot, lane_base<LO0, R0>(t), block_pos, nmask, p.logn, ftab);
+        });
+#pragma unroll
+        for (int k = 0; k < kRegs; ++k) ah[k] = v[k];
+        if constexpr (NR > 1) __syncthreads();       // a's last LDS reads before b's first LDS writes
+        const rsrc_t rb = make_rsrc(b + tile_base, tile_bytes);
+        ring_forward_tile<A, LT, MID, NR & 1, true>(v, w, lds, rb, ftab, block_pos, nmask, p, inverse_first);
+#pragma unroll
+        for (int k = 0; k < kRegs; ++k) v[k] = ring_product<A>(ah[k], v[k], p);
+    }
+
+    // inverse rounds (tile_inverse_body's schedule), the first one straight from registers
+    static_for<0, NR>([&](auto ic) {
+        constexpr int I = decltype(ic)::value;
+        constexpr int J = NR - 1 - I;
+        constexpr int LO = TileRound<LT, J>::LO, R = TileRound<LT, J>::R;
+        constexpr bool kLast = (I == NR - 1);
+        constexpr bool kFinal = kLast && !MID;
+        const uint32_t base = lane_base<LO, R>(t);
+        uint64_t* const row = lds + lds_slot(base);
+        if constexpr (I > 0) {
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) v[k] = elem_from_bits<A>(row[lds_slot(reg_offset<LO, R>(k))]);
+        }
+        if constexpr (!kLast) {
+            constexpr int LO1 = TileRound<LT, J - 1>::LO, R1 = TileRound<LT, J - 1>::R;
+            load_round_twiddles<A, LO1, R1, true, (I + 1 == NR - 1) && !MID>(w[(S1 + I + 1) & 1], lane_base<LO1, R1>(t), block_pos, nmask, p.logn, itab);
+        }
+        inverse_round<A, LO, R, kFinal>(v, w[(S1 + I) & 1], p, cs);
+        if constexpr (!kFinal) {
+            constexpr bool kAll = kLast || !A::kPartialRecentre;
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k)
+                if (kAll || A::template needs_recentre<R>(k & ((1 << R) - 1))) A::end_of_inverse_round(v[k], p);
+        }
+        if constexpr (kLast) {
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k)
+                buf_store64<MID ? 0 : kAuxStream>(out, base * 8u, reg_offset<LO, R>(k) * 8u, MID ? elem_bits<A>(v[k]) : A::store_reduced(v[k], p));
+        } else {
+            // (I = 0: these are the slots this lane read in the last forward round — no barrier needed before the store)
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) row[lds_slot(reg_offset<LO, R>(k))] = elem_bits<A>(v[k]);
+            __syncthreads();
+        }
+    });
+}
+
 // ---- strided round kernel (the TOP R index bits: lo + R == log n) ------------------------------------
 // Its butterfly groups are indexed by the polynomial only, so stage j (register bit j) uses the table entries
 // 2^(R-1-j) + u for every lane of every polynomial: compile-time indices, scalar loads, no VGPRs for twiddles.

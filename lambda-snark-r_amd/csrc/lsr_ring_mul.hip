@@ -1,0 +1,182 @@
+// Batched ring multiply c = a b in Z_q[X]/(X^n + 1) (negacyclic contexts) or Z_q[X]/(X^n - 1) (cyclic contexts): the composition
+// forward, forward, pointwise product, inverse that the reference leaves to its caller (cpp-core/src/ntt.cpp:106-119), fused.
+//   n <= 4096: ONE launch (ntt_tile_ring_mul): per tile both forward transforms, the product in registers, the inverse — 24 bytes
+//              of HBM traffic per output residue (read a, read b, write c).
+//   n > 4096:  per chunk of the batch the two-pass schedule with the product in the middle pass — strided forward round of b into the
+//              workspace, strided forward round of a into c, the tile kernel as middle pass (both tiles forward, product, inverse, in
+//              place in c), strided inverse round on c: 9 polynomial passes instead of the composed sequence's 15-19.
+//   b_rows == 1 (one b for every product): b is transformed once per call (launch_ntt) and the tile kernel reads b-hat at its
+//              last-round positions instead of transforming b.
+#include <algorithm>
+#include <cstring>
+
+#include "lambda_snark/batch.h"
+#include "lsr_flavour.hpp"
+#include "lsr_ntt_kernels.hpp"
+#include "lsr_runtime.hpp"
+
+namespace lsr {
+
+template <class A, int LT, bool MID, bool BHAT>
+static void ring_tile(const NttContext& c, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t total, hipStream_t s) {
+    const unsigned grid = static_cast<unsigned>((total + kTile - 1) / kTile);
+    hipLaunchKernelGGL((ntt_tile_ring_mul<A, LT, MID, BHAT>), dim3(grid), dim3(kThreads), 0, s, d_c, d_a, d_b, total, c.mod, Flavour<A>::fwd(c),
+                       Flavour<A>::inv(c), Flavour<A>::consts(c));
+}
+
+#define LSR_RING_CASE(LT) case LT: ring_tile<A, LT, MID, BHAT>(c, d_c, d_a, d_b, total, s); break;
+template <class A, bool MID, bool BHAT>
+static void ring_tile_lt(const NttContext& c, int lt, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t total, hipStream_t s) {
+    if constexpr (MID) {   // the low lt = log n - 4 (n = 2^17: - 5) bits of a two-pass transform
+        switch (lt) {
+            LSR_RING_CASE(9) LSR_RING_CASE(10) LSR_RING_CASE(11)
+            default: ring_tile<A, 12, MID, BHAT>(c, d_c, d_a, d_b, total, s); break;
+        }
+    } else {
+        switch (lt) {
+            LSR_RING_CASE(1) LSR_RING_CASE(2) LSR_RING_CASE(3) LSR_RING_CASE(4) LSR_RING_CASE(5) LSR_RING_CASE(6)
+            LSR_RING_CASE(7) LSR_RING_CASE(8) LSR_RING_CASE(9) LSR_RING_CASE(10) LSR_RING_CASE(11)
+            default: ring_tile<A, 12, MID, BHAT>(c, d_c, d_a, d_b, total, s); break;
+        }
+    }
+}
+#undef LSR_RING_CASE
+
+// Polynomials per chunk of an n > 4096 product: two arrays are live between passes (the c chunk and the workspace chunk), so each
+// gets half of the Infinity Cache budget of a two-pass transform (ntt_chunk_bytes(): 256 MiB -> 128 MiB each, 256 polynomials at
+// n = 2^16, 128 at n = 2^17).
+static size_t ring_chunk_polys(const NttContext& c) { return std::max<size_t>(1, (ntt_chunk_bytes() / 2) >> (c.logn + 3)); }
+// Workspace words: n > 4096 — one chunk of transformed b plus one b-hat row; n <= 4096 — one b-hat row.  A function of n (and of the
+// process-wide chunk size) only, never of the batch.
+static size_t ring_scratch_words(const NttContext& c) {
+    const size_t n = c.degree;
+    return c.logn > kTileLog ? ring_chunk_polys(c) * n + n : n;
+}
+
+template <class A>
+static void ring_mul_enqueue(const NttContext& c, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, bool shared_b, hipStream_t s) {
+    const size_t n = c.degree;
+    uint64_t* const ws = c.ring_scratch.ptr;
+    if (c.logn <= kTileLog) {
+        if (shared_b) {
+            launch_ntt(c, ws, 1, false, s, nullptr, nullptr, d_b);
+            ring_tile_lt<A, false, true>(c, c.logn, d_c, d_a, ws, batch * n, s);
+        } else {
+            ring_tile_lt<A, false, false>(c, c.logn, d_c, d_a, d_b, batch * n, s);
+        }
+        return;
+    }
+    const int lt = c.logn - std::max(c.logn - kTileLog, 4);
+    const size_t chunk = ring_chunk_polys(c);
+    uint64_t* const b_hat = ws + chunk * n;
+    if (shared_b) launch_ntt(c, b_hat, 1, false, s, nullptr, nullptr, d_b);
+    for (size_t first = 0; first < batch; first += chunk) {
+        const size_t now = std::min(chunk, batch - first), off = first * n;
+        uint64_t* const cc = d_c + off;
+        const uint64_t* const ac = d_a + off;
+        if (!shared_b) launch_strided_round(c, ws, d_b + off, now, false, s);     // before c is written: c may be b
+        launch_strided_round(c, cc, ac == cc ? nullptr : ac, now, false, s);
+        if (shared_b) ring_tile_lt<A, true, true>(c, lt, cc, cc, b_hat, now * n, s);
+        else ring_tile_lt<A, true, false>(c, lt, cc, cc, ws, now * n, s);
+        launch_strided_round(c, cc, nullptr, now, true, s);
+    }
+}
+
+// One call on the device (caller validated the arguments): workspace, ordering brackets, launches.
+static void ring_mul_device(const NttContext& c, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t b_rows, hipStream_t s) {
+    const bool shared_b = b_rows == 1 && batch > 1;
+    std::lock_guard<std::mutex> lock(c.ring_mutex);
+    const bool capturing = stream_is_capturing(s);
+    if ((c.logn > kTileLog || shared_b) && !c.ring_scratch.ptr) {
+        // the workspace is allocated once and never resized, so a graph captured after one eager call keeps valid pointers; an
+        // allocation inside the capture would not be part of the graph
+        if (capturing)
+            throw std::runtime_error("this call needs the context's workspace, which the first such call allocates: make one eager (uncaptured) "
+                                     "call on this context before capturing");
+        c.ring_scratch.allocate(ring_scratch_words(c));
+    }
+    // (a capturing stream: no brackets — lsr_runtime.hpp, stream_is_capturing)
+    if (!capturing && c.ring_event) LSR_HIP(hipStreamWaitEvent(s, c.ring_event, 0));
+    if (c.gold) ring_mul_enqueue<ArithGold>(c, d_c, d_a, d_b, batch, shared_b, s);
+    else if (c.use_f64) ring_mul_enqueue<ArithF64>(c, d_c, d_a, d_b, batch, shared_b, s);
+    else ring_mul_enqueue<ArithU64>(c, d_c, d_a, d_b, batch, shared_b, s);
+    LSR_HIP(hipGetLastError());
+    if (!capturing) {
+        if (!c.ring_event) LSR_HIP(hipEventCreateWithFlags(&c.ring_event, hipEventDisableTiming));
+        LSR_HIP(hipEventRecord(c.ring_event, s));
+    }
+}
+
+// host buffers through bounded device chunks on the context's work stream
+static void host_ring_mul(const NttContext& c, uint64_t* out, const uint64_t* a, const uint64_t* b, size_t batch, size_t b_rows) {
+    DeviceGuard guard(c.device);
+    const size_t n = c.degree;
+    const bool shared_b = b_rows == 1 && batch > 1;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, (256ull << 20) / (n * 8)));
+    DeviceBuffer<uint64_t> da(chunk * n), db(shared_b ? n : chunk * n);
+    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
+    hipStream_t s = work_stream(c);
+    if (shared_b) LSR_HIP(hipMemcpyAsync(db.ptr, b, n * 8, hipMemcpyHostToDevice, s));
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        LSR_HIP(hipMemcpyAsync(da.ptr, a + done * n, now * n * 8, hipMemcpyHostToDevice, s));
+        if (!shared_b) LSR_HIP(hipMemcpyAsync(db.ptr, b + done * n, now * n * 8, hipMemcpyHostToDevice, s));
+        ring_mul_device(c, da.ptr, da.ptr, db.ptr, now, shared_b ? 1 : now, s);
+        LSR_HIP(hipMemcpyAsync(out + done * n, da.ptr, now * n * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+}  // namespace lsr
+
+// ------------------------------------------------------------------------------------------------
+// C-ABI
+// ------------------------------------------------------------------------------------------------
+// Argument checks that need no device (and no dereference of ctx): -1 and a message, or 0 to go on.
+static int ring_mul_check(const char* where, const NttContext* ctx, const void* c, const void* a, const void* b, size_t batch, size_t b_rows) {
+    if (!ctx || !c || !a || !b) {
+        lsr::set_last_error(std::string(where) + ": NULL context or buffer");
+        return -1;
+    }
+    if (b_rows != 1 && b_rows != batch) {
+        lsr::set_last_error(std::string(where) + ": b_rows must be 1 or batch (" + std::to_string(batch) + "), got " + std::to_string(b_rows));
+        return -1;
+    }
+    return 0;
+}
+
+template <class F>
+static int ring_guarded(const char* where, F&& body) noexcept {
+    try {
+        if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
+        body();
+        return 0;
+    } catch (const std::exception& e) {
+        lsr::set_last_error(std::string(where) + ": " + e.what());
+        std::fprintf(stderr, "lambda_snark_core: %s failed: %s\n", where, e.what());
+        return -1;
+    } catch (...) {
+        lsr::set_last_error(std::string(where) + ": unknown exception");
+        return -1;
+    }
+}
+
+extern "C" {
+
+int lsr_ntt_ring_mul_batch(const NttContext* ctx, uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t b_rows) noexcept {
+    if (ring_mul_check("lsr_ntt_ring_mul_batch", ctx, c, a, b, batch, b_rows) != 0) return -1;
+    if (batch == 0) return 0;
+    return ring_guarded("lsr_ntt_ring_mul_batch", [&] { lsr::host_ring_mul(*ctx, c, a, b, batch, b_rows); });
+}
+
+int lsr_ntt_ring_mul_batch_device(const NttContext* ctx, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t b_rows,
+                                  void* stream) noexcept {
+    if (ring_mul_check("lsr_ntt_ring_mul_batch_device", ctx, d_c, d_a, d_b, batch, b_rows) != 0) return -1;
+    if (batch == 0) return 0;
+    return ring_guarded("lsr_ntt_ring_mul_batch_device", [&] {
+        lsr::DeviceGuard guard(ctx->device);
+        lsr::ring_mul_device(*ctx, d_c, d_a, d_b, batch, b_rows, static_cast<hipStream_t>(stream));
+    });
+}
+
+}  // extern "C"

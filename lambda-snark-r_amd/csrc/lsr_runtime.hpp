@@ -98,6 +98,13 @@ struct NttContext {
     // bring their stream, and every stream a process opens competes for the runtime's few hardware queues
     mutable std::mutex stream_mutex;
     mutable hipStream_t stream = nullptr;
+    // workspace of lsr_ntt_ring_mul_batch(_device) (lsr_ring_mul.hip): allocated by the first call that needs it at a size fixed by n
+    // alone, never resized (a graph captured after one eager call stays valid), freed with the context.  ring_mutex serialises the
+    // calls on the host; ring_event (recorded at the end of every call outside capture) orders each call behind the previous one
+    // on the device, whatever streams they were issued on.
+    mutable std::mutex ring_mutex;
+    mutable lsr::DeviceBuffer<uint64_t> ring_scratch;
+    mutable hipEvent_t ring_event = nullptr;
 };
 
 namespace lsr {
@@ -141,6 +148,11 @@ void launch_top_round_inverse_sampled(const NttContext& ctx, uint64_t* d_data, s
 // residues its inverse round will add, into sampler.side ([polys][n / 2^r][2^r / 16] words, int8 per sample)
 void launch_top_round_forward_sampling(const NttContext& ctx, uint64_t* d_dst, const uint64_t* d_src, size_t polys, hipStream_t stream,
                                        const BlindSampler& sampler);
+// the strided top-bits round of an n > 4096 transform in the context's flavour: forward reads canonical `src`, writes raw elements
+// to `d` (may alias); inverse turns raw elements into canonical residues, in place
+void launch_strided_round(const NttContext& ctx, uint64_t* d, const uint64_t* src, size_t polys, bool inverse, hipStream_t stream);
+// bytes of one chunk of a two-pass transform: the array written by one pass stays in the Infinity Cache for the next
+size_t ntt_chunk_bytes();
 void launch_pointwise(const NttContext& ctx, uint64_t* d_out, const uint64_t* d_a, const uint64_t* d_b, size_t count,
                       hipStream_t stream);
 // out[b][i] = in[b][bitrev_logn(i)] (out != in)
