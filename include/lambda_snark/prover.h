@@ -77,6 +77,42 @@ int lsr_r1cs_constraint_evals_batch(LsrR1csProver* prover, const uint64_t* witne
 int lsr_r1cs_quotient_batch(LsrR1csProver* prover, const uint64_t* witnesses, size_t batch, uint64_t* quotient,
                             uint32_t* quotient_len) LSR_NOEXCEPT;
 
+/* ---- prove_r1cs / prove_r1cs_zk and verify_r1cs / verify_r1cs_zk for a batch of witnesses (lib.rs:747-809, 877-980,
+ * 1016-1095, 1142-1215), NTT path only ----
+ * One proof = LSR_R1CS_PROOF_WORDS uint64 words in ProofR1CS / ProofR1csZk field order (the commitment is the separate row). */
+enum {
+    LSR_PROOF_ALPHA, LSR_PROOF_BETA, LSR_PROOF_Q_ALPHA, LSR_PROOF_Q_BETA,
+    LSR_PROOF_A_ALPHA, LSR_PROOF_B_ALPHA, LSR_PROOF_C_ALPHA,
+    LSR_PROOF_A_BETA, LSR_PROOF_B_BETA, LSR_PROOF_C_BETA,
+    LSR_PROOF_OPEN_ALPHA, LSR_PROOF_OPEN_BETA, LSR_PROOF_BLINDING, LSR_R1CS_PROOF_WORDS
+};
+/* witnesses [batch][n_vars]; seeds [batch] (0 = fresh OS entropy, as lwe_commit); blinding [batch] or NULL (NULL = prove_r1cs,
+ * else prove_r1cs_zk with r = blinding[i] mod q).  Out: rows [batch][lsr_lwe_commitment_words(lwe)] = lwe_commit of the
+ * (blinded) quotient reduced mod commit_modulus (Rust's LweContext::modulus()); proofs [batch][LSR_R1CS_PROOF_WORDS];
+ * hashes [batch][2][32] (the transcripts of alpha and beta, may be NULL); status [batch] = the quotient length, or 0 when
+ * witness i does not satisfy the R1CS (its row and proof words are then unspecified).  Host arrays, chunked staging.  0 / -1. */
+int lsr_r1cs_prove_batch(LsrR1csProver* prover, LweContext* lwe, uint64_t commit_modulus, const uint64_t* witnesses, size_t batch,
+                         size_t n_public, const uint64_t* seeds, const uint64_t* blinding, uint64_t* rows, uint64_t* proofs,
+                         uint8_t* hashes, uint32_t* status) LSR_NOEXCEPT;
+/* the same on device arrays on the prover's device, asynchronous on `stream`; `seeds` stays a HOST array and every seed must be
+ * non-zero (-1 otherwise, as lsr_lwe_commit_keys_device).  Not capturable into a HIP graph (-1). */
+int lsr_r1cs_prove_batch_device(LsrR1csProver* prover, LweContext* lwe, uint64_t commit_modulus, const uint64_t* d_witnesses,
+                                size_t batch, size_t n_public, const uint64_t* seeds, const uint64_t* d_blinding, uint64_t* d_rows,
+                                uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status, void* stream) LSR_NOEXCEPT;
+/* verify_r1cs (zk = 0) / verify_r1cs_zk (zk != 0) of `batch` proofs of one circuit with m constraints (a power of two):
+ * public_inputs [batch][n_public], rows [batch][words_per_row], proofs [batch][LSR_R1CS_PROOF_WORDS]; results[i] = 1 / 0.
+ * The host call needs no GPU.  0 / -1. */
+int lsr_r1cs_verify_batch(uint32_t m, const uint64_t* public_inputs, size_t n_public, const uint64_t* rows, size_t words_per_row,
+                          const uint64_t* proofs, size_t batch, int zk, int* results) LSR_NOEXCEPT;
+/* the same on device arrays (the calling thread's current device), asynchronous on `stream`; not capturable (-1) */
+int lsr_r1cs_verify_batch_device(uint32_t m, const uint64_t* d_public_inputs, size_t n_public, const uint64_t* d_rows,
+                                 size_t words_per_row, const uint64_t* d_proofs, size_t batch, int zk, int* d_results,
+                                 void* stream) LSR_NOEXCEPT;
+/* eval_poly (r1cs.rs:362-373) over NTT_MODULUS on device arrays: d_values[i][k] = sum_j (c_j mod q) (x mod q)^j mod q with
+ * c = d_coeffs[i][0..len), x = d_points[i][k], k < points_per_poly.  Asynchronous on `stream` (current device).  0 / -1. */
+int lsr_prover_eval_batch_device(const uint64_t* d_coeffs, size_t len, size_t batch, const uint64_t* d_points,
+                                 uint32_t points_per_poly, uint64_t* d_values, void* stream) LSR_NOEXCEPT;
+
 #ifdef __cplusplus
 }
 #endif

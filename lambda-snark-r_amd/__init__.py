@@ -644,6 +644,38 @@ class R1csProver:
             raise CoreError("lsr_r1cs_quotient_batch failed: " + _abi.last_error())
         return quot, lens
 
+    def prove_batch(self, ctx, witnesses, seeds, n_public, commit_modulus, blinding=None):
+        """``prove_r1cs`` (blinding None) or ``prove_r1cs_zk`` (lib.rs:747-809, 877-980) for a batch of witnesses, NTT path.
+        -> (rows [batch][ctx.commitment_words], proofs [batch][PROOF_WORDS], hashes [batch][2][32] uint8, status [batch]); status 0 marks
+        a witness that does not satisfy the R1CS.  commit_modulus is Rust's ``LweContext::modulus()`` (``ctx.modulus()``)."""
+        w, batch = self._witnesses(witnesses)
+        seeds = _u64_array(seeds)
+        if seeds.size != batch:
+            raise ValueError("one seed per witness")
+        blind = None if blinding is None else _u64_array(blinding)
+        if blind is not None and blind.size != batch:
+            raise ValueError("one blinding factor per witness")
+        rows = np.zeros((batch, ctx.commitment_words), dtype=np.uint64)
+        proofs = np.zeros((batch, PROOF_WORDS), dtype=np.uint64)
+        hashes = np.zeros((batch, 2, 32), dtype=np.uint8)
+        status = np.zeros(batch, dtype=np.uint32)
+        if batch and self._lib.lsr_r1cs_prove_batch(self._h, ctx.handle, int(commit_modulus), w.ctypes.data, batch, int(n_public), seeds.ctypes.data,
+                                                    None if blind is None else blind.ctypes.data, rows.ctypes.data, proofs.ctypes.data,
+                                                    hashes.ctypes.data, status.ctypes.data) != 0:
+            raise CoreError("lsr_r1cs_prove_batch failed: " + _abi.last_error())
+        return rows, proofs, hashes, status
+
+    def prove_batch_device(self, ctx, d_witnesses, batch, seeds, n_public, commit_modulus, d_rows, d_proofs, d_hashes, d_status, d_blinding=None,
+                           stream=0):
+        """``lsr_r1cs_prove_batch_device``: device pointers (ints, e.g. torch.Tensor.data_ptr()) in and out, host seeds (all non-zero),
+        asynchronous on `stream`."""
+        seeds = _u64_array(seeds)
+        if seeds.size != batch:
+            raise ValueError("one seed per witness")
+        if self._lib.lsr_r1cs_prove_batch_device(self._h, ctx.handle, int(commit_modulus), d_witnesses, batch, int(n_public), seeds.ctypes.data,
+                                                 d_blinding, d_rows, d_proofs, d_hashes, d_status, stream) != 0:
+            raise CoreError("lsr_r1cs_prove_batch_device failed: " + _abi.last_error())
+
     def compute_quotient_poly(self, witness):
         quot, lens = self.quotient_batch(witness)
         if lens[0] == 0:
@@ -661,3 +693,33 @@ class R1csProver:
         except Exception:
             pass
 
+
+PROOF_WORDS = 13
+PROOF_FIELDS = ("alpha", "beta", "q_alpha", "q_beta", "a_z_alpha", "b_z_alpha", "c_z_alpha", "a_z_beta", "b_z_beta", "c_z_beta", "opening_alpha",
+                "opening_beta", "blinding_factor")   # prover.h LSR_PROOF_*: ProofR1CS / ProofR1csZk field order
+
+
+def verify_r1cs_batch(m, publics, rows, proofs, zk=False):
+    """``verify_r1cs`` / ``verify_r1cs_zk`` (lib.rs:1016-1095, 1142-1215) for a batch, on the host (no GPU needed): -> int32 [batch] of 1 / 0.
+    publics [batch][n_public], rows [batch][words], proofs [batch][PROOF_WORDS]."""
+    proofs = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, PROOF_WORDS)
+    batch = proofs.shape[0]
+    rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(batch, -1)
+    publics = np.ascontiguousarray(publics, dtype=np.uint64).reshape(batch, -1)
+    results = np.zeros(batch, dtype=np.int32)
+    if batch and _abi.lib().lsr_r1cs_verify_batch(int(m), publics.ctypes.data if publics.size else None, publics.shape[1], rows.ctypes.data, rows.shape[1],
+                                                  proofs.ctypes.data, batch, 1 if zk else 0, results.ctypes.data) != 0:
+        raise CoreError("lsr_r1cs_verify_batch failed: " + _abi.last_error())
+    return results
+
+
+def verify_r1cs_batch_device(m, d_publics, n_public, d_rows, words_per_row, d_proofs, batch, d_results, zk=False, stream=0):
+    """``lsr_r1cs_verify_batch_device``: device pointers, int32 results, asynchronous on `stream`."""
+    if _abi.lib().lsr_r1cs_verify_batch_device(int(m), d_publics, n_public, d_rows, words_per_row, d_proofs, batch, 1 if zk else 0, d_results, stream) != 0:
+        raise CoreError("lsr_r1cs_verify_batch_device failed: " + _abi.last_error())
+
+
+def prover_eval_batch_device(d_coeffs, length, batch, d_points, points_per_poly, d_values, stream=0):
+    """``lsr_prover_eval_batch_device``: eval_poly (r1cs.rs:362-373) over NTT_MODULUS, values[i][k] = coeffs[i](points[i][k])."""
+    if _abi.lib().lsr_prover_eval_batch_device(d_coeffs, length, batch, d_points, points_per_poly, d_values, stream) != 0:
+        raise CoreError("lsr_prover_eval_batch_device failed: " + _abi.last_error())

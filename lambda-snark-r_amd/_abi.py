@@ -161,6 +161,11 @@ SIGNATURES = {
     "lsr_r1cs_prover_num_variables": (u32, [vp]),
     "lsr_r1cs_constraint_evals_batch": (c_int, [vp, vp, c_size, vp, vp, vp]),
     "lsr_r1cs_quotient_batch": (c_int, [vp, vp, c_size, vp, vp]),
+    "lsr_r1cs_prove_batch": (c_int, [vp, vp, u64, vp, c_size, c_size, vp, vp, vp, vp, vp, vp]),
+    "lsr_r1cs_prove_batch_device": (c_int, [vp, vp, u64, vp, c_size, c_size, vp, vp, vp, vp, vp, vp, vp]),
+    "lsr_r1cs_verify_batch": (c_int, [u32, vp, c_size, vp, c_size, vp, c_size, c_int, vp]),
+    "lsr_r1cs_verify_batch_device": (c_int, [u32, vp, c_size, vp, c_size, vp, c_size, c_int, vp, vp]),
+    "lsr_prover_eval_batch_device": (c_int, [vp, c_size, c_size, vp, u32, vp, vp]),
 }
 
 

@@ -5,6 +5,8 @@
 #include <cstring>
 
 #include "lambda_snark/prover.h"
+#include "lambda_snark/batch.h"
+#include "lsr_prove_kernels.hpp"
 #include "lsr_runtime.hpp"
 
 namespace lsr {
@@ -52,6 +54,13 @@ __global__ void __launch_bounds__(kBlock) check_kernel(const uint64_t* __restric
             atomicOr(&bad[i >> logm], 1u);
         }
     }
+}
+
+// the prove path's stash of A's and B's interpolated planes: 16-byte words, grid-stride (a device-to-device hipMemcpyAsync took
+// 7x as long on the same planes)
+__global__ void __launch_bounds__(kBlock) stash_kernel(const ulonglong2* __restrict__ src, ulonglong2* __restrict__ dst, size_t count) {
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) dst[i] = src[i];
 }
 
 // evaluations of A B on the coset, written over A's
@@ -210,8 +219,10 @@ static void ensure_workspace(LsrQuotientPlan& p, size_t chunk, bool host_io) {
 }
 
 // one pass over `count` <= plan.chunk instances, everything on `s`
+// stash (prove path, in-place calls only): receives [2][count][m] — A's and B's interpolated planes (m P coeffs) before the coset
+// transform overwrites them; C's stays in the third plane
 static void quotient_pass(LsrQuotientPlan& p, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, size_t count, uint64_t* d_q,
-                          uint32_t* d_len, hipStream_t s) {
+                          uint32_t* d_len, hipStream_t s, uint64_t* stash = nullptr) {
     const size_t per_vector = count << p.logm;
     uint64_t* work = p.work.ptr;
     uint32_t* top = p.flags.ptr;
@@ -226,6 +237,8 @@ static void quotient_pass(LsrQuotientPlan& p, const uint64_t* d_a, const uint64_
     if (p.ntt) {
         if (d_a == work) {                                                               // interpolation: r1cs.rs:489-491
             launch_ntt(*p.ntt, work, 3 * count, false, s);
+            if (stash) hipLaunchKernelGGL(stash_kernel, dim3(blocks_for(per_vector)), dim3(kBlock), 0, s, reinterpret_cast<const ulonglong2*>(work),
+                                          reinterpret_cast<ulonglong2*>(stash), per_vector);   // 2 per_vector words
         } else {   // out of place: the caller's arrays are read, the workspace planes written
             launch_ntt(*p.ntt, work, count, false, s, nullptr, nullptr, d_a);
             launch_ntt(*p.ntt, work + per_vector, count, false, s, nullptr, nullptr, d_b);
@@ -251,6 +264,8 @@ static void quotient_pass(LsrQuotientPlan& p, const uint64_t* d_a, const uint64_
         }
     } else {
         zero_words_async(d_q, per_vector, s);                                            // m = 1: constants, Q = 0 when a b = c
+        if (stash) hipLaunchKernelGGL(stash_kernel, dim3(blocks_for(per_vector)), dim3(kBlock), 0, s, reinterpret_cast<const ulonglong2*>(work),
+                                          reinterpret_cast<ulonglong2*>(stash), per_vector);   // 2 per_vector words
     }
     hipLaunchKernelGGL(quotient_len_kernel, dim3(blocks_for(count, ~0u)), dim3(kBlock), 0, s, d_len, top, bad, count);
     LSR_HIP(hipGetLastError());
@@ -394,6 +409,15 @@ struct LsrR1csProver {
     lsr::DeviceBuffer<uint64_t> val[3];
     lsr::DeviceBuffer<uint64_t> witness;    // [chunk][n_vars]
     size_t witness_chunk = 0;
+    // prove path (lsr_r1cs_prove_batch*), sized for prove_chunk instances:
+    lsr::DeviceBuffer<uint64_t> stash;      // A's and B's interpolated planes [2][chunk][m]
+    lsr::DeviceBuffer<uint64_t> quot;       // quotient [chunk][m]
+    lsr::DeviceBuffer<uint64_t> msg;        // commitment messages [chunk][m + 1]
+    lsr::DeviceBuffer<uint64_t> small;      // keys[4] alphas betas hash_a[4] hash_b[4] ev[8] blinding publics[n_public] per instance
+    lsr::DeviceBuffer<uint32_t> len;        // [chunk]
+    lsr::DeviceBuffer<uint64_t> io;         // host staging: rows [chunk][W] then proofs [chunk][13] then hashes [chunk][8]
+    lsr::DeviceBuffer<uint32_t> io_status;
+    size_t prove_chunk = 0, prove_publics = 0, prove_row_words = 0;
 };
 
 namespace lsr {
@@ -405,6 +429,7 @@ static void destroy_prover(LsrR1csProver* r) {
             DeviceGuard guard(r->plan->device);
             for (int k = 0; k < 3; ++k) { r->row_ptr[k].release(); r->col[k].release(); r->val[k].release(); }
             r->witness.release();
+            r->stash.release(); r->quot.release(); r->msg.release(); r->small.release(); r->len.release(); r->io.release(); r->io_status.release();
         } catch (...) {
         }
     }
@@ -496,6 +521,201 @@ static void prover_run(LsrR1csProver& r, const uint64_t* witnesses, size_t batch
         }
         LSR_HIP(hipStreamSynchronize(p.stream));
     }
+}
+
+// ---- prove_r1cs / prove_r1cs_zk for a batch (lib.rs:747-809, 877-980) ----------------------------------
+// Per chunk, all on one stream: constraint evals (from device witnesses) -> quotient pass with A's and B's interpolants stashed ->
+// message Q' mod commit_modulus -> keys -> rows -> alpha -> beta -> evaluations -> proof records.
+struct ProveArgs {
+    LweContext* lwe;
+    uint64_t commit_modulus;
+    size_t n_public;
+    const uint64_t* seeds;      // host
+    bool zk;
+};
+struct ProveSlots {             // one chunk's views into the prover's prove workspace
+    uint64_t *keys, *alphas, *betas, *hash_a, *hash_b, *ev, *blinding, *publics;
+};
+
+static ProveSlots prove_slots(LsrR1csProver& r, size_t chunk) {
+    uint64_t* b = r.small.ptr;
+    ProveSlots v;
+    v.keys = b;                 b += 4 * chunk;
+    v.alphas = b;               b += chunk;
+    v.betas = b;                b += chunk;
+    v.hash_a = b;               b += 4 * chunk;
+    v.hash_b = b;               b += 4 * chunk;
+    v.ev = b;                   b += 8 * chunk;
+    v.blinding = b;             b += chunk;
+    v.publics = b;
+    return v;
+}
+
+static void ensure_prove_workspace(LsrR1csProver& r, size_t chunk, size_t n_public, size_t row_words, bool host_io) {
+    LsrQuotientPlan& p = *r.plan;
+    ensure_workspace(p, chunk, false);
+    if (r.witness_chunk < chunk) {
+        r.witness.allocate(chunk * r.n_vars);
+        r.witness_chunk = chunk;
+    }
+    if (r.prove_chunk < chunk || r.prove_publics < n_public) {
+        r.prove_chunk = std::max(r.prove_chunk, chunk);
+        r.prove_publics = std::max(r.prove_publics, n_public);
+        r.stash.allocate(2 * r.prove_chunk * r.m);
+        r.quot.allocate(r.prove_chunk * r.m);
+        r.msg.allocate(r.prove_chunk * (r.m + 1));
+        r.small.allocate(r.prove_chunk * (23 + std::max<size_t>(1, r.prove_publics)));
+        r.len.allocate(r.prove_chunk);
+        r.io.release();
+        r.io_status.release();
+        r.prove_row_words = 0;
+    }
+    if (host_io && (!r.io.ptr || r.prove_row_words < row_words)) {
+        r.prove_row_words = std::max(r.prove_row_words, row_words);
+        r.io.allocate(r.prove_chunk * (r.prove_row_words + 13 + 8));
+        r.io_status.allocate(r.prove_chunk);
+    }
+}
+
+static void check_lwe_call(int rc, const char* what) {
+    if (rc != 0) throw std::runtime_error(std::string(what) + ": " + lsr_last_error());
+}
+
+// one chunk of `count` instances.  d_z [count][n_vars]; d_blind [count] or nullptr; outputs device arrays.  host_keys: derive the
+// keys on the host (seed 0 = fresh entropy) from the messages copied back.
+static void prove_chunk(LsrR1csProver& r, const ProveArgs& a, const uint64_t* d_z, const uint64_t* d_blind, const uint64_t* seeds, size_t count,
+                        uint64_t* d_rows, uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status, bool host_keys, hipStream_t s) {
+    LsrQuotientPlan& p = *r.plan;
+    const size_t per_vector = count << p.logm;
+    const size_t words = lsr_lwe_commitment_words(a.lwe);
+    const ProveSlots v = prove_slots(r, r.prove_chunk);
+    const CsrView ca{r.row_ptr[0].ptr, r.col[0].ptr, r.val[0].ptr}, cb{r.row_ptr[1].ptr, r.col[1].ptr, r.val[1].ptr},
+        cc{r.row_ptr[2].ptr, r.col[2].ptr, r.val[2].ptr};
+    uint64_t* work = p.work.ptr;
+    hipLaunchKernelGGL(constraint_evals_kernel, dim3(blocks_for(per_vector), 3), dim3(kBlock), 0, s, work, ca, cb, cc, d_z, r.n_vars, p.logm, per_vector);
+    LSR_HIP(hipGetLastError());
+    quotient_pass(p, work, work + per_vector, work + 2 * per_vector, count, r.quot.ptr, r.len.ptr, s, r.stash.ptr);
+    // commitment message: Q (plain) or Q' = Q + r (X^m - 1) (zk), mod commit_modulus
+    const uint32_t msg_len = r.m + (a.zk ? 1u : 0u);
+    hipLaunchKernelGGL(prove_message_kernel, dim3(blocks_for(count * msg_len)), dim3(kBlock), 0, s, r.quot.ptr, r.m, a.zk ? d_blind : nullptr,
+                       a.commit_modulus, r.msg.ptr, msg_len, count * (size_t)msg_len);
+    LSR_HIP(hipGetLastError());
+    if (host_keys) {
+        std::vector<uint64_t> msgs(count * msg_len), keys(4 * count);
+        LSR_HIP(hipMemcpyAsync(msgs.data(), r.msg.ptr, msgs.size() * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+        check_lwe_call(lsr_lwe_commit_keys(a.lwe, msgs.data(), msg_len, count, seeds, keys.data()), "lsr_lwe_commit_keys");
+        LSR_HIP(hipMemcpyAsync(v.keys, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, s));
+        LSR_HIP(hipStreamSynchronize(s));   // `keys` leaves scope
+    } else {
+        check_lwe_call(lsr_lwe_commit_keys_device(a.lwe, r.msg.ptr, msg_len, count, seeds, v.keys, s), "lsr_lwe_commit_keys_device");
+    }
+    check_lwe_call(lsr_lwe_commit_rows_device(a.lwe, r.msg.ptr, msg_len, count, v.keys, d_rows, s), "lsr_lwe_commit_rows_device");
+    // alpha = Challenge::derive(public_inputs, row), beta = Challenge::derive([alpha], row) (lib.rs:761-768)
+    if (a.n_public)
+        hipLaunchKernelGGL(gather_publics_kernel, dim3(blocks_for(count * a.n_public)), dim3(kBlock), 0, s, d_z, r.n_vars, (uint32_t)a.n_public,
+                           v.publics, count * a.n_public);
+    LSR_HIP(hipGetLastError());
+    check_lwe_call(lsr_fs_challenge_batch_device(a.n_public ? v.publics : nullptr, a.n_public, d_rows, words, count, kProverModulus, v.alphas,
+                                                 reinterpret_cast<uint8_t*>(v.hash_a), s), "lsr_fs_challenge_batch_device");
+    check_lwe_call(lsr_fs_challenge_batch_device(v.alphas, 1, d_rows, words, count, kProverModulus, v.betas, reinterpret_cast<uint8_t*>(v.hash_b), s),
+                   "lsr_fs_challenge_batch_device");
+    // A, B, C (stash, stash + per_vector, third plane: m P coeffs) and Q (natural order) at alpha and beta
+    const EvalPoints pts{{v.alphas, v.betas}, 1, 2};
+    const uint64_t m_inv = prover_montgomery(invmod_prime(r.m % kProverModulus, kProverModulus));
+    const EvalPolys abc{{r.stash.ptr, r.stash.ptr + per_vector, work + 2 * per_vector}, r.m, r.m};
+    hipLaunchKernelGGL((eval_kernel<true, 3>), dim3((unsigned)count, 1), dim3(kEvalBlock), 0, s, abc, pts, EvalOut{v.ev, 8, 2}, p.logm, m_inv);
+    const EvalPolys qp{{r.quot.ptr, r.quot.ptr, r.quot.ptr}, r.m, r.m};
+    hipLaunchKernelGGL((eval_kernel<false, 1>), dim3((unsigned)count, 1), dim3(kEvalBlock), 0, s, qp, pts, EvalOut{v.ev + 6, 8, 0}, p.logm,
+                       kGoldOneMont);
+    hipLaunchKernelGGL(prove_assemble_kernel, dim3(blocks_for(count, ~0u)), dim3(kBlock), 0, s, v.ev, v.alphas, v.betas, a.zk ? d_blind : nullptr,
+                       r.len.ptr, v.hash_a, v.hash_b, p.logm, d_proofs, reinterpret_cast<uint64_t*>(d_hashes), d_status, count);
+    LSR_HIP(hipGetLastError());
+}
+
+static void prove_device(LsrR1csProver& r, const ProveArgs& a, const uint64_t* d_w, size_t batch, const uint64_t* d_blind, uint64_t* d_rows,
+                         uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status, hipStream_t s) {
+    LsrQuotientPlan& p = *r.plan;
+    DeviceGuard guard(p.device);
+    std::lock_guard<std::mutex> lock(p.mutex);   // order: the plan's mutex, then (inside each commitment call) the LWE context's
+    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
+    const size_t words = lsr_lwe_commitment_words(a.lwe);
+    const size_t chunk = quotient_chunk(p, batch);
+    ensure_prove_workspace(r, chunk, a.n_public, words, false);
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        prove_chunk(r, a, d_w + done * r.n_vars, d_blind ? d_blind + done : nullptr, a.seeds + done, now, d_rows + done * words, d_proofs + done * 13,
+                    d_hashes ? d_hashes + done * 64 : nullptr, d_status + done, false, s);
+    }
+    if (!p.ev_last) LSR_HIP(hipEventCreateWithFlags(&p.ev_last, hipEventDisableTiming));
+    LSR_HIP(hipEventRecord(p.ev_last, s));
+}
+
+static void prove_host(LsrR1csProver& r, const ProveArgs& a, const uint64_t* w, size_t batch, const uint64_t* blind, uint64_t* rows, uint64_t* proofs,
+                       uint8_t* hashes, uint32_t* status) {
+    LsrQuotientPlan& p = *r.plan;
+    DeviceGuard guard(p.device);
+    std::lock_guard<std::mutex> lock(p.mutex);
+    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
+    const size_t words = lsr_lwe_commitment_words(a.lwe);
+    const size_t chunk = quotient_chunk(p, batch);
+    ensure_prove_workspace(r, chunk, a.n_public, words, true);
+    hipStream_t s = p.stream;
+    const ProveSlots v = prove_slots(r, r.prove_chunk);
+    uint64_t* d_rows = r.io.ptr;
+    uint64_t* d_proofs = d_rows + r.prove_chunk * r.prove_row_words;
+    uint64_t* d_hashes = d_proofs + r.prove_chunk * 13;
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        bool zero_seed = false;
+        for (size_t j = 0; j < now; ++j) zero_seed |= a.seeds[done + j] == 0;
+        LSR_HIP(hipMemcpyAsync(r.witness.ptr, w + done * r.n_vars, now * r.n_vars * 8, hipMemcpyHostToDevice, s));
+        if (blind) LSR_HIP(hipMemcpyAsync(v.blinding, blind + done, now * 8, hipMemcpyHostToDevice, s));
+        prove_chunk(r, a, r.witness.ptr, blind ? v.blinding : nullptr, a.seeds + done, now, d_rows, d_proofs, hashes ? reinterpret_cast<uint8_t*>(d_hashes) : nullptr,
+                    r.io_status.ptr, zero_seed, s);
+        LSR_HIP(hipMemcpyAsync(rows + done * words, d_rows, now * words * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(proofs + done * 13, d_proofs, now * 13 * 8, hipMemcpyDeviceToHost, s));
+        if (hashes) LSR_HIP(hipMemcpyAsync(hashes + done * 64, d_hashes, now * 64, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(status + done, r.io_status.ptr, now * 4, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+// verify on the host: the transcripts on the host pool (lsr_fs_challenge_batch_flat), then the checks
+static void verify_host(uint32_t m, const uint64_t* pub, size_t n_public, const uint64_t* rows, size_t words, const uint64_t* proofs, size_t batch, bool zk,
+                        int* results) {
+    std::vector<uint64_t> alphas(batch), betas(batch);
+    check_lwe_call(lsr_fs_challenge_batch_flat(pub, n_public, rows, words, batch, kProverModulus, alphas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
+    check_lwe_call(lsr_fs_challenge_batch_flat(alphas.data(), 1, rows, words, batch, kProverModulus, betas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
+    for (size_t i = 0; i < batch; ++i) results[i] = verify_one(proofs + i * 13, alphas[i], betas[i], m, zk);
+}
+
+static void verify_device(uint32_t m, const uint64_t* d_pub, size_t n_public, const uint64_t* d_rows, size_t words, const uint64_t* d_proofs, size_t batch,
+                          bool zk, int* d_results, hipStream_t s) {
+    uint64_t* d_ab = nullptr;   // alphas, betas: stream-ordered scratch
+    LSR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ab), 2 * batch * 8, s));
+    try {
+        check_lwe_call(lsr_fs_challenge_batch_device(d_pub, n_public, d_rows, words, batch, kProverModulus, d_ab, nullptr, s), "lsr_fs_challenge_batch_device");
+        check_lwe_call(lsr_fs_challenge_batch_device(d_ab, 1, d_rows, words, batch, kProverModulus, d_ab + batch, nullptr, s), "lsr_fs_challenge_batch_device");
+        hipLaunchKernelGGL(verify_check_kernel, dim3(blocks_for(batch, ~0u)), dim3(kBlock), 0, s, d_proofs, d_ab, d_ab + batch, m, zk ? 1 : 0, d_results, batch);
+        LSR_HIP(hipGetLastError());
+    } catch (...) {
+        (void)hipFreeAsync(d_ab, s);
+        throw;
+    }
+    LSR_HIP(hipFreeAsync(d_ab, s));
+}
+
+static void eval_device(const uint64_t* d_c, size_t len, size_t batch, const uint64_t* d_x, uint32_t ppp, uint64_t* d_v, hipStream_t s) {
+    for (size_t done = 0; done < batch; done += 0x7fffffffull) {   // grid.x bound
+        const size_t now = std::min<size_t>(0x7fffffffull, batch - done);
+        const uint64_t* c = d_c + done * len;
+        const EvalPolys polys{{c, c, c}, len, (uint32_t)len};
+        const EvalPoints pts{{d_x + done * ppp, d_x + done * ppp + 1}, ppp, ppp};
+        hipLaunchKernelGGL((eval_kernel<false, 1>), dim3((unsigned)now, (ppp + 1) / 2), dim3(kEvalBlock), 0, s, polys, pts, EvalOut{d_v + done * ppp, ppp, 0}, 0,
+                           kGoldOneMont);
+    }
+    LSR_HIP(hipGetLastError());
 }
 
 // natural-order transforms for host callers: ntt.rs:117-201
@@ -619,6 +839,90 @@ int lsr_r1cs_quotient_batch(LsrR1csProver* prover, const uint64_t* witnesses, si
     if (!prover || !witnesses || !quotient || !quotient_len) return -1;
     if (batch == 0) return 0;
     return guarded("lsr_r1cs_quotient_batch", [&] { lsr::prover_run(*prover, witnesses, batch, nullptr, quotient, quotient_len); });
+}
+
+// ---- batched prove / verify (prover.h) ----
+static int refuse(const char* where, const char* why) {
+    set_last_error(std::string(where) + ": " + why);
+    return -1;
+}
+
+static int prove_checks(const char* where, const LsrR1csProver* prover, const LweContext* lwe, uint64_t commit_modulus, const void* w, size_t n_public,
+                        const uint64_t* seeds, const void* rows, const void* proofs, const void* status) {
+    if (!prover || !lwe) return refuse(where, "NULL prover or LWE context");
+    if (!w || !seeds || !rows || !proofs || !status) return refuse(where, "NULL witnesses, seeds, rows, proofs or status");
+    if (n_public > prover->n_vars) return refuse(where, "n_public exceeds the circuit's variable count");
+    if (commit_modulus <= 1) return refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
+    const NttContext* ntt = lsr_lwe_ntt_context(lwe);
+    if (!ntt || ntt->device != prover->plan->device) return refuse(where, "the prover and the LWE context live on different devices");
+    return 0;
+}
+
+int lsr_r1cs_prove_batch(LsrR1csProver* prover, LweContext* lwe, uint64_t commit_modulus, const uint64_t* witnesses, size_t batch, size_t n_public,
+                         const uint64_t* seeds, const uint64_t* blinding, uint64_t* rows, uint64_t* proofs, uint8_t* hashes, uint32_t* status) noexcept {
+    const char* where = "lsr_r1cs_prove_batch";
+    if (prove_checks(where, prover, lwe, commit_modulus, witnesses, n_public, seeds, rows, proofs, status)) return -1;
+    if (batch == 0) return 0;
+    return guarded(where, [&] {
+        const lsr::ProveArgs a{lwe, commit_modulus, n_public, seeds, blinding != nullptr};
+        lsr::prove_host(*prover, a, witnesses, batch, blinding, rows, proofs, hashes, status);
+    });
+}
+
+int lsr_r1cs_prove_batch_device(LsrR1csProver* prover, LweContext* lwe, uint64_t commit_modulus, const uint64_t* d_witnesses, size_t batch, size_t n_public,
+                                const uint64_t* seeds, const uint64_t* d_blinding, uint64_t* d_rows, uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status,
+                                void* stream) noexcept {
+    const char* where = "lsr_r1cs_prove_batch_device";
+    if (prove_checks(where, prover, lwe, commit_modulus, d_witnesses, n_public, seeds, d_rows, d_proofs, d_status)) return -1;
+    if (batch == 0) return 0;
+    for (size_t i = 0; i < batch; ++i)
+        if (seeds[i] == 0) return refuse(where, "seed 0 asks for fresh OS entropy, which only the host call serves (lsr_r1cs_prove_batch)");
+    if (batch > 0x7fffffffull) return refuse(where, "batch exceeds 2^31 - 1 proofs");
+    return guarded(where, [&] {
+        lsr::DeviceGuard guard(prover->plan->device);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (lsr::stream_is_capturing(s)) throw std::runtime_error("not capturable into a HIP graph (host seeds, host-ordered workspace)");
+        const lsr::ProveArgs a{lwe, commit_modulus, n_public, seeds, d_blinding != nullptr};
+        lsr::prove_device(*prover, a, d_witnesses, batch, d_blinding, d_rows, d_proofs, d_hashes, d_status, s);
+    });
+}
+
+static int verify_checks(const char* where, uint32_t m, const void* pub, size_t n_public, const void* rows, size_t words, const void* proofs,
+                         const void* results) {
+    if ((!pub && n_public) || !rows || !proofs || !results) return refuse(where, "NULL public inputs, rows, proofs or results");
+    if (words == 0) return refuse(where, "words_per_row must be positive");
+    if (m == 0 || (m & (m - 1))) return refuse(where, "m must be a power of two (the NTT path, r1cs.rs:386-389)");
+    return 0;
+}
+
+int lsr_r1cs_verify_batch(uint32_t m, const uint64_t* public_inputs, size_t n_public, const uint64_t* rows, size_t words_per_row, const uint64_t* proofs,
+                          size_t batch, int zk, int* results) noexcept {
+    const char* where = "lsr_r1cs_verify_batch";
+    if (verify_checks(where, m, public_inputs, n_public, rows, words_per_row, proofs, results)) return -1;
+    if (batch == 0) return 0;
+    return guarded(where, [&] { lsr::verify_host(m, public_inputs, n_public, rows, words_per_row, proofs, batch, zk != 0, results); });
+}
+
+int lsr_r1cs_verify_batch_device(uint32_t m, const uint64_t* d_public_inputs, size_t n_public, const uint64_t* d_rows, size_t words_per_row,
+                                 const uint64_t* d_proofs, size_t batch, int zk, int* d_results, void* stream) noexcept {
+    const char* where = "lsr_r1cs_verify_batch_device";
+    if (verify_checks(where, m, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, d_results)) return -1;
+    if (batch == 0) return 0;
+    return guarded(where, [&] {
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (lsr::stream_is_capturing(s)) throw std::runtime_error("not capturable into a HIP graph (stream-ordered scratch)");
+        lsr::verify_device(m, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, batch, zk != 0, d_results, s);
+    });
+}
+
+int lsr_prover_eval_batch_device(const uint64_t* d_coeffs, size_t len, size_t batch, const uint64_t* d_points, uint32_t points_per_poly, uint64_t* d_values,
+                                 void* stream) noexcept {
+    const char* where = "lsr_prover_eval_batch_device";
+    if (!d_coeffs || !d_points || !d_values) return refuse(where, "NULL coefficients, points or values");
+    if (len == 0 || len > 0x80000000ull) return refuse(where, "len must be in [1, 2^31]");
+    if (points_per_poly == 0 || points_per_poly > 131070u) return refuse(where, "points_per_poly must be in [1, 131070]");
+    if (batch == 0) return 0;
+    return guarded(where, [&] { lsr::eval_device(d_coeffs, len, batch, d_points, points_per_poly, d_values, static_cast<hipStream_t>(stream)); });
 }
 
 }  // extern "C"
