@@ -113,6 +113,32 @@ int lsr_r1cs_verify_batch_device(uint32_t m, const uint64_t* d_public_inputs, si
 int lsr_prover_eval_batch_device(const uint64_t* d_coeffs, size_t len, size_t batch, const uint64_t* d_points,
                                  uint32_t points_per_poly, uint64_t* d_values, void* stream) LSR_NOEXCEPT;
 
+/* ---- the Lagrange (baseline) path: any other circuit (r1cs.rs:596-654, 746-828, 995-1065) ----
+ * lsr_r1cs_prover_create_mod builds, for modulus NTT_MODULUS and m a power of two, exactly what lsr_r1cs_prover_create builds;
+ * otherwise a Lagrange-path prover for odd 3 <= q < 2^64 and 1 <= m <= 8192.  Its interpolation domain is {omega^j} when
+ * q = 17592169062401 and m is in ROOTS_OF_UNITY (4 ... 8192, r1cs.rs:529-575), else {0, 1, ..., m-1}; the quotient always divides
+ * by Z_H = prod_{i<m} (X - i) (so on the omega domain a witness with non-zero evaluations leaves a remainder: status 0).  NULL
+ * (lsr_last_error says why) for an even q, m outside [1, 8192], a domain whose interpolation denominators are not all units mod q
+ * (where the reference panics, e.g. q = 2^44 + 1 with m >= 18), bad shapes, or without a GPU.
+ * lsr_r1cs_constraint_evals_batch, lsr_r1cs_quotient_batch and lsr_r1cs_prove_batch[_device] accept either kind with the
+ * contracts above (values mod q; the transcript challenges are taken mod q). */
+LsrR1csProver* lsr_r1cs_prover_create_mod(const SparseMatrix* A, const SparseMatrix* B, const SparseMatrix* C, uint64_t modulus,
+                                          int device) LSR_NOEXCEPT;
+uint64_t lsr_r1cs_prover_modulus(const LsrR1csProver* prover) LSR_NOEXCEPT;
+/* 1 for a prover on the NTT path, 0 for a Lagrange-path prover */
+int      lsr_r1cs_prover_uses_ntt(const LsrR1csProver* prover) LSR_NOEXCEPT;
+/* Lagrange-path provers only: a/b/c_coeffs [batch][m] receive the interpolated A_z, B_z, C_z (lagrange_interpolate). 0 / -1. */
+int lsr_r1cs_interpolate_batch(LsrR1csProver* prover, const uint64_t* witnesses, size_t batch, uint64_t* a_coeffs, uint64_t* b_coeffs,
+                               uint64_t* c_coeffs) LSR_NOEXCEPT;
+/* verify_r1cs / verify_r1cs_zk for a circuit with m constraints over `modulus` (odd, >= 3): eval_vanishing is x^m - 1 when
+ * modulus = NTT_MODULUS and m is a power of two (then exactly lsr_r1cs_verify_batch), else prod_{i<m} (x - i), m <= 8192.
+ * Arguments and results as lsr_r1cs_verify_batch[_device]; the host call needs no GPU.  0 / -1. */
+int lsr_r1cs_verify_batch_mod(uint32_t m, uint64_t modulus, const uint64_t* public_inputs, size_t n_public, const uint64_t* rows,
+                              size_t words_per_row, const uint64_t* proofs, size_t batch, int zk, int* results) LSR_NOEXCEPT;
+int lsr_r1cs_verify_batch_mod_device(uint32_t m, uint64_t modulus, const uint64_t* d_public_inputs, size_t n_public, const uint64_t* d_rows,
+                                     size_t words_per_row, const uint64_t* d_proofs, size_t batch, int zk, int* d_results,
+                                     void* stream) LSR_NOEXCEPT;
+
 #ifdef __cplusplus
 }
 #endif

@@ -607,9 +607,11 @@ class QuotientPlan:
 class R1csProver:
     """``R1CS`` restricted to what the prover's hot loop needs (rust-api/lambda-snark/src/r1cs.rs:88-137, 296-304, 474-506):
     the three matrices on the device, ``compute_constraint_evals`` and ``compute_quotient_poly`` for batches of witnesses.
-    ``a``, ``b``, ``c`` are lists of ``(row, col, value)`` entries of m x n matrices; modulus is NTT_MODULUS, m = 2^k."""
+    ``a``, ``b``, ``c`` are lists of ``(row, col, value)`` entries of m x n matrices.  ``modulus=None`` is NTT_MODULUS with m = 2^k
+    (``lsr_r1cs_prover_create``); any other modulus, or NTT_MODULUS with m not a power of two, takes the Lagrange path
+    (``lsr_r1cs_prover_create_mod``: odd q >= 3, 1 <= m <= 8192)."""
 
-    def __init__(self, m, n, a, b, c, device=-1):
+    def __init__(self, m, n, a, b, c, device=-1, modulus=None):
         self._lib = _abi.lib()
         self.m, self.n = int(m), int(n)
         keep, mats = [], []
@@ -619,9 +621,16 @@ class R1csProver:
                 arr[i] = _abi.SparseEntry(int(row), int(col), int(value))
             keep.append(arr)
             mats.append(_abi.SparseMatrix(ctypes.cast(arr, ctypes.POINTER(_abi.SparseEntry)), len(entries), self.m, self.n))
-        self._h = self._lib.lsr_r1cs_prover_create(ctypes.byref(mats[0]), ctypes.byref(mats[1]), ctypes.byref(mats[2]), device)
-        if not self._h:
-            raise CoreError(f"lsr_r1cs_prover_create(m={m}, n={n}) returned NULL: {_abi.last_error()}")
+        if modulus is None:
+            self._h = self._lib.lsr_r1cs_prover_create(ctypes.byref(mats[0]), ctypes.byref(mats[1]), ctypes.byref(mats[2]), device)
+            if not self._h:
+                raise CoreError(f"lsr_r1cs_prover_create(m={m}, n={n}) returned NULL: {_abi.last_error()}")
+        else:
+            self._h = self._lib.lsr_r1cs_prover_create_mod(ctypes.byref(mats[0]), ctypes.byref(mats[1]), ctypes.byref(mats[2]), int(modulus), device)
+            if not self._h:
+                raise CoreError(f"lsr_r1cs_prover_create_mod(m={m}, n={n}, modulus={modulus}) returned NULL: {_abi.last_error()}")
+        self.modulus = int(self._lib.lsr_r1cs_prover_modulus(self._h))
+        self.uses_ntt = bool(self._lib.lsr_r1cs_prover_uses_ntt(self._h))
 
     def _witnesses(self, witnesses):
         w = _u64_array(witnesses)
@@ -634,6 +643,14 @@ class R1csProver:
         out = [np.zeros((batch, self.m), dtype=np.uint64) for _ in range(3)]
         if batch and self._lib.lsr_r1cs_constraint_evals_batch(self._h, w.ctypes.data, batch, *(o.ctypes.data for o in out)) != 0:
             raise CoreError("lsr_r1cs_constraint_evals_batch failed: " + _abi.last_error())
+        return tuple(out)
+
+    def interpolate_batch(self, witnesses):
+        """Lagrange-path provers: the interpolated A_z, B_z, C_z (lagrange_interpolate) -> three [batch][m] coefficient arrays."""
+        w, batch = self._witnesses(witnesses)
+        out = [np.zeros((batch, self.m), dtype=np.uint64) for _ in range(3)]
+        if batch and self._lib.lsr_r1cs_interpolate_batch(self._h, w.ctypes.data, batch, *(o.ctypes.data for o in out)) != 0:
+            raise CoreError("lsr_r1cs_interpolate_batch failed: " + _abi.last_error())
         return tuple(out)
 
     def quotient_batch(self, witnesses):
@@ -699,22 +716,35 @@ PROOF_FIELDS = ("alpha", "beta", "q_alpha", "q_beta", "a_z_alpha", "b_z_alpha", 
                 "opening_beta", "blinding_factor")   # prover.h LSR_PROOF_*: ProofR1CS / ProofR1csZk field order
 
 
-def verify_r1cs_batch(m, publics, rows, proofs, zk=False):
+def verify_r1cs_batch(m, publics, rows, proofs, zk=False, modulus=None):
     """``verify_r1cs`` / ``verify_r1cs_zk`` (lib.rs:1016-1095, 1142-1215) for a batch, on the host (no GPU needed): -> int32 [batch] of 1 / 0.
-    publics [batch][n_public], rows [batch][words], proofs [batch][PROOF_WORDS]."""
+    publics [batch][n_public], rows [batch][words], proofs [batch][PROOF_WORDS].  ``modulus=None``: NTT_MODULUS, m = 2^k
+    (``lsr_r1cs_verify_batch``); else ``lsr_r1cs_verify_batch_mod``."""
     proofs = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, PROOF_WORDS)
     batch = proofs.shape[0]
     rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(batch, -1)
     publics = np.ascontiguousarray(publics, dtype=np.uint64).reshape(batch, -1)
     results = np.zeros(batch, dtype=np.int32)
+    if modulus is not None:
+        if batch and _abi.lib().lsr_r1cs_verify_batch_mod(int(m), int(modulus), publics.ctypes.data if publics.size else None, publics.shape[1],
+                                                          rows.ctypes.data, rows.shape[1], proofs.ctypes.data, batch, 1 if zk else 0,
+                                                          results.ctypes.data) != 0:
+            raise CoreError("lsr_r1cs_verify_batch_mod failed: " + _abi.last_error())
+        return results
     if batch and _abi.lib().lsr_r1cs_verify_batch(int(m), publics.ctypes.data if publics.size else None, publics.shape[1], rows.ctypes.data, rows.shape[1],
                                                   proofs.ctypes.data, batch, 1 if zk else 0, results.ctypes.data) != 0:
         raise CoreError("lsr_r1cs_verify_batch failed: " + _abi.last_error())
     return results
 
 
-def verify_r1cs_batch_device(m, d_publics, n_public, d_rows, words_per_row, d_proofs, batch, d_results, zk=False, stream=0):
-    """``lsr_r1cs_verify_batch_device``: device pointers, int32 results, asynchronous on `stream`."""
+def verify_r1cs_batch_device(m, d_publics, n_public, d_rows, words_per_row, d_proofs, batch, d_results, zk=False, stream=0, modulus=None):
+    """``lsr_r1cs_verify_batch_device``: device pointers, int32 results, asynchronous on `stream`.  ``modulus`` not None:
+    ``lsr_r1cs_verify_batch_mod_device``."""
+    if modulus is not None:
+        if _abi.lib().lsr_r1cs_verify_batch_mod_device(int(m), int(modulus), d_publics, n_public, d_rows, words_per_row, d_proofs, batch, 1 if zk else 0,
+                                                       d_results, stream) != 0:
+            raise CoreError("lsr_r1cs_verify_batch_mod_device failed: " + _abi.last_error())
+        return
     if _abi.lib().lsr_r1cs_verify_batch_device(int(m), d_publics, n_public, d_rows, words_per_row, d_proofs, batch, 1 if zk else 0, d_results, stream) != 0:
         raise CoreError("lsr_r1cs_verify_batch_device failed: " + _abi.last_error())
 

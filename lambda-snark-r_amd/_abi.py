@@ -165,6 +165,12 @@ SIGNATURES = {
     "lsr_r1cs_prove_batch_device": (c_int, [vp, vp, u64, vp, c_size, c_size, vp, vp, vp, vp, vp, vp, vp]),
     "lsr_r1cs_verify_batch": (c_int, [u32, vp, c_size, vp, c_size, vp, c_size, c_int, vp]),
     "lsr_r1cs_verify_batch_device": (c_int, [u32, vp, c_size, vp, c_size, vp, c_size, c_int, vp, vp]),
+    "lsr_r1cs_prover_create_mod": (vp, [ctypes.POINTER(SparseMatrix), ctypes.POINTER(SparseMatrix), ctypes.POINTER(SparseMatrix), u64, c_int]),
+    "lsr_r1cs_prover_modulus": (u64, [vp]),
+    "lsr_r1cs_prover_uses_ntt": (c_int, [vp]),
+    "lsr_r1cs_interpolate_batch": (c_int, [vp, vp, c_size, vp, vp, vp]),
+    "lsr_r1cs_verify_batch_mod": (c_int, [u32, u64, vp, c_size, vp, c_size, vp, c_size, c_int, vp]),
+    "lsr_r1cs_verify_batch_mod_device": (c_int, [u32, u64, vp, c_size, vp, c_size, vp, c_size, c_int, vp, vp]),
     "lsr_prover_eval_batch_device": (c_int, [vp, c_size, c_size, vp, u32, vp, vp]),
 }
 

@@ -1,0 +1,477 @@
+// The Lagrange (baseline) path of compute_quotient_poly / prove_r1cs / verify_r1cs for any odd modulus q < 2^64 and
+// 1 <= m <= 8192 constraints (rust-api/lambda-snark/src/r1cs.rs:596-654, 746-828, 995-1065; lib.rs:747-980, 1016-1215).
+// The plan holds the interpolation matrix L of its domain, the power series of 1 / rev(Z_H) and Z_H itself; a batch of
+// witnesses then costs one modular GEMM plus O(m^2) work per instance.  Kernels: lsr_lagrange_kernels.hpp.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+
+#include "lambda_snark/batch.h"
+#include "lambda_snark/prover.h"
+#include "lsr_lagrange.hpp"
+#include "lsr_lagrange_kernels.hpp"
+#include "lsr_runtime.hpp"
+
+namespace lsr {
+
+// ROOTS_OF_UNITY of r1cs.rs:533-547: the omega domain of NTT_FRIENDLY_MODULUS (get_ntt_root, r1cs.rs:563-575)
+static const struct { uint32_t m; uint64_t omega; } kQuirkRoots[] = {
+    {4, 981206394875ull},       {8, 4268641988953ull},      {16, 9400386778549ull},    {32, 15690227524213ull},
+    {64, 8332322609789ull},     {128, 9249819209096ull},    {256, 5221410271124ull},   {512, 9594533594163ull},
+    {1024, 11016271016603ull},  {2048, 14373677444369ull},  {4096, 11176258803537ull}, {8192, 9037003627149ull},
+};
+
+static MontQ make_mont(uint64_t q) {
+    MontQ M{};
+    M.q = q;
+    uint64_t inv = q;                       // Newton: q^-1 mod 2^64 (q odd; 5 steps from 3 correct bits)
+    for (int i = 0; i < 5; ++i) inv *= 2 - q * inv;
+    M.qinv = 0 - inv;
+    M.r1 = (uint64_t)(((unsigned __int128)1 << 64) % q);
+    M.r2 = mulmod(M.r1, M.r1, q);
+    M.r3 = mulmod(M.r2, M.r1, q);
+    return M;
+}
+
+// a^-1 mod q when gcd(a, q) = 1 (extended Euclid: q need not be prime)
+static bool invert(uint64_t a, uint64_t q, uint64_t& out) {
+    __int128 t = 0, nt = 1, r = q, nr = a % q;
+    while (nr != 0) {
+        const __int128 k = r / nr;
+        __int128 x = t - k * nt; t = nt; nt = x;
+        x = r - k * nr; r = nr; nr = x;
+    }
+    if (r != 1) return false;
+    if (t < 0) t += q;
+    out = (uint64_t)t;
+    return true;
+}
+
+static int blocks(size_t work, unsigned cap = 256 * 32) {
+    return (int)std::max<size_t>(1, std::min<size_t>((work + kLagBlock - 1) / kLagBlock, cap));
+}
+
+}  // namespace lsr
+
+namespace lsr {
+
+struct LagrangeProver {
+    uint32_t m = 0, n_vars = 0;
+    uint64_t q = 0;
+    int device = 0;
+    bool omega = false;                    // the quirk's domain {omega^j}
+    MontQ M{};
+    DeviceBuffer<uint32_t> row_ptr[3], col[3];
+    DeviceBuffer<uint64_t> val[3];         // Montgomery form
+    DeviceBuffer<uint64_t> lt;             // [m][m]: lt[i m + k] = L[k][i] 2^128
+    DeviceBuffer<uint64_t> tser;           // [max(1, m - 1)]: T 2^128
+    DeviceBuffer<uint64_t> zh_s, zh_m;     // [m + 1]: Z_H 2^128, Z_H 2^64
+    std::mutex mutex;                      // guards the workspace and `stream`
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_last = nullptr;          // end of the last asynchronous call: the next call (any stream) starts behind it
+    int chunk_log2 = 26;                   // LAMBDA_SNARK_QUOTIENT_CHUNK_LOG2, read once at creation
+    // workspace for `chunk` instances
+    size_t chunk = 0, publics = 0, row_words = 0;
+    DeviceBuffer<uint64_t> witness;        // [chunk][n_vars]
+    DeviceBuffer<uint64_t> evals, coef;    // [3][chunk][m]
+    DeviceBuffer<uint64_t> top;            // [chunk][max(1, m - 1)]
+    DeviceBuffer<uint64_t> quot;           // [chunk][m]
+    DeviceBuffer<uint64_t> qp, msg;        // [chunk][m + 1]
+    DeviceBuffer<uint64_t> small;          // keys[4] alphas betas hash_a[4] hash_b[4] ev[8] blinding publics[n_public] per instance
+    DeviceBuffer<uint32_t> flags;          // bad[chunk] len[chunk]
+    DeviceBuffer<uint64_t> io;             // host staging: rows [chunk][W] proofs [chunk][13] hashes [chunk][8]
+    DeviceBuffer<uint32_t> io_status;
+};
+
+// ---- plan tables, O(m^2) on the host ----------------------------------------------------------------------------------------
+// Z = prod_j (X - x_j) over the domain; P_i = Z / (X - x_i) by synthetic division; P_i(x_i) = prod_{j != i} (x_i - x_j) = 1 / w_i;
+// L[k][i] = w_i coef_k(P_i) (unique: any exact construction gives the reference's words).  Z_H = prod_{i<m} (X - i) always.
+static std::vector<uint64_t> vanishing(const std::vector<uint64_t>& x, const MontQ& M) {
+    std::vector<uint64_t> z(1, 1);
+    for (uint64_t xj : x) {
+        const uint64_t xm = mq_to(xj, M);
+        z.push_back(0);
+        for (size_t k = z.size() - 1; k > 0; --k) z[k] = mq_sub(z[k - 1], mq_mul(z[k], xm, M), M);
+        z[0] = mq_sub(0, mq_mul(z[0], xm, M), M);
+    }
+    return z;
+}
+
+static bool build_tables(LagrangeProver& p, std::string& why) {
+    const uint32_t m = p.m;
+    const MontQ& M = p.M;
+    const uint64_t q = p.q;
+    std::vector<uint64_t> x(m);
+    uint64_t omega = 0;
+    if (q == kQuirkModulus)
+        for (const auto& r : kQuirkRoots)
+            if (r.m == m) omega = r.omega;
+    p.omega = omega != 0;
+    for (uint32_t j = 0; j < m; ++j) x[j] = omega ? (j ? mulmod(x[j - 1], omega, q) : 1) : (uint64_t)j % q;
+    const std::vector<uint64_t> z = vanishing(x, M);
+    std::vector<uint64_t> zh = p.omega ? vanishing([&] { std::vector<uint64_t> s(m); for (uint32_t j = 0; j < m; ++j) s[j] = j % q; return s; }(), M) : z;
+    std::vector<uint64_t> lt((size_t)m * m), P(m);
+    for (uint32_t i = 0; i < m; ++i) {
+        const uint64_t xm = mq_to(x[i], M);
+        P[m - 1] = z[m];                                                     // = 1
+        for (uint32_t k = m - 1; k > 0; --k) P[k - 1] = mq_add(z[k], mq_mul(P[k], xm, M), M);
+        uint64_t d = 0;                                                      // P_i(x_i) by Horner
+        for (uint32_t k = m; k-- > 0;) d = mq_add(mq_mul(d, xm, M), P[k], M);
+        uint64_t w;
+        if (!invert(d, q, w)) {                                              // mod_inverse panics (arith.rs:66-85)
+            why = "the interpolation denominator prod_{j != " + std::to_string(i) + "} (x_i - x_j) is not a unit mod q (the reference panics in mod_inverse)";
+            return false;
+        }
+        const uint64_t ws = mulmod(w, M.r3, q);                              // w 2^192: mq_mul(P, ws) = w P 2^128
+        for (uint32_t k = 0; k < m; ++k) lt[(size_t)i * m + k] = mq_mul(P[k], ws, M);
+    }
+    // T = 1 / rev(Z_H) mod X^(m-1): T_0 = 1, T_l = -sum_{j=1}^{l} zh[m-j] T_{l-j}
+    const uint32_t w = std::max<uint32_t>(1, m - 1);
+    std::vector<uint64_t> T(w, 0), ts(w, 0);
+    T[0] = 1 % q;
+    for (uint32_t l = 1; l + 1 < m; ++l) {
+        Acc192 acc;
+        acc_zero(acc);
+        for (uint32_t j = 1; j <= l; ++j) acc_mac(acc, zh[m - j], T[l - j]);
+        T[l] = mq_sub(0, mq_mul(acc_reduce(acc, M), M.r3, M), M);
+    }
+    for (uint32_t l = 0; l < w; ++l) ts[l] = mulmod(T[l], M.r2, q);
+    std::vector<uint64_t> zs(m + 1), zm(m + 1);
+    for (uint32_t k = 0; k <= m; ++k) {
+        zs[k] = mulmod(zh[k], M.r2, q);
+        zm[k] = mulmod(zh[k], M.r1, q);
+    }
+    p.lt.upload(lt);
+    p.tser.upload(ts);
+    p.zh_s.upload(zs);
+    p.zh_m.upload(zm);
+    return true;
+}
+
+void lagrange_destroy(LagrangeProver* p) {
+    if (!p) return;
+    try {
+        DeviceGuard guard(p->device);
+        if (p->ev_last) {
+            (void)hipEventSynchronize(p->ev_last);
+            (void)hipEventDestroy(p->ev_last);
+        }
+        if (p->stream) (void)hipStreamDestroy(p->stream);
+        for (int k = 0; k < 3; ++k) { p->row_ptr[k].release(); p->col[k].release(); p->val[k].release(); }
+        p->lt.release(); p->tser.release(); p->zh_s.release(); p->zh_m.release();
+        p->witness.release(); p->evals.release(); p->coef.release(); p->top.release(); p->quot.release(); p->qp.release(); p->msg.release();
+        p->small.release(); p->flags.release(); p->io.release(); p->io_status.release();
+    } catch (...) {
+    }
+    delete p;
+}
+
+int lagrange_device(const LagrangeProver* p) { return p ? p->device : -1; }
+bool lagrange_omega_domain(const LagrangeProver* p) { return p && p->omega; }
+
+LagrangeProver* lagrange_create(const SparseMatrix* const mats[3], uint64_t q, int device) {
+    const char* where = "lsr_r1cs_prover_create_mod";
+    const uint32_t m = mats[0]->n_rows, n_vars = mats[0]->n_cols;
+    if (q < 3 || (q & 1) == 0) {
+        set_last_error(std::string(where) + ": the Lagrange path needs an odd modulus q >= 3 (for even q the reference succeeds only for m <= 2)");
+        return nullptr;
+    }
+    if (m == 0 || m > kLagrangeMaxM) {
+        set_last_error(std::string(where) + ": the Lagrange path takes 1 <= m <= 8192 constraints");
+        return nullptr;
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (mats[k]->n_rows != m || mats[k]->n_cols != n_vars || (mats[k]->n_entries && !mats[k]->entries) || mats[k]->n_entries > 0xFFFFFFF0ull) {
+            set_last_error(std::string(where) + ": A, B, C must share one shape");
+            return nullptr;
+        }
+        for (size_t e = 0; e < mats[k]->n_entries; ++e)
+            if (mats[k]->entries[e].row >= m || mats[k]->entries[e].col >= n_vars) {
+                set_last_error(std::string(where) + ": entry outside the matrix");
+                return nullptr;
+            }
+    }
+    if (n_vars == 0) {
+        set_last_error(std::string(where) + ": no variables");
+        return nullptr;
+    }
+    const int devices = visible_device_count();
+    if (devices <= 0) {
+        set_last_error(std::string(where) + ": no HIP device visible — this library has no CPU fallback");
+        return nullptr;
+    }
+    if (device < 0) device = default_device();
+    if (device < 0) return nullptr;
+    if (device >= devices) {
+        set_last_error(std::string(where) + ": device index out of range");
+        return nullptr;
+    }
+    auto* p = new LagrangeProver;
+    p->m = m;
+    p->n_vars = n_vars;
+    p->q = q;
+    p->device = device;
+    p->M = make_mont(q);
+    if (const char* e = std::getenv("LAMBDA_SNARK_QUOTIENT_CHUNK_LOG2")) {
+        const int v = std::atoi(e);
+        if (v >= 1 && v <= 30) p->chunk_log2 = v;
+    }
+    try {
+        DeviceGuard guard(device);
+        std::string why;
+        if (!build_tables(*p, why)) {
+            set_last_error(std::string(where) + ": " + why);
+            lagrange_destroy(p);
+            return nullptr;
+        }
+        for (int k = 0; k < 3; ++k) {   // coordinate form -> CSR (stable counting sort by row)
+            const SparseMatrix& A = *mats[k];
+            std::vector<uint32_t> ptr(m + 1, 0), cols(A.n_entries);
+            std::vector<uint64_t> vals(A.n_entries);
+            for (size_t e = 0; e < A.n_entries; ++e) ++ptr[A.entries[e].row + 1];
+            for (uint32_t i = 0; i < m; ++i) ptr[i + 1] += ptr[i];
+            std::vector<uint32_t> cursor(ptr.begin(), ptr.end() - 1);
+            for (size_t e = 0; e < A.n_entries; ++e) {
+                const uint32_t at = cursor[A.entries[e].row]++;
+                cols[at] = A.entries[e].col;
+                vals[at] = mq_to(A.entries[e].value, p->M);              // (val mod q) 2^64
+            }
+            p->row_ptr[k].upload(ptr);
+            if (A.n_entries == 0) { cols.push_back(0); vals.push_back(0); }
+            p->col[k].upload(cols);
+            p->val[k].upload(vals);
+        }
+        LSR_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+    } catch (const std::exception& e) {
+        set_last_error(std::string(where) + ": " + e.what());
+        lagrange_destroy(p);
+        return nullptr;
+    }
+    return p;
+}
+
+// ---- the pipeline ------------------------------------------------------------------------------------------------------------
+static size_t chunk_for(const LagrangeProver& p, size_t batch) {
+    return std::min(batch, std::max<size_t>(1, (size_t(1) << p.chunk_log2) / p.m));
+}
+
+static void ensure_workspace(LagrangeProver& p, size_t chunk, size_t n_public, size_t row_words, bool host_io) {
+    const size_t m = p.m;
+    if (chunk > p.chunk || n_public > p.publics) {
+        p.chunk = std::max(p.chunk, chunk);
+        p.publics = std::max(p.publics, n_public);
+        const size_t c = p.chunk;
+        p.witness.allocate(c * p.n_vars);
+        p.evals.allocate(3 * c * m);
+        p.coef.allocate(3 * c * m);
+        p.top.allocate(c * std::max<size_t>(1, m - 1));
+        p.quot.allocate(c * m);
+        p.qp.allocate(c * (m + 1));
+        p.msg.allocate(c * (m + 1));
+        p.small.allocate(c * (23 + std::max<size_t>(1, p.publics)));
+        p.flags.allocate(2 * c);
+        p.io.release();
+        p.io_status.release();
+        p.row_words = 0;
+    }
+    if (host_io && (!p.io.ptr || p.row_words < row_words)) {
+        p.row_words = std::max<size_t>({p.row_words, row_words, 1});
+        p.io.allocate(p.chunk * (p.row_words + 13 + 8));
+        p.io_status.allocate(p.chunk);
+    }
+}
+
+// constraint evaluations of `count` witnesses (device, [count][n_vars]) into p.evals; interpolation into p.coef (interp); the
+// quotient into p.quot with len [count] (quotient).  All on `s`.
+static void run_chunk(LagrangeProver& p, const uint64_t* d_z, size_t count, bool interp, bool quotient, uint32_t* d_len, hipStream_t s) {
+    const uint32_t m = p.m;
+    const size_t per_vector = count * m;
+    uint64_t* E = p.evals.ptr;
+    uint64_t* Cf = p.coef.ptr;
+    const LagCsr a{p.row_ptr[0].ptr, p.col[0].ptr, p.val[0].ptr}, b{p.row_ptr[1].ptr, p.col[1].ptr, p.val[1].ptr},
+        c{p.row_ptr[2].ptr, p.col[2].ptr, p.val[2].ptr};
+    hipLaunchKernelGGL(lag_constraint_evals_kernel, dim3(blocks(per_vector), 3), dim3(kLagBlock), 0, s, E, a, b, c, d_z, p.n_vars, m, per_vector, p.M);
+    if (interp) {
+        const size_t rows = 3 * count;
+        const unsigned row_tiles = (unsigned)((rows + kGemmTile - 1) / kGemmTile);
+        if (m <= (uint32_t)kSmallMaxM)
+            hipLaunchKernelGGL(lag_interp_small_kernel, dim3(row_tiles), dim3(kLagBlock), 0, s, E, p.lt.ptr, Cf, rows, m, p.M);
+        else
+            hipLaunchKernelGGL(lag_interp_tiled_kernel, dim3(row_tiles, (m + kGemmTile - 1) / kGemmTile), dim3(kLagBlock), 0, s, E, p.lt.ptr, Cf, rows, m, p.M);
+    }
+    if (quotient) {
+        uint32_t* bad = p.flags.ptr;
+        LSR_HIP(hipMemsetAsync(bad, 0, count * sizeof(uint32_t), s));
+        hipLaunchKernelGGL(lag_check_kernel, dim3(blocks(per_vector)), dim3(kLagBlock), 0, s, E, E + per_vector, E + 2 * per_vector, bad, m, per_vector, p.M);
+        if (m >= 2)
+            hipLaunchKernelGGL(lag_top_kernel, dim3(blocks(count * (m - 1))), dim3(kLagBlock), 0, s, Cf, Cf + per_vector, p.top.ptr, m,
+                               count * (m - 1), p.M);
+        hipLaunchKernelGGL(lag_toeplitz_kernel, dim3(blocks(per_vector)), dim3(kLagBlock), 0, s, p.top.ptr, p.tser.ptr, p.quot.ptr, m, per_vector, p.M);
+        if (p.omega)   // on {0..m-1} is_satisfied already implies Z_H | N
+            hipLaunchKernelGGL(lag_remainder_kernel, dim3(blocks(per_vector)), dim3(kLagBlock), 0, s, Cf, Cf + per_vector, Cf + 2 * per_vector, p.quot.ptr,
+                               p.zh_s.ptr, bad, m, per_vector, p.M);
+        hipLaunchKernelGGL(lag_len_kernel, dim3(blocks(count, ~0u)), dim3(kLagBlock), 0, s, p.quot.ptr, bad, d_len, m, count);
+    }
+    LSR_HIP(hipGetLastError());
+}
+
+void lagrange_host_run(LagrangeProver& p, const uint64_t* w, size_t batch, uint64_t* const evals[3], uint64_t* const coeffs[3], uint64_t* quotient,
+                       uint32_t* len) {
+    DeviceGuard guard(p.device);
+    std::lock_guard<std::mutex> lock(p.mutex);
+    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
+    const size_t chunk = chunk_for(p, batch);
+    ensure_workspace(p, chunk, 0, 0, false);
+    hipStream_t s = p.stream;
+    uint32_t* d_len = p.flags.ptr + p.chunk;
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        const size_t per_vector = now * p.m, off = done * p.m;
+        LSR_HIP(hipMemcpyAsync(p.witness.ptr, w + done * p.n_vars, now * p.n_vars * 8, hipMemcpyHostToDevice, s));
+        run_chunk(p, p.witness.ptr, now, !evals, !evals && !coeffs, d_len, s);
+        if (evals || coeffs) {
+            const uint64_t* src = evals ? p.evals.ptr : p.coef.ptr;
+            uint64_t* const* dst = evals ? evals : coeffs;
+            for (int k = 0; k < 3; ++k) LSR_HIP(hipMemcpyAsync(dst[k] + off, src + k * per_vector, per_vector * 8, hipMemcpyDeviceToHost, s));
+        } else {
+            LSR_HIP(hipMemcpyAsync(quotient + off, p.quot.ptr, per_vector * 8, hipMemcpyDeviceToHost, s));
+            LSR_HIP(hipMemcpyAsync(len + done, d_len, now * 4, hipMemcpyDeviceToHost, s));
+        }
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+static void check_call(int rc, const char* what) {
+    if (rc != 0) throw std::runtime_error(std::string(what) + ": " + lsr_last_error());
+}
+
+// one chunk of prove_r1cs / prove_r1cs_zk: evaluations -> interpolation -> quotient -> message -> keys -> rows -> alpha -> beta ->
+// evaluations at alpha and beta -> proof records
+static void prove_chunk(LagrangeProver& p, LweContext* lwe, uint64_t commit_modulus, size_t n_public, const uint64_t* d_z, const uint64_t* d_blind,
+                        const uint64_t* seeds, size_t count, uint64_t* d_rows, uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status, bool host_keys,
+                        hipStream_t s) {
+    const uint32_t m = p.m;
+    const size_t per_vector = count * m;
+    const size_t words = lsr_lwe_commitment_words(lwe);
+    uint64_t* sm = p.small.ptr;
+    const size_t C = p.chunk;
+    uint64_t *keys = sm, *alphas = sm + 4 * C, *betas = sm + 5 * C, *hash_a = sm + 6 * C, *hash_b = sm + 10 * C, *ev = sm + 14 * C,
+             *publics = sm + 23 * C;
+    uint32_t* d_len = p.flags.ptr + C;
+    run_chunk(p, d_z, count, true, true, d_len, s);
+    const uint32_t msg_len = m + (d_blind ? 1u : 0u);
+    hipLaunchKernelGGL(lag_message_kernel, dim3(blocks(count * (m + 1))), dim3(kLagBlock), 0, s, p.quot.ptr, d_blind, p.zh_m.ptr, p.qp.ptr, p.msg.ptr,
+                       msg_len, commit_modulus, m, count * (size_t)(m + 1), p.M);
+    LSR_HIP(hipGetLastError());
+    if (host_keys) {
+        std::vector<uint64_t> msgs(count * msg_len), hk(4 * count);
+        LSR_HIP(hipMemcpyAsync(msgs.data(), p.msg.ptr, msgs.size() * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+        check_call(lsr_lwe_commit_keys(lwe, msgs.data(), msg_len, count, seeds, hk.data()), "lsr_lwe_commit_keys");
+        LSR_HIP(hipMemcpyAsync(keys, hk.data(), hk.size() * 8, hipMemcpyHostToDevice, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    } else {
+        check_call(lsr_lwe_commit_keys_device(lwe, p.msg.ptr, msg_len, count, seeds, keys, s), "lsr_lwe_commit_keys_device");
+    }
+    check_call(lsr_lwe_commit_rows_device(lwe, p.msg.ptr, msg_len, count, keys, d_rows, s), "lsr_lwe_commit_rows_device");
+    if (n_public)
+        hipLaunchKernelGGL(lag_gather_publics_kernel, dim3(blocks(count * n_public)), dim3(kLagBlock), 0, s, d_z, p.n_vars, (uint32_t)n_public, publics,
+                           count * n_public);
+    LSR_HIP(hipGetLastError());
+    check_call(lsr_fs_challenge_batch_device(n_public ? publics : nullptr, n_public, d_rows, words, count, p.q, alphas,
+                                             reinterpret_cast<uint8_t*>(hash_a), s), "lsr_fs_challenge_batch_device");
+    check_call(lsr_fs_challenge_batch_device(alphas, 1, d_rows, words, count, p.q, betas, reinterpret_cast<uint8_t*>(hash_b), s),
+               "lsr_fs_challenge_batch_device");
+    LagEvalPolys polys;
+    for (int k = 0; k < 3; ++k) {
+        polys.poly[k] = p.coef.ptr + k * per_vector;
+        polys.stride[k] = m;
+        polys.len[k] = m;
+    }
+    polys.poly[3] = p.qp.ptr;
+    polys.stride[3] = m + 1;
+    polys.len[3] = m + 1;
+    hipLaunchKernelGGL(lag_eval_kernel, dim3((unsigned)count, 4), dim3(64), 0, s, polys, alphas, betas, ev, p.M);
+    hipLaunchKernelGGL(lag_assemble_kernel, dim3(blocks(count, ~0u)), dim3(kLagBlock), 0, s, ev, alphas, betas, d_blind, d_len, hash_a, hash_b, d_proofs,
+                       reinterpret_cast<uint64_t*>(d_hashes), d_status, count, p.q);
+    LSR_HIP(hipGetLastError());
+}
+
+void lagrange_prove_host(LagrangeProver& p, LweContext* lwe, uint64_t commit_modulus, const uint64_t* w, size_t batch, size_t n_public,
+                         const uint64_t* seeds, const uint64_t* blind, uint64_t* rows, uint64_t* proofs, uint8_t* hashes, uint32_t* status) {
+    DeviceGuard guard(p.device);
+    std::lock_guard<std::mutex> lock(p.mutex);   // prover first, then (inside each commitment call) the LWE context
+    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
+    const size_t words = lsr_lwe_commitment_words(lwe);
+    const size_t chunk = chunk_for(p, batch);
+    ensure_workspace(p, chunk, n_public, words, true);
+    hipStream_t s = p.stream;
+    uint64_t* d_blind = p.small.ptr + 22 * p.chunk;
+    uint64_t* d_rows = p.io.ptr;
+    uint64_t* d_proofs = d_rows + p.chunk * p.row_words;
+    uint64_t* d_hashes = d_proofs + p.chunk * 13;
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        bool zero_seed = false;
+        for (size_t j = 0; j < now; ++j) zero_seed |= seeds[done + j] == 0;
+        LSR_HIP(hipMemcpyAsync(p.witness.ptr, w + done * p.n_vars, now * p.n_vars * 8, hipMemcpyHostToDevice, s));
+        if (blind) LSR_HIP(hipMemcpyAsync(d_blind, blind + done, now * 8, hipMemcpyHostToDevice, s));
+        prove_chunk(p, lwe, commit_modulus, n_public, p.witness.ptr, blind ? d_blind : nullptr, seeds + done, now, d_rows, d_proofs,
+                    hashes ? reinterpret_cast<uint8_t*>(d_hashes) : nullptr, p.io_status.ptr, zero_seed, s);
+        LSR_HIP(hipMemcpyAsync(rows + done * words, d_rows, now * words * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(proofs + done * 13, d_proofs, now * 13 * 8, hipMemcpyDeviceToHost, s));
+        if (hashes) LSR_HIP(hipMemcpyAsync(hashes + done * 64, d_hashes, now * 64, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(status + done, p.io_status.ptr, now * 4, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+void lagrange_prove_device(LagrangeProver& p, LweContext* lwe, uint64_t commit_modulus, const uint64_t* d_w, size_t batch, size_t n_public,
+                           const uint64_t* seeds, const uint64_t* d_blind, uint64_t* d_rows, uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status,
+                           void* stream) {
+    DeviceGuard guard(p.device);
+    std::lock_guard<std::mutex> lock(p.mutex);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
+    const size_t words = lsr_lwe_commitment_words(lwe);
+    const size_t chunk = chunk_for(p, batch);
+    ensure_workspace(p, chunk, n_public, words, false);
+    for (size_t done = 0; done < batch; done += chunk) {
+        const size_t now = std::min(chunk, batch - done);
+        prove_chunk(p, lwe, commit_modulus, n_public, d_w + done * p.n_vars, d_blind ? d_blind + done : nullptr, seeds + done, now, d_rows + done * words,
+                    d_proofs + done * 13, d_hashes ? d_hashes + done * 64 : nullptr, d_status + done, false, s);
+    }
+    if (!p.ev_last) LSR_HIP(hipEventCreateWithFlags(&p.ev_last, hipEventDisableTiming));
+    LSR_HIP(hipEventRecord(p.ev_last, s));
+}
+
+// ---- verify on the baseline path ---------------------------------------------------------------------------------------------
+void verify_mod_host(uint32_t m, uint64_t q, const uint64_t* pub, size_t n_public, const uint64_t* rows, size_t words, const uint64_t* proofs,
+                     size_t batch, bool zk, int* results) {
+    std::vector<uint64_t> alphas(batch), betas(batch);
+    check_call(lsr_fs_challenge_batch_flat(pub, n_public, rows, words, batch, q, alphas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
+    check_call(lsr_fs_challenge_batch_flat(alphas.data(), 1, rows, words, batch, q, betas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
+    const MontQ M = make_mont(q);
+    for (size_t i = 0; i < batch; ++i) results[i] = verify_one_generic(proofs + i * 13, alphas[i], betas[i], m, zk, M);
+}
+
+void verify_mod_device(uint32_t m, uint64_t q, const uint64_t* d_pub, size_t n_public, const uint64_t* d_rows, size_t words, const uint64_t* d_proofs,
+                       size_t batch, bool zk, int* d_results, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint64_t* d_ab = nullptr;
+    LSR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ab), 2 * batch * 8, s));
+    try {
+        check_call(lsr_fs_challenge_batch_device(d_pub, n_public, d_rows, words, batch, q, d_ab, nullptr, s), "lsr_fs_challenge_batch_device");
+        check_call(lsr_fs_challenge_batch_device(d_ab, 1, d_rows, words, batch, q, d_ab + batch, nullptr, s), "lsr_fs_challenge_batch_device");
+        hipLaunchKernelGGL(lag_verify_kernel, dim3(blocks(batch, ~0u)), dim3(kLagBlock), 0, s, d_proofs, d_ab, d_ab + batch, m, zk ? 1 : 0, d_results, batch,
+                           make_mont(q));
+        LSR_HIP(hipGetLastError());
+    } catch (...) {
+        (void)hipFreeAsync(d_ab, s);
+        throw;
+    }
+    LSR_HIP(hipFreeAsync(d_ab, s));
+}
+
+}  // namespace lsr

@@ -6,6 +6,7 @@
 
 #include "lambda_snark/prover.h"
 #include "lambda_snark/batch.h"
+#include "lsr_lagrange.hpp"
 #include "lsr_prove_kernels.hpp"
 #include "lsr_runtime.hpp"
 
@@ -404,7 +405,9 @@ static LsrQuotientPlan* create_plan(uint32_t m, int device) {
 
 struct LsrR1csProver {
     uint32_t m = 0, n_vars = 0;
-    LsrQuotientPlan* plan = nullptr;
+    LsrQuotientPlan* plan = nullptr;        // NTT path
+    lsr::LagrangeProver* lag = nullptr;     // Lagrange path (lsr_r1cs_prover_create_mod, lsr_lagrange.hip): then plan == nullptr
+    uint64_t modulus = lsr::kProverModulus;
     lsr::DeviceBuffer<uint32_t> row_ptr[3], col[3];
     lsr::DeviceBuffer<uint64_t> val[3];
     lsr::DeviceBuffer<uint64_t> witness;    // [chunk][n_vars]
@@ -424,6 +427,7 @@ namespace lsr {
 
 static void destroy_prover(LsrR1csProver* r) {
     if (!r) return;
+    lagrange_destroy(r->lag);
     if (r->plan) {
         try {
             DeviceGuard guard(r->plan->device);
@@ -832,13 +836,17 @@ int lsr_r1cs_constraint_evals_batch(LsrR1csProver* prover, const uint64_t* witne
     if (batch == 0) return 0;
     return guarded("lsr_r1cs_constraint_evals_batch", [&] {
         uint64_t* const evals[3] = {a_evals, b_evals, c_evals};
-        lsr::prover_run(*prover, witnesses, batch, evals, nullptr, nullptr);
+        if (prover->lag) lsr::lagrange_host_run(*prover->lag, witnesses, batch, evals, nullptr, nullptr, nullptr);
+        else lsr::prover_run(*prover, witnesses, batch, evals, nullptr, nullptr);
     });
 }
 int lsr_r1cs_quotient_batch(LsrR1csProver* prover, const uint64_t* witnesses, size_t batch, uint64_t* quotient, uint32_t* quotient_len) noexcept {
     if (!prover || !witnesses || !quotient || !quotient_len) return -1;
     if (batch == 0) return 0;
-    return guarded("lsr_r1cs_quotient_batch", [&] { lsr::prover_run(*prover, witnesses, batch, nullptr, quotient, quotient_len); });
+    return guarded("lsr_r1cs_quotient_batch", [&] {
+        if (prover->lag) lsr::lagrange_host_run(*prover->lag, witnesses, batch, nullptr, nullptr, quotient, quotient_len);
+        else lsr::prover_run(*prover, witnesses, batch, nullptr, quotient, quotient_len);
+    });
 }
 
 // ---- batched prove / verify (prover.h) ----
@@ -847,6 +855,8 @@ static int refuse(const char* where, const char* why) {
     return -1;
 }
 
+static int prover_device(const LsrR1csProver* p) { return p->lag ? lsr::lagrange_device(p->lag) : p->plan->device; }
+
 static int prove_checks(const char* where, const LsrR1csProver* prover, const LweContext* lwe, uint64_t commit_modulus, const void* w, size_t n_public,
                         const uint64_t* seeds, const void* rows, const void* proofs, const void* status) {
     if (!prover || !lwe) return refuse(where, "NULL prover or LWE context");
@@ -854,7 +864,7 @@ static int prove_checks(const char* where, const LsrR1csProver* prover, const Lw
     if (n_public > prover->n_vars) return refuse(where, "n_public exceeds the circuit's variable count");
     if (commit_modulus <= 1) return refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
     const NttContext* ntt = lsr_lwe_ntt_context(lwe);
-    if (!ntt || ntt->device != prover->plan->device) return refuse(where, "the prover and the LWE context live on different devices");
+    if (!ntt || ntt->device != prover_device(prover)) return refuse(where, "the prover and the LWE context live on different devices");
     return 0;
 }
 
@@ -864,6 +874,10 @@ int lsr_r1cs_prove_batch(LsrR1csProver* prover, LweContext* lwe, uint64_t commit
     if (prove_checks(where, prover, lwe, commit_modulus, witnesses, n_public, seeds, rows, proofs, status)) return -1;
     if (batch == 0) return 0;
     return guarded(where, [&] {
+        if (prover->lag) {
+            lsr::lagrange_prove_host(*prover->lag, lwe, commit_modulus, witnesses, batch, n_public, seeds, blinding, rows, proofs, hashes, status);
+            return;
+        }
         const lsr::ProveArgs a{lwe, commit_modulus, n_public, seeds, blinding != nullptr};
         lsr::prove_host(*prover, a, witnesses, batch, blinding, rows, proofs, hashes, status);
     });
@@ -879,9 +893,14 @@ int lsr_r1cs_prove_batch_device(LsrR1csProver* prover, LweContext* lwe, uint64_t
         if (seeds[i] == 0) return refuse(where, "seed 0 asks for fresh OS entropy, which only the host call serves (lsr_r1cs_prove_batch)");
     if (batch > 0x7fffffffull) return refuse(where, "batch exceeds 2^31 - 1 proofs");
     return guarded(where, [&] {
-        lsr::DeviceGuard guard(prover->plan->device);
+        lsr::DeviceGuard guard(prover_device(prover));
         hipStream_t s = static_cast<hipStream_t>(stream);
         if (lsr::stream_is_capturing(s)) throw std::runtime_error("not capturable into a HIP graph (host seeds, host-ordered workspace)");
+        if (prover->lag) {
+            lsr::lagrange_prove_device(*prover->lag, lwe, commit_modulus, d_witnesses, batch, n_public, seeds, d_blinding, d_rows, d_proofs, d_hashes,
+                                       d_status, stream);
+            return;
+        }
         const lsr::ProveArgs a{lwe, commit_modulus, n_public, seeds, d_blinding != nullptr};
         lsr::prove_device(*prover, a, d_witnesses, batch, d_blinding, d_rows, d_proofs, d_hashes, d_status, s);
     });
@@ -923,6 +942,78 @@ int lsr_prover_eval_batch_device(const uint64_t* d_coeffs, size_t len, size_t ba
     if (points_per_poly == 0 || points_per_poly > 131070u) return refuse(where, "points_per_poly must be in [1, 131070]");
     if (batch == 0) return 0;
     return guarded(where, [&] { lsr::eval_device(d_coeffs, len, batch, d_points, points_per_poly, d_values, static_cast<hipStream_t>(stream)); });
+}
+
+// ---- the Lagrange path (prover.h) ----
+LsrR1csProver* lsr_r1cs_prover_create_mod(const SparseMatrix* A, const SparseMatrix* B, const SparseMatrix* C, uint64_t modulus, int device) noexcept {
+    if (!A || !B || !C) {
+        set_last_error("lsr_r1cs_prover_create_mod: NULL matrix");
+        return nullptr;
+    }
+    const uint32_t m = A->n_rows;
+    if (modulus == lsr::kProverModulus && m != 0 && (m & (m - 1)) == 0) return lsr_r1cs_prover_create(A, B, C, device);   // should_use_ntt
+    try {
+        const SparseMatrix* const mats[3] = {A, B, C};
+        lsr::LagrangeProver* lag = lsr::lagrange_create(mats, modulus, device);
+        if (!lag) return nullptr;
+        auto* r = new LsrR1csProver;
+        r->m = m;
+        r->n_vars = A->n_cols;
+        r->lag = lag;
+        r->modulus = modulus;
+        return r;
+    } catch (...) {
+        set_last_error("lsr_r1cs_prover_create_mod: allocation failed");
+        return nullptr;
+    }
+}
+uint64_t lsr_r1cs_prover_modulus(const LsrR1csProver* prover) noexcept { return prover ? prover->modulus : 0; }
+int lsr_r1cs_prover_uses_ntt(const LsrR1csProver* prover) noexcept { return prover && prover->plan ? 1 : 0; }
+
+int lsr_r1cs_interpolate_batch(LsrR1csProver* prover, const uint64_t* witnesses, size_t batch, uint64_t* a_coeffs, uint64_t* b_coeffs,
+                               uint64_t* c_coeffs) noexcept {
+    const char* where = "lsr_r1cs_interpolate_batch";
+    if (!prover || !witnesses || !a_coeffs || !b_coeffs || !c_coeffs) return refuse(where, "NULL prover, witnesses or output");
+    if (!prover->lag) return refuse(where, "only a Lagrange-path prover (lsr_r1cs_prover_uses_ntt == 0) exposes its interpolants");
+    if (batch == 0) return 0;
+    return guarded(where, [&] {
+        uint64_t* const out[3] = {a_coeffs, b_coeffs, c_coeffs};
+        lsr::lagrange_host_run(*prover->lag, witnesses, batch, nullptr, out, nullptr, nullptr);
+    });
+}
+
+static bool ntt_path(uint32_t m, uint64_t q) { return q == lsr::kProverModulus && (m & (m - 1)) == 0; }
+
+static int verify_mod_checks(const char* where, uint32_t m, uint64_t q, const void* pub, size_t n_public, const void* rows, size_t words,
+                             const void* proofs, const void* results) {
+    if ((!pub && n_public) || !rows || !proofs || !results) return refuse(where, "NULL public inputs, rows, proofs or results");
+    if (words == 0) return refuse(where, "words_per_row must be positive");
+    if (q < 3 || (q & 1) == 0) return refuse(where, "the modulus must be odd and >= 3");
+    if (m == 0) return refuse(where, "m must be positive");
+    if (!ntt_path(m, q) && m > lsr::kLagrangeMaxM) return refuse(where, "the Lagrange path takes m <= 8192");
+    return 0;
+}
+
+int lsr_r1cs_verify_batch_mod(uint32_t m, uint64_t modulus, const uint64_t* public_inputs, size_t n_public, const uint64_t* rows, size_t words_per_row,
+                              const uint64_t* proofs, size_t batch, int zk, int* results) noexcept {
+    const char* where = "lsr_r1cs_verify_batch_mod";
+    if (verify_mod_checks(where, m, modulus, public_inputs, n_public, rows, words_per_row, proofs, results)) return -1;
+    if (ntt_path(m, modulus)) return lsr_r1cs_verify_batch(m, public_inputs, n_public, rows, words_per_row, proofs, batch, zk, results);
+    if (batch == 0) return 0;
+    return guarded(where, [&] { lsr::verify_mod_host(m, modulus, public_inputs, n_public, rows, words_per_row, proofs, batch, zk != 0, results); });
+}
+
+int lsr_r1cs_verify_batch_mod_device(uint32_t m, uint64_t modulus, const uint64_t* d_public_inputs, size_t n_public, const uint64_t* d_rows,
+                                     size_t words_per_row, const uint64_t* d_proofs, size_t batch, int zk, int* d_results, void* stream) noexcept {
+    const char* where = "lsr_r1cs_verify_batch_mod_device";
+    if (verify_mod_checks(where, m, modulus, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, d_results)) return -1;
+    if (ntt_path(m, modulus))
+        return lsr_r1cs_verify_batch_device(m, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, batch, zk, d_results, stream);
+    if (batch == 0) return 0;
+    return guarded(where, [&] {
+        if (lsr::stream_is_capturing(static_cast<hipStream_t>(stream))) throw std::runtime_error("not capturable into a HIP graph (stream-ordered scratch)");
+        lsr::verify_mod_device(m, modulus, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, batch, zk != 0, d_results, stream);
+    });
 }
 
 }  // extern "C"
