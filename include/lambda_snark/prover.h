@@ -139,6 +139,56 @@ int lsr_r1cs_verify_batch_mod_device(uint32_t m, uint64_t modulus, const uint64_
                                      size_t words_per_row, const uint64_t* d_proofs, size_t batch, int zk, int* d_results,
                                      void* stream) LSR_NOEXCEPT;
 
+/* ---- the witness-polynomial proofs: prove_simple, prove_zk, simulate_proof and verify_simple (lib.rs:465-491, 551-585, 657-681,
+ * 1269-1285; opening.rs:104-115, 160-264; polynomial.rs) ----
+ * One proof = LSR_SIMPLE_PROOF_WORDS uint64 words: the challenge alpha, Opening.evaluation and Opening.witness[0] (the commit seed).
+ * The commitment is the separate row and Opening.witness[1..] the separate coefficient array coeffs [len] (f' mod q).
+ * Moduli: odd 3 <= q < 2^64 (an even q or q < 3: -1 / NULL and lsr_last_error). */
+enum { LSR_SIMPLE_ALPHA, LSR_SIMPLE_EVAL, LSR_SIMPLE_SEED, LSR_SIMPLE_PROOF_WORDS };
+/* f' = w mod q (prove_simple), f' = (w mod q) + r (prove_zk), f' = r (simulate_proof; no witness), r = random_blinding */
+enum { LSR_SIMPLE_PLAIN, LSR_SIMPLE_ZK, LSR_SIMPLE_SIMULATE };
+/* ChaCha20Rng::seed_from_u64 (rand_core 0.6.4): keys [count][4] = the 256-bit ChaCha20 keys as little-endian 64-bit words.  Host, no GPU. */
+int lsr_chacha20rng_keys_from_u64(const uint64_t* seeds, size_t count, uint64_t* keys) LSR_NOEXCEPT;
+/* Polynomial::random_blinding(len - 1, q, .) per key: out[i][j] = (u64 draw j of ChaCha20Rng with key i) mod q, out [batch][len].
+ * Host, no GPU.  0 / -1. */
+int lsr_random_blinding(const uint64_t* keys, size_t batch, size_t len, uint64_t q, uint64_t* out) LSR_NOEXCEPT;
+/* the same on device arrays (the calling thread's current device), asynchronous on `stream`.  0 / -1. */
+int lsr_random_blinding_device(const uint64_t* d_keys, size_t batch, size_t len, uint64_t q, uint64_t* d_out, void* stream) LSR_NOEXCEPT;
+
+typedef struct LsrSimpleProver LsrSimpleProver;
+/* the Montgomery constants of q and a bounded device workspace on `device` (-1 = default).  NULL for a bad q or without a GPU. */
+LsrSimpleProver* lsr_simple_prover_create(uint64_t q, int device) LSR_NOEXCEPT;
+void     lsr_simple_prover_free(LsrSimpleProver* prover) LSR_NOEXCEPT;
+uint64_t lsr_simple_prover_modulus(const LsrSimpleProver* prover) LSR_NOEXCEPT;
+/* `batch` proofs of one length len >= 1 (1 <= len < 2^32).  witnesses [batch][len] (NULL in SIMULATE); public_inputs [batch][n_public]
+ * (raw words, hashed as given); seeds [batch] (the commit seeds; 0 = fresh OS entropy for that commitment, as lwe_commit);
+ * blinding_keys [batch][4] (ZK / SIMULATE; lsr_chacha20rng_keys_from_u64 of the blinding / sim seeds; NULL = fresh OS entropy per
+ * proof, ChaCha20Rng::from_entropy).  Out: rows [batch][lsr_lwe_commitment_words(lwe)] = lwe_commit(f' mod commit_modulus, len, seed)
+ * (commit_modulus: Rust's LweContext::modulus()); coeffs [batch][len] = f'; proofs [batch][LSR_SIMPLE_PROOF_WORDS]; hashes
+ * [batch][32] (the transcript hash of alpha, may be NULL).  Host arrays, chunked staging.  0 / -1. */
+int lsr_simple_prove_batch(LsrSimpleProver* prover, LweContext* lwe, uint64_t commit_modulus, int mode, const uint64_t* witnesses,
+                           size_t len, size_t batch, const uint64_t* public_inputs, size_t n_public, const uint64_t* seeds,
+                           const uint64_t* blinding_keys, uint64_t* rows, uint64_t* coeffs, uint64_t* proofs, uint8_t* hashes) LSR_NOEXCEPT;
+/* the same on device arrays on the prover's device, asynchronous on `stream`.  `seeds` stays a HOST array and every seed must be
+ * non-zero; ZK and SIMULATE need d_blinding_keys.  Not capturable into a HIP graph (-1). */
+int lsr_simple_prove_batch_device(LsrSimpleProver* prover, LweContext* lwe, uint64_t commit_modulus, int mode, const uint64_t* d_witnesses,
+                                  size_t len, size_t batch, const uint64_t* d_public_inputs, size_t n_public, const uint64_t* seeds,
+                                  const uint64_t* d_blinding_keys, uint64_t* d_rows, uint64_t* d_coeffs, uint64_t* d_proofs,
+                                  uint8_t* d_hashes, void* stream) LSR_NOEXCEPT;
+/* verify_simple for `batch` proofs over q: public_inputs [batch][n_public], rows [batch][words_per_row], proofs
+ * [batch][LSR_SIMPLE_PROOF_WORDS], coeffs [batch][len] (may be NULL when len = 0); results[i] = 1 / 0.  lwe != NULL adds the binding
+ * check of verify_opening_with_context: lwe_verify_opening(lwe, row, (c mod q) mod commit_modulus, len) == 1 (words_per_row must then
+ * be lsr_lwe_commitment_words(lwe); a coefficient >= t never opens, as in the reference).  With lwe == NULL the host call needs no
+ * GPU.  0 / -1. */
+int lsr_simple_verify_batch(uint64_t q, const uint64_t* public_inputs, size_t n_public, const uint64_t* rows, size_t words_per_row,
+                            const uint64_t* proofs, const uint64_t* coeffs, size_t len, size_t batch, const LweContext* lwe,
+                            uint64_t commit_modulus, int* results) LSR_NOEXCEPT;
+/* the same on device arrays (the context's device when lwe != NULL, else the calling thread's current device), asynchronous on
+ * `stream` with stream-ordered scratch; not capturable (-1). */
+int lsr_simple_verify_batch_device(uint64_t q, const uint64_t* d_public_inputs, size_t n_public, const uint64_t* d_rows,
+                                   size_t words_per_row, const uint64_t* d_proofs, const uint64_t* d_coeffs, size_t len, size_t batch,
+                                   const LweContext* lwe, uint64_t commit_modulus, int* d_results, void* stream) LSR_NOEXCEPT;
+
 #ifdef __cplusplus
 }
 #endif

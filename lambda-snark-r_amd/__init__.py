@@ -8,6 +8,7 @@ C-ABI are mirrored here in Python with the same names, argument meaning and erro
 * ``verify_opening_with_context`` <-> rust-api/lambda-snark/src/opening.rs:160-222
 * ``NttContext``  <-> the ``ntt_*`` symbols (only exercised by cpp-core/tests/test_ntt.cpp in the reference)
 * ``CyclicNtt`` / ``QuotientPlan`` <-> rust-api/lambda-snark/src/ntt.rs:117-233 and r1cs.rs:474-506 (prover path)
+* ``SimpleProver`` / ``verify_simple_batch`` <-> prove_simple, prove_zk, simulate_proof and verify_simple (lib.rs:465-681, 1269-1285)
 
 All arithmetic happens in liblambda_snark_core.so (HIP, gfx950).  Nothing here computes; there is no
 CPU fallback.  (The directory name has a hyphen; load it through ``__graft_entry__.load_package()``.)
@@ -23,6 +24,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
+    "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -753,3 +755,127 @@ def prover_eval_batch_device(d_coeffs, length, batch, d_points, points_per_poly,
     """``lsr_prover_eval_batch_device``: eval_poly (r1cs.rs:362-373) over NTT_MODULUS, values[i][k] = coeffs[i](points[i][k])."""
     if _abi.lib().lsr_prover_eval_batch_device(d_coeffs, length, batch, d_points, points_per_poly, d_values, stream) != 0:
         raise CoreError("lsr_prover_eval_batch_device failed: " + _abi.last_error())
+
+
+# ---- the witness-polynomial proofs: prove_simple / prove_zk / simulate_proof / verify_simple (lib.rs:465-681, 1269-1285) ----------
+SIMPLE_PROOF_WORDS = 3
+SIMPLE_PROOF_FIELDS = ("alpha", "evaluation", "seed")   # prover.h LSR_SIMPLE_*: the challenge, Opening.evaluation, Opening.witness[0]
+SIMPLE_MODES = {"plain": 0, "zk": 1, "simulate": 2}      # prove_simple, prove_zk, simulate_proof
+
+
+def _simple_mode(mode):
+    if mode not in SIMPLE_MODES:
+        raise ValueError(f"mode must be one of {sorted(SIMPLE_MODES)}")
+    return SIMPLE_MODES[mode]
+
+
+def chacha20rng_keys(seeds):
+    """``lsr_chacha20rng_keys_from_u64``: ``ChaCha20Rng::seed_from_u64`` keys, [count][4] uint64 (no GPU needed)."""
+    seeds = _u64_array(seeds, "seeds").ravel()
+    keys = np.zeros((seeds.size, 4), dtype=np.uint64)
+    if seeds.size and _abi.lib().lsr_chacha20rng_keys_from_u64(seeds.ctypes.data, seeds.size, keys.ctypes.data) != 0:
+        raise CoreError("lsr_chacha20rng_keys_from_u64 failed: " + _abi.last_error())
+    return keys
+
+
+def random_blinding(keys, length, modulus):
+    """``lsr_random_blinding``: ``Polynomial::random_blinding(length - 1, modulus, .)`` per key (polynomial.rs:176-187) on the host,
+    -> [batch][length] uint64."""
+    keys = _u64_array(keys, "keys").reshape(-1, 4)
+    out = np.zeros((keys.shape[0], int(length)), dtype=np.uint64)
+    if _abi.lib().lsr_random_blinding(keys.ctypes.data, keys.shape[0], int(length), int(modulus), out.ctypes.data if out.size else None) != 0:
+        raise CoreError("lsr_random_blinding failed: " + _abi.last_error())
+    return out
+
+
+def random_blinding_device(d_keys, batch, length, modulus, d_out, stream=0):
+    """``lsr_random_blinding_device``: device pointers, asynchronous on `stream`."""
+    if _abi.lib().lsr_random_blinding_device(d_keys, batch, int(length), int(modulus), d_out, stream) != 0:
+        raise CoreError("lsr_random_blinding_device failed: " + _abi.last_error())
+
+
+class SimpleProver:
+    """``prove_simple`` / ``prove_zk`` / ``simulate_proof`` (lib.rs:465-491, 551-585, 657-681) for batches of one length over an odd
+    field modulus q (``lsr_simple_prover_create``)."""
+
+    def __init__(self, modulus, device=-1):
+        self._lib = _abi.lib()
+        self._h = self._lib.lsr_simple_prover_create(int(modulus), device)
+        if not self._h:
+            raise CoreError(f"lsr_simple_prover_create(modulus={modulus}) returned NULL: {_abi.last_error()}")
+        self.modulus = int(self._lib.lsr_simple_prover_modulus(self._h))
+
+    def prove_batch(self, ctx, witnesses, publics, seeds, commit_modulus, mode="plain", blinding_keys=None, length=None):
+        """-> (rows [batch][ctx.commitment_words], coeffs [batch][length] (f' mod q = Opening.witness[1..]), proofs
+        [batch][SIMPLE_PROOF_WORDS], hashes [batch][32] uint8).  witnesses [batch][length] (None for "simulate", which then needs
+        ``length``); publics [batch][n_public]; seeds [batch] (0 = fresh entropy); blinding_keys [batch][4] (``chacha20rng_keys`` of the
+        blinding / sim seeds; None = fresh entropy); commit_modulus is Rust's ``LweContext::modulus()`` (``ctx.modulus()``)."""
+        m = _simple_mode(mode)
+        seeds = _u64_array(seeds, "seeds").ravel()
+        batch = seeds.size
+        if witnesses is None:
+            if m != SIMPLE_MODES["simulate"] or length is None:
+                raise ValueError("witnesses are needed unless mode='simulate' with a length")
+            w, length = None, int(length)
+        else:
+            w = _u64_array(witnesses, "witnesses").reshape(batch, -1)
+            length = w.shape[1]
+        pub = np.ascontiguousarray(publics, dtype=np.uint64).reshape(batch, -1)
+        keys = None if blinding_keys is None else _u64_array(blinding_keys, "blinding_keys").reshape(batch, 4)
+        rows = np.zeros((batch, ctx.commitment_words), dtype=np.uint64)
+        coeffs = np.zeros((batch, length), dtype=np.uint64)
+        proofs = np.zeros((batch, SIMPLE_PROOF_WORDS), dtype=np.uint64)
+        hashes = np.zeros((batch, 32), dtype=np.uint8)
+        if self._lib.lsr_simple_prove_batch(self._h, ctx.handle, int(commit_modulus), m, None if w is None else w.ctypes.data, length, batch,
+                                            pub.ctypes.data if pub.size else None, pub.shape[1], seeds.ctypes.data,
+                                            None if keys is None else keys.ctypes.data, rows.ctypes.data, coeffs.ctypes.data if coeffs.size else None,
+                                            proofs.ctypes.data, hashes.ctypes.data) != 0:
+            raise CoreError("lsr_simple_prove_batch failed: " + _abi.last_error())
+        return rows, coeffs, proofs, hashes
+
+    def prove_batch_device(self, ctx, d_witnesses, length, batch, d_publics, n_public, seeds, commit_modulus, d_rows, d_coeffs, d_proofs, d_hashes=None,
+                           mode="plain", d_blinding_keys=None, stream=0):
+        """``lsr_simple_prove_batch_device``: device pointers (ints) in and out, host seeds (all non-zero), asynchronous on `stream`."""
+        seeds = _u64_array(seeds, "seeds").ravel()
+        if seeds.size != batch:
+            raise ValueError("one seed per proof")
+        if self._lib.lsr_simple_prove_batch_device(self._h, ctx.handle, int(commit_modulus), _simple_mode(mode), d_witnesses, int(length), batch, d_publics,
+                                                   int(n_public), seeds.ctypes.data, d_blinding_keys, d_rows, d_coeffs, d_proofs, d_hashes, stream) != 0:
+            raise CoreError("lsr_simple_prove_batch_device failed: " + _abi.last_error())
+
+    def close(self):
+        if self._h:
+            self._lib.lsr_simple_prover_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def verify_simple_batch(modulus, publics, rows, proofs, coeffs, ctx=None, commit_modulus=None):
+    """``verify_simple`` (lib.rs:1269-1285) for a batch on the host -> int32 [batch] of 1 / 0; no GPU needed without ``ctx``.  With ``ctx``
+    the binding check of ``verify_opening_with_context`` (opening.rs:160-222) is added (commit_modulus defaults to ``ctx.modulus()``)."""
+    proofs = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, SIMPLE_PROOF_WORDS)
+    batch = proofs.shape[0]
+    rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(batch, -1)
+    publics = np.ascontiguousarray(publics, dtype=np.uint64).reshape(batch, -1)
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(batch, -1)
+    results = np.zeros(batch, dtype=np.int32)
+    cm = 0 if ctx is None else int(ctx.modulus() if commit_modulus is None else commit_modulus)
+    if batch and _abi.lib().lsr_simple_verify_batch(int(modulus), publics.ctypes.data if publics.size else None, publics.shape[1], rows.ctypes.data,
+                                                    rows.shape[1], proofs.ctypes.data, coeffs.ctypes.data if coeffs.size else None, coeffs.shape[1],
+                                                    batch, None if ctx is None else ctx.handle, cm, results.ctypes.data) != 0:
+        raise CoreError("lsr_simple_verify_batch failed: " + _abi.last_error())
+    return results
+
+
+def verify_simple_batch_device(modulus, d_publics, n_public, d_rows, words_per_row, d_proofs, d_coeffs, length, batch, d_results, ctx=None,
+                               commit_modulus=None, stream=0):
+    """``lsr_simple_verify_batch_device``: device pointers, int32 results, asynchronous on `stream`."""
+    cm = 0 if ctx is None else int(ctx.modulus() if commit_modulus is None else commit_modulus)
+    if _abi.lib().lsr_simple_verify_batch_device(int(modulus), d_publics, int(n_public), d_rows, words_per_row, d_proofs, d_coeffs, int(length), batch,
+                                                 None if ctx is None else ctx.handle, cm, d_results, stream) != 0:
+        raise CoreError("lsr_simple_verify_batch_device failed: " + _abi.last_error())

@@ -172,6 +172,16 @@ SIGNATURES = {
     "lsr_r1cs_verify_batch_mod": (c_int, [u32, u64, vp, c_size, vp, c_size, vp, c_size, c_int, vp]),
     "lsr_r1cs_verify_batch_mod_device": (c_int, [u32, u64, vp, c_size, vp, c_size, vp, c_size, c_int, vp, vp]),
     "lsr_prover_eval_batch_device": (c_int, [vp, c_size, c_size, vp, u32, vp, vp]),
+    "lsr_chacha20rng_keys_from_u64": (c_int, [vp, c_size, vp]),
+    "lsr_random_blinding": (c_int, [vp, c_size, c_size, u64, vp]),
+    "lsr_random_blinding_device": (c_int, [vp, c_size, c_size, u64, vp, vp]),
+    "lsr_simple_prover_create": (vp, [u64, c_int]),
+    "lsr_simple_prover_free": (None, [vp]),
+    "lsr_simple_prover_modulus": (u64, [vp]),
+    "lsr_simple_prove_batch": (c_int, [vp, vp, u64, c_int, vp, c_size, c_size, vp, c_size, vp, vp, vp, vp, vp, vp]),
+    "lsr_simple_prove_batch_device": (c_int, [vp, vp, u64, c_int, vp, c_size, c_size, vp, c_size, vp, vp, vp, vp, vp, vp, vp]),
+    "lsr_simple_verify_batch": (c_int, [u64, vp, c_size, vp, c_size, vp, vp, c_size, c_size, vp, u64, vp]),
+    "lsr_simple_verify_batch_device": (c_int, [u64, vp, c_size, vp, c_size, vp, vp, c_size, c_size, vp, u64, vp, vp]),
 }
 
 

@@ -22,18 +22,6 @@ static const struct { uint32_t m; uint64_t omega; } kQuirkRoots[] = {
     {1024, 11016271016603ull},  {2048, 14373677444369ull},  {4096, 11176258803537ull}, {8192, 9037003627149ull},
 };
 
-static MontQ make_mont(uint64_t q) {
-    MontQ M{};
-    M.q = q;
-    uint64_t inv = q;                       // Newton: q^-1 mod 2^64 (q odd; 5 steps from 3 correct bits)
-    for (int i = 0; i < 5; ++i) inv *= 2 - q * inv;
-    M.qinv = 0 - inv;
-    M.r1 = (uint64_t)(((unsigned __int128)1 << 64) % q);
-    M.r2 = mulmod(M.r1, M.r1, q);
-    M.r3 = mulmod(M.r2, M.r1, q);
-    return M;
-}
-
 // a^-1 mod q when gcd(a, q) = 1 (extended Euclid: q need not be prime)
 static bool invert(uint64_t a, uint64_t q, uint64_t& out) {
     __int128 t = 0, nt = 1, r = q, nr = a % q;

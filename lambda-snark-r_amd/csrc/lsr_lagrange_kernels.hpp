@@ -1,4 +1,4 @@
-// Kernels of the Lagrange (baseline) prove path (lsr_lagrange.hip): Montgomery arithmetic for any odd q < 2^64,
+// Kernels of the Lagrange (baseline) prove path (lsr_lagrange.hip), on the Montgomery arithmetic of lsr_montq.hpp:
 // the batched interpolation GEMM against the plan's resident L, the top half of A B, the Toeplitz quotient, the remainder test of
 // the omega domain, the commitment message, polynomial evaluation, the proof records and the generic-modulus verifier.
 #pragma once
@@ -6,48 +6,9 @@
 #include <cstdint>
 
 #include "lsr_arith.hpp"
+#include "lsr_montq.hpp"
 
 namespace lsr {
-
-// ---- Montgomery arithmetic modulo any odd q < 2^64 (host and device) --------------------------------------------------------
-// qinv = -q^-1 mod 2^64; r1, r2, r3 = 2^64, 2^128, 2^192 mod q.  Every value named "canonical" is < q.
-struct MontQ {
-    uint64_t q, qinv, r1, r2, r3;
-};
-
-__host__ __device__ inline uint64_t mq_mulhi(uint64_t a, uint64_t b) {
-#ifdef __HIP_DEVICE_COMPILE__
-    return __umul64hi(a, b);
-#else
-    return (uint64_t)(((unsigned __int128)a * b) >> 64);
-#endif
-}
-
-// (hi:lo) 2^-64 mod q, canonical, for hi:lo < q 2^64.  With t = lo qinv, lo + (t q mod 2^64) is 0 or exactly 2^64, so
-// (hi:lo + t q) / 2^64 = hi + mulhi(t, q) + [lo != 0] < 2q: one subtraction, where a carry out of 64 bits means >= q.
-__host__ __device__ inline uint64_t mq_redc(uint64_t hi, uint64_t lo, const MontQ& M) {
-    const uint64_t t = lo * M.qinv;
-    const uint64_t th = mq_mulhi(t, M.q);
-    uint64_t s = hi + th;
-    bool carry = s < hi;
-    const uint64_t c = lo != 0 ? 1u : 0u;
-    s += c;
-    carry |= s < c;
-    if (carry || s >= M.q) s -= M.q;
-    return s;
-}
-// a b 2^-64 mod q, canonical: needs a < q or b < q (then a b < q 2^64)
-__host__ __device__ inline uint64_t mq_mul(uint64_t a, uint64_t b, const MontQ& M) { return mq_redc(mq_mulhi(a, b), a * b, M); }
-__host__ __device__ inline uint64_t mq_add(uint64_t a, uint64_t b, const MontQ& M) {   // a, b canonical
-    uint64_t s = a + b;
-    if (s < a || s >= M.q) s -= M.q;
-    return s;
-}
-__host__ __device__ inline uint64_t mq_sub(uint64_t a, uint64_t b, const MontQ& M) {   // a, b canonical
-    return a >= b ? a - b : a - b + M.q;
-}
-__host__ __device__ inline uint64_t mq_to(uint64_t x, const MontQ& M) { return mq_mul(x, M.r2, M); }   // x 2^64 (any 64-bit x)
-__host__ __device__ inline uint64_t mq_canon(uint64_t x, const MontQ& M) { return mq_redc(0, mq_mul(x, M.r2, M), M); }   // x mod q
 
 // ---- wide accumulator: sum of 128-bit products in 192 bits, one reduction per output -----------------------------------------
 // Every sum below has at most m <= 8192 products of canonical words, so it is < 2^13 q^2 < 2^141: t2 < 2^13, nothing overflows.
