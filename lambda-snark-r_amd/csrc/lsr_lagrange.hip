@@ -11,6 +11,7 @@
 #include "lambda_snark/prover.h"
 #include "lsr_lagrange.hpp"
 #include "lsr_lagrange_kernels.hpp"
+#include "lsr_prove_common.hpp"
 #include "lsr_runtime.hpp"
 
 namespace lsr {
@@ -59,17 +60,14 @@ struct LagrangeProver {
     hipStream_t stream = nullptr;
     hipEvent_t ev_last = nullptr;          // end of the last asynchronous call: the next call (any stream) starts behind it
     int chunk_log2 = 26;                   // LAMBDA_SNARK_QUOTIENT_CHUNK_LOG2, read once at creation
-    // workspace for `chunk` instances
-    size_t chunk = 0, publics = 0, row_words = 0;
+    // workspace for ws.chunk instances
+    R1csScratch ws;                        // per-instance scratch and host staging
     DeviceBuffer<uint64_t> witness;        // [chunk][n_vars]
     DeviceBuffer<uint64_t> evals, coef;    // [3][chunk][m]
     DeviceBuffer<uint64_t> top;            // [chunk][max(1, m - 1)]
     DeviceBuffer<uint64_t> quot;           // [chunk][m]
     DeviceBuffer<uint64_t> qp, msg;        // [chunk][m + 1]
-    DeviceBuffer<uint64_t> small;          // keys[4] alphas betas hash_a[4] hash_b[4] ev[8] blinding publics[n_public] per instance
     DeviceBuffer<uint32_t> flags;          // bad[chunk] len[chunk]
-    DeviceBuffer<uint64_t> io;             // host staging: rows [chunk][W] proofs [chunk][13] hashes [chunk][8]
-    DeviceBuffer<uint32_t> io_status;
 };
 
 // ---- plan tables, O(m^2) on the host ----------------------------------------------------------------------------------------
@@ -149,7 +147,7 @@ void lagrange_destroy(LagrangeProver* p) {
         for (int k = 0; k < 3; ++k) { p->row_ptr[k].release(); p->col[k].release(); p->val[k].release(); }
         p->lt.release(); p->tser.release(); p->zh_s.release(); p->zh_m.release();
         p->witness.release(); p->evals.release(); p->coef.release(); p->top.release(); p->quot.release(); p->qp.release(); p->msg.release();
-        p->small.release(); p->flags.release(); p->io.release(); p->io_status.release();
+        p->flags.release(); p->ws.release();
     } catch (...) {
     }
     delete p;
@@ -244,30 +242,17 @@ static size_t chunk_for(const LagrangeProver& p, size_t batch) {
     return std::min(batch, std::max<size_t>(1, (size_t(1) << p.chunk_log2) / p.m));
 }
 
-static void ensure_workspace(LagrangeProver& p, size_t chunk, size_t n_public, size_t row_words, bool host_io) {
-    const size_t m = p.m;
-    if (chunk > p.chunk || n_public > p.publics) {
-        p.chunk = std::max(p.chunk, chunk);
-        p.publics = std::max(p.publics, n_public);
-        const size_t c = p.chunk;
-        p.witness.allocate(c * p.n_vars);
-        p.evals.allocate(3 * c * m);
-        p.coef.allocate(3 * c * m);
-        p.top.allocate(c * std::max<size_t>(1, m - 1));
-        p.quot.allocate(c * m);
-        p.qp.allocate(c * (m + 1));
-        p.msg.allocate(c * (m + 1));
-        p.small.allocate(c * (23 + std::max<size_t>(1, p.publics)));
-        p.flags.allocate(2 * c);
-        p.io.release();
-        p.io_status.release();
-        p.row_words = 0;
-    }
-    if (host_io && (!p.io.ptr || p.row_words < row_words)) {
-        p.row_words = std::max<size_t>({p.row_words, row_words, 1});
-        p.io.allocate(p.chunk * (p.row_words + 13 + 8));
-        p.io_status.allocate(p.chunk);
-    }
+static void ensure_workspace(LagrangeProver& p, size_t chunk, size_t n_public) {
+    if (!p.ws.grow(chunk, n_public)) return;
+    const size_t m = p.m, c = p.ws.chunk;
+    p.witness.allocate(c * p.n_vars);
+    p.evals.allocate(3 * c * m);
+    p.coef.allocate(3 * c * m);
+    p.top.allocate(c * std::max<size_t>(1, m - 1));
+    p.quot.allocate(c * m);
+    p.qp.allocate(c * (m + 1));
+    p.msg.allocate(c * (m + 1));
+    p.flags.allocate(2 * c);
 }
 
 // constraint evaluations of `count` witnesses (device, [count][n_vars]) into p.evals; interpolation into p.coef (interp); the
@@ -310,9 +295,9 @@ void lagrange_host_run(LagrangeProver& p, const uint64_t* w, size_t batch, uint6
     std::lock_guard<std::mutex> lock(p.mutex);
     if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
     const size_t chunk = chunk_for(p, batch);
-    ensure_workspace(p, chunk, 0, 0, false);
+    ensure_workspace(p, chunk, 0);
     hipStream_t s = p.stream;
-    uint32_t* d_len = p.flags.ptr + p.chunk;
+    uint32_t* d_len = p.flags.ptr + p.ws.chunk;
     for (size_t done = 0; done < batch; done += chunk) {
         const size_t now = std::min(chunk, batch - done);
         const size_t per_vector = now * p.m, off = done * p.m;
@@ -330,47 +315,22 @@ void lagrange_host_run(LagrangeProver& p, const uint64_t* w, size_t batch, uint6
     }
 }
 
-static void check_call(int rc, const char* what) {
-    if (rc != 0) throw std::runtime_error(std::string(what) + ": " + lsr_last_error());
-}
-
 // one chunk of prove_r1cs / prove_r1cs_zk: evaluations -> interpolation -> quotient -> message -> keys -> rows -> alpha -> beta ->
 // evaluations at alpha and beta -> proof records
-static void prove_chunk(LagrangeProver& p, LweContext* lwe, uint64_t commit_modulus, size_t n_public, const uint64_t* d_z, const uint64_t* d_blind,
-                        const uint64_t* seeds, size_t count, uint64_t* d_rows, uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status, bool host_keys,
-                        hipStream_t s) {
+static void prove_chunk(LagrangeProver& p, const R1csProveCall& a, const uint64_t* d_z, const uint64_t* d_blind, const uint64_t* seeds, size_t count,
+                        uint64_t* d_rows, uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status, bool host_keys, hipStream_t s) {
     const uint32_t m = p.m;
     const size_t per_vector = count * m;
-    const size_t words = lsr_lwe_commitment_words(lwe);
-    uint64_t* sm = p.small.ptr;
-    const size_t C = p.chunk;
-    uint64_t *keys = sm, *alphas = sm + 4 * C, *betas = sm + 5 * C, *hash_a = sm + 6 * C, *hash_b = sm + 10 * C, *ev = sm + 14 * C,
-             *publics = sm + 23 * C;
-    uint32_t* d_len = p.flags.ptr + C;
+    const size_t words = lsr_lwe_commitment_words(a.lwe);
+    const R1csSlots v = p.ws.slots();
+    uint32_t* d_len = p.flags.ptr + p.ws.chunk;
     run_chunk(p, d_z, count, true, true, d_len, s);
     const uint32_t msg_len = m + (d_blind ? 1u : 0u);
     hipLaunchKernelGGL(lag_message_kernel, dim3(blocks(count * (m + 1))), dim3(kLagBlock), 0, s, p.quot.ptr, d_blind, p.zh_m.ptr, p.qp.ptr, p.msg.ptr,
-                       msg_len, commit_modulus, m, count * (size_t)(m + 1), p.M);
+                       msg_len, a.commit_modulus, m, count * (size_t)(m + 1), p.M);
     LSR_HIP(hipGetLastError());
-    if (host_keys) {
-        std::vector<uint64_t> msgs(count * msg_len), hk(4 * count);
-        LSR_HIP(hipMemcpyAsync(msgs.data(), p.msg.ptr, msgs.size() * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-        check_call(lsr_lwe_commit_keys(lwe, msgs.data(), msg_len, count, seeds, hk.data()), "lsr_lwe_commit_keys");
-        LSR_HIP(hipMemcpyAsync(keys, hk.data(), hk.size() * 8, hipMemcpyHostToDevice, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    } else {
-        check_call(lsr_lwe_commit_keys_device(lwe, p.msg.ptr, msg_len, count, seeds, keys, s), "lsr_lwe_commit_keys_device");
-    }
-    check_call(lsr_lwe_commit_rows_device(lwe, p.msg.ptr, msg_len, count, keys, d_rows, s), "lsr_lwe_commit_rows_device");
-    if (n_public)
-        hipLaunchKernelGGL(lag_gather_publics_kernel, dim3(blocks(count * n_public)), dim3(kLagBlock), 0, s, d_z, p.n_vars, (uint32_t)n_public, publics,
-                           count * n_public);
-    LSR_HIP(hipGetLastError());
-    check_call(lsr_fs_challenge_batch_device(n_public ? publics : nullptr, n_public, d_rows, words, count, p.q, alphas,
-                                             reinterpret_cast<uint8_t*>(hash_a), s), "lsr_fs_challenge_batch_device");
-    check_call(lsr_fs_challenge_batch_device(alphas, 1, d_rows, words, count, p.q, betas, reinterpret_cast<uint8_t*>(hash_b), s),
-               "lsr_fs_challenge_batch_device");
+    commit_messages(a.lwe, p.msg.ptr, msg_len, count, seeds, v.keys, d_rows, host_keys, s);
+    r1cs_transcript(lag_gather_publics_kernel, v, d_z, p.n_vars, a.n_public, d_rows, words, count, p.q, s);
     LagEvalPolys polys;
     for (int k = 0; k < 3; ++k) {
         polys.poly[k] = p.coef.ptr + k * per_vector;
@@ -380,86 +340,34 @@ static void prove_chunk(LagrangeProver& p, LweContext* lwe, uint64_t commit_modu
     polys.poly[3] = p.qp.ptr;
     polys.stride[3] = m + 1;
     polys.len[3] = m + 1;
-    hipLaunchKernelGGL(lag_eval_kernel, dim3((unsigned)count, 4), dim3(64), 0, s, polys, alphas, betas, ev, p.M);
-    hipLaunchKernelGGL(lag_assemble_kernel, dim3(blocks(count, ~0u)), dim3(kLagBlock), 0, s, ev, alphas, betas, d_blind, d_len, hash_a, hash_b, d_proofs,
-                       reinterpret_cast<uint64_t*>(d_hashes), d_status, count, p.q);
+    hipLaunchKernelGGL(lag_eval_kernel, dim3((unsigned)count, 4), dim3(64), 0, s, polys, v.alphas, v.betas, v.ev, p.M);
+    hipLaunchKernelGGL(lag_assemble_kernel, dim3(blocks(count, ~0u)), dim3(kLagBlock), 0, s, v.ev, v.alphas, v.betas, d_blind, d_len, v.hash_a, v.hash_b,
+                       d_proofs, reinterpret_cast<uint64_t*>(d_hashes), d_status, count, p.q);
     LSR_HIP(hipGetLastError());
 }
 
-void lagrange_prove_host(LagrangeProver& p, LweContext* lwe, uint64_t commit_modulus, const uint64_t* w, size_t batch, size_t n_public,
-                         const uint64_t* seeds, const uint64_t* blind, uint64_t* rows, uint64_t* proofs, uint8_t* hashes, uint32_t* status) {
-    DeviceGuard guard(p.device);
-    std::lock_guard<std::mutex> lock(p.mutex);   // prover first, then (inside each commitment call) the LWE context
-    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
-    const size_t words = lsr_lwe_commitment_words(lwe);
-    const size_t chunk = chunk_for(p, batch);
-    ensure_workspace(p, chunk, n_public, words, true);
-    hipStream_t s = p.stream;
-    uint64_t* d_blind = p.small.ptr + 22 * p.chunk;
-    uint64_t* d_rows = p.io.ptr;
-    uint64_t* d_proofs = d_rows + p.chunk * p.row_words;
-    uint64_t* d_hashes = d_proofs + p.chunk * 13;
-    for (size_t done = 0; done < batch; done += chunk) {
-        const size_t now = std::min(chunk, batch - done);
-        bool zero_seed = false;
-        for (size_t j = 0; j < now; ++j) zero_seed |= seeds[done + j] == 0;
-        LSR_HIP(hipMemcpyAsync(p.witness.ptr, w + done * p.n_vars, now * p.n_vars * 8, hipMemcpyHostToDevice, s));
-        if (blind) LSR_HIP(hipMemcpyAsync(d_blind, blind + done, now * 8, hipMemcpyHostToDevice, s));
-        prove_chunk(p, lwe, commit_modulus, n_public, p.witness.ptr, blind ? d_blind : nullptr, seeds + done, now, d_rows, d_proofs,
-                    hashes ? reinterpret_cast<uint8_t*>(d_hashes) : nullptr, p.io_status.ptr, zero_seed, s);
-        LSR_HIP(hipMemcpyAsync(rows + done * words, d_rows, now * words * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipMemcpyAsync(proofs + done * 13, d_proofs, now * 13 * 8, hipMemcpyDeviceToHost, s));
-        if (hashes) LSR_HIP(hipMemcpyAsync(hashes + done * 64, d_hashes, now * 64, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipMemcpyAsync(status + done, p.io_status.ptr, now * 4, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
-}
-
-void lagrange_prove_device(LagrangeProver& p, LweContext* lwe, uint64_t commit_modulus, const uint64_t* d_w, size_t batch, size_t n_public,
-                           const uint64_t* seeds, const uint64_t* d_blind, uint64_t* d_rows, uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status,
-                           void* stream) {
-    DeviceGuard guard(p.device);
-    std::lock_guard<std::mutex> lock(p.mutex);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
-    const size_t words = lsr_lwe_commitment_words(lwe);
-    const size_t chunk = chunk_for(p, batch);
-    ensure_workspace(p, chunk, n_public, words, false);
-    for (size_t done = 0; done < batch; done += chunk) {
-        const size_t now = std::min(chunk, batch - done);
-        prove_chunk(p, lwe, commit_modulus, n_public, d_w + done * p.n_vars, d_blind ? d_blind + done : nullptr, seeds + done, now, d_rows + done * words,
-                    d_proofs + done * 13, d_hashes ? d_hashes + done * 64 : nullptr, d_status + done, false, s);
-    }
-    if (!p.ev_last) LSR_HIP(hipEventCreateWithFlags(&p.ev_last, hipEventDisableTiming));
-    LSR_HIP(hipEventRecord(p.ev_last, s));
+void lagrange_prove(LagrangeProver& p, const R1csProveCall& c, bool on_device, hipStream_t s) {
+    const R1csProverRef ref{p.device, p.mutex, p.ev_last, p.stream, p.witness, p.n_vars, p.ws};
+    const auto grow = [&](size_t chunk) { ensure_workspace(p, chunk, c.n_public); };
+    const auto chunk = [&](auto... args) { prove_chunk(p, c, args...); };
+    if (on_device) r1cs_prove_device(ref, c, chunk_for(p, c.batch), grow, chunk, s);
+    else r1cs_prove_host(ref, c, chunk_for(p, c.batch), grow, chunk);
 }
 
 // ---- verify on the baseline path ---------------------------------------------------------------------------------------------
 void verify_mod_host(uint32_t m, uint64_t q, const uint64_t* pub, size_t n_public, const uint64_t* rows, size_t words, const uint64_t* proofs,
                      size_t batch, bool zk, int* results) {
-    std::vector<uint64_t> alphas(batch), betas(batch);
-    check_call(lsr_fs_challenge_batch_flat(pub, n_public, rows, words, batch, q, alphas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
-    check_call(lsr_fs_challenge_batch_flat(alphas.data(), 1, rows, words, batch, q, betas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
     const MontQ M = make_mont(q);
-    for (size_t i = 0; i < batch; ++i) results[i] = verify_one_generic(proofs + i * 13, alphas[i], betas[i], m, zk, M);
+    r1cs_verify_host(q, pub, n_public, rows, words, proofs, batch, results,
+                     [&](const uint64_t* proof, uint64_t alpha, uint64_t beta) { return verify_one_generic(proof, alpha, beta, m, zk, M); });
 }
 
 void verify_mod_device(uint32_t m, uint64_t q, const uint64_t* d_pub, size_t n_public, const uint64_t* d_rows, size_t words, const uint64_t* d_proofs,
-                       size_t batch, bool zk, int* d_results, void* stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint64_t* d_ab = nullptr;
-    LSR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ab), 2 * batch * 8, s));
-    try {
-        check_call(lsr_fs_challenge_batch_device(d_pub, n_public, d_rows, words, batch, q, d_ab, nullptr, s), "lsr_fs_challenge_batch_device");
-        check_call(lsr_fs_challenge_batch_device(d_ab, 1, d_rows, words, batch, q, d_ab + batch, nullptr, s), "lsr_fs_challenge_batch_device");
-        hipLaunchKernelGGL(lag_verify_kernel, dim3(blocks(batch, ~0u)), dim3(kLagBlock), 0, s, d_proofs, d_ab, d_ab + batch, m, zk ? 1 : 0, d_results, batch,
+                       size_t batch, bool zk, int* d_results, hipStream_t s) {
+    r1cs_verify_device(q, d_pub, n_public, d_rows, words, batch, s, [&](const uint64_t* d_alphas, const uint64_t* d_betas) {
+        hipLaunchKernelGGL(lag_verify_kernel, dim3(blocks(batch, ~0u)), dim3(kLagBlock), 0, s, d_proofs, d_alphas, d_betas, m, zk ? 1 : 0, d_results, batch,
                            make_mont(q));
-        LSR_HIP(hipGetLastError());
-    } catch (...) {
-        (void)hipFreeAsync(d_ab, s);
-        throw;
-    }
-    LSR_HIP(hipFreeAsync(d_ab, s));
+    });
 }
 
 }  // namespace lsr

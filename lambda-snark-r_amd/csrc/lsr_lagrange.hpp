@@ -7,6 +7,7 @@
 
 #include "lambda_snark/r1cs.h"
 #include "lambda_snark/types.h"
+#include "lsr_prove_common.hpp"
 
 namespace lsr {
 
@@ -24,16 +25,13 @@ bool lagrange_omega_domain(const LagrangeProver* p);
 // host arrays.  evals != nullptr: A z, B z, C z; coeffs != nullptr: the interpolated A, B, C; else quotient / len.  Throws.
 void lagrange_host_run(LagrangeProver& p, const uint64_t* w, size_t batch, uint64_t* const evals[3], uint64_t* const coeffs[3], uint64_t* quotient,
                        uint32_t* len);
-void lagrange_prove_host(LagrangeProver& p, LweContext* lwe, uint64_t commit_modulus, const uint64_t* w, size_t batch, size_t n_public,
-                         const uint64_t* seeds, const uint64_t* blinding, uint64_t* rows, uint64_t* proofs, uint8_t* hashes, uint32_t* status);
-void lagrange_prove_device(LagrangeProver& p, LweContext* lwe, uint64_t commit_modulus, const uint64_t* d_w, size_t batch, size_t n_public,
-                           const uint64_t* seeds, const uint64_t* d_blinding, uint64_t* d_rows, uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status,
-                           void* stream);
+// prove_r1cs[_zk] for a batch: device arrays on `s` (on_device) or host arrays through the prover's own stream.  Throws.
+void lagrange_prove(LagrangeProver& p, const R1csProveCall& c, bool on_device, hipStream_t s);
 
 // verify_r1cs[_zk] on the baseline path (eval_vanishing = prod (x - i)) for modulus q
 void verify_mod_host(uint32_t m, uint64_t q, const uint64_t* pub, size_t n_public, const uint64_t* rows, size_t words, const uint64_t* proofs,
                      size_t batch, bool zk, int* results);
 void verify_mod_device(uint32_t m, uint64_t q, const uint64_t* d_pub, size_t n_public, const uint64_t* d_rows, size_t words, const uint64_t* d_proofs,
-                       size_t batch, bool zk, int* d_results, void* stream);
+                       size_t batch, bool zk, int* d_results, hipStream_t s);
 
 }  // namespace lsr

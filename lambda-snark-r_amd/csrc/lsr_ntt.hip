@@ -557,22 +557,8 @@ static void host_pointwise(const NttContext& c, uint64_t* result, const uint64_t
 // ------------------------------------------------------------------------------------------------
 // C-ABI
 // ------------------------------------------------------------------------------------------------
+using lsr::abi_guarded;
 using lsr::set_last_error;
-
-template <class F>
-static int guarded(const char* where, F&& body) noexcept {
-    try {
-        body();
-        return 0;
-    } catch (const std::exception& e) {
-        set_last_error(std::string(where) + ": " + e.what());
-        std::fprintf(stderr, "lambda_snark_core: %s failed: %s\n", where, e.what());
-        return -1;
-    } catch (...) {
-        set_last_error(std::string(where) + ": unknown exception");
-        return -1;
-    }
-}
 
 extern "C" {
 
@@ -602,42 +588,42 @@ int lsr_ntt_context_uses_f64(const NttContext* ctx) noexcept { return ctx && ctx
 
 int ntt_forward(const NttContext* ctx, uint64_t* coeffs, uint32_t n) noexcept {
     if (!ctx || !coeffs || n != ctx->degree) return -1;   // ntt.cpp:81
-    return guarded("ntt_forward", [&] { lsr::host_ntt(*ctx, coeffs, 1, false); });
+    return abi_guarded("ntt_forward", [&] { lsr::host_ntt(*ctx, coeffs, 1, false); });
 }
 int ntt_inverse(const NttContext* ctx, uint64_t* evals, uint32_t n) noexcept {
     if (!ctx || !evals || n != ctx->degree) return -1;    // ntt.cpp:96
-    return guarded("ntt_inverse", [&] { lsr::host_ntt(*ctx, evals, 1, true); });
+    return abi_guarded("ntt_inverse", [&] { lsr::host_ntt(*ctx, evals, 1, true); });
 }
 void ntt_mul_pointwise(const NttContext* ctx, uint64_t* result, const uint64_t* a, const uint64_t* b, uint32_t n) noexcept {
     if (!ctx || !result || !a || !b) return;              // ntt.cpp:113
-    (void)guarded("ntt_mul_pointwise", [&] { lsr::host_pointwise(*ctx, result, a, b, n); });
+    (void)abi_guarded("ntt_mul_pointwise", [&] { lsr::host_pointwise(*ctx, result, a, b, n); });
 }
 
 int ntt_forward_batch(const NttContext* ctx, uint64_t* polys, size_t batch) noexcept {
     if (!ctx || !polys) return -1;
     if (batch == 0) return 0;
-    return guarded("ntt_forward_batch", [&] { lsr::host_ntt(*ctx, polys, batch, false); });
+    return abi_guarded("ntt_forward_batch", [&] { lsr::host_ntt(*ctx, polys, batch, false); });
 }
 int ntt_inverse_batch(const NttContext* ctx, uint64_t* polys, size_t batch) noexcept {
     if (!ctx || !polys) return -1;
     if (batch == 0) return 0;
-    return guarded("ntt_inverse_batch", [&] { lsr::host_ntt(*ctx, polys, batch, true); });
+    return abi_guarded("ntt_inverse_batch", [&] { lsr::host_ntt(*ctx, polys, batch, true); });
 }
 int ntt_mul_pointwise_batch(const NttContext* ctx, uint64_t* result, const uint64_t* a, const uint64_t* b, size_t batch) noexcept {
     if (!ctx || !result || !a || !b) return -1;
-    return guarded("ntt_mul_pointwise_batch", [&] { lsr::host_pointwise(*ctx, result, a, b, batch * ctx->degree); });
+    return abi_guarded("ntt_mul_pointwise_batch", [&] { lsr::host_pointwise(*ctx, result, a, b, batch * ctx->degree); });
 }
 
 int lsr_ntt_forward_batch_device(const NttContext* ctx, uint64_t* d_polys, size_t batch, void* stream) noexcept {
     if (!ctx || !d_polys) return -1;
-    return guarded("lsr_ntt_forward_batch_device", [&] {
+    return abi_guarded("lsr_ntt_forward_batch_device", [&] {
         lsr::DeviceGuard guard(ctx->device);
         lsr::launch_ntt(*ctx, d_polys, batch, false, static_cast<hipStream_t>(stream));
     });
 }
 int lsr_ntt_inverse_batch_device(const NttContext* ctx, uint64_t* d_polys, size_t batch, void* stream) noexcept {
     if (!ctx || !d_polys) return -1;
-    return guarded("lsr_ntt_inverse_batch_device", [&] {
+    return abi_guarded("lsr_ntt_inverse_batch_device", [&] {
         lsr::DeviceGuard guard(ctx->device);
         lsr::launch_ntt(*ctx, d_polys, batch, true, static_cast<hipStream_t>(stream));
     });
@@ -645,7 +631,7 @@ int lsr_ntt_inverse_batch_device(const NttContext* ctx, uint64_t* d_polys, size_
 int lsr_ntt_mul_pointwise_device(const NttContext* ctx, uint64_t* d_result, const uint64_t* d_a, const uint64_t* d_b, size_t count,
                                  void* stream) noexcept {
     if (!ctx || !d_result || !d_a || !d_b) return -1;
-    return guarded("lsr_ntt_mul_pointwise_device", [&] {
+    return abi_guarded("lsr_ntt_mul_pointwise_device", [&] {
         lsr::DeviceGuard guard(ctx->device);
         lsr::launch_pointwise(*ctx, d_result, d_a, d_b, count, static_cast<hipStream_t>(stream));
     });

@@ -1,0 +1,226 @@
+// Host pipeline shared by the prover paths: the NTT path (lsr_prover.hip), the Lagrange path (lsr_lagrange.hip) and the simple
+// proofs (lsr_simple.hip).  The kernels stay with their paths; this holds the steps around them — the commitment step, the R1CS
+// transcript, scratch layout, chunk drivers and verifier — and the refusals of the batched device entry points.
+#pragma once
+
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "lambda_snark/batch.h"
+#include "lsr_runtime.hpp"
+
+namespace lsr {
+
+// an ABI return code of a commitment or transcript entry point, as an exception
+inline void check_call(int rc, const char* what) {
+    if (rc != 0) throw std::runtime_error(std::string(what) + ": " + lsr_last_error());
+}
+
+// keys and rows of `count` commitments to the device messages d_msg [count][msg_len], all on `s`.  host_keys: derive the keys on
+// the host (seed 0 = fresh entropy) from the messages copied back; else on the device.
+inline void commit_messages(LweContext* lwe, const uint64_t* d_msg, size_t msg_len, size_t count, const uint64_t* seeds, uint64_t* d_keys,
+                            uint64_t* d_rows, bool host_keys, hipStream_t s) {
+    if (host_keys) {
+        std::vector<uint64_t> msgs(count * msg_len), keys(4 * count);
+        LSR_HIP(hipMemcpyAsync(msgs.data(), d_msg, msgs.size() * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+        check_call(lsr_lwe_commit_keys(lwe, msgs.data(), msg_len, count, seeds, keys.data()), "lsr_lwe_commit_keys");
+        LSR_HIP(hipMemcpyAsync(d_keys, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, s));
+        LSR_HIP(hipStreamSynchronize(s));   // `keys` leaves scope
+    } else {
+        check_call(lsr_lwe_commit_keys_device(lwe, d_msg, msg_len, count, seeds, d_keys, s), "lsr_lwe_commit_keys_device");
+    }
+    check_call(lsr_lwe_commit_rows_device(lwe, d_msg, msg_len, count, d_keys, d_rows, s), "lsr_lwe_commit_rows_device");
+}
+
+// The entry of a batched prove call on the device: refuses a seed 0 (fresh OS entropy, which only the host call `host_call` serves)
+// and a batch beyond 2^31 - 1, then runs body(stream) on `device` unless the stream is being captured into a HIP graph.
+template <class F>
+int abi_prove_device(const char* where, const char* host_call, const uint64_t* seeds, size_t batch, int device, void* stream, F&& body) noexcept {
+    for (size_t i = 0; i < batch; ++i)
+        if (seeds[i] == 0)
+            return abi_refuse(where, std::string("seed 0 asks for fresh OS entropy, which only the host call serves (") + host_call + ")");
+    if (batch > 0x7fffffffull) return abi_refuse(where, "batch exceeds 2^31 - 1 proofs");
+    return abi_guarded(where, [&] {
+        DeviceGuard guard(device);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (stream_is_capturing(s)) throw std::runtime_error("not capturable into a HIP graph (host seeds, host-ordered workspace)");
+        body(s);
+    });
+}
+
+// ---- prove_r1cs / prove_r1cs_zk (lib.rs:747-809, 877-980), both R1CS paths ---------------------------------------------------------
+
+struct R1csSlots {             // one chunk's views into the per-instance scratch
+    uint64_t *keys, *alphas, *betas, *hash_a, *hash_b, *ev, *blinding, *publics;
+};
+
+// The per-instance scratch of an R1CS prover and its host staging, sized for `chunk` instances.  A path grows its own chunk-sized
+// buffers to `chunk` whenever grow() says the scratch grew.
+struct R1csScratch {
+    size_t chunk = 0, publics = 0, row_words = 0;
+    DeviceBuffer<uint64_t> small;      // keys[4] alphas betas hash_a[4] hash_b[4] ev[8] blinding publics[n_public] per instance
+    DeviceBuffer<uint64_t> io;         // host staging: rows [chunk][row_words] then proofs [chunk][13] then hashes [chunk][8]
+    DeviceBuffer<uint32_t> io_status;  // [chunk]
+
+    R1csSlots slots() const {
+        uint64_t* b = small.ptr;
+        R1csSlots v;
+        v.keys = b;                 b += 4 * chunk;
+        v.alphas = b;               b += chunk;
+        v.betas = b;                b += chunk;
+        v.hash_a = b;               b += 4 * chunk;
+        v.hash_b = b;               b += 4 * chunk;
+        v.ev = b;                   b += 8 * chunk;
+        v.blinding = b;             b += chunk;
+        v.publics = b;
+        return v;
+    }
+    // true when the scratch grew (to at least `want` instances and `n_public` publics); the staging is then dropped
+    bool grow(size_t want, size_t n_public) {
+        if (want <= chunk && n_public <= publics) return false;
+        chunk = std::max(chunk, want);
+        publics = std::max(publics, n_public);
+        small.allocate(chunk * (23 + std::max<size_t>(1, publics)));
+        io.release();
+        io_status.release();
+        row_words = 0;
+        return true;
+    }
+    // the host staging, for rows of `words` words
+    void stage(size_t words) {
+        if (io.ptr && row_words >= words) return;
+        row_words = std::max<size_t>({row_words, words, 1});
+        io.allocate(chunk * (row_words + 13 + 8));
+        io_status.allocate(chunk);
+    }
+    void release() {
+        small.release();
+        io.release();
+        io_status.release();
+    }
+};
+
+// alpha = Challenge::derive(public_inputs, row), beta = Challenge::derive([alpha], row) (lib.rs:761-768) of `count` instances, with the
+// hash outputs, all on `s`.  `gather` is the path's kernel that copies the n_public leading words of each witness d_z [count][n_vars].
+using GatherPublicsKernel = void (*)(const uint64_t*, uint32_t, uint32_t, uint64_t*, size_t);
+inline void r1cs_transcript(GatherPublicsKernel gather, const R1csSlots& v, const uint64_t* d_z, uint32_t n_vars, size_t n_public, const uint64_t* d_rows,
+                            size_t words, size_t count, uint64_t q, hipStream_t s) {
+    if (n_public) {
+        const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((count * n_public + 255) / 256, 256 * 32));
+        hipLaunchKernelGGL(gather, dim3(grid), dim3(256), 0, s, d_z, n_vars, (uint32_t)n_public, v.publics, count * n_public);
+    }
+    LSR_HIP(hipGetLastError());
+    check_call(lsr_fs_challenge_batch_device(n_public ? v.publics : nullptr, n_public, d_rows, words, count, q, v.alphas,
+                                             reinterpret_cast<uint8_t*>(v.hash_a), s), "lsr_fs_challenge_batch_device");
+    check_call(lsr_fs_challenge_batch_device(v.alphas, 1, d_rows, words, count, q, v.betas, reinterpret_cast<uint8_t*>(v.hash_b), s),
+               "lsr_fs_challenge_batch_device");
+}
+
+// One batched call: host arrays (r1cs_prove_host) or device arrays (r1cs_prove_device); `seeds` is a host array either way.
+struct R1csProveCall {
+    LweContext* lwe;
+    uint64_t commit_modulus;
+    size_t n_public;
+    const uint64_t* seeds;     // [batch]
+    const uint64_t* w;         // witnesses [batch][n_vars]
+    const uint64_t* blind;     // [batch] (prove_r1cs_zk) or nullptr
+    uint64_t* rows;            // [batch][lsr_lwe_commitment_words(lwe)]
+    uint64_t* proofs;          // [batch][13]
+    uint8_t* hashes;           // [batch][64] or nullptr
+    uint32_t* status;          // [batch]
+    size_t batch;
+};
+
+// What a path lends the drivers.  Its mutex is taken first, then (inside each commitment call) the LWE context's; ev_last marks the
+// end of its last asynchronous call.
+struct R1csProverRef {
+    int device;
+    std::mutex& mutex;
+    hipEvent_t& ev_last;
+    hipStream_t stream;                  // the path's own stream: host calls
+    DeviceBuffer<uint64_t>& witness;     // [chunk][n_vars]: host calls
+    uint32_t n_vars;
+    R1csScratch& ws;
+};
+
+// The drivers take the path's chunk size, grow(chunk) that sizes its workspace and the scratch, and
+// prove_chunk(d_z, d_blind, seeds, count, d_rows, d_proofs, d_hashes, d_status, host_keys, s) that proves `count` instances on `s`.
+template <class Grow, class ProveChunk>
+void r1cs_prove_host(const R1csProverRef& r, const R1csProveCall& c, size_t chunk, Grow&& grow, ProveChunk&& prove_chunk) {
+    DeviceGuard guard(r.device);
+    std::lock_guard<std::mutex> lock(r.mutex);
+    if (r.ev_last) LSR_HIP(hipEventSynchronize(r.ev_last));
+    const size_t words = lsr_lwe_commitment_words(c.lwe);
+    grow(chunk);
+    r.ws.stage(words);
+    hipStream_t s = r.stream;
+    uint64_t* d_blind = r.ws.slots().blinding;
+    uint64_t* d_rows = r.ws.io.ptr;
+    uint64_t* d_proofs = d_rows + r.ws.chunk * r.ws.row_words;
+    uint64_t* d_hashes = d_proofs + r.ws.chunk * 13;
+    for (size_t done = 0; done < c.batch; done += chunk) {
+        const size_t now = std::min(chunk, c.batch - done);
+        bool zero_seed = false;
+        for (size_t j = 0; j < now; ++j) zero_seed |= c.seeds[done + j] == 0;
+        LSR_HIP(hipMemcpyAsync(r.witness.ptr, c.w + done * r.n_vars, now * r.n_vars * 8, hipMemcpyHostToDevice, s));
+        if (c.blind) LSR_HIP(hipMemcpyAsync(d_blind, c.blind + done, now * 8, hipMemcpyHostToDevice, s));
+        prove_chunk(r.witness.ptr, c.blind ? d_blind : nullptr, c.seeds + done, now, d_rows, d_proofs, c.hashes ? reinterpret_cast<uint8_t*>(d_hashes) : nullptr,
+                    r.ws.io_status.ptr, zero_seed, s);
+        LSR_HIP(hipMemcpyAsync(c.rows + done * words, d_rows, now * words * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(c.proofs + done * 13, d_proofs, now * 13 * 8, hipMemcpyDeviceToHost, s));
+        if (c.hashes) LSR_HIP(hipMemcpyAsync(c.hashes + done * 64, d_hashes, now * 64, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(c.status + done, r.ws.io_status.ptr, now * 4, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+template <class Grow, class ProveChunk>
+void r1cs_prove_device(const R1csProverRef& r, const R1csProveCall& c, size_t chunk, Grow&& grow, ProveChunk&& prove_chunk, hipStream_t s) {
+    DeviceGuard guard(r.device);
+    std::lock_guard<std::mutex> lock(r.mutex);
+    if (r.ev_last) LSR_HIP(hipEventSynchronize(r.ev_last));
+    const size_t words = lsr_lwe_commitment_words(c.lwe);
+    grow(chunk);
+    for (size_t done = 0; done < c.batch; done += chunk) {
+        const size_t now = std::min(chunk, c.batch - done);
+        prove_chunk(c.w + done * r.n_vars, c.blind ? c.blind + done : nullptr, c.seeds + done, now, c.rows + done * words, c.proofs + done * 13,
+                    c.hashes ? c.hashes + done * 64 : nullptr, c.status + done, false, s);
+    }
+    if (!r.ev_last) LSR_HIP(hipEventCreateWithFlags(&r.ev_last, hipEventDisableTiming));
+    LSR_HIP(hipEventRecord(r.ev_last, s));
+}
+
+// ---- verify_r1cs / verify_r1cs_zk, both R1CS paths: the two transcripts, then the path's per-proof check -----------------------------
+
+// on the host (transcripts on the host pool, lsr_fs_challenge_batch_flat): results[i] = check(proof i, alpha_i, beta_i)
+template <class Check>
+void r1cs_verify_host(uint64_t q, const uint64_t* pub, size_t n_public, const uint64_t* rows, size_t words, const uint64_t* proofs, size_t batch,
+                      int* results, Check&& check) {
+    std::vector<uint64_t> alphas(batch), betas(batch);
+    check_call(lsr_fs_challenge_batch_flat(pub, n_public, rows, words, batch, q, alphas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
+    check_call(lsr_fs_challenge_batch_flat(alphas.data(), 1, rows, words, batch, q, betas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
+    for (size_t i = 0; i < batch; ++i) results[i] = check(proofs + i * 13, alphas[i], betas[i]);
+}
+
+// on the device, all on `s`: alphas and betas in stream-ordered scratch, then launch_check(d_alphas, d_betas) enqueues the check kernel
+template <class LaunchCheck>
+void r1cs_verify_device(uint64_t q, const uint64_t* d_pub, size_t n_public, const uint64_t* d_rows, size_t words, size_t batch, hipStream_t s,
+                        LaunchCheck&& launch_check) {
+    if (stream_is_capturing(s)) throw std::runtime_error("not capturable into a HIP graph (stream-ordered scratch)");
+    uint64_t* d_ab = nullptr;
+    LSR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ab), 2 * batch * 8, s));
+    try {
+        check_call(lsr_fs_challenge_batch_device(d_pub, n_public, d_rows, words, batch, q, d_ab, nullptr, s), "lsr_fs_challenge_batch_device");
+        check_call(lsr_fs_challenge_batch_device(d_ab, 1, d_rows, words, batch, q, d_ab + batch, nullptr, s), "lsr_fs_challenge_batch_device");
+        launch_check(d_ab, d_ab + batch);
+        LSR_HIP(hipGetLastError());
+    } catch (...) {
+        (void)hipFreeAsync(d_ab, s);
+        throw;
+    }
+    LSR_HIP(hipFreeAsync(d_ab, s));
+}
+
+}  // namespace lsr

@@ -7,6 +7,7 @@
 #include "lambda_snark/prover.h"
 #include "lambda_snark/batch.h"
 #include "lsr_lagrange.hpp"
+#include "lsr_prove_common.hpp"
 #include "lsr_prove_kernels.hpp"
 #include "lsr_runtime.hpp"
 
@@ -416,11 +417,8 @@ struct LsrR1csProver {
     lsr::DeviceBuffer<uint64_t> stash;      // A's and B's interpolated planes [2][chunk][m]
     lsr::DeviceBuffer<uint64_t> quot;       // quotient [chunk][m]
     lsr::DeviceBuffer<uint64_t> msg;        // commitment messages [chunk][m + 1]
-    lsr::DeviceBuffer<uint64_t> small;      // keys[4] alphas betas hash_a[4] hash_b[4] ev[8] blinding publics[n_public] per instance
     lsr::DeviceBuffer<uint32_t> len;        // [chunk]
-    lsr::DeviceBuffer<uint64_t> io;         // host staging: rows [chunk][W] then proofs [chunk][13] then hashes [chunk][8]
-    lsr::DeviceBuffer<uint32_t> io_status;
-    size_t prove_chunk = 0, prove_publics = 0, prove_row_words = 0;
+    lsr::R1csScratch ws;                    // per-instance scratch and host staging; its chunk sizes the buffers above
 };
 
 namespace lsr {
@@ -433,7 +431,7 @@ static void destroy_prover(LsrR1csProver* r) {
             DeviceGuard guard(r->plan->device);
             for (int k = 0; k < 3; ++k) { r->row_ptr[k].release(); r->col[k].release(); r->val[k].release(); }
             r->witness.release();
-            r->stash.release(); r->quot.release(); r->msg.release(); r->small.release(); r->len.release(); r->io.release(); r->io_status.release();
+            r->stash.release(); r->quot.release(); r->msg.release(); r->len.release(); r->ws.release();
         } catch (...) {
         }
     }
@@ -530,69 +528,28 @@ static void prover_run(LsrR1csProver& r, const uint64_t* witnesses, size_t batch
 // ---- prove_r1cs / prove_r1cs_zk for a batch (lib.rs:747-809, 877-980) ----------------------------------
 // Per chunk, all on one stream: constraint evals (from device witnesses) -> quotient pass with A's and B's interpolants stashed ->
 // message Q' mod commit_modulus -> keys -> rows -> alpha -> beta -> evaluations -> proof records.
-struct ProveArgs {
-    LweContext* lwe;
-    uint64_t commit_modulus;
-    size_t n_public;
-    const uint64_t* seeds;      // host
-    bool zk;
-};
-struct ProveSlots {             // one chunk's views into the prover's prove workspace
-    uint64_t *keys, *alphas, *betas, *hash_a, *hash_b, *ev, *blinding, *publics;
-};
-
-static ProveSlots prove_slots(LsrR1csProver& r, size_t chunk) {
-    uint64_t* b = r.small.ptr;
-    ProveSlots v;
-    v.keys = b;                 b += 4 * chunk;
-    v.alphas = b;               b += chunk;
-    v.betas = b;                b += chunk;
-    v.hash_a = b;               b += 4 * chunk;
-    v.hash_b = b;               b += 4 * chunk;
-    v.ev = b;                   b += 8 * chunk;
-    v.blinding = b;             b += chunk;
-    v.publics = b;
-    return v;
-}
-
-static void ensure_prove_workspace(LsrR1csProver& r, size_t chunk, size_t n_public, size_t row_words, bool host_io) {
-    LsrQuotientPlan& p = *r.plan;
-    ensure_workspace(p, chunk, false);
+static void ensure_prove_workspace(LsrR1csProver& r, size_t chunk, size_t n_public) {
+    ensure_workspace(*r.plan, chunk, false);
     if (r.witness_chunk < chunk) {
         r.witness.allocate(chunk * r.n_vars);
         r.witness_chunk = chunk;
     }
-    if (r.prove_chunk < chunk || r.prove_publics < n_public) {
-        r.prove_chunk = std::max(r.prove_chunk, chunk);
-        r.prove_publics = std::max(r.prove_publics, n_public);
-        r.stash.allocate(2 * r.prove_chunk * r.m);
-        r.quot.allocate(r.prove_chunk * r.m);
-        r.msg.allocate(r.prove_chunk * (r.m + 1));
-        r.small.allocate(r.prove_chunk * (23 + std::max<size_t>(1, r.prove_publics)));
-        r.len.allocate(r.prove_chunk);
-        r.io.release();
-        r.io_status.release();
-        r.prove_row_words = 0;
-    }
-    if (host_io && (!r.io.ptr || r.prove_row_words < row_words)) {
-        r.prove_row_words = std::max(r.prove_row_words, row_words);
-        r.io.allocate(r.prove_chunk * (r.prove_row_words + 13 + 8));
-        r.io_status.allocate(r.prove_chunk);
-    }
+    if (!r.ws.grow(chunk, n_public)) return;
+    const size_t c = r.ws.chunk;
+    r.stash.allocate(2 * c * r.m);
+    r.quot.allocate(c * r.m);
+    r.msg.allocate(c * (r.m + 1));
+    r.len.allocate(c);
 }
 
-static void check_lwe_call(int rc, const char* what) {
-    if (rc != 0) throw std::runtime_error(std::string(what) + ": " + lsr_last_error());
-}
-
-// one chunk of `count` instances.  d_z [count][n_vars]; d_blind [count] or nullptr; outputs device arrays.  host_keys: derive the
+// one chunk of `count` instances.  d_z [count][n_vars]; d_blind [count] (zk) or nullptr; outputs device arrays.  host_keys: derive the
 // keys on the host (seed 0 = fresh entropy) from the messages copied back.
-static void prove_chunk(LsrR1csProver& r, const ProveArgs& a, const uint64_t* d_z, const uint64_t* d_blind, const uint64_t* seeds, size_t count,
+static void prove_chunk(LsrR1csProver& r, const R1csProveCall& a, const uint64_t* d_z, const uint64_t* d_blind, const uint64_t* seeds, size_t count,
                         uint64_t* d_rows, uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status, bool host_keys, hipStream_t s) {
     LsrQuotientPlan& p = *r.plan;
     const size_t per_vector = count << p.logm;
     const size_t words = lsr_lwe_commitment_words(a.lwe);
-    const ProveSlots v = prove_slots(r, r.prove_chunk);
+    const R1csSlots v = r.ws.slots();
     const CsrView ca{r.row_ptr[0].ptr, r.col[0].ptr, r.val[0].ptr}, cb{r.row_ptr[1].ptr, r.col[1].ptr, r.val[1].ptr},
         cc{r.row_ptr[2].ptr, r.col[2].ptr, r.val[2].ptr};
     uint64_t* work = p.work.ptr;
@@ -600,30 +557,12 @@ static void prove_chunk(LsrR1csProver& r, const ProveArgs& a, const uint64_t* d_
     LSR_HIP(hipGetLastError());
     quotient_pass(p, work, work + per_vector, work + 2 * per_vector, count, r.quot.ptr, r.len.ptr, s, r.stash.ptr);
     // commitment message: Q (plain) or Q' = Q + r (X^m - 1) (zk), mod commit_modulus
-    const uint32_t msg_len = r.m + (a.zk ? 1u : 0u);
-    hipLaunchKernelGGL(prove_message_kernel, dim3(blocks_for(count * msg_len)), dim3(kBlock), 0, s, r.quot.ptr, r.m, a.zk ? d_blind : nullptr,
-                       a.commit_modulus, r.msg.ptr, msg_len, count * (size_t)msg_len);
+    const uint32_t msg_len = r.m + (d_blind ? 1u : 0u);
+    hipLaunchKernelGGL(prove_message_kernel, dim3(blocks_for(count * msg_len)), dim3(kBlock), 0, s, r.quot.ptr, r.m, d_blind, a.commit_modulus, r.msg.ptr,
+                       msg_len, count * (size_t)msg_len);
     LSR_HIP(hipGetLastError());
-    if (host_keys) {
-        std::vector<uint64_t> msgs(count * msg_len), keys(4 * count);
-        LSR_HIP(hipMemcpyAsync(msgs.data(), r.msg.ptr, msgs.size() * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-        check_lwe_call(lsr_lwe_commit_keys(a.lwe, msgs.data(), msg_len, count, seeds, keys.data()), "lsr_lwe_commit_keys");
-        LSR_HIP(hipMemcpyAsync(v.keys, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, s));
-        LSR_HIP(hipStreamSynchronize(s));   // `keys` leaves scope
-    } else {
-        check_lwe_call(lsr_lwe_commit_keys_device(a.lwe, r.msg.ptr, msg_len, count, seeds, v.keys, s), "lsr_lwe_commit_keys_device");
-    }
-    check_lwe_call(lsr_lwe_commit_rows_device(a.lwe, r.msg.ptr, msg_len, count, v.keys, d_rows, s), "lsr_lwe_commit_rows_device");
-    // alpha = Challenge::derive(public_inputs, row), beta = Challenge::derive([alpha], row) (lib.rs:761-768)
-    if (a.n_public)
-        hipLaunchKernelGGL(gather_publics_kernel, dim3(blocks_for(count * a.n_public)), dim3(kBlock), 0, s, d_z, r.n_vars, (uint32_t)a.n_public,
-                           v.publics, count * a.n_public);
-    LSR_HIP(hipGetLastError());
-    check_lwe_call(lsr_fs_challenge_batch_device(a.n_public ? v.publics : nullptr, a.n_public, d_rows, words, count, kProverModulus, v.alphas,
-                                                 reinterpret_cast<uint8_t*>(v.hash_a), s), "lsr_fs_challenge_batch_device");
-    check_lwe_call(lsr_fs_challenge_batch_device(v.alphas, 1, d_rows, words, count, kProverModulus, v.betas, reinterpret_cast<uint8_t*>(v.hash_b), s),
-                   "lsr_fs_challenge_batch_device");
+    commit_messages(a.lwe, r.msg.ptr, msg_len, count, seeds, v.keys, d_rows, host_keys, s);
+    r1cs_transcript(gather_publics_kernel, v, d_z, r.n_vars, a.n_public, d_rows, words, count, kProverModulus, s);
     // A, B, C (stash, stash + per_vector, third plane: m P coeffs) and Q (natural order) at alpha and beta
     const EvalPoints pts{{v.alphas, v.betas}, 1, 2};
     const uint64_t m_inv = prover_montgomery(invmod_prime(r.m % kProverModulus, kProverModulus));
@@ -632,82 +571,32 @@ static void prove_chunk(LsrR1csProver& r, const ProveArgs& a, const uint64_t* d_
     const EvalPolys qp{{r.quot.ptr, r.quot.ptr, r.quot.ptr}, r.m, r.m};
     hipLaunchKernelGGL((eval_kernel<false, 1>), dim3((unsigned)count, 1), dim3(kEvalBlock), 0, s, qp, pts, EvalOut{v.ev + 6, 8, 0}, p.logm,
                        kGoldOneMont);
-    hipLaunchKernelGGL(prove_assemble_kernel, dim3(blocks_for(count, ~0u)), dim3(kBlock), 0, s, v.ev, v.alphas, v.betas, a.zk ? d_blind : nullptr,
-                       r.len.ptr, v.hash_a, v.hash_b, p.logm, d_proofs, reinterpret_cast<uint64_t*>(d_hashes), d_status, count);
+    hipLaunchKernelGGL(prove_assemble_kernel, dim3(blocks_for(count, ~0u)), dim3(kBlock), 0, s, v.ev, v.alphas, v.betas, d_blind, r.len.ptr, v.hash_a,
+                       v.hash_b, p.logm, d_proofs, reinterpret_cast<uint64_t*>(d_hashes), d_status, count);
     LSR_HIP(hipGetLastError());
 }
 
-static void prove_device(LsrR1csProver& r, const ProveArgs& a, const uint64_t* d_w, size_t batch, const uint64_t* d_blind, uint64_t* d_rows,
-                         uint64_t* d_proofs, uint8_t* d_hashes, uint32_t* d_status, hipStream_t s) {
+// device arrays on `s` (on_device) or host arrays through the plan's stream
+static void prove(LsrR1csProver& r, const R1csProveCall& c, bool on_device, hipStream_t s) {
     LsrQuotientPlan& p = *r.plan;
-    DeviceGuard guard(p.device);
-    std::lock_guard<std::mutex> lock(p.mutex);   // order: the plan's mutex, then (inside each commitment call) the LWE context's
-    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
-    const size_t words = lsr_lwe_commitment_words(a.lwe);
-    const size_t chunk = quotient_chunk(p, batch);
-    ensure_prove_workspace(r, chunk, a.n_public, words, false);
-    for (size_t done = 0; done < batch; done += chunk) {
-        const size_t now = std::min(chunk, batch - done);
-        prove_chunk(r, a, d_w + done * r.n_vars, d_blind ? d_blind + done : nullptr, a.seeds + done, now, d_rows + done * words, d_proofs + done * 13,
-                    d_hashes ? d_hashes + done * 64 : nullptr, d_status + done, false, s);
-    }
-    if (!p.ev_last) LSR_HIP(hipEventCreateWithFlags(&p.ev_last, hipEventDisableTiming));
-    LSR_HIP(hipEventRecord(p.ev_last, s));
+    const R1csProverRef ref{p.device, p.mutex, p.ev_last, p.stream, r.witness, r.n_vars, r.ws};
+    const auto grow = [&](size_t chunk) { ensure_prove_workspace(r, chunk, c.n_public); };
+    const auto chunk = [&](auto... args) { prove_chunk(r, c, args...); };
+    if (on_device) r1cs_prove_device(ref, c, quotient_chunk(p, c.batch), grow, chunk, s);
+    else r1cs_prove_host(ref, c, quotient_chunk(p, c.batch), grow, chunk);
 }
 
-static void prove_host(LsrR1csProver& r, const ProveArgs& a, const uint64_t* w, size_t batch, const uint64_t* blind, uint64_t* rows, uint64_t* proofs,
-                       uint8_t* hashes, uint32_t* status) {
-    LsrQuotientPlan& p = *r.plan;
-    DeviceGuard guard(p.device);
-    std::lock_guard<std::mutex> lock(p.mutex);
-    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
-    const size_t words = lsr_lwe_commitment_words(a.lwe);
-    const size_t chunk = quotient_chunk(p, batch);
-    ensure_prove_workspace(r, chunk, a.n_public, words, true);
-    hipStream_t s = p.stream;
-    const ProveSlots v = prove_slots(r, r.prove_chunk);
-    uint64_t* d_rows = r.io.ptr;
-    uint64_t* d_proofs = d_rows + r.prove_chunk * r.prove_row_words;
-    uint64_t* d_hashes = d_proofs + r.prove_chunk * 13;
-    for (size_t done = 0; done < batch; done += chunk) {
-        const size_t now = std::min(chunk, batch - done);
-        bool zero_seed = false;
-        for (size_t j = 0; j < now; ++j) zero_seed |= a.seeds[done + j] == 0;
-        LSR_HIP(hipMemcpyAsync(r.witness.ptr, w + done * r.n_vars, now * r.n_vars * 8, hipMemcpyHostToDevice, s));
-        if (blind) LSR_HIP(hipMemcpyAsync(v.blinding, blind + done, now * 8, hipMemcpyHostToDevice, s));
-        prove_chunk(r, a, r.witness.ptr, blind ? v.blinding : nullptr, a.seeds + done, now, d_rows, d_proofs, hashes ? reinterpret_cast<uint8_t*>(d_hashes) : nullptr,
-                    r.io_status.ptr, zero_seed, s);
-        LSR_HIP(hipMemcpyAsync(rows + done * words, d_rows, now * words * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipMemcpyAsync(proofs + done * 13, d_proofs, now * 13 * 8, hipMemcpyDeviceToHost, s));
-        if (hashes) LSR_HIP(hipMemcpyAsync(hashes + done * 64, d_hashes, now * 64, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipMemcpyAsync(status + done, r.io_status.ptr, now * 4, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
-}
-
-// verify on the host: the transcripts on the host pool (lsr_fs_challenge_batch_flat), then the checks
 static void verify_host(uint32_t m, const uint64_t* pub, size_t n_public, const uint64_t* rows, size_t words, const uint64_t* proofs, size_t batch, bool zk,
                         int* results) {
-    std::vector<uint64_t> alphas(batch), betas(batch);
-    check_lwe_call(lsr_fs_challenge_batch_flat(pub, n_public, rows, words, batch, kProverModulus, alphas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
-    check_lwe_call(lsr_fs_challenge_batch_flat(alphas.data(), 1, rows, words, batch, kProverModulus, betas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
-    for (size_t i = 0; i < batch; ++i) results[i] = verify_one(proofs + i * 13, alphas[i], betas[i], m, zk);
+    r1cs_verify_host(kProverModulus, pub, n_public, rows, words, proofs, batch, results,
+                     [&](const uint64_t* proof, uint64_t alpha, uint64_t beta) { return verify_one(proof, alpha, beta, m, zk); });
 }
 
 static void verify_device(uint32_t m, const uint64_t* d_pub, size_t n_public, const uint64_t* d_rows, size_t words, const uint64_t* d_proofs, size_t batch,
                           bool zk, int* d_results, hipStream_t s) {
-    uint64_t* d_ab = nullptr;   // alphas, betas: stream-ordered scratch
-    LSR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ab), 2 * batch * 8, s));
-    try {
-        check_lwe_call(lsr_fs_challenge_batch_device(d_pub, n_public, d_rows, words, batch, kProverModulus, d_ab, nullptr, s), "lsr_fs_challenge_batch_device");
-        check_lwe_call(lsr_fs_challenge_batch_device(d_ab, 1, d_rows, words, batch, kProverModulus, d_ab + batch, nullptr, s), "lsr_fs_challenge_batch_device");
-        hipLaunchKernelGGL(verify_check_kernel, dim3(blocks_for(batch, ~0u)), dim3(kBlock), 0, s, d_proofs, d_ab, d_ab + batch, m, zk ? 1 : 0, d_results, batch);
-        LSR_HIP(hipGetLastError());
-    } catch (...) {
-        (void)hipFreeAsync(d_ab, s);
-        throw;
-    }
-    LSR_HIP(hipFreeAsync(d_ab, s));
+    r1cs_verify_device(kProverModulus, d_pub, n_public, d_rows, words, batch, s, [&](const uint64_t* d_alphas, const uint64_t* d_betas) {
+        hipLaunchKernelGGL(verify_check_kernel, dim3(blocks_for(batch, ~0u)), dim3(kBlock), 0, s, d_proofs, d_alphas, d_betas, m, zk ? 1 : 0, d_results, batch);
+    });
 }
 
 static void eval_device(const uint64_t* d_c, size_t len, size_t batch, const uint64_t* d_x, uint32_t ppp, uint64_t* d_v, hipStream_t s) {
@@ -748,20 +637,8 @@ static void cyclic_host(const NttContext& c, uint64_t* values, size_t batch, boo
 
 using lsr::set_last_error;
 
-template <class F>
-static int guarded(const char* where, F&& body) noexcept {
-    try {
-        body();
-        return 0;
-    } catch (const std::exception& e) {
-        set_last_error(std::string(where) + ": " + e.what());
-        std::fprintf(stderr, "lambda_snark_core: %s failed: %s\n", where, e.what());
-        return -1;
-    } catch (...) {
-        set_last_error(std::string(where) + ": unknown exception");
-        return -1;
-    }
-}
+using lsr::abi_guarded;
+using lsr::abi_refuse;
 
 extern "C" {
 
@@ -781,16 +658,16 @@ int lsr_ntt_context_is_cyclic(const NttContext* ctx) noexcept { return ctx && ct
 int lsr_cyclic_ntt_forward_batch(const NttContext* ctx, uint64_t* values, size_t batch) noexcept {
     if (!ctx || !values || !ctx->cyclic) return -1;
     if (batch == 0) return 0;
-    return guarded("lsr_cyclic_ntt_forward_batch", [&] { lsr::cyclic_host(*ctx, values, batch, false); });
+    return abi_guarded("lsr_cyclic_ntt_forward_batch", [&] { lsr::cyclic_host(*ctx, values, batch, false); });
 }
 int lsr_cyclic_ntt_inverse_batch(const NttContext* ctx, uint64_t* values, size_t batch) noexcept {
     if (!ctx || !values || !ctx->cyclic) return -1;
     if (batch == 0) return 0;
-    return guarded("lsr_cyclic_ntt_inverse_batch", [&] { lsr::cyclic_host(*ctx, values, batch, true); });
+    return abi_guarded("lsr_cyclic_ntt_inverse_batch", [&] { lsr::cyclic_host(*ctx, values, batch, true); });
 }
 int lsr_bit_reverse_device(uint64_t* d_out, const uint64_t* d_in, int logn, size_t batch, void* stream) noexcept {
     if (!d_out || !d_in || d_out == d_in || logn < 1 || logn > 31) return -1;
-    return guarded("lsr_bit_reverse_device", [&] { lsr::launch_bit_reverse(d_out, d_in, logn, batch, static_cast<hipStream_t>(stream)); });
+    return abi_guarded("lsr_bit_reverse_device", [&] { lsr::launch_bit_reverse(d_out, d_in, logn, batch, static_cast<hipStream_t>(stream)); });
 }
 
 LsrQuotientPlan* lsr_quotient_plan_create(uint32_t m, int device) noexcept {
@@ -807,13 +684,13 @@ int lsr_quotient_batch(LsrQuotientPlan* plan, const uint64_t* a_evals, const uin
                        uint64_t* quotient, uint32_t* quotient_len) noexcept {
     if (!plan || !a_evals || !b_evals || !c_evals || !quotient || !quotient_len) return -1;
     if (batch == 0) return 0;
-    return guarded("lsr_quotient_batch", [&] { lsr::quotient_host(*plan, a_evals, b_evals, c_evals, batch, quotient, quotient_len); });
+    return abi_guarded("lsr_quotient_batch", [&] { lsr::quotient_host(*plan, a_evals, b_evals, c_evals, batch, quotient, quotient_len); });
 }
 int lsr_quotient_batch_device(LsrQuotientPlan* plan, const uint64_t* d_a, const uint64_t* d_b, const uint64_t* d_c, size_t batch, uint64_t* d_quotient,
                               uint32_t* d_quotient_len, void* stream) noexcept {
     if (!plan || !d_a || !d_b || !d_c || !d_quotient || !d_quotient_len) return -1;
     if (batch == 0) return 0;
-    return guarded("lsr_quotient_batch_device",
+    return abi_guarded("lsr_quotient_batch_device",
                    [&] { lsr::quotient_device(*plan, d_a, d_b, d_c, batch, d_quotient, d_quotient_len, static_cast<hipStream_t>(stream)); });
 }
 
@@ -834,7 +711,7 @@ int lsr_r1cs_constraint_evals_batch(LsrR1csProver* prover, const uint64_t* witne
                                     uint64_t* c_evals) noexcept {
     if (!prover || !witnesses || !a_evals || !b_evals || !c_evals) return -1;
     if (batch == 0) return 0;
-    return guarded("lsr_r1cs_constraint_evals_batch", [&] {
+    return abi_guarded("lsr_r1cs_constraint_evals_batch", [&] {
         uint64_t* const evals[3] = {a_evals, b_evals, c_evals};
         if (prover->lag) lsr::lagrange_host_run(*prover->lag, witnesses, batch, evals, nullptr, nullptr, nullptr);
         else lsr::prover_run(*prover, witnesses, batch, evals, nullptr, nullptr);
@@ -843,28 +720,23 @@ int lsr_r1cs_constraint_evals_batch(LsrR1csProver* prover, const uint64_t* witne
 int lsr_r1cs_quotient_batch(LsrR1csProver* prover, const uint64_t* witnesses, size_t batch, uint64_t* quotient, uint32_t* quotient_len) noexcept {
     if (!prover || !witnesses || !quotient || !quotient_len) return -1;
     if (batch == 0) return 0;
-    return guarded("lsr_r1cs_quotient_batch", [&] {
+    return abi_guarded("lsr_r1cs_quotient_batch", [&] {
         if (prover->lag) lsr::lagrange_host_run(*prover->lag, witnesses, batch, nullptr, nullptr, quotient, quotient_len);
         else lsr::prover_run(*prover, witnesses, batch, nullptr, quotient, quotient_len);
     });
 }
 
 // ---- batched prove / verify (prover.h) ----
-static int refuse(const char* where, const char* why) {
-    set_last_error(std::string(where) + ": " + why);
-    return -1;
-}
-
 static int prover_device(const LsrR1csProver* p) { return p->lag ? lsr::lagrange_device(p->lag) : p->plan->device; }
 
 static int prove_checks(const char* where, const LsrR1csProver* prover, const LweContext* lwe, uint64_t commit_modulus, const void* w, size_t n_public,
                         const uint64_t* seeds, const void* rows, const void* proofs, const void* status) {
-    if (!prover || !lwe) return refuse(where, "NULL prover or LWE context");
-    if (!w || !seeds || !rows || !proofs || !status) return refuse(where, "NULL witnesses, seeds, rows, proofs or status");
-    if (n_public > prover->n_vars) return refuse(where, "n_public exceeds the circuit's variable count");
-    if (commit_modulus <= 1) return refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
+    if (!prover || !lwe) return abi_refuse(where, "NULL prover or LWE context");
+    if (!w || !seeds || !rows || !proofs || !status) return abi_refuse(where, "NULL witnesses, seeds, rows, proofs or status");
+    if (n_public > prover->n_vars) return abi_refuse(where, "n_public exceeds the circuit's variable count");
+    if (commit_modulus <= 1) return abi_refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
     const NttContext* ntt = lsr_lwe_ntt_context(lwe);
-    if (!ntt || ntt->device != prover_device(prover)) return refuse(where, "the prover and the LWE context live on different devices");
+    if (!ntt || ntt->device != prover_device(prover)) return abi_refuse(where, "the prover and the LWE context live on different devices");
     return 0;
 }
 
@@ -873,13 +745,10 @@ int lsr_r1cs_prove_batch(LsrR1csProver* prover, LweContext* lwe, uint64_t commit
     const char* where = "lsr_r1cs_prove_batch";
     if (prove_checks(where, prover, lwe, commit_modulus, witnesses, n_public, seeds, rows, proofs, status)) return -1;
     if (batch == 0) return 0;
-    return guarded(where, [&] {
-        if (prover->lag) {
-            lsr::lagrange_prove_host(*prover->lag, lwe, commit_modulus, witnesses, batch, n_public, seeds, blinding, rows, proofs, hashes, status);
-            return;
-        }
-        const lsr::ProveArgs a{lwe, commit_modulus, n_public, seeds, blinding != nullptr};
-        lsr::prove_host(*prover, a, witnesses, batch, blinding, rows, proofs, hashes, status);
+    const lsr::R1csProveCall c{lwe, commit_modulus, n_public, seeds, witnesses, blinding, rows, proofs, hashes, status, batch};
+    return abi_guarded(where, [&] {
+        if (prover->lag) lsr::lagrange_prove(*prover->lag, c, false, nullptr);
+        else lsr::prove(*prover, c, false, nullptr);
     });
 }
 
@@ -889,28 +758,18 @@ int lsr_r1cs_prove_batch_device(LsrR1csProver* prover, LweContext* lwe, uint64_t
     const char* where = "lsr_r1cs_prove_batch_device";
     if (prove_checks(where, prover, lwe, commit_modulus, d_witnesses, n_public, seeds, d_rows, d_proofs, d_status)) return -1;
     if (batch == 0) return 0;
-    for (size_t i = 0; i < batch; ++i)
-        if (seeds[i] == 0) return refuse(where, "seed 0 asks for fresh OS entropy, which only the host call serves (lsr_r1cs_prove_batch)");
-    if (batch > 0x7fffffffull) return refuse(where, "batch exceeds 2^31 - 1 proofs");
-    return guarded(where, [&] {
-        lsr::DeviceGuard guard(prover_device(prover));
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        if (lsr::stream_is_capturing(s)) throw std::runtime_error("not capturable into a HIP graph (host seeds, host-ordered workspace)");
-        if (prover->lag) {
-            lsr::lagrange_prove_device(*prover->lag, lwe, commit_modulus, d_witnesses, batch, n_public, seeds, d_blinding, d_rows, d_proofs, d_hashes,
-                                       d_status, stream);
-            return;
-        }
-        const lsr::ProveArgs a{lwe, commit_modulus, n_public, seeds, d_blinding != nullptr};
-        lsr::prove_device(*prover, a, d_witnesses, batch, d_blinding, d_rows, d_proofs, d_hashes, d_status, s);
+    const lsr::R1csProveCall c{lwe, commit_modulus, n_public, seeds, d_witnesses, d_blinding, d_rows, d_proofs, d_hashes, d_status, batch};
+    return lsr::abi_prove_device(where, "lsr_r1cs_prove_batch", seeds, batch, prover_device(prover), stream, [&](hipStream_t s) {
+        if (prover->lag) lsr::lagrange_prove(*prover->lag, c, true, s);
+        else lsr::prove(*prover, c, true, s);
     });
 }
 
 static int verify_checks(const char* where, uint32_t m, const void* pub, size_t n_public, const void* rows, size_t words, const void* proofs,
                          const void* results) {
-    if ((!pub && n_public) || !rows || !proofs || !results) return refuse(where, "NULL public inputs, rows, proofs or results");
-    if (words == 0) return refuse(where, "words_per_row must be positive");
-    if (m == 0 || (m & (m - 1))) return refuse(where, "m must be a power of two (the NTT path, r1cs.rs:386-389)");
+    if ((!pub && n_public) || !rows || !proofs || !results) return abi_refuse(where, "NULL public inputs, rows, proofs or results");
+    if (words == 0) return abi_refuse(where, "words_per_row must be positive");
+    if (m == 0 || (m & (m - 1))) return abi_refuse(where, "m must be a power of two (the NTT path, r1cs.rs:386-389)");
     return 0;
 }
 
@@ -919,7 +778,7 @@ int lsr_r1cs_verify_batch(uint32_t m, const uint64_t* public_inputs, size_t n_pu
     const char* where = "lsr_r1cs_verify_batch";
     if (verify_checks(where, m, public_inputs, n_public, rows, words_per_row, proofs, results)) return -1;
     if (batch == 0) return 0;
-    return guarded(where, [&] { lsr::verify_host(m, public_inputs, n_public, rows, words_per_row, proofs, batch, zk != 0, results); });
+    return abi_guarded(where, [&] { lsr::verify_host(m, public_inputs, n_public, rows, words_per_row, proofs, batch, zk != 0, results); });
 }
 
 int lsr_r1cs_verify_batch_device(uint32_t m, const uint64_t* d_public_inputs, size_t n_public, const uint64_t* d_rows, size_t words_per_row,
@@ -927,21 +786,19 @@ int lsr_r1cs_verify_batch_device(uint32_t m, const uint64_t* d_public_inputs, si
     const char* where = "lsr_r1cs_verify_batch_device";
     if (verify_checks(where, m, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, d_results)) return -1;
     if (batch == 0) return 0;
-    return guarded(where, [&] {
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        if (lsr::stream_is_capturing(s)) throw std::runtime_error("not capturable into a HIP graph (stream-ordered scratch)");
-        lsr::verify_device(m, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, batch, zk != 0, d_results, s);
+    return abi_guarded(where, [&] {
+        lsr::verify_device(m, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, batch, zk != 0, d_results, static_cast<hipStream_t>(stream));
     });
 }
 
 int lsr_prover_eval_batch_device(const uint64_t* d_coeffs, size_t len, size_t batch, const uint64_t* d_points, uint32_t points_per_poly, uint64_t* d_values,
                                  void* stream) noexcept {
     const char* where = "lsr_prover_eval_batch_device";
-    if (!d_coeffs || !d_points || !d_values) return refuse(where, "NULL coefficients, points or values");
-    if (len == 0 || len > 0x80000000ull) return refuse(where, "len must be in [1, 2^31]");
-    if (points_per_poly == 0 || points_per_poly > 131070u) return refuse(where, "points_per_poly must be in [1, 131070]");
+    if (!d_coeffs || !d_points || !d_values) return abi_refuse(where, "NULL coefficients, points or values");
+    if (len == 0 || len > 0x80000000ull) return abi_refuse(where, "len must be in [1, 2^31]");
+    if (points_per_poly == 0 || points_per_poly > 131070u) return abi_refuse(where, "points_per_poly must be in [1, 131070]");
     if (batch == 0) return 0;
-    return guarded(where, [&] { lsr::eval_device(d_coeffs, len, batch, d_points, points_per_poly, d_values, static_cast<hipStream_t>(stream)); });
+    return abi_guarded(where, [&] { lsr::eval_device(d_coeffs, len, batch, d_points, points_per_poly, d_values, static_cast<hipStream_t>(stream)); });
 }
 
 // ---- the Lagrange path (prover.h) ----
@@ -973,10 +830,10 @@ int lsr_r1cs_prover_uses_ntt(const LsrR1csProver* prover) noexcept { return prov
 int lsr_r1cs_interpolate_batch(LsrR1csProver* prover, const uint64_t* witnesses, size_t batch, uint64_t* a_coeffs, uint64_t* b_coeffs,
                                uint64_t* c_coeffs) noexcept {
     const char* where = "lsr_r1cs_interpolate_batch";
-    if (!prover || !witnesses || !a_coeffs || !b_coeffs || !c_coeffs) return refuse(where, "NULL prover, witnesses or output");
-    if (!prover->lag) return refuse(where, "only a Lagrange-path prover (lsr_r1cs_prover_uses_ntt == 0) exposes its interpolants");
+    if (!prover || !witnesses || !a_coeffs || !b_coeffs || !c_coeffs) return abi_refuse(where, "NULL prover, witnesses or output");
+    if (!prover->lag) return abi_refuse(where, "only a Lagrange-path prover (lsr_r1cs_prover_uses_ntt == 0) exposes its interpolants");
     if (batch == 0) return 0;
-    return guarded(where, [&] {
+    return abi_guarded(where, [&] {
         uint64_t* const out[3] = {a_coeffs, b_coeffs, c_coeffs};
         lsr::lagrange_host_run(*prover->lag, witnesses, batch, nullptr, out, nullptr, nullptr);
     });
@@ -986,11 +843,11 @@ static bool ntt_path(uint32_t m, uint64_t q) { return q == lsr::kProverModulus &
 
 static int verify_mod_checks(const char* where, uint32_t m, uint64_t q, const void* pub, size_t n_public, const void* rows, size_t words,
                              const void* proofs, const void* results) {
-    if ((!pub && n_public) || !rows || !proofs || !results) return refuse(where, "NULL public inputs, rows, proofs or results");
-    if (words == 0) return refuse(where, "words_per_row must be positive");
-    if (q < 3 || (q & 1) == 0) return refuse(where, "the modulus must be odd and >= 3");
-    if (m == 0) return refuse(where, "m must be positive");
-    if (!ntt_path(m, q) && m > lsr::kLagrangeMaxM) return refuse(where, "the Lagrange path takes m <= 8192");
+    if ((!pub && n_public) || !rows || !proofs || !results) return abi_refuse(where, "NULL public inputs, rows, proofs or results");
+    if (words == 0) return abi_refuse(where, "words_per_row must be positive");
+    if (q < 3 || (q & 1) == 0) return abi_refuse(where, "the modulus must be odd and >= 3");
+    if (m == 0) return abi_refuse(where, "m must be positive");
+    if (!ntt_path(m, q) && m > lsr::kLagrangeMaxM) return abi_refuse(where, "the Lagrange path takes m <= 8192");
     return 0;
 }
 
@@ -1000,7 +857,7 @@ int lsr_r1cs_verify_batch_mod(uint32_t m, uint64_t modulus, const uint64_t* publ
     if (verify_mod_checks(where, m, modulus, public_inputs, n_public, rows, words_per_row, proofs, results)) return -1;
     if (ntt_path(m, modulus)) return lsr_r1cs_verify_batch(m, public_inputs, n_public, rows, words_per_row, proofs, batch, zk, results);
     if (batch == 0) return 0;
-    return guarded(where, [&] { lsr::verify_mod_host(m, modulus, public_inputs, n_public, rows, words_per_row, proofs, batch, zk != 0, results); });
+    return abi_guarded(where, [&] { lsr::verify_mod_host(m, modulus, public_inputs, n_public, rows, words_per_row, proofs, batch, zk != 0, results); });
 }
 
 int lsr_r1cs_verify_batch_mod_device(uint32_t m, uint64_t modulus, const uint64_t* d_public_inputs, size_t n_public, const uint64_t* d_rows,
@@ -1010,9 +867,8 @@ int lsr_r1cs_verify_batch_mod_device(uint32_t m, uint64_t modulus, const uint64_
     if (ntt_path(m, modulus))
         return lsr_r1cs_verify_batch_device(m, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, batch, zk, d_results, stream);
     if (batch == 0) return 0;
-    return guarded(where, [&] {
-        if (lsr::stream_is_capturing(static_cast<hipStream_t>(stream))) throw std::runtime_error("not capturable into a HIP graph (stream-ordered scratch)");
-        lsr::verify_mod_device(m, modulus, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, batch, zk != 0, d_results, stream);
+    return abi_guarded(where, [&] {
+        lsr::verify_mod_device(m, modulus, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, batch, zk != 0, d_results, static_cast<hipStream_t>(stream));
     });
 }
 

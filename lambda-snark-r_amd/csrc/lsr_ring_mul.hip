@@ -134,31 +134,14 @@ static void host_ring_mul(const NttContext& c, uint64_t* out, const uint64_t* a,
 // ------------------------------------------------------------------------------------------------
 // Argument checks that need no device (and no dereference of ctx): -1 and a message, or 0 to go on.
 static int ring_mul_check(const char* where, const NttContext* ctx, const void* c, const void* a, const void* b, size_t batch, size_t b_rows) {
-    if (!ctx || !c || !a || !b) {
-        lsr::set_last_error(std::string(where) + ": NULL context or buffer");
-        return -1;
-    }
-    if (b_rows != 1 && b_rows != batch) {
-        lsr::set_last_error(std::string(where) + ": b_rows must be 1 or batch (" + std::to_string(batch) + "), got " + std::to_string(b_rows));
-        return -1;
-    }
+    if (!ctx || !c || !a || !b) return lsr::abi_refuse(where, "NULL context or buffer");
+    if (b_rows != 1 && b_rows != batch)
+        return lsr::abi_refuse(where, "b_rows must be 1 or batch (" + std::to_string(batch) + "), got " + std::to_string(b_rows));
     return 0;
 }
 
-template <class F>
-static int ring_guarded(const char* where, F&& body) noexcept {
-    try {
-        if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
-        body();
-        return 0;
-    } catch (const std::exception& e) {
-        lsr::set_last_error(std::string(where) + ": " + e.what());
-        std::fprintf(stderr, "lambda_snark_core: %s failed: %s\n", where, e.what());
-        return -1;
-    } catch (...) {
-        lsr::set_last_error(std::string(where) + ": unknown exception");
-        return -1;
-    }
+static void require_device() {
+    if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
 }
 
 extern "C" {
@@ -166,14 +149,18 @@ extern "C" {
 int lsr_ntt_ring_mul_batch(const NttContext* ctx, uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t b_rows) noexcept {
     if (ring_mul_check("lsr_ntt_ring_mul_batch", ctx, c, a, b, batch, b_rows) != 0) return -1;
     if (batch == 0) return 0;
-    return ring_guarded("lsr_ntt_ring_mul_batch", [&] { lsr::host_ring_mul(*ctx, c, a, b, batch, b_rows); });
+    return lsr::abi_guarded("lsr_ntt_ring_mul_batch", [&] {
+        require_device();
+        lsr::host_ring_mul(*ctx, c, a, b, batch, b_rows);
+    });
 }
 
 int lsr_ntt_ring_mul_batch_device(const NttContext* ctx, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t b_rows,
                                   void* stream) noexcept {
     if (ring_mul_check("lsr_ntt_ring_mul_batch_device", ctx, d_c, d_a, d_b, batch, b_rows) != 0) return -1;
     if (batch == 0) return 0;
-    return ring_guarded("lsr_ntt_ring_mul_batch_device", [&] {
+    return lsr::abi_guarded("lsr_ntt_ring_mul_batch_device", [&] {
+        require_device();
         lsr::DeviceGuard guard(ctx->device);
         lsr::ring_mul_device(*ctx, d_c, d_a, d_b, batch, b_rows, static_cast<hipStream_t>(stream));
     });

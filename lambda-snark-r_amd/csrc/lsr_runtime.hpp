@@ -29,6 +29,28 @@ struct HipFailure : std::runtime_error {
             throw ::lsr::HipFailure(std::string(#expr) + ": " + hipGetErrorString(lsr_e_));                  \
     } while (0)
 
+// The C-ABI error boundary: runs `body`; an exception becomes -1, lsr_last_error "<where>: <what>" and a line on stderr.
+template <class F>
+int abi_guarded(const char* where, F&& body) noexcept {
+    try {
+        body();
+        return 0;
+    } catch (const std::exception& e) {
+        set_last_error(std::string(where) + ": " + e.what());
+        std::fprintf(stderr, "lambda_snark_core: %s failed: %s\n", where, e.what());
+        return -1;
+    } catch (...) {
+        set_last_error(std::string(where) + ": unknown exception");
+        return -1;
+    }
+}
+
+// An argument refusal at the C-ABI: -1 and lsr_last_error "<where>: <why>" (nothing on stderr).
+inline int abi_refuse(const char* where, const std::string& why) {
+    set_last_error(std::string(where) + ": " + why);
+    return -1;
+}
+
 // Device selection that does not leak into the caller's thread state (Rust wrappers are Send, not
 // Sync: the calling thread may change between calls — SURVEY.md §8(b) "Threading").
 class DeviceGuard {

@@ -10,6 +10,7 @@
 #include "lambda_snark/batch.h"
 #include "lambda_snark/prover.h"
 #include "lsr_keys.hpp"
+#include "lsr_prove_common.hpp"
 #include "lsr_runtime.hpp"
 #include "lsr_simple_kernels.hpp"
 
@@ -25,10 +26,6 @@ static unsigned simple_blocks(size_t work, unsigned cap = 256 * 32) {
 }
 
 static bool odd_modulus(uint64_t q) { return q >= 3 && (q & 1) != 0; }
-
-static void check_call(int rc, const char* what) {
-    if (rc != 0) throw std::runtime_error(std::string(what) + ": " + lsr_last_error());
-}
 
 }  // namespace lsr
 
@@ -117,17 +114,7 @@ static void prove_chunk(LsrSimpleProver& p, LweContext* lwe, uint64_t commit_mod
                         const SimpleLayout& L, const SimpleChunk& c, hipStream_t s) {
     const size_t words = lsr_lwe_commitment_words(lwe);
     launch_message(mode, c.w, c.bkeys, c.coeffs, L.msg, len, msg_len, commit_modulus, c.count, p.M, s);
-    if (c.host_keys) {
-        std::vector<uint64_t> msgs(c.count * msg_len), hk(4 * c.count);
-        LSR_HIP(hipMemcpyAsync(msgs.data(), L.msg, msgs.size() * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-        check_call(lsr_lwe_commit_keys(lwe, msgs.data(), msg_len, c.count, c.seeds, hk.data()), "lsr_lwe_commit_keys");
-        LSR_HIP(hipMemcpyAsync(L.keys, hk.data(), hk.size() * 8, hipMemcpyHostToDevice, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    } else {
-        check_call(lsr_lwe_commit_keys_device(lwe, L.msg, msg_len, c.count, c.seeds, L.keys, s), "lsr_lwe_commit_keys_device");
-    }
-    check_call(lsr_lwe_commit_rows_device(lwe, L.msg, msg_len, c.count, L.keys, c.rows, s), "lsr_lwe_commit_rows_device");
+    commit_messages(lwe, L.msg, msg_len, c.count, c.seeds, L.keys, c.rows, c.host_keys, s);
     check_call(lsr_fs_challenge_batch_device(n_public ? c.pub : nullptr, n_public, c.rows, words, c.count, p.q, L.alphas, c.hashes, s),
                "lsr_fs_challenge_batch_device");
     if (len <= kSimpleLaneMaxL)
@@ -292,25 +279,8 @@ static void random_blinding_host(const uint64_t* keys, size_t batch, size_t len,
 
 }  // namespace lsr
 
-template <class F>
-static int simple_guarded(const char* where, F&& body) noexcept {
-    try {
-        body();
-        return 0;
-    } catch (const std::exception& e) {
-        lsr::set_last_error(std::string(where) + ": " + e.what());
-        std::fprintf(stderr, "lambda_snark_core: %s failed: %s\n", where, e.what());
-        return -1;
-    } catch (...) {
-        lsr::set_last_error(std::string(where) + ": unknown exception");
-        return -1;
-    }
-}
-
-static int simple_refuse(const char* where, const char* why) {
-    lsr::set_last_error(std::string(where) + ": " + why);
-    return -1;
-}
+using lsr::abi_guarded;
+using lsr::abi_refuse;
 
 static void destroy_simple(LsrSimpleProver* p) {
     if (!p) return;
@@ -331,28 +301,28 @@ static void destroy_simple(LsrSimpleProver* p) {
 
 static int prove_args(const char* where, const LsrSimpleProver* p, const LweContext* lwe, uint64_t commit_modulus, int mode, const void* w, size_t len,
                       size_t batch, const void* pub, size_t n_public, const void* seeds, const void* rows, const void* coeffs, const void* proofs) {
-    if (!p || !lwe) return simple_refuse(where, "NULL prover or LWE context");
-    if (mode != LSR_SIMPLE_PLAIN && mode != LSR_SIMPLE_ZK && mode != LSR_SIMPLE_SIMULATE) return simple_refuse(where, "unknown mode");
-    if (len == 0) return simple_refuse(where, "Witness cannot be empty (len must be >= 1)");
-    if (len > 0xffffffffull) return simple_refuse(where, "len must be below 2^32");
+    if (!p || !lwe) return abi_refuse(where, "NULL prover or LWE context");
+    if (mode != LSR_SIMPLE_PLAIN && mode != LSR_SIMPLE_ZK && mode != LSR_SIMPLE_SIMULATE) return abi_refuse(where, "unknown mode");
+    if (len == 0) return abi_refuse(where, "Witness cannot be empty (len must be >= 1)");
+    if (len > 0xffffffffull) return abi_refuse(where, "len must be below 2^32");
     if (batch == 0) return 0;
     if ((mode != LSR_SIMPLE_SIMULATE && !w) || (!pub && n_public) || !seeds || !rows || !coeffs || !proofs)
-        return simple_refuse(where, "NULL witnesses, public inputs, seeds or output");
-    if (commit_modulus <= 1) return simple_refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
+        return abi_refuse(where, "NULL witnesses, public inputs, seeds or output");
+    if (commit_modulus <= 1) return abi_refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
     const NttContext* ntt = lsr_lwe_ntt_context(lwe);
-    if (!ntt || ntt->device != p->device) return simple_refuse(where, "the prover and the LWE context live on different devices");
+    if (!ntt || ntt->device != p->device) return abi_refuse(where, "the prover and the LWE context live on different devices");
     return 0;
 }
 
 static int verify_args(const char* where, uint64_t q, const void* pub, size_t n_public, const void* rows, size_t words, const void* proofs,
                        const void* coeffs, size_t len, const LweContext* lwe, uint64_t commit_modulus, const void* results) {
-    if (!lsr::odd_modulus(q)) return simple_refuse(where, "the modulus must be odd and >= 3");
-    if ((!pub && n_public) || !rows || !proofs || (!coeffs && len) || !results) return simple_refuse(where, "NULL public inputs, rows, proofs, coefficients or results");
-    if (words == 0) return simple_refuse(where, "words_per_row must be positive");
-    if (len > 0xffffffffull) return simple_refuse(where, "len must be below 2^32");
+    if (!lsr::odd_modulus(q)) return abi_refuse(where, "the modulus must be odd and >= 3");
+    if ((!pub && n_public) || !rows || !proofs || (!coeffs && len) || !results) return abi_refuse(where, "NULL public inputs, rows, proofs, coefficients or results");
+    if (words == 0) return abi_refuse(where, "words_per_row must be positive");
+    if (len > 0xffffffffull) return abi_refuse(where, "len must be below 2^32");
     if (lwe) {
-        if (commit_modulus <= 1) return simple_refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
-        if (words != lsr_lwe_commitment_words(lwe)) return simple_refuse(where, "words_per_row must be the context's commitment words");
+        if (commit_modulus <= 1) return abi_refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
+        if (words != lsr_lwe_commitment_words(lwe)) return abi_refuse(where, "words_per_row must be the context's commitment words");
     }
     return 0;
 }
@@ -360,26 +330,26 @@ static int verify_args(const char* where, uint64_t q, const void* pub, size_t n_
 extern "C" {
 
 int lsr_chacha20rng_keys_from_u64(const uint64_t* seeds, size_t count, uint64_t* keys) noexcept {
-    if (count && (!seeds || !keys)) return simple_refuse("lsr_chacha20rng_keys_from_u64", "NULL seeds or keys");
+    if (count && (!seeds || !keys)) return abi_refuse("lsr_chacha20rng_keys_from_u64", "NULL seeds or keys");
     for (size_t i = 0; i < count; ++i) lsr::pcg32_key(seeds[i], keys + 4 * i);
     return 0;
 }
 
 int lsr_random_blinding(const uint64_t* keys, size_t batch, size_t len, uint64_t q, uint64_t* out) noexcept {
     const char* where = "lsr_random_blinding";
-    if (!lsr::odd_modulus(q)) return simple_refuse(where, "the modulus must be odd and >= 3");
-    if (batch && len && (!keys || !out)) return simple_refuse(where, "NULL keys or output");
-    if (len > 0xffffffffull) return simple_refuse(where, "len must be below 2^32");
-    return simple_guarded(where, [&] { lsr::random_blinding_host(keys, batch, len, q, out); });
+    if (!lsr::odd_modulus(q)) return abi_refuse(where, "the modulus must be odd and >= 3");
+    if (batch && len && (!keys || !out)) return abi_refuse(where, "NULL keys or output");
+    if (len > 0xffffffffull) return abi_refuse(where, "len must be below 2^32");
+    return abi_guarded(where, [&] { lsr::random_blinding_host(keys, batch, len, q, out); });
 }
 
 int lsr_random_blinding_device(const uint64_t* d_keys, size_t batch, size_t len, uint64_t q, uint64_t* d_out, void* stream) noexcept {
     const char* where = "lsr_random_blinding_device";
-    if (!lsr::odd_modulus(q)) return simple_refuse(where, "the modulus must be odd and >= 3");
-    if (batch && len && (!d_keys || !d_out)) return simple_refuse(where, "NULL keys or output");
-    if (len > 0xffffffffull) return simple_refuse(where, "len must be below 2^32");
+    if (!lsr::odd_modulus(q)) return abi_refuse(where, "the modulus must be odd and >= 3");
+    if (batch && len && (!d_keys || !d_out)) return abi_refuse(where, "NULL keys or output");
+    if (len > 0xffffffffull) return abi_refuse(where, "len must be below 2^32");
     if (batch == 0 || len == 0) return 0;
-    return simple_guarded(where, [&] {
+    return abi_guarded(where, [&] {
         lsr::launch_message(lsr::kSimpleSimulate, nullptr, d_keys, d_out, nullptr, len, 0, 1, batch, lsr::make_mont(q), static_cast<hipStream_t>(stream));
     });
 }
@@ -387,18 +357,18 @@ int lsr_random_blinding_device(const uint64_t* d_keys, size_t batch, size_t len,
 LsrSimpleProver* lsr_simple_prover_create(uint64_t q, int device) noexcept {
     const char* where = "lsr_simple_prover_create";
     if (!lsr::odd_modulus(q)) {
-        simple_refuse(where, "the modulus must be odd and >= 3");
+        abi_refuse(where, "the modulus must be odd and >= 3");
         return nullptr;
     }
     const int devices = lsr::visible_device_count();
     if (devices <= 0) {
-        simple_refuse(where, "no HIP device visible — this library has no CPU fallback");
+        abi_refuse(where, "no HIP device visible — this library has no CPU fallback");
         return nullptr;
     }
     if (device < 0) device = lsr::default_device();
     if (device < 0) return nullptr;
     if (device >= devices) {
-        simple_refuse(where, "device index out of range");
+        abi_refuse(where, "device index out of range");
         return nullptr;
     }
     LsrSimpleProver* p = nullptr;
@@ -411,7 +381,7 @@ LsrSimpleProver* lsr_simple_prover_create(uint64_t q, int device) noexcept {
         LSR_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
         return p;
     } catch (const std::exception& e) {
-        simple_refuse(where, e.what());
+        abi_refuse(where, e.what());
         destroy_simple(p);
         return nullptr;
     }
@@ -426,7 +396,7 @@ int lsr_simple_prove_batch(LsrSimpleProver* prover, LweContext* lwe, uint64_t co
     const char* where = "lsr_simple_prove_batch";
     if (prove_args(where, prover, lwe, commit_modulus, mode, witnesses, len, batch, public_inputs, n_public, seeds, rows, coeffs, proofs)) return -1;
     if (batch == 0) return 0;
-    return simple_guarded(where, [&] {
+    return abi_guarded(where, [&] {
         lsr::prove_host(*prover, lwe, commit_modulus, mode, witnesses, len, batch, public_inputs, n_public, seeds, blinding_keys, rows, coeffs, proofs,
                         hashes);
     });
@@ -438,14 +408,8 @@ int lsr_simple_prove_batch_device(LsrSimpleProver* prover, LweContext* lwe, uint
     const char* where = "lsr_simple_prove_batch_device";
     if (prove_args(where, prover, lwe, commit_modulus, mode, d_witnesses, len, batch, d_public_inputs, n_public, seeds, d_rows, d_coeffs, d_proofs)) return -1;
     if (batch == 0) return 0;
-    if (mode != LSR_SIMPLE_PLAIN && !d_blinding_keys) return simple_refuse(where, "ZK and SIMULATE need device blinding keys (fresh entropy is the host call's)");
-    for (size_t i = 0; i < batch; ++i)
-        if (seeds[i] == 0) return simple_refuse(where, "seed 0 asks for fresh OS entropy, which only the host call serves (lsr_simple_prove_batch)");
-    if (batch > 0x7fffffffull) return simple_refuse(where, "batch exceeds 2^31 - 1 proofs");
-    return simple_guarded(where, [&] {
-        lsr::DeviceGuard guard(prover->device);
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        if (lsr::stream_is_capturing(s)) throw std::runtime_error("not capturable into a HIP graph (host seeds, host-ordered workspace)");
+    if (mode != LSR_SIMPLE_PLAIN && !d_blinding_keys) return abi_refuse(where, "ZK and SIMULATE need device blinding keys (fresh entropy is the host call's)");
+    return lsr::abi_prove_device(where, "lsr_simple_prove_batch", seeds, batch, prover->device, stream, [&](hipStream_t s) {
         lsr::prove_device(*prover, lwe, commit_modulus, mode, d_witnesses, len, batch, d_public_inputs, n_public, seeds, d_blinding_keys, d_rows, d_coeffs,
                           d_proofs, d_hashes, s);
     });
@@ -456,7 +420,7 @@ int lsr_simple_verify_batch(uint64_t q, const uint64_t* public_inputs, size_t n_
     const char* where = "lsr_simple_verify_batch";
     if (verify_args(where, q, public_inputs, n_public, rows, words_per_row, proofs, coeffs, len, lwe, commit_modulus, results)) return -1;
     if (batch == 0) return 0;
-    return simple_guarded(where, [&] {
+    return abi_guarded(where, [&] {
         lsr::verify_host(q, public_inputs, n_public, rows, words_per_row, proofs, coeffs, len, batch, lwe, commit_modulus, results);
     });
 }
@@ -467,8 +431,8 @@ int lsr_simple_verify_batch_device(uint64_t q, const uint64_t* d_public_inputs, 
     const char* where = "lsr_simple_verify_batch_device";
     if (verify_args(where, q, d_public_inputs, n_public, d_rows, words_per_row, d_proofs, d_coeffs, len, lwe, commit_modulus, d_results)) return -1;
     if (batch == 0) return 0;
-    if (batch > 0x7fffffffull) return simple_refuse(where, "batch exceeds 2^31 - 1 proofs");
-    return simple_guarded(where, [&] {
+    if (batch > 0x7fffffffull) return abi_refuse(where, "batch exceeds 2^31 - 1 proofs");
+    return abi_guarded(where, [&] {
         const NttContext* ntt = lwe ? lsr_lwe_ntt_context(lwe) : nullptr;
         if (lwe && !ntt) throw std::runtime_error("the LWE context has no device");
         int device = 0;
