@@ -50,7 +50,7 @@ struct LweContext {
     int logn = 0;
     double sigma = 0;
     int device = 0;
-    NttContext* ntt = nullptr;
+    lsr::NttContextPtr ntt;           // declared first: released after every buffer of the context
     lsr::DeviceBuffer<uint64_t> a_hat, s_hat, b_hat, cdf;
     uint32_t cdf_entries = 0;
     lsr::ContextKeys keys{};          // key schedule of this context (lsr_keys.hpp); keys.sec is secret
@@ -60,11 +60,9 @@ struct LweContext {
     mutable std::mutex mutex;
     mutable lsr::DeviceBuffer<uint64_t> ws_r, ws_e1, ws_e2, ws_u, ws_v, ws_dm, ws_keys;   // ws_keys: [batch][4]
     mutable lsr::DeviceBuffer<unsigned long long> ws_flag;
-    mutable size_t ws_batch = 0, ws_in_batch = 0;
     mutable std::vector<uint64_t> ws_key_host;    // source of an asynchronous upload: must outlive the call that fills it
     // pinned host staging for the gather of a batch (two bulk D2H copies instead of two per commitment)
-    mutable uint64_t* host_stage = nullptr;
-    mutable size_t host_stage_words = 0;
+    mutable lsr::PinnedBuffer<uint64_t> host_stage{hipHostMallocPortable};   // any device of the node may DMA into it
     // fused matrix–vector pipeline (lsr_commit_fused.hpp): lane-major copy of A_hat, per-lane chunk workspaces, side streams
     static constexpr int kMaxSide = 3;
     lsr::DeviceBuffer<double> a_perm;       // [tile][k][k]: the A^T product (n = 2^16 / 2^17)
@@ -76,16 +74,15 @@ struct LweContext {
     mutable lsr::DeviceBuffer<unsigned long long> ws_vflags;        // openings: per-row OR of decoded ^ claimed
     mutable uint32_t* ws_vbad = nullptr;                            // openings: per-row "not a canonical commitment of this context" (inside ws_vflags)
     mutable lsr::DeviceBuffer<uint64_t> ws_mid, ws_e1_slots;
-    mutable hipStream_t side[kMaxSide] = {nullptr, nullptr, nullptr};
-    mutable hipEvent_t ev_fork = nullptr, ev_join[kMaxSide] = {nullptr, nullptr, nullptr};
-    mutable int n_side = 0;
+    mutable lsr::Stream side[kMaxSide];
+    mutable lsr::Event ev_fork, ev_join[kMaxSide];
     // asynchronous entry points share the context's workspaces and side streams: each call's stream first waits for the previous
     // call's last kernel (recorded here), so calls on one context are ordered whatever streams the caller brings
-    mutable hipEvent_t ev_last = nullptr;
+    mutable lsr::Event ev_last;
     // device -> host gathers of the host-array entry points run on their own stream, so that the copy of one chunk overlaps the
     // kernels of the next (config 4: the gather, not the compute, is the long pole)
-    mutable hipStream_t copy_stream = nullptr;
-    mutable hipEvent_t ev_chunk[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
+    mutable lsr::Stream copy_stream;
+    mutable lsr::Event ev_chunk[2], ev_copied[2];
     // pipeline selection, read from the environment ONCE when the context is created (include/lambda_snark/batch.h lists the
     // variables): a context never changes the kernels that sign its commitments under the caller's feet
     struct Tuning {
@@ -94,15 +91,14 @@ struct LweContext {
     } tuning;
     // small commitment batches (a single legacy lwe_commit above all): stream keys and messages go up in ONE copy from page-locked memory
     static constexpr size_t kSmallInWords = 8192 + 256;
-    mutable uint64_t* host_in = nullptr;              // page-locked, kSmallInWords
+    mutable lsr::PinnedBuffer<uint64_t> host_in{hipHostMallocPortable};   // kSmallInWords
     mutable lsr::DeviceBuffer<uint64_t> ws_in;        // its device twin: [keys 4 b | messages b x msg_len]
     mutable lsr::DeviceBuffer<uint64_t> ws_body;      // lwe_verify_opening: the body u || v of one commitment
     // lsr_lwe_commit_keys_device: the seeds of a batch go up through a page-locked block of their own (the call is asynchronous:
     // ev_seeds = that copy has been read, the block may be rewritten)
-    mutable uint64_t* host_seeds = nullptr;
-    mutable size_t host_seeds_words = 0;
+    mutable lsr::PinnedBuffer<uint64_t> host_seeds{hipHostMallocPortable};
     mutable lsr::DeviceBuffer<uint64_t> ws_seeds;
-    mutable hipEvent_t ev_seeds = nullptr;
+    mutable lsr::Event ev_seeds;
 };
 
 namespace lsr {
@@ -153,24 +149,22 @@ static void matvec_square(const LweContext& c, uint64_t* out, const uint64_t* ma
 
 // staging of a batch's stream keys and messages (every commit path), grown on demand
 static void ensure_input_space(const LweContext& c, size_t batch) {
-    if (batch <= c.ws_in_batch) return;
-    c.ws_dm.allocate(batch * c.n);   // message slots of a batch (at most n per commitment); verify's message buffer
-    c.ws_keys.allocate(batch * 4);
-    LSR_HIP(hipMemset(c.ws_keys.ptr, 0xA5, batch * 32));   // never a valid stale key: a use before the upload shows up in the parity tests
-    if (!c.ws_flag.ptr) c.ws_flag.allocate(1);
-    c.ws_in_batch = batch;
+    c.ws_dm.reserve(batch * c.n);    // message slots of a batch (at most n per commitment); verify's message buffer
+    if (c.ws_keys.count < batch * 4) {
+        c.ws_keys.allocate(batch * 4);
+        LSR_HIP(hipMemset(c.ws_keys.ptr, 0xA5, batch * 32));   // never a valid stale key: a use before the upload shows up in the parity tests
+    }
+    c.ws_flag.reserve(1);
 }
 // arrays of the general (unfused) kernels
 static void ensure_workspace(const LweContext& c, size_t batch) {
     ensure_input_space(c, batch);
-    if (batch <= c.ws_batch) return;
     const size_t kn = (size_t)c.k * c.n;
-    c.ws_r.allocate(batch * kn);
-    c.ws_e1.allocate(batch * kn);
-    c.ws_u.allocate(batch * kn);
-    c.ws_e2.allocate(batch * c.n);
-    c.ws_v.allocate(batch * c.n);
-    c.ws_batch = batch;
+    c.ws_r.reserve(batch * kn);
+    c.ws_e1.reserve(batch * kn);
+    c.ws_u.reserve(batch * kn);
+    c.ws_e2.reserve(batch * c.n);
+    c.ws_v.reserve(batch * c.n);
 }
 
 // the fused pipeline exists for the FP64 flavour, two-pass degrees whose low pass is a full 4096-residue tile, ranks <= 4
@@ -220,7 +214,7 @@ static LweContext* create_lwe_context(const PublicParams* params, uint64_t key_s
                      64 - __builtin_clzll(q), n, k);
         return nullptr;
     }
-    c->ntt = create_ntt_context(q, n, device);
+    c->ntt.reset(create_ntt_context(q, n, device));
     if (!c->ntt) {
         std::fprintf(stderr, "lwe_context_create error: %s\n", last_error_cstr());
         return nullptr;
@@ -265,7 +259,6 @@ static LweContext* create_lwe_context(const PublicParams* params, uint64_t key_s
     } catch (const std::exception& e) {
         set_last_error(std::string("lwe_context_create: ") + e.what());
         std::fprintf(stderr, "lwe_context_create error: %s\n", e.what());
-        destroy_ntt_context(c->ntt);
         return nullptr;
     }
     return c.release();
@@ -275,57 +268,26 @@ static void destroy_lwe_context(LweContext* c) {
     if (!c) return;
     try {
         DeviceGuard guard(c->device);
-        if (c->ev_last) (void)hipEventSynchronize(c->ev_last);      // an asynchronous call still running on a caller's stream: let it finish first
+        try {
+            c->ev_last.sync();  // an asynchronous call still running on a caller's stream: let it finish first
+        } catch (...) {         // (the secrets are wiped all the same)
+        }
         // zeroize the secret key and the scratch that held commitment randomness (commitment.h:34)
+        // (ws_mid: the fused pipelines' chunk workspace holds transformed commitment randomness between their launches)
         volatile uint32_t* secret = c->keys.sec.w;
         for (int i = 0; i < 8; ++i) secret[i] = 0;
         volatile uint64_t* hk = c->ws_key_host.data();
         for (size_t i = 0; i < c->ws_key_host.size(); ++i) hk[i] = 0;
-        // (ws_mid: the fused pipelines' chunk workspace holds transformed commitment randomness between their launches)
-        for (lsr::DeviceBuffer<uint64_t>* b : {&c->s_hat, &c->ws_r, &c->ws_e1, &c->ws_e2, &c->ws_keys, &c->ws_mid})
-            if (b->ptr) (void)hipMemset(b->ptr, 0, b->count * 8);
+        c->host_in.wipe();
+        c->host_seeds.wipe();
+        for (DeviceBuffer<uint64_t>* b : {&c->s_hat, &c->ws_r, &c->ws_e1, &c->ws_e2, &c->ws_keys, &c->ws_mid, &c->ws_e1_slots, &c->ws_in, &c->ws_seeds})
+            b->wipe();
+        c->s_perm.wipe();
         (void)hipDeviceSynchronize();
-        c->a_hat.release(); c->s_hat.release(); c->b_hat.release(); c->cdf.release();
-        c->ws_r.release(); c->ws_e1.release(); c->ws_e2.release(); c->ws_u.release(); c->ws_v.release();
-        c->ws_dm.release(); c->ws_keys.release(); c->ws_flag.release();
-        c->a_perm.release(); c->ab_perm.release(); c->b_perm.release(); c->ws_mid.release(); c->ws_rows.release();
-        c->ws_vflags.release();
-        if (c->s_perm.ptr) (void)hipMemset(c->s_perm.ptr, 0, c->s_perm.count * 8);
-        c->s_perm.release();
-        if (c->ws_e1_slots.ptr) (void)hipMemset(c->ws_e1_slots.ptr, 0, c->ws_e1_slots.count * 8);
-        c->ws_e1_slots.release();
-        for (int i = 0; i < c->n_side; ++i) {
-            if (c->side[i]) (void)hipStreamDestroy(c->side[i]);
-            if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
-        }
-        if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-        if (c->ev_last) (void)hipEventDestroy(c->ev_last);
-        if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-        for (int i = 0; i < 2; ++i) {
-            if (c->ev_chunk[i]) (void)hipEventDestroy(c->ev_chunk[i]);
-            if (c->ev_copied[i]) (void)hipEventDestroy(c->ev_copied[i]);
-        }
-        if (c->host_stage) (void)hipHostFree(c->host_stage);
-        if (c->host_in) {
-            volatile uint64_t* hi = c->host_in;
-            for (size_t i = 0; i < LweContext::kSmallInWords; ++i) hi[i] = 0;
-            (void)hipHostFree(c->host_in);
-        }
-        if (c->ws_in.ptr) (void)hipMemset(c->ws_in.ptr, 0, c->ws_in.count * 8);
-        c->ws_in.release();
-        if (c->host_seeds) {
-            volatile uint64_t* hs = c->host_seeds;
-            for (size_t i = 0; i < c->host_seeds_words; ++i) hs[i] = 0;
-            (void)hipHostFree(c->host_seeds);
-        }
-        if (c->ws_seeds.ptr) (void)hipMemset(c->ws_seeds.ptr, 0, c->ws_seeds.count * 8);
-        c->ws_seeds.release();
-        if (c->ev_seeds) (void)hipEventDestroy(c->ev_seeds);
-        c->ws_body.release();
+        delete c;               // the members release themselves on the context's device, its NTT context last
     } catch (...) {
+        delete c;
     }
-    destroy_ntt_context(c->ntt);
-    delete c;
 }
 
 // Build-time constants of the chunk schedules (round 2 measured the alternatives: profiles/r02_mixed_launch.txt,
@@ -368,39 +330,33 @@ static void launch_mid(const LweContext& c, const uint64_t* ws, uint64_t* d_u, s
 // lanes 1.. of a chunk schedule (lane 0 is the caller's stream: every stream a process opens competes for the runtime's few
 // hardware queues, and two lanes that land on one queue overlap nothing — profiles/r02_commit_hw_queues.txt)
 static void ensure_side_streams(const LweContext& c, int lanes) {
-    while (c.n_side < lanes - 1) {
-        LSR_HIP(hipStreamCreateWithFlags(&c.side[c.n_side], hipStreamNonBlocking));
-        LSR_HIP(hipEventCreateWithFlags(&c.ev_join[c.n_side], hipEventDisableTiming));
-        ++c.n_side;
-    }
-    if (!c.ev_fork) LSR_HIP(hipEventCreateWithFlags(&c.ev_fork, hipEventDisableTiming));
+    for (int i = 0; i < lanes - 1; ++i)
+        if (!c.side[i].handle) LSR_HIP(hipStreamCreateWithFlags(&c.side[i].handle, hipStreamNonBlocking));
 }
 static void fork_lanes(const LweContext& c, hipStream_t s, int lanes) {
     if (lanes <= 1) return;
-    LSR_HIP(hipEventRecord(c.ev_fork, s));
-    for (int i = 1; i < lanes; ++i) LSR_HIP(hipStreamWaitEvent(c.side[i - 1], c.ev_fork, 0));
+    c.ev_fork.record(s);
+    for (int i = 1; i < lanes; ++i) c.ev_fork.wait(c.side[i - 1]);
 }
 static void join_lanes(const LweContext& c, hipStream_t s, int lanes) {
     for (int i = 1; i < lanes; ++i) {
-        LSR_HIP(hipEventRecord(c.ev_join[i - 1], c.side[i - 1]));
-        LSR_HIP(hipStreamWaitEvent(s, c.ev_join[i - 1], 0));
+        c.ev_join[i - 1].record(c.side[i - 1]);
+        c.ev_join[i - 1].wait(s);
     }
 }
 
 // bracket of an asynchronous entry point (caller holds c.mutex): order this call behind the previous one on the same context
 // (a stream that records into a HIP graph: no bracket — lsr_runtime.hpp, stream_is_capturing)
 static void begin_async(const LweContext& c, hipStream_t s) {
-    if (c.ev_last && !stream_is_capturing(s)) LSR_HIP(hipStreamWaitEvent(s, c.ev_last, 0));
+    if (!stream_is_capturing(s)) c.ev_last.wait(s);
 }
 static void end_async(const LweContext& c, hipStream_t s) {
-    if (stream_is_capturing(s)) return;
-    if (!c.ev_last) LSR_HIP(hipEventCreateWithFlags(&c.ev_last, hipEventDisableTiming));
-    LSR_HIP(hipEventRecord(c.ev_last, s));
+    if (!stream_is_capturing(s)) c.ev_last.record(s);
 }
 // a SYNCHRONOUS entry point (its work runs on the context's own stream and is complete when it returns; caller holds c.mutex):
 // an asynchronous call enqueued earlier on a caller's stream may still be using the workspaces — wait for it first
 static void wait_for_async(const LweContext& c) {
-    if (c.ev_last) LSR_HIP(hipEventSynchronize(c.ev_last));
+    c.ev_last.sync();
 }
 
 // MIXED schedule of the 4 + 12 pipeline (n = 2^16, blinding residues given; caller holds c.mutex): launch t carries the
@@ -426,7 +382,7 @@ static void mlwe_matvec_mixed(const LweContext& c, const uint64_t* d_r, const ui
     // (3.05 -> 2.95 ms per 1024 vectors, profiles/r02_mixed_launch.txt)
     const int lanes = static_cast<int>(std::min<long>(kMixedLanes, chunks));
     const size_t slot_words = std::min(chunk, batch) * vec_words;
-    if (c.ws_mid.count < slot_words * 2 * lanes) c.ws_mid.allocate(slot_words * 2 * lanes);
+    c.ws_mid.reserve(slot_words * 2 * lanes);
     ensure_side_streams(c, lanes);
     fork_lanes(c, s, lanes);
     for (long t = -1;; ++t) {
@@ -507,10 +463,10 @@ static void mlwe_matvec_fused(const LweContext& c, const uint64_t* d_r, const ui
     ensure_side_streams(c, streams);
     auto lane = [&](size_t i) { return i == 0 ? s : c.side[i - 1]; };
     const size_t slot_words = std::min(chunk, batch) * vec_words;
-    if (c.ws_mid.count < slot_words * streams) c.ws_mid.allocate(slot_words * streams);
+    c.ws_mid.reserve(slot_words * streams);
     const bool split_sampling = sample && c.cdf_entries <= 127;
     const size_t side_words = slot_words / 16;                    // int8 samples of half the rows: 1/16 of the chunk's words
-    if (split_sampling && c.ws_e1_slots.count < side_words * streams) c.ws_e1_slots.allocate(side_words * streams);
+    if (split_sampling) c.ws_e1_slots.reserve(side_words * streams);
     fork_lanes(c, s, streams);
     size_t index = 0;
     for (size_t first = 0; first < batch; first += chunk, ++index) {
@@ -549,16 +505,6 @@ static void mlwe_matvec_device(const LweContext& c, uint64_t* d_r, const uint64_
     matvec_square(c, d_u, c.a_hat.ptr, d_r, nullptr, true, batch, s);
     // inverse transform with the blinding add fused into its final store
     launch_ntt(*c.ntt, d_u, batch * k, true, s, d_e1);
-}
-
-// pinned host staging (guarded by c.mutex), grown on demand
-static void ensure_host_stage(const LweContext& c, size_t words) {
-    if (words <= c.host_stage_words) return;
-    if (c.host_stage) (void)hipHostFree(c.host_stage);
-    c.host_stage = nullptr;
-    c.host_stage_words = 0;
-    LSR_HIP(hipHostMalloc(reinterpret_cast<void**>(&c.host_stage), words * 8, hipHostMallocPortable));   // any device of the node may DMA into it
-    c.host_stage_words = words;
 }
 
 static LweCommitment* new_commitment(size_t words) {
@@ -635,13 +581,11 @@ static void stage_commit_inputs(const LweContext& c, const uint64_t* messages, s
     if (in_words <= LweContext::kSmallInWords) {
         // one upload from page-locked memory instead of two staged ones (every caller synchronises the stream before it returns, so
         // the staging area is free again by the next call)
-        if (!c.host_in) {
-            LSR_HIP(hipHostMalloc(reinterpret_cast<void**>(&c.host_in), LweContext::kSmallInWords * 8, hipHostMallocPortable));
-            c.ws_in.allocate(LweContext::kSmallInWords);
-        }
-        std::memcpy(c.host_in, key_host.data(), batch * 32);
-        if (copy) std::memcpy(c.host_in + batch * 4, messages, batch * msg_len * 8);
-        LSR_HIP(hipMemcpyAsync(c.ws_in.ptr, c.host_in, in_words * 8, hipMemcpyHostToDevice, s));
+        c.host_in.reserve(LweContext::kSmallInWords);
+        c.ws_in.reserve(LweContext::kSmallInWords);
+        std::memcpy(c.host_in.ptr, key_host.data(), batch * 32);
+        if (copy) std::memcpy(c.host_in.ptr + batch * 4, messages, batch * msg_len * 8);
+        LSR_HIP(hipMemcpyAsync(c.ws_in.ptr, c.host_in.ptr, in_words * 8, hipMemcpyHostToDevice, s));
         in->d_keys = c.ws_in.ptr;
         in->d_msgs = c.ws_in.ptr + batch * 4;
         return;
@@ -725,7 +669,7 @@ static void commit_rows_fused(const LweContext& c, const uint64_t* d_msgs, size_
     const int streams = static_cast<int>(std::min<size_t>((size_t)kFusedStreams, (batch + chunk - 1) / chunk));
     ensure_side_streams(c, streams);
     const size_t slot_words = std::min(chunk, batch) * vec_words;
-    if (c.ws_mid.count < slot_words * streams) c.ws_mid.allocate(slot_words * streams);
+    c.ws_mid.reserve(slot_words * streams);
     const RoundConsts<ArithF64> cs{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64};
     const int r = c.logn - 12, lo = 12;                                  // top R = 4 (n = 2^16) or 5 (2^17) index bits in the outer rounds
     fork_lanes(c, s, streams);
@@ -771,20 +715,16 @@ static void commit_rows_device(const LweContext& c, const uint64_t* d_msgs, size
 }
 
 static void ensure_copy_stream(const LweContext& c) {
-    if (c.copy_stream) return;
+    if (c.copy_stream.handle) return;
     // A stream of ANOTHER priority than the compute streams: the runtime multiplexes a process's streams onto a few hardware queues
     // per priority level, and a copy stream that lands on the compute stream's queue serialises with it — the copy of piece i then
     // sits in front of piece i + 1's kernels and nothing overlaps (seen in bench.py, whose process has opened a dozen streams by then:
     // 5.7 ms per 2048 rows against 3.9 ms in a fresh process; profiles/r02_commit_hw_queues.txt is the same effect between lanes).
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || least == greatest ||
-        hipStreamCreateWithPriority(&c.copy_stream, hipStreamNonBlocking, greatest) != hipSuccess) {
+        hipStreamCreateWithPriority(&c.copy_stream.handle, hipStreamNonBlocking, greatest) != hipSuccess) {
         (void)hipGetLastError();
-        LSR_HIP(hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking));
-    }
-    for (int i = 0; i < 2; ++i) {
-        LSR_HIP(hipEventCreateWithFlags(&c.ev_chunk[i], hipEventDisableTiming));
-        LSR_HIP(hipEventCreateWithFlags(&c.ev_copied[i], hipEventDisableTiming));
+        LSR_HIP(hipStreamCreateWithFlags(&c.copy_stream.handle, hipStreamNonBlocking));
     }
 }
 
@@ -797,21 +737,21 @@ static void commit_batch_flat_host(const LweContext& c, const uint64_t* messages
     ensure_copy_stream(c);
     const size_t slot = std::min(chunk, batch) * words;
     const bool two = batch > chunk;
-    if (c.ws_rows.count < slot * (two ? 2 : 1)) c.ws_rows.allocate(slot * (two ? 2 : 1));
+    c.ws_rows.reserve(slot * (two ? 2 : 1));
     size_t index = 0;
     try {
         for (size_t done = 0; done < batch; done += chunk, ++index) {
             const size_t now = std::min(chunk, batch - done);
             const int b = static_cast<int>(index & 1);
             uint64_t* const rows = c.ws_rows.ptr + (two ? b * slot : 0);
-            if (index >= 2) LSR_HIP(hipEventSynchronize(c.ev_copied[b]));            // this buffer's previous rows have left
+            if (index >= 2) c.ev_copied[b].sync();                                   // this buffer's previous rows have left
             StagedInputs in;
             stage_commit_inputs(c, messages + done * msg_len, msg_len, now, seeds ? seeds + done : nullptr, s, &in);
             commit_rows_device(c, in.d_msgs, msg_len, now, in.d_keys, rows, s);
-            LSR_HIP(hipEventRecord(c.ev_chunk[b], s));
-            LSR_HIP(hipStreamWaitEvent(c.copy_stream, c.ev_chunk[b], 0));
+            c.ev_chunk[b].record(s);
+            c.ev_chunk[b].wait(c.copy_stream);
             LSR_HIP(hipMemcpyAsync(out_words + done * words, rows, now * words * 8, hipMemcpyDeviceToHost, c.copy_stream));
-            LSR_HIP(hipEventRecord(c.ev_copied[b], c.copy_stream));
+            c.ev_copied[b].record(c.copy_stream);
             LSR_HIP(hipStreamSynchronize(s));      // the staging areas of the inputs (pinned host block, key vector) are reused by the next chunk
         }
     } catch (...) {
@@ -832,7 +772,7 @@ static void commit_chunk_flat(const LweContext& c, const uint64_t* messages, siz
     stage_commit_inputs(c, messages, msg_len, batch, seeds, s, &in);
     uint64_t* rows = out_words;
     if (!to_device) {
-        if (c.ws_rows.count < batch * words) c.ws_rows.allocate(batch * words);
+        c.ws_rows.reserve(batch * words);
         rows = c.ws_rows.ptr;
     }
     commit_rows_device(c, in.d_msgs, msg_len, batch, in.d_keys, rows, s);
@@ -845,12 +785,12 @@ static void commit_chunk(const LweContext& c, const uint64_t* messages, size_t m
     hipStream_t s = work_stream(*c.ntt);
     StagedInputs in;
     stage_commit_inputs(c, messages, msg_len, batch, seeds, s, &in);
-    if (c.ws_rows.count < batch * words) c.ws_rows.allocate(batch * words);
+    c.ws_rows.reserve(batch * words);
     commit_rows_device(c, in.d_msgs, msg_len, batch, in.d_keys, c.ws_rows.ptr, s);
     // gather: the rows of the whole chunk come back in one bulk copy into pinned memory; the per-commitment arrays (which the ABI
     // wants as separate new[] allocations, commitment.cpp:50-57) are filled from there by a few threads
-    ensure_host_stage(c, batch * words);
-    LSR_HIP(hipMemcpyAsync(c.host_stage, c.ws_rows.ptr, batch * words * 8, hipMemcpyDeviceToHost, s));
+    c.host_stage.reserve(batch * words);
+    LSR_HIP(hipMemcpyAsync(c.host_stage.ptr, c.ws_rows.ptr, batch * words * 8, hipMemcpyDeviceToHost, s));
     std::vector<LweCommitment*> made(batch, nullptr);
     const size_t workers = std::min<size_t>(8, std::max<size_t>(1, (batch * words * 8) >> 22));   // one thread per ~4 MiB, at most 8
     const size_t per = (batch + workers - 1) / workers;
@@ -881,7 +821,7 @@ static void commit_chunk(const LweContext& c, const uint64_t* messages, size_t m
         throw HipFailure(std::string("hipStreamSynchronize: ") + hipGetErrorString(synced));
     }
     in_parallel([&](size_t lo, size_t hi) {
-        for (size_t j = lo; j < hi; ++j) std::memcpy(made[j]->data, c.host_stage + j * words, words * 8);
+        for (size_t j = lo; j < hi; ++j) std::memcpy(made[j]->data, c.host_stage.ptr + j * words, words * 8);
     });
     for (size_t j = 0; j < batch; ++j) out[j] = made[j];
 }
@@ -915,7 +855,7 @@ static void verify_rows_device(const LweContext& c, const uint64_t* d_rows, cons
     const size_t kn = (size_t)k * n, row = kHeaderWords + kn + n;
     // one allocation, one clear, one copy back: [flags: count x u64 | bad: count x u32]
     const size_t state_words = count + (count + 1) / 2;
-    if (c.ws_vflags.count < state_words) c.ws_vflags.allocate(state_words);
+    c.ws_vflags.reserve(state_words);
     c.ws_vbad = reinterpret_cast<uint32_t*>(c.ws_vflags.ptr + count);
     zero_words_async(reinterpret_cast<uint64_t*>(c.ws_vflags.ptr), state_words, s);
     if (c.s_perm.ptr && c.logn == 12) {     // one launch, one workgroup per opening: the row is read once (lsr_commit_tile.hpp)
@@ -937,7 +877,7 @@ static void verify_rows_device(const LweContext& c, const uint64_t* d_rows, cons
         const int streams = static_cast<int>(std::min<size_t>((size_t)kVerifyStreams, (count + chunk - 1) / chunk));
         ensure_side_streams(c, streams);
         const size_t slot_words = slot * (vec_words + n);
-        if (c.ws_mid.count < slot_words * streams) c.ws_mid.allocate(slot_words * streams);
+        c.ws_mid.reserve(slot_words * streams);
         const RoundConsts<ArithF64> cs{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64};
         const int r = c.logn - 12, lo = 12;
         fork_lanes(c, s, streams);                    // behind the clear of the verdict state above
@@ -990,7 +930,7 @@ static size_t verify_chunk(const LweContext& c, size_t count) {
 static void verify_host_rows(const LweContext& c, const uint64_t* rows, const uint64_t* messages, size_t msg_len, size_t count, int* results, hipStream_t s) {
     const size_t row = kHeaderWords + ((size_t)c.k + 1) * c.n;
     const size_t chunk = verify_chunk(c, count);
-    if (c.ws_rows.count < chunk * row) c.ws_rows.allocate(chunk * row);
+    c.ws_rows.reserve(chunk * row);
     ensure_input_space(c, chunk);                            // ws_dm: chunk x n message slots (msg_len <= n here), no allocation per call
     uint64_t* const d_msgs = c.ws_dm.ptr;
     std::vector<unsigned long long> state(chunk + (chunk + 1) / 2);
@@ -1051,9 +991,9 @@ static void verify_opening_batch(const LweContext& c, const LweCommitment* const
     wait_for_async(c);
     hipStream_t s = work_stream(*c.ntt);
     const size_t chunk = verify_chunk(c, live.size());
-    ensure_host_stage(c, chunk * (row + msg_len));
-    uint64_t* const h_rows = c.host_stage;
-    uint64_t* const h_msgs = c.host_stage + chunk * row;
+    c.host_stage.reserve(chunk * (row + msg_len));
+    uint64_t* const h_rows = c.host_stage.ptr;
+    uint64_t* const h_msgs = c.host_stage.ptr + chunk * row;
     std::vector<int> part(chunk);
     for (size_t first = 0; first < live.size(); first += chunk) {
         const size_t now = std::min(chunk, live.size() - first);
@@ -1108,9 +1048,9 @@ static LweCommitment* linear_combine(const LweContext& c, const LweCommitment** 
     // bodies are gathered `group` at a time (<= 64 MiB) in pinned memory, uploaded in one copy and folded in by one kernel
     const size_t group = std::max<size_t>(1, std::min<size_t>(count, (size_t(64) << 20) / (body_words * 8)));
     DeviceBuffer<uint64_t> acc(body_words), terms(group * body_words), d_coeffs(group);
-    ensure_host_stage(c, group * (body_words + 1));
-    uint64_t* const h_terms = c.host_stage;
-    uint64_t* const h_coeffs = c.host_stage + group * body_words;
+    c.host_stage.reserve(group * (body_words + 1));
+    uint64_t* const h_terms = c.host_stage.ptr;
+    uint64_t* const h_coeffs = c.host_stage.ptr + group * body_words;
     LSR_HIP(hipMemsetAsync(acc.ptr, 0, body_words * 8, s));
     // noise budget of the result: sum_i |c_i| (centred mod t) fresh-commitment noises must still decode (8-sigma tail below Delta / 2).
     // The reference's 72-bit SEAL modulus absorbs any c_i < t (commitment.cpp:88-96,247-266); a 44-bit modulus does not, and a
@@ -1264,7 +1204,7 @@ uint64_t lsr_lwe_plain_modulus(const LweContext* ctx) noexcept { return ctx ? ct
 uint32_t lsr_lwe_ring_degree(const LweContext* ctx) noexcept { return ctx ? ctx->n : 0; }
 uint32_t lsr_lwe_module_rank(const LweContext* ctx) noexcept { return ctx ? ctx->k : 0; }
 size_t lsr_lwe_commitment_words(const LweContext* ctx) noexcept { return ctx ? lsr::kHeaderWords + (size_t)(ctx->k + 1) * ctx->n : 0; }
-const NttContext* lsr_lwe_ntt_context(const LweContext* ctx) noexcept { return ctx ? ctx->ntt : nullptr; }
+const NttContext* lsr_lwe_ntt_context(const LweContext* ctx) noexcept { return ctx ? ctx->ntt.get() : nullptr; }
 
 int lsr_lwe_public_matrix(const LweContext* ctx, uint64_t* a_hat) noexcept {
     if (!ctx || !a_hat) return -1;
@@ -1388,23 +1328,15 @@ int lsr_lwe_commit_keys_device(LweContext* ctx, const uint64_t* d_messages, size
             return -1;
         }
         lsr::begin_async(*ctx, s);
-        if (ctx->ev_seeds) LSR_HIP(hipEventSynchronize(ctx->ev_seeds));       // the previous call's upload has left the page-locked block
-        if (ctx->host_seeds_words < batch) {
-            if (ctx->host_seeds) {
-                std::memset(ctx->host_seeds, 0, ctx->host_seeds_words * 8);
-                LSR_HIP(hipHostFree(ctx->host_seeds));
-                ctx->host_seeds = nullptr;
-                ctx->host_seeds_words = 0;
-            }
-            const size_t words = std::max<size_t>(batch, 4096);
-            LSR_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->host_seeds), words * 8, hipHostMallocPortable));
-            ctx->host_seeds_words = words;
+        ctx->ev_seeds.sync();       // the previous call's upload has left the page-locked block
+        if (ctx->host_seeds.count < batch) {
+            ctx->host_seeds.wipe();
+            ctx->host_seeds.allocate(std::max<size_t>(batch, 4096));
         }
         if (ctx->ws_seeds.count < batch) ctx->ws_seeds.allocate(std::max<size_t>(batch, 4096));
-        std::memcpy(ctx->host_seeds, seeds, batch * 8);
-        LSR_HIP(hipMemcpyAsync(ctx->ws_seeds.ptr, ctx->host_seeds, batch * 8, hipMemcpyHostToDevice, s));
-        if (!ctx->ev_seeds) LSR_HIP(hipEventCreateWithFlags(&ctx->ev_seeds, hipEventDisableTiming));
-        LSR_HIP(hipEventRecord(ctx->ev_seeds, s));
+        std::memcpy(ctx->host_seeds.ptr, seeds, batch * 8);
+        LSR_HIP(hipMemcpyAsync(ctx->ws_seeds.ptr, ctx->host_seeds.ptr, batch * 8, hipMemcpyHostToDevice, s));
+        ctx->ev_seeds.record(s);
         lsr::launch_commit_keys(*ctx, d_messages, msg_len, batch, ctx->ws_seeds.ptr, d_keys, s);
         lsr::end_async(*ctx, s);
         return 0;
@@ -1609,25 +1541,17 @@ static int mlwe_matvec_batch_sharded(LweContext* const* ctxs, int shards, uint64
         // takes about max(compute, gather) + one piece instead of their sum.  Eight pieces, at least 32 vectors each (one chunk of the
         // mixed-launch schedule at rank 4)
         const size_t piece = std::max<size_t>(std::min<size_t>(count, 32), (count + 7) / 8);
-        std::vector<hipEvent_t> done_ev;
-        hipEvent_t first_copy = nullptr, last_kernel = nullptr;
-        LSR_HIP(hipEventCreate(&first_copy));
-        LSR_HIP(hipEventCreate(&last_kernel));
+        std::vector<lsr::Event> done((count + piece - 1) / piece);   // destroyed after the catch below has drained both streams
         const auto t0 = std::chrono::steady_clock::now();
         try {
             for (size_t lo = 0; lo < count; lo += piece) {
                 const size_t now = std::min(piece, count - lo);
                 lsr::mlwe_matvec_device(c, d_r[g] + lo * vec_words, d_e1[g] + lo * vec_words, d_u.ptr + lo * vec_words, now, s, true);
-                hipEvent_t ev = nullptr;
-                LSR_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                done_ev.push_back(ev);
-                LSR_HIP(hipEventRecord(ev, s));
-                LSR_HIP(hipStreamWaitEvent(c.copy_stream, ev, 0));
-                if (lo == 0) LSR_HIP(hipEventRecord(first_copy, c.copy_stream));
+                done[lo / piece].record(s);
+                done[lo / piece].wait(c.copy_stream);
                 // this shard's slice goes straight into its place in the caller's single (ideally pinned) array
                 LSR_HIP(hipMemcpyAsync(host_u + (first + lo) * vec_words, d_u.ptr + lo * vec_words, now * vec_words * 8, hipMemcpyDeviceToHost, c.copy_stream));
             }
-            LSR_HIP(hipEventRecord(last_kernel, s));
             LSR_HIP(hipStreamSynchronize(s));
             const auto t1 = std::chrono::steady_clock::now();
             LSR_HIP(hipStreamSynchronize(c.copy_stream));
@@ -1637,12 +1561,8 @@ static int mlwe_matvec_batch_sharded(LweContext* const* ctxs, int shards, uint64
         } catch (...) {
             (void)hipStreamSynchronize(s);
             (void)hipStreamSynchronize(c.copy_stream);
-            for (hipEvent_t ev : done_ev) (void)hipEventDestroy(ev);
-            (void)hipEventDestroy(first_copy); (void)hipEventDestroy(last_kernel);
             throw;
         }
-        for (hipEvent_t ev : done_ev) (void)hipEventDestroy(ev);
-        (void)hipEventDestroy(first_copy); (void)hipEventDestroy(last_kernel);
     });
     if (seconds) {
         seconds[0] = *std::max_element(compute.begin(), compute.end());

@@ -57,8 +57,8 @@ struct LagrangeProver {
     DeviceBuffer<uint64_t> tser;           // [max(1, m - 1)]: T 2^128
     DeviceBuffer<uint64_t> zh_s, zh_m;     // [m + 1]: Z_H 2^128, Z_H 2^64
     std::mutex mutex;                      // guards the workspace and `stream`
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_last = nullptr;          // end of the last asynchronous call: the next call (any stream) starts behind it
+    Stream stream;
+    Event ev_last;                         // end of the last asynchronous call: the next call (any stream) starts behind it
     int chunk_log2 = 26;                   // LAMBDA_SNARK_QUOTIENT_CHUNK_LOG2, read once at creation
     // workspace for ws.chunk instances
     R1csScratch ws;                        // per-instance scratch and host staging
@@ -139,18 +139,11 @@ void lagrange_destroy(LagrangeProver* p) {
     if (!p) return;
     try {
         DeviceGuard guard(p->device);
-        if (p->ev_last) {
-            (void)hipEventSynchronize(p->ev_last);
-            (void)hipEventDestroy(p->ev_last);
-        }
-        if (p->stream) (void)hipStreamDestroy(p->stream);
-        for (int k = 0; k < 3; ++k) { p->row_ptr[k].release(); p->col[k].release(); p->val[k].release(); }
-        p->lt.release(); p->tser.release(); p->zh_s.release(); p->zh_m.release();
-        p->witness.release(); p->evals.release(); p->coef.release(); p->top.release(); p->quot.release(); p->qp.release(); p->msg.release();
-        p->flags.release(); p->ws.release();
+        p->ev_last.sync();
+        delete p;
     } catch (...) {
+        delete p;
     }
-    delete p;
 }
 
 int lagrange_device(const LagrangeProver* p) { return p ? p->device : -1; }
@@ -167,33 +160,10 @@ LagrangeProver* lagrange_create(const SparseMatrix* const mats[3], uint64_t q, i
         set_last_error(std::string(where) + ": the Lagrange path takes 1 <= m <= 8192 constraints");
         return nullptr;
     }
-    for (int k = 0; k < 3; ++k) {
-        if (mats[k]->n_rows != m || mats[k]->n_cols != n_vars || (mats[k]->n_entries && !mats[k]->entries) || mats[k]->n_entries > 0xFFFFFFF0ull) {
-            set_last_error(std::string(where) + ": A, B, C must share one shape");
-            return nullptr;
-        }
-        for (size_t e = 0; e < mats[k]->n_entries; ++e)
-            if (mats[k]->entries[e].row >= m || mats[k]->entries[e].col >= n_vars) {
-                set_last_error(std::string(where) + ": entry outside the matrix");
-                return nullptr;
-            }
-    }
-    if (n_vars == 0) {
-        set_last_error(std::string(where) + ": no variables");
-        return nullptr;
-    }
-    const int devices = visible_device_count();
-    if (devices <= 0) {
-        set_last_error(std::string(where) + ": no HIP device visible — this library has no CPU fallback");
-        return nullptr;
-    }
-    if (device < 0) device = default_device();
+    if (!r1cs_shape_ok(where, mats)) return nullptr;
+    device = resolve_device(where, device, false);
     if (device < 0) return nullptr;
-    if (device >= devices) {
-        set_last_error(std::string(where) + ": device index out of range");
-        return nullptr;
-    }
-    auto* p = new LagrangeProver;
+    LagrangeProverPtr p(new LagrangeProver);
     p->m = m;
     p->n_vars = n_vars;
     p->q = q;
@@ -208,33 +178,16 @@ LagrangeProver* lagrange_create(const SparseMatrix* const mats[3], uint64_t q, i
         std::string why;
         if (!build_tables(*p, why)) {
             set_last_error(std::string(where) + ": " + why);
-            lagrange_destroy(p);
             return nullptr;
         }
-        for (int k = 0; k < 3; ++k) {   // coordinate form -> CSR (stable counting sort by row)
-            const SparseMatrix& A = *mats[k];
-            std::vector<uint32_t> ptr(m + 1, 0), cols(A.n_entries);
-            std::vector<uint64_t> vals(A.n_entries);
-            for (size_t e = 0; e < A.n_entries; ++e) ++ptr[A.entries[e].row + 1];
-            for (uint32_t i = 0; i < m; ++i) ptr[i + 1] += ptr[i];
-            std::vector<uint32_t> cursor(ptr.begin(), ptr.end() - 1);
-            for (size_t e = 0; e < A.n_entries; ++e) {
-                const uint32_t at = cursor[A.entries[e].row]++;
-                cols[at] = A.entries[e].col;
-                vals[at] = mq_to(A.entries[e].value, p->M);              // (val mod q) 2^64
-            }
-            p->row_ptr[k].upload(ptr);
-            if (A.n_entries == 0) { cols.push_back(0); vals.push_back(0); }
-            p->col[k].upload(cols);
-            p->val[k].upload(vals);
-        }
-        LSR_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+        const MontQ& M = p->M;
+        upload_csr(mats, p->row_ptr, p->col, p->val, [&](uint64_t v) { return mq_to(v, M); });   // (val mod q) 2^64
+        LSR_HIP(hipStreamCreateWithFlags(&p->stream.handle, hipStreamNonBlocking));
     } catch (const std::exception& e) {
         set_last_error(std::string(where) + ": " + e.what());
-        lagrange_destroy(p);
         return nullptr;
     }
-    return p;
+    return p.release();
 }
 
 // ---- the pipeline ------------------------------------------------------------------------------------------------------------
@@ -243,16 +196,16 @@ static size_t chunk_for(const LagrangeProver& p, size_t batch) {
 }
 
 static void ensure_workspace(LagrangeProver& p, size_t chunk, size_t n_public) {
-    if (!p.ws.grow(chunk, n_public)) return;
-    const size_t m = p.m, c = p.ws.chunk;
-    p.witness.allocate(c * p.n_vars);
-    p.evals.allocate(3 * c * m);
-    p.coef.allocate(3 * c * m);
-    p.top.allocate(c * std::max<size_t>(1, m - 1));
-    p.quot.allocate(c * m);
-    p.qp.allocate(c * (m + 1));
-    p.msg.allocate(c * (m + 1));
-    p.flags.allocate(2 * c);
+    const size_t m = p.m, c = std::max(p.ws.chunk, chunk);
+    p.witness.reserve(c * p.n_vars);
+    p.evals.reserve(3 * c * m);
+    p.coef.reserve(3 * c * m);
+    p.top.reserve(c * std::max<size_t>(1, m - 1));
+    p.quot.reserve(c * m);
+    p.qp.reserve(c * (m + 1));
+    p.msg.reserve(c * (m + 1));
+    p.flags.reserve(2 * c);
+    p.ws.grow(c, n_public);
 }
 
 // constraint evaluations of `count` witnesses (device, [count][n_vars]) into p.evals; interpolation into p.coef (interp); the
@@ -293,7 +246,7 @@ void lagrange_host_run(LagrangeProver& p, const uint64_t* w, size_t batch, uint6
                        uint32_t* len) {
     DeviceGuard guard(p.device);
     std::lock_guard<std::mutex> lock(p.mutex);
-    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
+    p.ev_last.sync();
     const size_t chunk = chunk_for(p, batch);
     ensure_workspace(p, chunk, 0);
     hipStream_t s = p.stream;

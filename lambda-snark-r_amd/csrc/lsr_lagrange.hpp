@@ -19,6 +19,7 @@ constexpr uint64_t kQuirkModulus = 17592169062401ull;   // NTT_FRIENDLY_MODULUS,
 // nullptr (+ lsr_last_error) on bad shapes, an even q or q < 3, m outside [1, 8192], a non-unit interpolation denominator, or no GPU
 LagrangeProver* lagrange_create(const SparseMatrix* const mats[3], uint64_t q, int device);
 void lagrange_destroy(LagrangeProver* p);
+using LagrangeProverPtr = std::unique_ptr<LagrangeProver, HandleDeleter<LagrangeProver, lagrange_destroy>>;
 int lagrange_device(const LagrangeProver* p);
 bool lagrange_omega_domain(const LagrangeProver* p);
 

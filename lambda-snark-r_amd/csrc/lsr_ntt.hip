@@ -98,22 +98,25 @@ static ModParams make_mod_params(uint64_t q, int logn) {
     return p;
 }
 
-static NttContext* build_context(const char* where, uint64_t q, uint32_t n, int logn, int device, const TwiddleTables& tw, bool cyclic) {
+int resolve_device(const char* where, int device, bool announce) {
     const int devices = visible_device_count();
     if (devices <= 0) {
         set_last_error(std::string(where) + ": no HIP device visible — this library has no CPU fallback");
-        std::fprintf(stderr, "lambda_snark_core: no HIP device visible; the MI355X backend has no CPU fallback\n");
-        return nullptr;
+        if (announce) std::fprintf(stderr, "lambda_snark_core: no HIP device visible; the MI355X backend has no CPU fallback\n");
+        return -1;
     }
-    if (device < 0) {
-        device = default_device();
-        if (device < 0) return nullptr;                      // message already set
-    }
+    if (device < 0) return default_device();                 // -1 with its message when that names no visible device
     if (device >= devices) {
         set_last_error(std::string(where) + ": device index out of range");
-        return nullptr;
+        return -1;
     }
-    auto* ctx = new NttContext;
+    return device;
+}
+
+static NttContext* build_context(const char* where, uint64_t q, uint32_t n, int logn, int device, const TwiddleTables& tw, bool cyclic) {
+    device = resolve_device(where, device, true);
+    if (device < 0) return nullptr;
+    NttContextPtr ctx(new NttContext);
     try {
         DeviceGuard guard(device);
         ctx->modulus = q;
@@ -161,10 +164,9 @@ static NttContext* build_context(const char* where, uint64_t q, uint32_t n, int 
     } catch (const std::exception& e) {
         set_last_error(std::string(where) + ": " + e.what());
         std::fprintf(stderr, "lambda_snark_core: %s failed: %s\n", where, e.what());
-        destroy_ntt_context(ctx);
         return nullptr;
     }
-    return ctx;
+    return ctx.release();
 }
 
 NttContext* create_ntt_context(uint64_t q, uint32_t n, int device) {
@@ -193,9 +195,9 @@ NttContext* create_cyclic_ntt_context(uint64_t q, uint32_t n, uint64_t omega, in
 
 hipStream_t work_stream(const NttContext& c) {
     std::lock_guard<std::mutex> lock(c.stream_mutex);
-    if (!c.stream) {
+    if (!c.stream.handle) {
         DeviceGuard guard(c.device);
-        LSR_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+        LSR_HIP(hipStreamCreateWithFlags(&c.stream.handle, hipStreamNonBlocking));
     }
     return c.stream;
 }
@@ -204,22 +206,11 @@ void destroy_ntt_context(NttContext* ctx) {
     if (!ctx) return;
     try {
         DeviceGuard guard(ctx->device);
-        if (ctx->ring_event) {                      // a ring multiply still in flight may be using ring_scratch
-            (void)hipEventSynchronize(ctx->ring_event);
-            (void)hipEventDestroy(ctx->ring_event);
-        }
-        ctx->ring_scratch.release();
-        if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-        ctx->staging.release();
-        ctx->fwd_f64.release();
-        ctx->inv_f64.release();
-        ctx->fwd_u64.release();
-        ctx->inv_u64.release();
-        ctx->fwd_gold.release();
-        ctx->inv_gold.release();
+        ctx->ring_event.sync();                     // a ring multiply still in flight may be using ring_scratch
+        delete ctx;
     } catch (...) {
+        delete ctx;
     }
-    delete ctx;
 }
 
 // ------------------------------------------------------------------------------------------------

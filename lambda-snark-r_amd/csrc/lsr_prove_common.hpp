@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "lambda_snark/batch.h"
+#include "lambda_snark/r1cs.h"
 #include "lsr_runtime.hpp"
 
 namespace lsr {
@@ -50,14 +51,61 @@ int abi_prove_device(const char* where, const char* host_call, const uint64_t* s
     });
 }
 
+// ---- the R1CS matrices of a prover, both R1CS paths ---------------------------------------------------------------------------------
+
+// A, B, C share one m x n_vars shape, n_vars > 0, and every entry lies inside it; else false and lsr_last_error "<where>: <why>"
+inline bool r1cs_shape_ok(const char* where, const SparseMatrix* const mats[3]) {
+    const uint32_t m = mats[0]->n_rows, n_vars = mats[0]->n_cols;
+    for (int k = 0; k < 3; ++k) {
+        if (mats[k]->n_rows != m || mats[k]->n_cols != n_vars || (mats[k]->n_entries && !mats[k]->entries) || mats[k]->n_entries > 0xFFFFFFF0ull) {
+            set_last_error(std::string(where) + ": A, B, C must share one shape");
+            return false;
+        }
+        for (size_t e = 0; e < mats[k]->n_entries; ++e)
+            if (mats[k]->entries[e].row >= m || mats[k]->entries[e].col >= n_vars) {
+                set_last_error(std::string(where) + ": entry outside the matrix");
+                return false;
+            }
+    }
+    if (n_vars == 0) {
+        set_last_error(std::string(where) + ": no variables");
+        return false;
+    }
+    return true;
+}
+
+// the coordinate form of checked matrices -> CSR on the device (stable counting sort by row); value(v) is an entry's value in the path's form
+template <class Value>
+void upload_csr(const SparseMatrix* const mats[3], DeviceBuffer<uint32_t> (&row_ptr)[3], DeviceBuffer<uint32_t> (&col)[3], DeviceBuffer<uint64_t> (&val)[3],
+                Value&& value) {
+    const uint32_t m = mats[0]->n_rows;
+    for (int k = 0; k < 3; ++k) {
+        const SparseMatrix& M = *mats[k];
+        std::vector<uint32_t> ptr(m + 1, 0), cols(M.n_entries);
+        std::vector<uint64_t> vals(M.n_entries);
+        for (size_t e = 0; e < M.n_entries; ++e) ++ptr[M.entries[e].row + 1];
+        for (uint32_t i = 0; i < m; ++i) ptr[i + 1] += ptr[i];
+        std::vector<uint32_t> cursor(ptr.begin(), ptr.end() - 1);
+        for (size_t e = 0; e < M.n_entries; ++e) {
+            const uint32_t at = cursor[M.entries[e].row]++;
+            cols[at] = M.entries[e].col;
+            vals[at] = value(M.entries[e].value);
+        }
+        row_ptr[k].upload(ptr);
+        if (M.n_entries == 0) { cols.push_back(0); vals.push_back(0); }   // keep the pointers non-null
+        col[k].upload(cols);
+        val[k].upload(vals);
+    }
+}
+
 // ---- prove_r1cs / prove_r1cs_zk (lib.rs:747-809, 877-980), both R1CS paths ---------------------------------------------------------
 
 struct R1csSlots {             // one chunk's views into the per-instance scratch
     uint64_t *keys, *alphas, *betas, *hash_a, *hash_b, *ev, *blinding, *publics;
 };
 
-// The per-instance scratch of an R1CS prover and its host staging, sized for `chunk` instances.  A path grows its own chunk-sized
-// buffers to `chunk` whenever grow() says the scratch grew.
+// The per-instance scratch of an R1CS prover and its host staging.  chunk, publics and row_words describe the layout of the buffers:
+// each is committed only once the buffers laid out by it are allocated, and every gate reads the buffers' own counts.
 struct R1csScratch {
     size_t chunk = 0, publics = 0, row_words = 0;
     DeviceBuffer<uint64_t> small;      // keys[4] alphas betas hash_a[4] hash_b[4] ev[8] blinding publics[n_public] per instance
@@ -77,28 +125,26 @@ struct R1csScratch {
         v.publics = b;
         return v;
     }
-    // true when the scratch grew (to at least `want` instances and `n_public` publics); the staging is then dropped
-    bool grow(size_t want, size_t n_public) {
-        if (want <= chunk && n_public <= publics) return false;
-        chunk = std::max(chunk, want);
-        publics = std::max(publics, n_public);
-        small.allocate(chunk * (23 + std::max<size_t>(1, publics)));
+    // sizes the scratch for at least `want` instances and `n_public` publics (grows only; the staging is then dropped).  A path first
+    // reserves its own chunk-sized buffers for max(chunk, want) instances, then calls this.
+    void grow(size_t want, size_t n_public) {
+        const size_t c = std::max(chunk, want), pub = std::max(publics, n_public);
+        const size_t words = c * (23 + std::max<size_t>(1, pub));
+        if (small.count >= words) return;
         io.release();
         io_status.release();
         row_words = 0;
-        return true;
+        small.allocate(words);
+        chunk = c;
+        publics = pub;
     }
     // the host staging, for rows of `words` words
     void stage(size_t words) {
-        if (io.ptr && row_words >= words) return;
-        row_words = std::max<size_t>({row_words, words, 1});
-        io.allocate(chunk * (row_words + 13 + 8));
+        const size_t rw = std::max<size_t>({row_words, words, 1});
+        if (io.count >= chunk * (rw + 13 + 8) && io_status.count >= chunk) return;
+        io.allocate(chunk * (rw + 13 + 8));
         io_status.allocate(chunk);
-    }
-    void release() {
-        small.release();
-        io.release();
-        io_status.release();
+        row_words = rw;
     }
 };
 
@@ -138,7 +184,7 @@ struct R1csProveCall {
 struct R1csProverRef {
     int device;
     std::mutex& mutex;
-    hipEvent_t& ev_last;
+    Event& ev_last;
     hipStream_t stream;                  // the path's own stream: host calls
     DeviceBuffer<uint64_t>& witness;     // [chunk][n_vars]: host calls
     uint32_t n_vars;
@@ -151,7 +197,7 @@ template <class Grow, class ProveChunk>
 void r1cs_prove_host(const R1csProverRef& r, const R1csProveCall& c, size_t chunk, Grow&& grow, ProveChunk&& prove_chunk) {
     DeviceGuard guard(r.device);
     std::lock_guard<std::mutex> lock(r.mutex);
-    if (r.ev_last) LSR_HIP(hipEventSynchronize(r.ev_last));
+    r.ev_last.sync();
     const size_t words = lsr_lwe_commitment_words(c.lwe);
     grow(chunk);
     r.ws.stage(words);
@@ -180,7 +226,7 @@ template <class Grow, class ProveChunk>
 void r1cs_prove_device(const R1csProverRef& r, const R1csProveCall& c, size_t chunk, Grow&& grow, ProveChunk&& prove_chunk, hipStream_t s) {
     DeviceGuard guard(r.device);
     std::lock_guard<std::mutex> lock(r.mutex);
-    if (r.ev_last) LSR_HIP(hipEventSynchronize(r.ev_last));
+    r.ev_last.sync();
     const size_t words = lsr_lwe_commitment_words(c.lwe);
     grow(chunk);
     for (size_t done = 0; done < c.batch; done += chunk) {
@@ -188,8 +234,7 @@ void r1cs_prove_device(const R1csProverRef& r, const R1csProveCall& c, size_t ch
         prove_chunk(c.w + done * r.n_vars, c.blind ? c.blind + done : nullptr, c.seeds + done, now, c.rows + done * words, c.proofs + done * 13,
                     c.hashes ? c.hashes + done * 64 : nullptr, c.status + done, false, s);
     }
-    if (!r.ev_last) LSR_HIP(hipEventCreateWithFlags(&r.ev_last, hipEventDisableTiming));
-    LSR_HIP(hipEventRecord(r.ev_last, s));
+    r.ev_last.record(s);
 }
 
 // ---- verify_r1cs / verify_r1cs_zk, both R1CS paths: the two transcripts, then the path's per-proof check -----------------------------

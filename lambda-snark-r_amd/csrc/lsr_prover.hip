@@ -180,7 +180,7 @@ struct LsrQuotientPlan {
     uint32_t m = 0;
     int logm = 0;
     int device = 0;
-    NttContext* ntt = nullptr;                // size m, on the conjugate root omega_m^-1 (absent for m = 1)
+    lsr::NttContextPtr ntt;                   // size m, on the conjugate root omega_m^-1 (absent for m = 1); released after the buffers
     lsr::DeviceBuffer<uint64_t> twist;        // psi^bitrev(p), p < m                  } all three in Montgomery form
     lsr::DeviceBuffer<uint64_t> untwist;      // (2m)^-1 psi^-bitrev(p), p < m         } (gold_mul_mont)
     uint64_t half_m_inv = 0;                  // (2m)^-1                               }
@@ -189,9 +189,9 @@ struct LsrQuotientPlan {
     lsr::DeviceBuffer<uint32_t> flags;        // top[chunk], bad[chunk]
     lsr::DeviceBuffer<uint64_t> io;           // host-API staging of the quotient: [chunk][m]
     lsr::DeviceBuffer<uint32_t> io_len;
-    size_t chunk = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_last = nullptr;             // end of the last asynchronous call: the next call on this plan (any stream) starts behind it
+    size_t chunk = 0;                         // instances the planes are laid out for (committed once they are allocated)
+    lsr::Stream stream;
+    lsr::Event ev_last;                       // end of the last asynchronous call: the next call on this plan (any stream) starts behind it
     // read from the environment ONCE, when the plan is created
     int chunk_log2 = 26;                      // LAMBDA_SNARK_QUOTIENT_CHUNK_LOG2: evaluations per pass and plane
     bool fuse = true;                         // LAMBDA_SNARK_QUOTIENT_FUSE=0: the a b = c test and the coset product as kernels of their own
@@ -207,17 +207,18 @@ static size_t quotient_chunk(const LsrQuotientPlan& p, size_t batch) {
 }
 
 static void ensure_workspace(LsrQuotientPlan& p, size_t chunk, bool host_io) {
-    if (chunk > p.chunk) {
-        p.work.allocate(3 * chunk * p.m);
-        p.flags.allocate(2 * chunk);
+    const size_t c = std::max(p.chunk, chunk);
+    if (c > p.chunk) {          // the host staging follows the planes' layout: dropped, re-made by the next host call
         p.io.release();
         p.io_len.release();
-        p.chunk = chunk;
     }
-    if (host_io && p.io.count < p.chunk * p.m) {
-        p.io.allocate(p.chunk * p.m);
-        p.io_len.allocate(p.chunk);
+    p.work.reserve(3 * c * p.m);
+    p.flags.reserve(2 * c);
+    if (host_io) {
+        p.io.reserve(c * p.m);
+        p.io_len.reserve(c);
     }
+    p.chunk = c;
 }
 
 // one pass over `count` <= plan.chunk instances, everything on `s`
@@ -281,7 +282,7 @@ static void quotient_device(LsrQuotientPlan& p, const uint64_t* d_a, const uint6
     // workspace about to grow is not freed under a call that still uses it)
     // (not while `s` records into a HIP graph: a captured sequence is ordered by the capture, lsr_runtime.hpp stream_is_capturing)
     const bool capturing = stream_is_capturing(s);
-    if (p.ev_last && !capturing) LSR_HIP(hipEventSynchronize(p.ev_last));
+    if (!capturing) p.ev_last.sync();
     const size_t chunk = quotient_chunk(p, batch);
     ensure_workspace(p, chunk, false);
     for (size_t done = 0; done < batch; done += chunk) {
@@ -289,15 +290,13 @@ static void quotient_device(LsrQuotientPlan& p, const uint64_t* d_a, const uint6
         const size_t off = done << p.logm;
         quotient_pass(p, d_a + off, d_b + off, d_c + off, now, d_q + off, d_len + done, s);
     }
-    if (capturing) return;
-    if (!p.ev_last) LSR_HIP(hipEventCreateWithFlags(&p.ev_last, hipEventDisableTiming));
-    LSR_HIP(hipEventRecord(p.ev_last, s));
+    if (!capturing) p.ev_last.record(s);
 }
 
 static void quotient_host(LsrQuotientPlan& p, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t batch, uint64_t* q, uint32_t* len) {
     DeviceGuard guard(p.device);
     std::lock_guard<std::mutex> lock(p.mutex);
-    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));      // an asynchronous call still using the planes
+    p.ev_last.sync();      // an asynchronous call still using the planes
     const size_t chunk = quotient_chunk(p, batch);
     ensure_workspace(p, chunk, true);
     for (size_t done = 0; done < batch; done += chunk) {
@@ -318,41 +317,22 @@ static void destroy_plan(LsrQuotientPlan* p) {
     if (!p) return;
     try {
         DeviceGuard guard(p->device);
-        if (p->ev_last) {
-            (void)hipEventSynchronize(p->ev_last);
-            (void)hipEventDestroy(p->ev_last);
-        }
-        if (p->stream) (void)hipStreamDestroy(p->stream);
-        p->work.release();
-        p->flags.release();
-        p->io.release();
-        p->io_len.release();
-        p->twist.release();
-        p->untwist.release();
+        p->ev_last.sync();
+        delete p;
     } catch (...) {
+        delete p;
     }
-    destroy_ntt_context(p->ntt);
-    delete p;
 }
+using QuotientPlanPtr = std::unique_ptr<LsrQuotientPlan, HandleDeleter<LsrQuotientPlan, destroy_plan>>;
 
 static LsrQuotientPlan* create_plan(uint32_t m, int device) {
     if (m == 0 || m > 131072 || (m & (m - 1))) {
         set_last_error("lsr_quotient_plan_create: m must be a power of two in [1, 131072] (r1cs.rs:386-389)");
         return nullptr;
     }
-    const int devices = visible_device_count();
-    if (devices <= 0) {
-        set_last_error("lsr_quotient_plan_create: no HIP device visible — this library has no CPU fallback");
-        std::fprintf(stderr, "lambda_snark_core: no HIP device visible; the MI355X backend has no CPU fallback\n");
-        return nullptr;
-    }
-    if (device < 0) device = default_device();
-    if (device < 0) return nullptr;                          // LOCAL_RANK / LAMBDA_SNARK_DEVICE names no visible device: message already set
-    if (device >= devices) {
-        set_last_error("lsr_quotient_plan_create: device index out of range");
-        return nullptr;
-    }
-    auto* p = new LsrQuotientPlan;
+    device = resolve_device("lsr_quotient_plan_create", device, true);
+    if (device < 0) return nullptr;
+    QuotientPlanPtr p(new LsrQuotientPlan);
     p->m = m;
     p->device = device;
     if (const char* e = std::getenv("LAMBDA_SNARK_QUOTIENT_CHUNK_LOG2")) {
@@ -363,11 +343,8 @@ static LsrQuotientPlan* create_plan(uint32_t m, int device) {
     while ((1u << p->logm) < m) ++p->logm;
     const uint64_t q = kProverModulus;
     if (m >= 2) {
-        p->ntt = create_cyclic_ntt_context(q, m, invmod_prime(prover_root_of_unity(q, m), q), device);
-        if (!p->ntt) {
-            delete p;
-            return nullptr;
-        }
+        p->ntt.reset(create_cyclic_ntt_context(q, m, invmod_prime(prover_root_of_unity(q, m), q), device));
+        if (!p->ntt) return nullptr;
     }
     try {
         DeviceGuard guard(device);
@@ -393,102 +370,64 @@ static LsrQuotientPlan* create_plan(uint32_t m, int device) {
             p->twist.upload(twist);
             p->untwist.upload(untwist);
         }
-        LSR_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+        LSR_HIP(hipStreamCreateWithFlags(&p->stream.handle, hipStreamNonBlocking));
     } catch (const std::exception& e) {
         set_last_error(std::string("lsr_quotient_plan_create: ") + e.what());
-        destroy_plan(p);
         return nullptr;
     }
-    return p;
+    return p.release();
 }
 
 }  // namespace lsr
 
 struct LsrR1csProver {
     uint32_t m = 0, n_vars = 0;
-    LsrQuotientPlan* plan = nullptr;        // NTT path
-    lsr::LagrangeProver* lag = nullptr;     // Lagrange path (lsr_r1cs_prover_create_mod, lsr_lagrange.hip): then plan == nullptr
+    // (declared before the buffers: released after them)
+    lsr::QuotientPlanPtr plan;              // NTT path
+    lsr::LagrangeProverPtr lag;             // Lagrange path (lsr_r1cs_prover_create_mod, lsr_lagrange.hip): then plan == nullptr
     uint64_t modulus = lsr::kProverModulus;
     lsr::DeviceBuffer<uint32_t> row_ptr[3], col[3];
     lsr::DeviceBuffer<uint64_t> val[3];
     lsr::DeviceBuffer<uint64_t> witness;    // [chunk][n_vars]
-    size_t witness_chunk = 0;
     // prove path (lsr_r1cs_prove_batch*), sized for prove_chunk instances:
     lsr::DeviceBuffer<uint64_t> stash;      // A's and B's interpolated planes [2][chunk][m]
     lsr::DeviceBuffer<uint64_t> quot;       // quotient [chunk][m]
     lsr::DeviceBuffer<uint64_t> msg;        // commitment messages [chunk][m + 1]
     lsr::DeviceBuffer<uint32_t> len;        // [chunk]
     lsr::R1csScratch ws;                    // per-instance scratch and host staging; its chunk sizes the buffers above
+    int device() const { return plan ? plan->device : lsr::lagrange_device(lag.get()); }
 };
 
 namespace lsr {
 
 static void destroy_prover(LsrR1csProver* r) {
     if (!r) return;
-    lagrange_destroy(r->lag);
-    if (r->plan) {
-        try {
-            DeviceGuard guard(r->plan->device);
-            for (int k = 0; k < 3; ++k) { r->row_ptr[k].release(); r->col[k].release(); r->val[k].release(); }
-            r->witness.release();
-            r->stash.release(); r->quot.release(); r->msg.release(); r->len.release(); r->ws.release();
-        } catch (...) {
-        }
+    try {
+        DeviceGuard guard(r->device());
+        if (r->plan) r->plan->ev_last.sync();   // an asynchronous prove call still using the buffers below
+        delete r;
+    } catch (...) {
+        delete r;
     }
-    destroy_plan(r->plan);
-    delete r;
 }
+using R1csProverPtr = std::unique_ptr<LsrR1csProver, HandleDeleter<LsrR1csProver, destroy_prover>>;
 
 static LsrR1csProver* create_prover(const SparseMatrix* const mats[3], int device) {
-    const uint32_t m = mats[0]->n_rows, n_vars = mats[0]->n_cols;
-    for (int k = 0; k < 3; ++k) {
-        if (mats[k]->n_rows != m || mats[k]->n_cols != n_vars || (mats[k]->n_entries && !mats[k]->entries) || mats[k]->n_entries > 0xFFFFFFF0ull) {
-            set_last_error("lsr_r1cs_prover_create: A, B, C must share one shape");
-            return nullptr;
-        }
-        for (size_t e = 0; e < mats[k]->n_entries; ++e)
-            if (mats[k]->entries[e].row >= m || mats[k]->entries[e].col >= n_vars) {
-                set_last_error("lsr_r1cs_prover_create: entry outside the matrix");
-                return nullptr;
-            }
-    }
-    if (n_vars == 0) {
-        set_last_error("lsr_r1cs_prover_create: no variables");
-        return nullptr;
-    }
-    auto* r = new LsrR1csProver;
-    r->m = m;
-    r->n_vars = n_vars;
-    r->plan = create_plan(m, device);
-    if (!r->plan) {
-        delete r;
-        return nullptr;
-    }
+    if (!r1cs_shape_ok("lsr_r1cs_prover_create", mats)) return nullptr;
+    QuotientPlanPtr plan(create_plan(mats[0]->n_rows, device));
+    if (!plan) return nullptr;
+    R1csProverPtr r(new LsrR1csProver);
+    r->m = mats[0]->n_rows;
+    r->n_vars = mats[0]->n_cols;
+    r->plan = std::move(plan);
     try {
         DeviceGuard guard(r->plan->device);
-        for (int k = 0; k < 3; ++k) {   // coordinate form -> CSR (stable counting sort by row)
-            const SparseMatrix& M = *mats[k];
-            std::vector<uint32_t> ptr(m + 1, 0), cols(M.n_entries);
-            std::vector<uint64_t> vals(M.n_entries);
-            for (size_t e = 0; e < M.n_entries; ++e) ++ptr[M.entries[e].row + 1];
-            for (uint32_t i = 0; i < m; ++i) ptr[i + 1] += ptr[i];
-            std::vector<uint32_t> cursor(ptr.begin(), ptr.end() - 1);
-            for (size_t e = 0; e < M.n_entries; ++e) {
-                const uint32_t at = cursor[M.entries[e].row]++;
-                cols[at] = M.entries[e].col;
-                vals[at] = prover_montgomery(M.entries[e].value);     // mul_vec: val % modulus (held in Montgomery form)
-            }
-            r->row_ptr[k].upload(ptr);
-            if (M.n_entries == 0) { cols.push_back(0); vals.push_back(0); }   // keep the pointers non-null
-            r->col[k].upload(cols);
-            r->val[k].upload(vals);
-        }
+        upload_csr(mats, r->row_ptr, r->col, r->val, [](uint64_t v) { return prover_montgomery(v); });   // mul_vec: val % modulus (held in Montgomery form)
     } catch (const std::exception& e) {
         set_last_error(std::string("lsr_r1cs_prover_create: ") + e.what());
-        destroy_prover(r);
         return nullptr;
     }
-    return r;
+    return r.release();
 }
 
 // witnesses (host) -> constraint evaluations in the plan's workspace planes, chunk by chunk; then either copy them out
@@ -497,13 +436,10 @@ static void prover_run(LsrR1csProver& r, const uint64_t* witnesses, size_t batch
     LsrQuotientPlan& p = *r.plan;
     DeviceGuard guard(p.device);
     std::lock_guard<std::mutex> lock(p.mutex);
-    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));      // an asynchronous lsr_quotient_batch_device call still using the planes
+    p.ev_last.sync();      // an asynchronous lsr_quotient_batch_device call still using the planes
     const size_t chunk = quotient_chunk(p, batch);
     ensure_workspace(p, chunk, true);
-    if (r.witness_chunk < p.chunk) {
-        r.witness.allocate(p.chunk * r.n_vars);
-        r.witness_chunk = p.chunk;
-    }
+    r.witness.reserve(p.chunk * r.n_vars);
     const CsrView a{r.row_ptr[0].ptr, r.col[0].ptr, r.val[0].ptr}, b{r.row_ptr[1].ptr, r.col[1].ptr, r.val[1].ptr},
         c{r.row_ptr[2].ptr, r.col[2].ptr, r.val[2].ptr};
     for (size_t done = 0; done < batch; done += chunk) {
@@ -530,16 +466,13 @@ static void prover_run(LsrR1csProver& r, const uint64_t* witnesses, size_t batch
 // message Q' mod commit_modulus -> keys -> rows -> alpha -> beta -> evaluations -> proof records.
 static void ensure_prove_workspace(LsrR1csProver& r, size_t chunk, size_t n_public) {
     ensure_workspace(*r.plan, chunk, false);
-    if (r.witness_chunk < chunk) {
-        r.witness.allocate(chunk * r.n_vars);
-        r.witness_chunk = chunk;
-    }
-    if (!r.ws.grow(chunk, n_public)) return;
-    const size_t c = r.ws.chunk;
-    r.stash.allocate(2 * c * r.m);
-    r.quot.allocate(c * r.m);
-    r.msg.allocate(c * (r.m + 1));
-    r.len.allocate(c);
+    r.witness.reserve(chunk * r.n_vars);
+    const size_t c = std::max(r.ws.chunk, chunk);
+    r.stash.reserve(2 * c * r.m);
+    r.quot.reserve(c * r.m);
+    r.msg.reserve(c * (r.m + 1));
+    r.len.reserve(c);
+    r.ws.grow(c, n_public);
 }
 
 // one chunk of `count` instances.  d_z [count][n_vars]; d_blind [count] (zk) or nullptr; outputs device arrays.  host_keys: derive the
@@ -727,8 +660,6 @@ int lsr_r1cs_quotient_batch(LsrR1csProver* prover, const uint64_t* witnesses, si
 }
 
 // ---- batched prove / verify (prover.h) ----
-static int prover_device(const LsrR1csProver* p) { return p->lag ? lsr::lagrange_device(p->lag) : p->plan->device; }
-
 static int prove_checks(const char* where, const LsrR1csProver* prover, const LweContext* lwe, uint64_t commit_modulus, const void* w, size_t n_public,
                         const uint64_t* seeds, const void* rows, const void* proofs, const void* status) {
     if (!prover || !lwe) return abi_refuse(where, "NULL prover or LWE context");
@@ -736,7 +667,7 @@ static int prove_checks(const char* where, const LsrR1csProver* prover, const Lw
     if (n_public > prover->n_vars) return abi_refuse(where, "n_public exceeds the circuit's variable count");
     if (commit_modulus <= 1) return abi_refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
     const NttContext* ntt = lsr_lwe_ntt_context(lwe);
-    if (!ntt || ntt->device != prover_device(prover)) return abi_refuse(where, "the prover and the LWE context live on different devices");
+    if (!ntt || ntt->device != prover->device()) return abi_refuse(where, "the prover and the LWE context live on different devices");
     return 0;
 }
 
@@ -759,7 +690,7 @@ int lsr_r1cs_prove_batch_device(LsrR1csProver* prover, LweContext* lwe, uint64_t
     if (prove_checks(where, prover, lwe, commit_modulus, d_witnesses, n_public, seeds, d_rows, d_proofs, d_status)) return -1;
     if (batch == 0) return 0;
     const lsr::R1csProveCall c{lwe, commit_modulus, n_public, seeds, d_witnesses, d_blinding, d_rows, d_proofs, d_hashes, d_status, batch};
-    return lsr::abi_prove_device(where, "lsr_r1cs_prove_batch", seeds, batch, prover_device(prover), stream, [&](hipStream_t s) {
+    return lsr::abi_prove_device(where, "lsr_r1cs_prove_batch", seeds, batch, prover->device(), stream, [&](hipStream_t s) {
         if (prover->lag) lsr::lagrange_prove(*prover->lag, c, true, s);
         else lsr::prove(*prover, c, true, s);
     });
@@ -811,12 +742,12 @@ LsrR1csProver* lsr_r1cs_prover_create_mod(const SparseMatrix* A, const SparseMat
     if (modulus == lsr::kProverModulus && m != 0 && (m & (m - 1)) == 0) return lsr_r1cs_prover_create(A, B, C, device);   // should_use_ntt
     try {
         const SparseMatrix* const mats[3] = {A, B, C};
-        lsr::LagrangeProver* lag = lsr::lagrange_create(mats, modulus, device);
+        lsr::LagrangeProverPtr lag(lsr::lagrange_create(mats, modulus, device));
         if (!lag) return nullptr;
         auto* r = new LsrR1csProver;
         r->m = m;
         r->n_vars = A->n_cols;
-        r->lag = lag;
+        r->lag = std::move(lag);
         r->modulus = modulus;
         return r;
     } catch (...) {

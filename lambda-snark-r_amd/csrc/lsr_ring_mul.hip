@@ -96,15 +96,12 @@ static void ring_mul_device(const NttContext& c, uint64_t* d_c, const uint64_t* 
         c.ring_scratch.allocate(ring_scratch_words(c));
     }
     // (a capturing stream: no brackets — lsr_runtime.hpp, stream_is_capturing)
-    if (!capturing && c.ring_event) LSR_HIP(hipStreamWaitEvent(s, c.ring_event, 0));
+    if (!capturing) c.ring_event.wait(s);
     if (c.gold) ring_mul_enqueue<ArithGold>(c, d_c, d_a, d_b, batch, shared_b, s);
     else if (c.use_f64) ring_mul_enqueue<ArithF64>(c, d_c, d_a, d_b, batch, shared_b, s);
     else ring_mul_enqueue<ArithU64>(c, d_c, d_a, d_b, batch, shared_b, s);
     LSR_HIP(hipGetLastError());
-    if (!capturing) {
-        if (!c.ring_event) LSR_HIP(hipEventCreateWithFlags(&c.ring_event, hipEventDisableTiming));
-        LSR_HIP(hipEventRecord(c.ring_event, s));
-    }
+    if (!capturing) c.ring_event.record(s);
 }
 
 // host buffers through bounded device chunks on the context's work stream

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -67,7 +68,12 @@ private:
 
 int default_device();          // LAMBDA_SNARK_DEVICE, else LOCAL_RANK, else 0; -1 (+ message) when that index is not a visible device
 int visible_device_count();    // 0 if the runtime cannot see a GPU
+// the device a handle is created on: `device`, or default_device() for a negative one; -1 (+ lsr_last_error "<where>: ...") when
+// there is none.  announce: also say on stderr that no device is visible
+int resolve_device(const char* where, int device, bool announce);
 
+// The owners below release what they hold in their destructors (which never throw) and cannot be copied.  A buffer's `count` is the
+// only record of its capacity: ptr != nullptr <=> count > 0, also after a failed allocation (the buffer is then empty).
 template <class T>
 struct DeviceBuffer {
     T* ptr = nullptr;
@@ -79,10 +85,16 @@ struct DeviceBuffer {
     DeviceBuffer& operator=(const DeviceBuffer&) = delete;
     void allocate(size_t n) {
         release();
-        if (n) LSR_HIP(hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T)));
+        if (!n) return;
+        void* p = nullptr;
+        LSR_HIP(hipMalloc(&p, n * sizeof(T)));
+        ptr = static_cast<T*>(p);
         count = n;
     }
-    void release() {
+    void reserve(size_t n) {   // grows only
+        if (count < n) allocate(n);
+    }
+    void release() noexcept {
         if (ptr) (void)hipFree(ptr);
         ptr = nullptr;
         count = 0;
@@ -91,6 +103,85 @@ struct DeviceBuffer {
         allocate(host.size());
         if (!host.empty()) LSR_HIP(hipMemcpy(ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
     }
+    void wipe() noexcept {     // zeroes the contents (a secret); synchronous on the null stream
+        if (ptr) (void)hipMemset(ptr, 0, count * sizeof(T));
+    }
+};
+
+// page-locked host memory; flags: hipHostMallocPortable (any device of the node may DMA into it) or hipHostMallocDefault
+template <class T>
+struct PinnedBuffer {
+    T* ptr = nullptr;
+    size_t count = 0;
+    explicit PinnedBuffer(unsigned flags) : flags_(flags) {}
+    ~PinnedBuffer() { release(); }
+    PinnedBuffer(const PinnedBuffer&) = delete;
+    PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+    void allocate(size_t n) {
+        release();
+        if (!n) return;
+        void* p = nullptr;
+        LSR_HIP(hipHostMalloc(&p, n * sizeof(T), flags_));
+        ptr = static_cast<T*>(p);
+        count = n;
+    }
+    void reserve(size_t n) {   // grows only
+        if (count < n) allocate(n);
+    }
+    void release() noexcept {
+        if (ptr) (void)hipHostFree(ptr);
+        ptr = nullptr;
+        count = 0;
+    }
+    void wipe() noexcept {     // zeroes the contents (a secret)
+        volatile T* v = ptr;
+        for (size_t i = 0; i < count; ++i) v[i] = 0;
+    }
+
+private:
+    unsigned flags_;
+};
+
+// An event without timing, created by its first record(); sync() and wait() do nothing before that.
+class Event {
+public:
+    Event() = default;
+    ~Event() {
+        if (ev_) (void)hipEventDestroy(ev_);
+    }
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    void record(hipStream_t s) {
+        if (!ev_) LSR_HIP(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
+        LSR_HIP(hipEventRecord(ev_, s));
+    }
+    void sync() const {        // the host waits for the last record
+        if (ev_) LSR_HIP(hipEventSynchronize(ev_));
+    }
+    void wait(hipStream_t s) const {   // `s` waits for the last record
+        if (ev_) LSR_HIP(hipStreamWaitEvent(s, ev_, 0));
+    }
+
+private:
+    hipEvent_t ev_ = nullptr;
+};
+
+// One stream: the owner creates it into `handle` where it is needed (with the flags and priority of that place).
+struct Stream {
+    hipStream_t handle = nullptr;
+    Stream() = default;
+    ~Stream() {
+        if (handle) (void)hipStreamDestroy(handle);
+    }
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    operator hipStream_t() const { return handle; }
+};
+
+// the deleter of a handle owned by another handle: its destroy function
+template <class T, void (*Destroy)(T*)>
+struct HandleDeleter {
+    void operator()(T* p) const noexcept { Destroy(p); }
 };
 
 }  // namespace lsr
@@ -119,14 +210,14 @@ struct NttContext {
     // the context's own stream for the host-pointer entry points — created on first use (lsr::work_stream): device-API callers
     // bring their stream, and every stream a process opens competes for the runtime's few hardware queues
     mutable std::mutex stream_mutex;
-    mutable hipStream_t stream = nullptr;
+    mutable lsr::Stream stream;
     // workspace of lsr_ntt_ring_mul_batch(_device) (lsr_ring_mul.hip): allocated by the first call that needs it at a size fixed by n
     // alone, never resized (a graph captured after one eager call stays valid), freed with the context.  ring_mutex serialises the
     // calls on the host; ring_event (recorded at the end of every call outside capture) orders each call behind the previous one
     // on the device, whatever streams they were issued on.
     mutable std::mutex ring_mutex;
     mutable lsr::DeviceBuffer<uint64_t> ring_scratch;
-    mutable hipEvent_t ring_event = nullptr;
+    mutable lsr::Event ring_event;
 };
 
 namespace lsr {
@@ -135,6 +226,7 @@ NttContext* create_ntt_context(uint64_t q, uint32_t n, int device);
 // cyclic transform over F_q with the given primitive n-th root (0 = the reference's root for NTT_MODULUS)
 NttContext* create_cyclic_ntt_context(uint64_t q, uint32_t n, uint64_t omega, int device);
 void destroy_ntt_context(NttContext* ctx);
+using NttContextPtr = std::unique_ptr<NttContext, HandleDeleter<NttContext, destroy_ntt_context>>;
 hipStream_t work_stream(const NttContext& ctx);
 // asynchronous launches on `stream`, data resident on ctx->device
 // add_on_inverse (optional): canonical residues [batch][n] added to the outputs of an inverse transform in its final

@@ -34,12 +34,11 @@ struct LsrSimpleProver {
     int device = 0;
     lsr::MontQ M{};
     std::mutex mutex;                       // guards the workspace, the pinned seeds and `stream`; taken before the LWE context's
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_last = nullptr;           // end of the last asynchronous call: the next call (any stream) starts behind it
+    lsr::Stream stream;
+    lsr::Event ev_last;                     // end of the last asynchronous call: the next call (any stream) starts behind it
     lsr::DeviceBuffer<uint64_t> ws;         // chunk workspace (layout: simple_layout)
     lsr::DeviceBuffer<uint64_t> d_seeds;    // [batch] commit seeds of the current call
-    uint64_t* h_seeds = nullptr;            // their page-locked host copy
-    size_t seeds_cap = 0;
+    lsr::PinnedBuffer<uint64_t> h_seeds{hipHostMallocDefault};   // their page-locked host copy
 };
 
 namespace lsr {
@@ -56,7 +55,7 @@ static SimpleLayout simple_layout(LsrSimpleProver& p, size_t batch, size_t len, 
     SimpleLayout L{};
     L.chunk = std::min(batch, std::max<size_t>(1, kSimpleWorkspaceBytes / 8 / (dev + io)));
     const size_t C = L.chunk, words = C * (dev + io);
-    if (p.ws.count < words) p.ws.allocate(words);
+    p.ws.reserve(words);
     uint64_t* at = p.ws.ptr;
     auto take = [&](size_t n) { uint64_t* r = at; at += n; return r; };
     L.msg = take(C * msg_len);
@@ -75,16 +74,10 @@ static SimpleLayout simple_layout(LsrSimpleProver& p, size_t batch, size_t len, 
 }
 
 static void upload_seeds(LsrSimpleProver& p, const uint64_t* seeds, size_t batch, hipStream_t s) {
-    if (p.seeds_cap < batch) {
-        if (p.h_seeds) LSR_HIP(hipHostFree(p.h_seeds));
-        p.h_seeds = nullptr;
-        p.seeds_cap = 0;
-        LSR_HIP(hipHostMalloc(reinterpret_cast<void**>(&p.h_seeds), batch * 8, hipHostMallocDefault));
-        p.d_seeds.allocate(batch);
-        p.seeds_cap = batch;
-    }
-    std::memcpy(p.h_seeds, seeds, batch * 8);
-    LSR_HIP(hipMemcpyAsync(p.d_seeds.ptr, p.h_seeds, batch * 8, hipMemcpyHostToDevice, s));
+    p.h_seeds.reserve(batch);
+    p.d_seeds.reserve(batch);
+    std::memcpy(p.h_seeds.ptr, seeds, batch * 8);
+    LSR_HIP(hipMemcpyAsync(p.d_seeds.ptr, p.h_seeds.ptr, batch * 8, hipMemcpyHostToDevice, s));
 }
 
 static void launch_message(int mode, const uint64_t* w, const uint64_t* bkeys, uint64_t* coeffs, uint64_t* msg, size_t len, size_t msg_len,
@@ -133,7 +126,7 @@ static void prove_host(LsrSimpleProver& p, LweContext* lwe, uint64_t commit_modu
                        uint64_t* proofs, uint8_t* hashes) {
     DeviceGuard guard(p.device);
     std::lock_guard<std::mutex> lock(p.mutex);   // prover first, then (inside each commitment call) the LWE context
-    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
+    p.ev_last.sync();
     hipStream_t s = p.stream;
     const size_t W = lsr_lwe_commitment_words(lwe), msg_len = msg_len_for(lwe, len);
     std::vector<uint64_t> fresh;                 // ChaCha20Rng::from_entropy for every proof when no keys are given
@@ -167,7 +160,7 @@ static void prove_device(LsrSimpleProver& p, LweContext* lwe, uint64_t commit_mo
                          uint64_t* d_proofs, uint8_t* d_hashes, hipStream_t s) {
     DeviceGuard guard(p.device);
     std::lock_guard<std::mutex> lock(p.mutex);
-    if (p.ev_last) LSR_HIP(hipEventSynchronize(p.ev_last));
+    p.ev_last.sync();
     const size_t W = lsr_lwe_commitment_words(lwe), msg_len = msg_len_for(lwe, len);
     const SimpleLayout L = simple_layout(p, batch, len, msg_len, n_public, W, false);
     upload_seeds(p, seeds, batch, s);
@@ -178,8 +171,7 @@ static void prove_device(LsrSimpleProver& p, LweContext* lwe, uint64_t commit_mo
                             d_hashes ? d_hashes + done * 32 : nullptr, now, false};
         prove_chunk(p, lwe, commit_modulus, mode, len, msg_len, n_public, L, c, s);
     }
-    if (!p.ev_last) LSR_HIP(hipEventCreateWithFlags(&p.ev_last, hipEventDisableTiming));
-    LSR_HIP(hipEventRecord(p.ev_last, s));
+    p.ev_last.record(s);
 }
 
 // ---- verify_simple ---------------------------------------------------------------------------------------------------------------
@@ -286,17 +278,11 @@ static void destroy_simple(LsrSimpleProver* p) {
     if (!p) return;
     try {
         lsr::DeviceGuard guard(p->device);
-        if (p->ev_last) {
-            (void)hipEventSynchronize(p->ev_last);
-            (void)hipEventDestroy(p->ev_last);
-        }
-        if (p->stream) (void)hipStreamDestroy(p->stream);
-        if (p->h_seeds) (void)hipHostFree(p->h_seeds);
-        p->ws.release();
-        p->d_seeds.release();
+        p->ev_last.sync();
+        delete p;
     } catch (...) {
+        delete p;
     }
-    delete p;
 }
 
 static int prove_args(const char* where, const LsrSimpleProver* p, const LweContext* lwe, uint64_t commit_modulus, int mode, const void* w, size_t len,
@@ -360,29 +346,18 @@ LsrSimpleProver* lsr_simple_prover_create(uint64_t q, int device) noexcept {
         abi_refuse(where, "the modulus must be odd and >= 3");
         return nullptr;
     }
-    const int devices = lsr::visible_device_count();
-    if (devices <= 0) {
-        abi_refuse(where, "no HIP device visible — this library has no CPU fallback");
-        return nullptr;
-    }
-    if (device < 0) device = lsr::default_device();
+    device = lsr::resolve_device(where, device, false);
     if (device < 0) return nullptr;
-    if (device >= devices) {
-        abi_refuse(where, "device index out of range");
-        return nullptr;
-    }
-    LsrSimpleProver* p = nullptr;
     try {
-        p = new LsrSimpleProver;
+        std::unique_ptr<LsrSimpleProver, lsr::HandleDeleter<LsrSimpleProver, destroy_simple>> p(new LsrSimpleProver);
         p->q = q;
         p->device = device;
         p->M = lsr::make_mont(q);
         lsr::DeviceGuard guard(device);
-        LSR_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-        return p;
+        LSR_HIP(hipStreamCreateWithFlags(&p->stream.handle, hipStreamNonBlocking));
+        return p.release();
     } catch (const std::exception& e) {
         abi_refuse(where, e.what());
-        destroy_simple(p);
         return nullptr;
     }
 }

@@ -125,6 +125,7 @@ def test_no_device_memory_growth(pkg):
         ctx = pkg.NttContext(17592182243329, 65536)
         a = np.arange(2 * 65536, dtype=np.uint64).reshape(2, 65536)
         ctx.inverse_batch(ctx.forward_batch(a))
+        ctx.ring_mul(a, a[0])      # allocates the context's ring_scratch
         ctx.close()
         lctx = pkg.LweContext(pkg.Params(q=12289, n=4096, k=2, sigma=3.19))
         coms = pkg.Commitment.batch(lctx, np.ones((5, 4), dtype=np.uint64), np.arange(1, 6, dtype=np.uint64))
@@ -362,6 +363,15 @@ def test_prover_handles_do_not_leak(pkg):
         prover = pkg.R1csProver(2, 6, [(0, 1, 1), (1, 3, 1)], [(0, 2, 1), (1, 4, 1)], [(0, 3, 1), (1, 5, 1)])
         prover.quotient_batch([1, 2, 3, 6, 4, 24])
         prover.close()
+        lctx = pkg.LweContext(pkg.Params(q=17592186044417, n=4096, k=2, sigma=3.19), key_seed=7)
+        prover = pkg.R1csProver(2, 6, [(0, 1, 1), (1, 3, 1)], [(0, 2, 1), (1, 4, 1)], [(0, 3, 1), (1, 5, 1)], modulus=(1 << 31) - 1)
+        witness = np.array([[1, 2, 3, 6, 4, 24]], dtype=np.uint64)
+        prover.prove_batch(lctx, witness, np.array([1], dtype=np.uint64), 1, lctx.modulus())
+        prover.close()
+        simple = pkg.SimpleProver((1 << 31) - 1)
+        simple.prove_batch(lctx, witness, witness[:, :1], np.array([1], dtype=np.uint64), lctx.modulus())
+        simple.close()
+        lctx.close()
 
     for _ in range(3):
         cycle()
