@@ -29,6 +29,15 @@ uint64_t lsr_prover_root_of_unity(uint64_t n) LSR_NOEXCEPT;
  * The ntt.h / batch.h transforms accept such a context and then run the cyclic butterfly network in its
  * native order: forward = natural in -> bit-reversed out, inverse = bit-reversed in -> natural out. */
 NttContext* lsr_cyclic_ntt_context_create(uint64_t q, uint32_t n, uint64_t omega, int device) LSR_NOEXCEPT;
+/* log2 of the largest transform size / constraint count of the *_large constructors and of lsr_r1cs_prover_create[_mod]: 22 */
+uint32_t lsr_prover_max_log2_size(void) LSR_NOEXCEPT;
+/* The same contract with n = 2^k in [2, 2^22]; at n <= 131072 it builds what lsr_cyclic_ntt_context_create builds.  Above 131072 the
+ * transform runs three passes (two strided rounds and the tile pass) and q must be NTT_MODULUS: the FP64 and Shoup
+ * flavours of the other primes are not carried through the extra round, so such a q returns NULL with a text in lsr_last_error.
+ * Every transform entry point (ntt_forward/inverse[_batch], lsr_ntt_*_batch_device, lsr_cyclic_ntt_*_batch) takes the context;
+ * lsr_ntt_ring_mul_batch[_device] returns -1 on a context above 131072.  One context holds two tables of n words and 3 n words of
+ * staging on the device (160 MiB at n = 2^22). */
+NttContext* lsr_cyclic_ntt_context_create_large(uint64_t q, uint32_t n, uint64_t omega, int device) LSR_NOEXCEPT;
 int lsr_ntt_context_is_cyclic(const NttContext* ctx) LSR_NOEXCEPT;
 
 /* ntt_forward / ntt_inverse of ntt.rs:117-201 for `batch` contiguous vectors of ctx->n words, natural order in
@@ -42,6 +51,10 @@ int lsr_bit_reverse_device(uint64_t* d_out, const uint64_t* d_in, int logn, size
 typedef struct LsrQuotientPlan LsrQuotientPlan;
 /* m = number of constraints, a power of two in [1, 131072]; NULL otherwise or without a GPU */
 LsrQuotientPlan* lsr_quotient_plan_create(uint32_t m, int device) LSR_NOEXCEPT;
+/* the same with m a power of two in [1, 2^22] (lsr_prover_max_log2_size); at m <= 131072 it builds what lsr_quotient_plan_create
+ * builds.  Workspace: three planes of chunk * m words, chunk = min(batch, 2^26 / m) instances per pass (16 at m = 2^22: 1.5 GiB),
+ * plus one plane for the quotient in the host call. */
+LsrQuotientPlan* lsr_quotient_plan_create_large(uint32_t m, int device) LSR_NOEXCEPT;
 void lsr_quotient_plan_free(LsrQuotientPlan* plan) LSR_NOEXCEPT;
 uint32_t lsr_quotient_plan_size(const LsrQuotientPlan* plan) LSR_NOEXCEPT;
 /* `batch` independent instances.  a/b/c_evals = [batch][m] constraint evaluations (A z, B z, C z of
@@ -62,8 +75,11 @@ int lsr_quotient_batch_device(LsrQuotientPlan* plan, const uint64_t* d_a_evals, 
 /* ---- compute_quotient_poly(witness) in full, for one R1CS and many witnesses (r1cs.rs:474-506) ----
  * The three sparse products of compute_constraint_evals (r1cs.rs:296-304, SparseMatrix::mul_vec sparse_matrix.rs:259-289:
  * values and witness words reduced mod q as unsigned integers) run on the device in front of the pipeline above.
- * A, B, C: m x n_vars in the FFI's coordinate form (r1cs.h; duplicate (row, col) entries add up), m = 2^k in [1, 131072],
- * modulus NTT_MODULUS.  The matrices are copied; NULL on bad shapes / indices or without a GPU. */
+ * A, B, C: m x n_vars in the FFI's coordinate form (r1cs.h; duplicate (row, col) entries add up), m = 2^k in [1, 2^22]
+ * (lsr_prover_max_log2_size), modulus NTT_MODULUS.  The matrices are copied; NULL on bad shapes / indices or without a GPU.
+ * Device memory of a prove call: 7 planes of chunk * m words (3 of the quotient plan, A's and B's interpolants, the quotient, the
+ * commitment message), chunk = min(batch, 2^26 / m) — a peak of 3.5 GiB from m = 2^22 (16 instances per pass) down to any m with
+ * batch * m >= 2^26; a quotient longer than the LWE ring degree is committed truncated to it, as lwe_commit truncates. */
 typedef struct LsrR1csProver LsrR1csProver;
 LsrR1csProver* lsr_r1cs_prover_create(const SparseMatrix* A, const SparseMatrix* B, const SparseMatrix* C, int device) LSR_NOEXCEPT;
 void     lsr_r1cs_prover_free(LsrR1csProver* prover) LSR_NOEXCEPT;

@@ -350,7 +350,10 @@ class Commitment:
             self._p = _raw
             return
         # commitment.rs:33-36: every coefficient is reduced mod ctx.modulus() before the call
-        msg = np.array([int(m) % ctx.modulus() for m in message], dtype=np.uint64)
+        if isinstance(message, np.ndarray) and message.dtype == np.uint64 and message.ndim == 1:    # (a 2^22-word quotient: no Python loop)
+            msg = np.ascontiguousarray(message % np.uint64(ctx.modulus()))
+        else:
+            msg = np.array([int(m) % ctx.modulus() for m in message], dtype=np.uint64)
         self._p = self._lib.lwe_commit(ctx.handle, msg.ctypes.data, msg.size, int(seed))
         if not self._p:
             raise CoreError("CommitmentFailed")   # commitment.rs:40-42
@@ -504,16 +507,26 @@ def compute_root_of_unity(n, modulus=NTT_MODULUS, primitive_root=NTT_PRIMITIVE_R
     return pow(primitive_root, (1 << 32) // n, modulus)
 
 
+MAX_TWO_PASS_SIZE = 1 << 17   # above it the *_large constructors (prover.h): n, m up to 2^lsr_prover_max_log2_size() = 2^22
+
+
+def prover_max_log2_size():
+    """``lsr_prover_max_log2_size``: log2 of the largest cyclic transform / constraint count (22)."""
+    return int(_abi.lib().lsr_prover_max_log2_size())
+
+
 class CyclicNtt:
     """The transform pair of rust-api/lambda-snark/src/ntt.rs: ``forward(coeffs)`` = ``ntt_forward(coeffs, modulus, omega)``
-    (natural order in and out), ``inverse(evals)`` = ``ntt_inverse``.  One handle per (modulus, n, omega)."""
+    (natural order in and out), ``inverse(evals)`` = ``ntt_inverse``.  One handle per (modulus, n, omega).  n above 2^17 (up to 2^22,
+    NTT_MODULUS only) goes through ``lsr_cyclic_ntt_context_create_large``."""
 
     def __init__(self, n, modulus=NTT_MODULUS, omega=0, device=-1):
         self._lib = _abi.lib()
         self.n, self.modulus = int(n), int(modulus)
-        self._h = self._lib.lsr_cyclic_ntt_context_create(self.modulus, self.n, int(omega), device)
+        name = "lsr_cyclic_ntt_context_create_large" if self.n > MAX_TWO_PASS_SIZE else "lsr_cyclic_ntt_context_create"
+        self._h = getattr(self._lib, name)(self.modulus, self.n, int(omega), device)
         if not self._h:
-            raise CoreError(f"lsr_cyclic_ntt_context_create({modulus}, {n}) returned NULL: {_abi.last_error()}")
+            raise CoreError(f"{name}({modulus}, {n}) returned NULL: {_abi.last_error()}")
 
     @property
     def handle(self):
@@ -563,9 +576,10 @@ class QuotientPlan:
     def __init__(self, m, device=-1):
         self._lib = _abi.lib()
         self.m = int(m)
-        self._h = self._lib.lsr_quotient_plan_create(self.m, device)
+        name = "lsr_quotient_plan_create_large" if self.m > MAX_TWO_PASS_SIZE else "lsr_quotient_plan_create"
+        self._h = getattr(self._lib, name)(self.m, device)
         if not self._h:
-            raise CoreError(f"lsr_quotient_plan_create({m}) returned NULL: {_abi.last_error()}")
+            raise CoreError(f"{name}({m}) returned NULL: {_abi.last_error()}")
 
     @property
     def handle(self):
@@ -606,18 +620,27 @@ class QuotientPlan:
             pass
 
 
+SPARSE_ENTRY_DTYPE = np.dtype([("row", "<u4"), ("col", "<u4"), ("value", "<u8")])   # r1cs.h SparseEntry, 16 bytes
+
+
 class R1csProver:
     """``R1CS`` restricted to what the prover's hot loop needs (rust-api/lambda-snark/src/r1cs.rs:88-137, 296-304, 474-506):
     the three matrices on the device, ``compute_constraint_evals`` and ``compute_quotient_poly`` for batches of witnesses.
     ``a``, ``b``, ``c`` are lists of ``(row, col, value)`` entries of m x n matrices.  ``modulus=None`` is NTT_MODULUS with m = 2^k
     (``lsr_r1cs_prover_create``); any other modulus, or NTT_MODULUS with m not a power of two, takes the Lagrange path
-    (``lsr_r1cs_prover_create_mod``: odd q >= 3, 1 <= m <= 8192)."""
+    (``lsr_r1cs_prover_create_mod``: odd q >= 3, 1 <= m <= 8192).  On the NTT path m goes up to 2^22; a matrix may
+    then also be a numpy array of dtype ``SPARSE_ENTRY_DTYPE`` (the FFI's coordinate entries), which is handed over without a copy."""
 
     def __init__(self, m, n, a, b, c, device=-1, modulus=None):
         self._lib = _abi.lib()
         self.m, self.n = int(m), int(n)
         keep, mats = [], []
         for entries in (a, b, c):
+            if isinstance(entries, np.ndarray) and entries.dtype == SPARSE_ENTRY_DTYPE:
+                arr = np.ascontiguousarray(entries if len(entries) else np.zeros(1, dtype=SPARSE_ENTRY_DTYPE))
+                keep.append(arr)
+                mats.append(_abi.SparseMatrix(ctypes.cast(arr.ctypes.data, ctypes.POINTER(_abi.SparseEntry)), len(entries), self.m, self.n))
+                continue
             arr = (_abi.SparseEntry * max(1, len(entries)))()
             for i, (row, col, value) in enumerate(entries):
                 arr[i] = _abi.SparseEntry(int(row), int(col), int(value))

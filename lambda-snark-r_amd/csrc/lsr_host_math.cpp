@@ -107,8 +107,8 @@ TwiddleTables build_twiddles(uint64_t q, uint32_t n, int logn, uint64_t psi) {
     return t;
 }
 
-bool cyclic_params_valid(uint64_t q, uint32_t n, uint64_t omega, int* logn_out) {
-    if (n < 2 || n > 131072 || (n & (n - 1))) return false;
+bool cyclic_params_valid(uint64_t q, uint32_t n, uint64_t omega, int* logn_out, int max_log2) {
+    if (n < 2 || n > (1u << max_log2) || (n & (n - 1))) return false;
     if (q != kProverModulus && (q >> 61)) return false;
     if (q < 3 || (q - 1) % n != 0 || !is_prime_u64(q)) return false;
     if (omega == 0 || omega >= q || powmod(omega, n / 2, q) != q - 1) return false;   // exact order n

@@ -47,8 +47,13 @@ constexpr uint64_t kProverModulus = 0xFFFFFFFF00000001ull;       // NTT_MODULUS,
 constexpr uint64_t kProverRoot2_32 = 1753635133440165772ull;     // NTT_PRIMITIVE_ROOT, lib.rs:78
 // Montgomery form w 2^64 mod NTT_MODULUS of a residue: how the Goldilocks kernels hold their multipliers (gold_mul_mont)
 inline uint64_t prover_montgomery(uint64_t w) { return mulmod(w % kProverModulus, 0xFFFFFFFFull, kProverModulus); }   // 2^64 = 2^32 - 1
-// n = 2^k in [2, 131072], prime q (q = NTT_MODULUS or q < 2^61), omega of exact order n.
-bool cyclic_params_valid(uint64_t q, uint32_t n, uint64_t omega, int* logn_out);
+// Size ceilings of the cyclic transforms and of everything built on them (quotient plan, R1CS prover): the entry points of the first
+// five rounds stop at 2^17 (one strided round in front of the tile pass), the *_large constructors and the R1CS prover at 2^22 (two
+// strided rounds; NTT_MODULUS only above 2^17).  lsr_prover_max_log2_size() reports the second.
+constexpr int kTwoPassMaxLog2 = 17;
+constexpr int kProverMaxLog2 = 22;
+// n = 2^k in [2, 2^max_log2], prime q (q = NTT_MODULUS or q < 2^61), omega of exact order n.
+bool cyclic_params_valid(uint64_t q, uint32_t n, uint64_t omega, int* logn_out, int max_log2 = kTwoPassMaxLog2);
 // omega_n of compute_root_of_unity (ntt.rs:226-233); 0 unless q = NTT_MODULUS
 uint64_t prover_root_of_unity(uint64_t q, uint64_t n);
 TwiddleTables build_cyclic_twiddles(uint64_t q, uint32_t n, int logn, uint64_t omega);

@@ -183,14 +183,19 @@ NttContext* create_ntt_context(uint64_t q, uint32_t n, int device) {
     return build_context("ntt_context_create", q, n, logn, device, build_twiddles(q, n, logn, psi), false);
 }
 
-NttContext* create_cyclic_ntt_context(uint64_t q, uint32_t n, uint64_t omega, int device) {
+NttContext* create_cyclic_ntt_context(uint64_t q, uint32_t n, uint64_t omega, int device, bool large, const char* where) {
     if (omega == 0) omega = prover_root_of_unity(q, n);
     int logn = 0;
-    if (!cyclic_params_valid(q, n, omega, &logn)) {
-        set_last_error("lsr_cyclic_ntt_context_create: need n = 2^k in [2,131072], prime q (NTT_MODULUS or < 2^61), omega of order n");
+    if (!cyclic_params_valid(q, n, omega, &logn, large ? kProverMaxLog2 : kTwoPassMaxLog2)) {
+        set_last_error(std::string(where) + ": need n = 2^k in [2," + std::to_string(1u << (large ? kProverMaxLog2 : kTwoPassMaxLog2)) +
+                       "], prime q (NTT_MODULUS or < 2^61), omega of order n");
         return nullptr;
     }
-    return build_context("lsr_cyclic_ntt_context_create", q, n, logn, device, build_cyclic_twiddles(q, n, logn, omega), true);
+    if (logn > kTwoPassMaxLog2 && q != kProverModulus) {   // the three-pass schedule exists in the Goldilocks flavour only (run_ntt)
+        set_last_error(std::string(where) + ": n above 131072 needs q = NTT_MODULUS (the F64 / Shoup flavours stop at two passes)");
+        return nullptr;
+    }
+    return build_context(where, q, n, logn, device, build_cyclic_twiddles(q, n, logn, omega), true);
 }
 
 hipStream_t work_stream(const NttContext& c) {
@@ -318,6 +323,24 @@ static void small_inverse(const NttContext& c, uint64_t* d, size_t total, hipStr
     }
 }
 
+// Three-pass schedule of n = 2^18 .. 2^22: the top r_top index bits and the r_inner bits below them through one
+// strided round each, the low lt bits through the tile kernel.  Radix-16 rounds wherever the size allows (5-stage rounds measured
+// slower, profiles/README.md), the tile as large as possible.
+struct LargeSchedule {
+    int r_top, r_inner, lt;
+};
+static LargeSchedule large_schedule(int logn) {
+    const int r_top = logn >= 21 ? 5 : 4, r_inner = logn >= 22 ? 5 : 4;
+    return {r_top, r_inner, logn - r_top - r_inner};            // lt = 10, 11, 12, 12, 12
+}
+template <class A, bool INVERSE>
+static void inner_round(const NttContext& c, uint64_t* d, size_t total, int lo, int r, hipStream_t s) {
+    const unsigned grid = static_cast<unsigned>((total >> r) / kThreads);
+    const auto* tw = INVERSE ? Flavour<A>::inv(c) : Flavour<A>::fwd(c);
+    if (r == 4) hipLaunchKernelGGL((ntt_inner_round<A, 4, INVERSE>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw);
+    else hipLaunchKernelGGL((ntt_inner_round<A, 5, INVERSE>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw);
+}
+
 size_t ntt_chunk_bytes() {
     static const size_t bytes = [] {
         if (const char* e = std::getenv("LAMBDA_SNARK_NTT_CHUNK_MIB")) {
@@ -341,8 +364,12 @@ static void run_ntt(const NttContext& c, uint64_t* d, size_t batch, bool inverse
     }
     // n > 4096: the top 4 (n = 2^17: 5) index bits go through ONE strided round, the low `lt` = 9..12 bits through the
     // tile kernel.  (5- and 6-stage strided rounds were measured slower at n = 2^16: profiles/README.md.)
-    const int r_top = std::max(c.logn - kTileLog, 4);
-    const int lt = c.logn - r_top;
+    // n > 2^17: a second strided round between the two (large_schedule).
+    const bool three = c.logn > kTwoPassMaxLog2;
+    if (three && !std::is_same_v<A, ArithGold>) throw std::runtime_error("transforms above n = 131072: NTT_MODULUS contexts only");
+    const LargeSchedule ls = three ? large_schedule(c.logn) : LargeSchedule{std::max(c.logn - kTileLog, 4), 0, 0};
+    const int r_top = ls.r_top;
+    const int lt = three ? ls.lt : c.logn - r_top;
     // Walk the batch in chunks small enough that the array written by one pass is still resident in the
     // 256 MiB Infinity Cache when the next pass reads it (MI355X_MICROARCH.md "Infinity Cache").
     const size_t chunk_polys = std::max<size_t>(1, ntt_chunk_bytes() >> (c.logn + 3));
@@ -353,9 +380,15 @@ static void run_ntt(const NttContext& c, uint64_t* d, size_t batch, bool inverse
         hipStream_t cs = s;
         if (!inverse) {
             strided<A, false, false, true>(c, base, count, c.logn - r_top, r_top, cs, src ? src + (first << c.logn) : nullptr);
+            if constexpr (std::is_same_v<A, ArithGold>) {
+                if (three) inner_round<A, false>(c, base, count, lt, ls.r_inner, cs);
+            }
             pass_forward<A>(c, lt, base, count, cs);
         } else {
             pass_inverse<A>(c, lt, base, count, cs, pre);
+            if constexpr (std::is_same_v<A, ArithGold>) {
+                if (three) inner_round<A, true>(c, base, count, lt, ls.r_inner, cs);
+            }
             strided<A, true, true, false>(c, base, count, c.logn - r_top, r_top, cs, add ? add + (first << c.logn) : nullptr);
         }
     }
@@ -435,7 +468,7 @@ void launch_top_round_inverse(const NttContext& c, uint64_t* data, size_t polys,
 // The strided round of an n > 4096 transform in any flavour (the outer passes of the ring multiply, lsr_ring_mul.hip): forward reads
 // canonical `src` and writes raw elements to `d` (may alias); inverse turns raw elements of `d` into canonical residues in place.
 void launch_strided_round(const NttContext& c, uint64_t* d, const uint64_t* src, size_t polys, bool inverse, hipStream_t s) {
-    if (c.logn <= kTileLog) throw std::runtime_error("strided round: n > 4096 only");
+    if (c.logn <= kTileLog || c.logn > kTwoPassMaxLog2) throw std::runtime_error("strided round: 4096 < n <= 131072 only");
     const int r_top = std::max(c.logn - kTileLog, 4), lo = c.logn - r_top;
     const size_t total = polys << c.logn;
     if (inverse) {

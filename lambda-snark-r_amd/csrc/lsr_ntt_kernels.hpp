@@ -15,6 +15,8 @@
 //   * strided round kernel — the top 4 (n = 2^17: 5) index bits of n > 4096: 16 registers hold residues
 //     n/16 apart, all 256 lanes of a workgroup walk consecutive addresses, no LDS, twiddles are the
 //     first 15 table entries (scalar loads).
+//   * inner strided round kernel — n > 2^17 (Goldilocks contexts, up to 2^22): the 4 or 5 index bits between the top round's and the
+//     tile's; the upper index bits select its twiddles, the same for all lanes of a workgroup (scalar loads again).
 // The intermediate array between two kernels of one transform is private, so it is left in the
 // arithmetic's raw element form (f64 bit patterns for ArithF64) — no conversion at pass boundaries.
 #pragma once
@@ -819,6 +821,66 @@ __global__ void __launch_bounds__(kThreads) ntt_strided_round_sampling(uint64_t*
                                                                          const typename A::twid* __restrict__ tw, RoundConsts<A> cs,
                                                                          const uint64_t* __restrict__ src, BlindSampler bs) {
     strided_round_body<A, R, false, false, true, false, 3>(data, total, lo, p, tw, cs, src, bs);
+}
+
+// ---- inner strided round (index bits [lo, lo + R) with lo + R < log n: the second round of an n > 2^17 transform) ----
+// Stage s of the transform multiplies by twiddle[2^s + (index >> (L - s))]: for register bit j (index bit lo + j) that is entry
+// ((2^H + h) << (R-1-j)) + u, with H = log n - lo - R, h = the index bits above the round and u = the register bits above j.  The top
+// round is the case H = 0, h = 0.  A workgroup's 256 lanes walk consecutive addresses and lo >= 8, so h (taken from the block index
+// alone) is the same for all of them and the 2^R - 1 twiddles are scalar loads like the top round's (runs of 2^(R-1-j) consecutive
+// entries per stage).  Raw elements in and out, in place; the inverse mirrors the forward (Gentleman-Sande, low bit first, inverse
+// table).  Exactness: the round runs the butterflies A::ct / A::gs of the other rounds on their own hand-off contract; for
+// Goldilocks forward values are any 64-bit representative and inverse values canonical (lsr_arith.hpp), whatever the number of
+// rounds.  The F64 / U64 flavours bound their raw values by the number of stages between reductions and are not carried through a
+// third pass: lsr_ntt.hip instantiates this kernel for ArithGold only.  (No unit-twiddle skip: only h = 0 has omega^0 entries.)
+template <class A, int R, bool INVERSE>
+__global__ void __launch_bounds__(kThreads) ntt_inner_round(uint64_t* __restrict__ data, size_t total, int lo, ModParams p,
+                                                              const typename A::twid* __restrict__ tw) {
+    using elem = typename A::elem;
+    constexpr int N = 1 << R;
+    const uint32_t per_high = 1u << (lo - 8);                       // workgroups per value of the upper bits
+    const size_t high = (size_t)(blockIdx.x >> (lo - 8));          // polynomial | index bits above the round: workgroup-uniform
+    const size_t low = (size_t)((blockIdx.x & (per_high - 1u)) << 8) | threadIdx.x;
+    const size_t idx0 = (high << (lo + R)) | low;
+    if (idx0 + ((size_t)(N - 1) << lo) >= total) return;            // (the grid is exact: total >> R is a multiple of kThreads)
+    const int hbits = p.logn - lo - R;
+    const uint32_t tbase = (1u << hbits) | ((uint32_t)high & ((1u << hbits) - 1u));
+    elem v[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = elem_from_bits<A>(data[idx0 + ((size_t)k << lo)]);
+    if (!INVERSE) {
+#pragma unroll
+        for (int j = R - 1; j >= 0; --j) {
+            const int half = 1 << j;
+#pragma unroll
+            for (int u = 0; u < (1 << (R - 1 - j)); ++u) {
+                const typename A::twid w = tw[(tbase << (R - 1 - j)) + u];
+#pragma unroll
+                for (int l = 0; l < half; ++l) {
+                    const int kx = (u << (j + 1)) | l;
+                    A::ct(v[kx], v[kx + half], w, p);
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            const int half = 1 << j;
+#pragma unroll
+            for (int u = 0; u < (1 << (R - 1 - j)); ++u) {
+                const typename A::twid w = tw[(tbase << (R - 1 - j)) + u];
+#pragma unroll
+                for (int l = 0; l < half; ++l) {
+                    const int kx = (u << (j + 1)) | l;
+                    A::gs(v[kx], v[kx + half], w, p);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k) A::end_of_inverse_round(v[k], p);
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) data[idx0 + ((size_t)k << lo)] = elem_bits<A>(v[k]);
 }
 
 // ---- pointwise product (ntt.cpp:106-119) ------------------------------------------------------------

@@ -43,8 +43,13 @@ __device__ __forceinline__ uint32_t rev_bits(uint32_t v, int bits) { return bits
 // table T (LDS, one entry per row, broadcast reads) on the row only.  One Montgomery product per coefficient and point; the
 // lane's sum is multiplied by f_t once and the workgroup adds its 256 partial sums.  The sums are exact residues: any order
 // gives the same words.
+// More than 2^17 coefficients are walked in PASSES of 512 rows that reuse the table: row r = pass 512 + rr, and
+//   NATURAL: e = t + (rr << 8) + (pass << 17)                                          -> f_t T[rr] (x^(2^17))^pass;
+//   BITREV:  e = rev8(t) << (logm - 8) | rev9(rr) << (logm - 17) | rev_{logm-17}(pass)  -> f_t T[rr] x^rev(pass).
+// eval_partial covers the rows [row0, row0 + row_count) that exist (whole passes or a part of one) and returns, in lanes
+// t < 2 NPOLY, the workgroup's unscaled sum of polynomial t >> 1 at point t & 1.
 template <bool BITREV, int NPOLY>
-__global__ void __launch_bounds__(kEvalBlock) eval_kernel(EvalPolys polys, EvalPoints pts, EvalOut out, int logm, uint64_t scale_mont) {
+__device__ __forceinline__ uint64_t eval_partial(const EvalPolys& polys, const EvalPoints& pts, int logm, uint32_t row0, uint32_t row_count) {
     __shared__ uint64_t table[2][kEvalRows];
     __shared__ uint64_t partial[kEvalBlock / 64][NPOLY][2];
     const size_t inst = blockIdx.x;
@@ -53,25 +58,28 @@ __global__ void __launch_bounds__(kEvalBlock) eval_kernel(EvalPolys polys, EvalP
     const int npts = (pts.count - first) >= 2 ? 2 : 1;
     const uint32_t len = polys.len;
     const uint32_t rows = (len + kEvalBlock - 1) / kEvalBlock;
-    // BITREV: pos = r 256 + t, e = bitrev_lo(t) << hi | bitrev_hi(r) with lo = min(logm, 8) bits of lane and hi = logm - lo
+    // BITREV: pos = r 256 + t with lo = min(logm, 8) bits of lane and hi = logm - lo bits of row, of which the top pass_bits count passes
     const int lo_bits = logm < 8 ? logm : 8, hi_bits = logm - lo_bits;
-    uint64_t lane_f[2], step[2];   // step: x^(2^17) for the natural order's passes (Montgomery)
+    const int pass_bits = BITREV && hi_bits > 9 ? hi_bits - 9 : 0, row_bits = hi_bits - pass_bits;
+    const int exp_bits = BITREV && logm > 17 ? logm : 17;
+    uint64_t lane_f[2], step[2], xm[2];   // step: x^(2^17) for the natural order's passes; xm: x (both Montgomery)
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const uint64_t raw = k < npts ? pts.x[k][inst * pts.stride + first] : 0;
         uint64_t sq = gold_mul(gold_canonical(raw), kGoldEpsilon);   // x^(2^b) in Montgomery form, b = 0, 1, ...
+        xm[k] = sq;
         uint64_t f = kGoldOneMont, e0 = kGoldOneMont, e1 = kGoldOneMont;
         const uint32_t lane_exp = BITREV ? (rev_bits((uint32_t)t & ((1u << lo_bits) - 1u), lo_bits) << hi_bits) : (uint32_t)t;
         const uint32_t r0 = (uint32_t)t, r1 = (uint32_t)t + kEvalBlock;
-        const uint32_t x0 = BITREV ? rev_bits(r0, hi_bits) : r0 << 8, x1 = BITREV ? rev_bits(r1, hi_bits) : r1 << 8;
-        for (int b = 0; b < 17; ++b) {
+        const uint32_t x0 = BITREV ? rev_bits(r0, row_bits) << pass_bits : r0 << 8, x1 = BITREV ? rev_bits(r1, row_bits) << pass_bits : r1 << 8;
+        for (int b = 0; b < exp_bits; ++b) {
             if ((lane_exp >> b) & 1u) f = gold_mul_mont(f, sq);
             if ((x0 >> b) & 1u) e0 = gold_mul_mont(e0, sq);
             if ((x1 >> b) & 1u) e1 = gold_mul_mont(e1, sq);
+            if (b == 16) step[k] = gold_mul_mont(sq, sq);      // x^(2^17)
             sq = gold_mul_mont(sq, sq);
         }
         lane_f[k] = f;
-        step[k] = sq;                                      // x^(2^17)
         table[k][r0] = e0;
         table[k][r1] = e1;
     }
@@ -79,13 +87,26 @@ __global__ void __launch_bounds__(kEvalBlock) eval_kernel(EvalPolys polys, EvalP
     uint64_t total[NPOLY][2];
 #pragma unroll
     for (int j = 0; j < NPOLY; ++j) total[j][0] = total[j][1] = 0;
-    uint64_t pass_f[2] = {kGoldOneMont, kGoldOneMont};
-    for (uint32_t base = 0; base < rows; base += kEvalRows) {   // BITREV: m <= 2^17, one pass
-        const uint32_t end = rows - base < (uint32_t)kEvalRows ? rows : base + kEvalRows;
+    uint64_t pass_f[2] = {kGoldOneMont, kGoldOneMont};         // NATURAL: (x^(2^17))^pass
+    if (!BITREV) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            uint64_t sq = step[k];
+            for (uint32_t e = row0 / (uint32_t)kEvalRows; e; e >>= 1) {
+                if (e & 1u) pass_f[k] = gold_mul_mont(pass_f[k], sq);
+                sq = gold_mul_mont(sq, sq);
+            }
+        }
+    }
+    const uint32_t row_end = (row0 >= rows || row_count > rows - row0) ? rows : row0 + row_count;
+    for (uint32_t pass = row0 / (uint32_t)kEvalRows; pass * (uint32_t)kEvalRows < row_end && row0 < row_end; ++pass) {
+        const uint32_t base = pass * (uint32_t)kEvalRows;
+        const uint32_t begin = base > row0 ? base : row0;
+        const uint32_t end = row_end - base < (uint32_t)kEvalRows ? row_end : base + kEvalRows;
         uint64_t acc[NPOLY][2];
 #pragma unroll
         for (int j = 0; j < NPOLY; ++j) acc[j][0] = acc[j][1] = 0;
-        for (uint32_t r = base; r < end; ++r) {
+        for (uint32_t r = begin; r < end; ++r) {
             const uint32_t pos = r * kEvalBlock + (uint32_t)t;
             const uint64_t w0 = table[0][r - base], w1 = table[1][r - base];
             if (pos < len) {
@@ -99,7 +120,17 @@ __global__ void __launch_bounds__(kEvalBlock) eval_kernel(EvalPolys polys, EvalP
         }
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const uint64_t g = gold_mul_mont(lane_f[k], pass_f[k]);
+            uint64_t pf = pass_f[k];
+            if (BITREV) {                                      // x^rev(pass): pass_bits <= 5 squarings
+                pf = kGoldOneMont;
+                uint64_t sq = xm[k];
+                const uint32_t e = rev_bits(pass, pass_bits);
+                for (int b = 0; b < pass_bits; ++b) {
+                    if ((e >> b) & 1u) pf = gold_mul_mont(pf, sq);
+                    sq = gold_mul_mont(sq, sq);
+                }
+            }
+            const uint64_t g = gold_mul_mont(lane_f[k], pf);
 #pragma unroll
             for (int j = 0; j < NPOLY; ++j) total[j][k] = gold_add(total[j][k], gold_mul_mont(acc[j][k], g));
             pass_f[k] = gold_mul_mont(pass_f[k], step[k]);
@@ -118,13 +149,51 @@ __global__ void __launch_bounds__(kEvalBlock) eval_kernel(EvalPolys polys, EvalP
             if ((t & 63) == 0) partial[t >> 6][j][k] = v;
         }
     __syncthreads();
-    if (t < NPOLY * 2 && (t & 1) < npts) {
+    uint64_t v = 0;
+    if (t < NPOLY * 2) {
         const int j = t >> 1, k = t & 1;
-        uint64_t v = 0;
 #pragma unroll
         for (int w = 0; w < kEvalBlock / 64; ++w) v = gold_add(v, partial[w][j][k]);
-        out.v[inst * out.inst_stride + (size_t)j * out.poly_stride + first + k] = gold_mul_mont(v, scale_mont);
     }
+    return v;
+}
+
+// one workgroup walks every pass of its polynomials (grid: instances x point pairs)
+template <bool BITREV, int NPOLY>
+__global__ void __launch_bounds__(kEvalBlock) eval_kernel(EvalPolys polys, EvalPoints pts, EvalOut out, int logm, uint64_t scale_mont) {
+    const uint64_t v = eval_partial<BITREV, NPOLY>(polys, pts, logm, 0u, ~0u);
+    const int t = threadIdx.x;
+    const uint32_t first = 2u * blockIdx.y;
+    if (t < NPOLY * 2 && first + (uint32_t)(t & 1) < pts.count)
+        out.v[blockIdx.x * out.inst_stride + (size_t)(t >> 1) * out.poly_stride + first + (t & 1)] = gold_mul_mont(v, scale_mont);
+}
+
+// Long polynomials in few instances (m > 2^17: a chunk of the prove call holds 16 instances or fewer at m = 2^22): the passes are
+// spread over gridDim.z slices of `rows_per_slice` 256-coefficient rows each (gridDim.y already walks the point pairs; a slice may be a
+// part of a pass: the m = 4096 workload runs 16 rows per workgroup the same way), every slice leaves its sums in
+// part[((inst pairs + pair) slices + slice)][NPOLY][2], and eval_combine_kernel adds the slices and scales.  Exact residues: the same
+// words as the single-workgroup walk.
+template <bool BITREV, int NPOLY>
+__global__ void __launch_bounds__(kEvalBlock) eval_slice_kernel(EvalPolys polys, EvalPoints pts, uint64_t* __restrict__ part, int logm,
+                                                                uint32_t rows_per_slice) {
+    const uint64_t v = eval_partial<BITREV, NPOLY>(polys, pts, logm, blockIdx.z * rows_per_slice, rows_per_slice);
+    const size_t cell = ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * gridDim.z + blockIdx.z;
+    if (threadIdx.x < NPOLY * 2) part[cell * (NPOLY * 2) + threadIdx.x] = v;
+}
+// one lane per (instance, point pair, polynomial, point of the pair)
+template <int NPOLY>
+__global__ void __launch_bounds__(256) eval_combine_kernel(const uint64_t* __restrict__ part, uint32_t pairs, uint32_t slices, uint32_t count,
+                                                           EvalOut out, uint64_t scale_mont, size_t lanes) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= lanes) return;
+    const uint32_t jk = (uint32_t)(i % (NPOLY * 2));
+    const size_t cell = i / (NPOLY * 2);                       // inst pairs + pair
+    const size_t inst = cell / pairs;
+    const uint32_t first = 2u * (uint32_t)(cell - inst * pairs);
+    if (first + (jk & 1u) >= count) return;
+    uint64_t v = 0;
+    for (uint32_t s = 0; s < slices; ++s) v = gold_add(v, part[(cell * slices + s) * (NPOLY * 2) + jk]);
+    out.v[inst * out.inst_stride + (size_t)(jk >> 1) * out.poly_stride + first + (jk & 1u)] = gold_mul_mont(v, scale_mont);
 }
 
 // the commitment message of prove_r1cs / prove_r1cs_zk: msg[i][j] = Q'_j mod commit_modulus, Q' = Q + r (X^m - 1) built as poly_add

@@ -325,12 +325,14 @@ static void destroy_plan(LsrQuotientPlan* p) {
 }
 using QuotientPlanPtr = std::unique_ptr<LsrQuotientPlan, HandleDeleter<LsrQuotientPlan, destroy_plan>>;
 
-static LsrQuotientPlan* create_plan(uint32_t m, int device) {
-    if (m == 0 || m > 131072 || (m & (m - 1))) {
-        set_last_error("lsr_quotient_plan_create: m must be a power of two in [1, 131072] (r1cs.rs:386-389)");
+// large: the ceiling is 2^22 (lsr_quotient_plan_create_large, the R1CS prover) instead of 2^17; `where` names the entry point
+static LsrQuotientPlan* create_plan(uint32_t m, int device, bool large, const char* where) {
+    const uint32_t max_m = 1u << (large ? kProverMaxLog2 : kTwoPassMaxLog2);
+    if (m == 0 || m > max_m || (m & (m - 1))) {
+        set_last_error(std::string(where) + ": m must be a power of two in [1, " + std::to_string(max_m) + "] (r1cs.rs:386-389)");
         return nullptr;
     }
-    device = resolve_device("lsr_quotient_plan_create", device, true);
+    device = resolve_device(where, device, true);
     if (device < 0) return nullptr;
     QuotientPlanPtr p(new LsrQuotientPlan);
     p->m = m;
@@ -343,7 +345,7 @@ static LsrQuotientPlan* create_plan(uint32_t m, int device) {
     while ((1u << p->logm) < m) ++p->logm;
     const uint64_t q = kProverModulus;
     if (m >= 2) {
-        p->ntt.reset(create_cyclic_ntt_context(q, m, invmod_prime(prover_root_of_unity(q, m), q), device));
+        p->ntt.reset(create_cyclic_ntt_context(q, m, invmod_prime(prover_root_of_unity(q, m), q), device, large, where));
         if (!p->ntt) return nullptr;
     }
     try {
@@ -372,7 +374,7 @@ static LsrQuotientPlan* create_plan(uint32_t m, int device) {
         }
         LSR_HIP(hipStreamCreateWithFlags(&p->stream.handle, hipStreamNonBlocking));
     } catch (const std::exception& e) {
-        set_last_error(std::string("lsr_quotient_plan_create: ") + e.what());
+        set_last_error(std::string(where) + ": " + e.what());
         return nullptr;
     }
     return p.release();
@@ -394,6 +396,7 @@ struct LsrR1csProver {
     lsr::DeviceBuffer<uint64_t> quot;       // quotient [chunk][m]
     lsr::DeviceBuffer<uint64_t> msg;        // commitment messages [chunk][m + 1]
     lsr::DeviceBuffer<uint32_t> len;        // [chunk]
+    lsr::DeviceBuffer<uint64_t> eval_part;  // m > 2^17: per-slice sums of the evaluation stage [chunk][slices <= 1024][3][2]
     lsr::R1csScratch ws;                    // per-instance scratch and host staging; its chunk sizes the buffers above
     int device() const { return plan ? plan->device : lsr::lagrange_device(lag.get()); }
 };
@@ -414,7 +417,7 @@ using R1csProverPtr = std::unique_ptr<LsrR1csProver, HandleDeleter<LsrR1csProver
 
 static LsrR1csProver* create_prover(const SparseMatrix* const mats[3], int device) {
     if (!r1cs_shape_ok("lsr_r1cs_prover_create", mats)) return nullptr;
-    QuotientPlanPtr plan(create_plan(mats[0]->n_rows, device));
+    QuotientPlanPtr plan(create_plan(mats[0]->n_rows, device, true, "lsr_r1cs_prover_create"));
     if (!plan) return nullptr;
     R1csProverPtr r(new LsrR1csProver);
     r->m = mats[0]->n_rows;
@@ -461,6 +464,34 @@ static void prover_run(LsrR1csProver& r, const uint64_t* witnesses, size_t batch
     }
 }
 
+// Split of an evaluation over slices (lsr_prove_kernels.hpp eval_slice_kernel) for `groups` = instances x point pairs polynomials
+// of `len` coefficients: none up to 2^17 coefficients (the single-workgroup kernel, as before); above, slices of 16 .. 512 rows (doubling
+// while that still leaves 2048 workgroups) and at most kEvalMaxSlices of them, so four instances at m = 2^20 run 1024 workgroups instead of 4.
+constexpr uint32_t kEvalMaxSlices = 1024;
+struct EvalSplit {
+    uint32_t slices, rows;
+};
+static EvalSplit eval_split(size_t len, size_t groups) {
+    if (len <= (size_t)kEvalPass) return {1u, 0u};
+    const size_t rows = (len + kEvalBlock - 1) / kEvalBlock;
+    size_t per = 16;
+    while ((per < (size_t)kEvalRows && rows * groups / (2 * per) >= 2048) || (rows + per - 1) / per > kEvalMaxSlices) per *= 2;
+    return {(uint32_t)((rows + per - 1) / per), (uint32_t)per};
+}
+
+template <bool BITREV, int NPOLY>
+static void launch_eval(const EvalPolys& polys, const EvalPoints& pts, const EvalOut& out, int logm, uint64_t scale_mont, size_t count, uint32_t pairs,
+                        uint32_t slices, uint32_t rows_per_slice, uint64_t* part, hipStream_t s) {
+    if (slices <= 1) {
+        hipLaunchKernelGGL((eval_kernel<BITREV, NPOLY>), dim3((unsigned)count, pairs), dim3(kEvalBlock), 0, s, polys, pts, out, logm, scale_mont);
+        return;
+    }
+    hipLaunchKernelGGL((eval_slice_kernel<BITREV, NPOLY>), dim3((unsigned)count, pairs, slices), dim3(kEvalBlock), 0, s, polys, pts, part, logm,
+                       rows_per_slice);
+    const size_t lanes = count * pairs * (size_t)(NPOLY * 2);
+    hipLaunchKernelGGL((eval_combine_kernel<NPOLY>), dim3(blocks_for(lanes, ~0u)), dim3(kBlock), 0, s, part, pairs, slices, pts.count, out, scale_mont, lanes);
+}
+
 // ---- prove_r1cs / prove_r1cs_zk for a batch (lib.rs:747-809, 877-980) ----------------------------------
 // Per chunk, all on one stream: constraint evals (from device witnesses) -> quotient pass with A's and B's interpolants stashed ->
 // message Q' mod commit_modulus -> keys -> rows -> alpha -> beta -> evaluations -> proof records.
@@ -472,6 +503,7 @@ static void ensure_prove_workspace(LsrR1csProver& r, size_t chunk, size_t n_publ
     r.quot.reserve(c * r.m);
     r.msg.reserve(c * (r.m + 1));
     r.len.reserve(c);
+    if (r.m > (uint32_t)kEvalPass) r.eval_part.reserve(c * kEvalMaxSlices * 6);
     r.ws.grow(c, n_public);
 }
 
@@ -500,10 +532,10 @@ static void prove_chunk(LsrR1csProver& r, const R1csProveCall& a, const uint64_t
     const EvalPoints pts{{v.alphas, v.betas}, 1, 2};
     const uint64_t m_inv = prover_montgomery(invmod_prime(r.m % kProverModulus, kProverModulus));
     const EvalPolys abc{{r.stash.ptr, r.stash.ptr + per_vector, work + 2 * per_vector}, r.m, r.m};
-    hipLaunchKernelGGL((eval_kernel<true, 3>), dim3((unsigned)count, 1), dim3(kEvalBlock), 0, s, abc, pts, EvalOut{v.ev, 8, 2}, p.logm, m_inv);
+    const EvalSplit split = eval_split(r.m, count);
+    launch_eval<true, 3>(abc, pts, EvalOut{v.ev, 8, 2}, p.logm, m_inv, count, 1, split.slices, split.rows, r.eval_part.ptr, s);
     const EvalPolys qp{{r.quot.ptr, r.quot.ptr, r.quot.ptr}, r.m, r.m};
-    hipLaunchKernelGGL((eval_kernel<false, 1>), dim3((unsigned)count, 1), dim3(kEvalBlock), 0, s, qp, pts, EvalOut{v.ev + 6, 8, 0}, p.logm,
-                       kGoldOneMont);
+    launch_eval<false, 1>(qp, pts, EvalOut{v.ev + 6, 8, 0}, p.logm, kGoldOneMont, count, 1, split.slices, split.rows, r.eval_part.ptr, s);
     hipLaunchKernelGGL(prove_assemble_kernel, dim3(blocks_for(count, ~0u)), dim3(kBlock), 0, s, v.ev, v.alphas, v.betas, d_blind, r.len.ptr, v.hash_a,
                        v.hash_b, p.logm, d_proofs, reinterpret_cast<uint64_t*>(d_hashes), d_status, count);
     LSR_HIP(hipGetLastError());
@@ -533,15 +565,28 @@ static void verify_device(uint32_t m, const uint64_t* d_pub, size_t n_public, co
 }
 
 static void eval_device(const uint64_t* d_c, size_t len, size_t batch, const uint64_t* d_x, uint32_t ppp, uint64_t* d_v, hipStream_t s) {
-    for (size_t done = 0; done < batch; done += 0x7fffffffull) {   // grid.x bound
-        const size_t now = std::min<size_t>(0x7fffffffull, batch - done);
-        const uint64_t* c = d_c + done * len;
-        const EvalPolys polys{{c, c, c}, len, (uint32_t)len};
-        const EvalPoints pts{{d_x + done * ppp, d_x + done * ppp + 1}, ppp, ppp};
-        hipLaunchKernelGGL((eval_kernel<false, 1>), dim3((unsigned)now, (ppp + 1) / 2), dim3(kEvalBlock), 0, s, polys, pts, EvalOut{d_v + done * ppp, ppp, 0}, 0,
-                           kGoldOneMont);
+    // Few long polynomials (fewer than 1024 workgroups of more than 2^17 coefficients): the rows are spread over slices (eval_split), with
+    // the per-slice sums in stream-ordered scratch.  A capturing stream (no allocation inside a capture) keeps the one-workgroup walk.
+    const uint32_t pairs = (ppp + 1) / 2;
+    EvalSplit split{1u, 0u};
+    if (batch * pairs < 1024 && !stream_is_capturing(s)) split = eval_split(len, batch * pairs);
+    const uint32_t slices = split.slices, per_slice = split.rows;
+    uint64_t* part = nullptr;
+    if (slices > 1) LSR_HIP(hipMallocAsync(reinterpret_cast<void**>(&part), batch * pairs * slices * 2 * 8, s));
+    try {
+        for (size_t done = 0; done < batch; done += 0x7fffffffull) {   // grid.x bound (a sliced call has batch < 1024: one trip)
+            const size_t now = std::min<size_t>(0x7fffffffull, batch - done);
+            const uint64_t* c = d_c + done * len;
+            const EvalPolys polys{{c, c, c}, len, (uint32_t)len};
+            const EvalPoints pts{{d_x + done * ppp, d_x + done * ppp + 1}, ppp, ppp};
+            launch_eval<false, 1>(polys, pts, EvalOut{d_v + done * ppp, ppp, 0}, 0, kGoldOneMont, now, pairs, slices, per_slice, part, s);
+        }
+        LSR_HIP(hipGetLastError());
+    } catch (...) {
+        if (part) (void)hipFreeAsync(part, s);
+        throw;
     }
-    LSR_HIP(hipGetLastError());
+    if (part) LSR_HIP(hipFreeAsync(part, s));
 }
 
 // natural-order transforms for host callers: ntt.rs:117-201
@@ -586,6 +631,14 @@ NttContext* lsr_cyclic_ntt_context_create(uint64_t q, uint32_t n, uint64_t omega
         return nullptr;
     }
 }
+NttContext* lsr_cyclic_ntt_context_create_large(uint64_t q, uint32_t n, uint64_t omega, int device) noexcept {
+    try {
+        return lsr::create_cyclic_ntt_context(q, n, omega, device, true, "lsr_cyclic_ntt_context_create_large");
+    } catch (...) {
+        return nullptr;
+    }
+}
+uint32_t lsr_prover_max_log2_size(void) noexcept { return lsr::kProverMaxLog2; }
 int lsr_ntt_context_is_cyclic(const NttContext* ctx) noexcept { return ctx && ctx->cyclic ? 1 : 0; }
 
 int lsr_cyclic_ntt_forward_batch(const NttContext* ctx, uint64_t* values, size_t batch) noexcept {
@@ -605,7 +658,14 @@ int lsr_bit_reverse_device(uint64_t* d_out, const uint64_t* d_in, int logn, size
 
 LsrQuotientPlan* lsr_quotient_plan_create(uint32_t m, int device) noexcept {
     try {
-        return lsr::create_plan(m, device);
+        return lsr::create_plan(m, device, false, "lsr_quotient_plan_create");
+    } catch (...) {
+        return nullptr;
+    }
+}
+LsrQuotientPlan* lsr_quotient_plan_create_large(uint32_t m, int device) noexcept {
+    try {
+        return lsr::create_plan(m, device, true, "lsr_quotient_plan_create_large");
     } catch (...) {
         return nullptr;
     }

@@ -83,7 +83,12 @@ static void ring_mul_enqueue(const NttContext& c, uint64_t* d_c, const uint64_t*
 }
 
 // One call on the device (caller validated the arguments): workspace, ordering brackets, launches.
+static void refuse_large(const NttContext& c) {   // the middle pass below assumes ONE strided round on either side
+    if (c.logn > kTwoPassMaxLog2) throw std::runtime_error("ring multiply on a context above n = 131072 is not supported (lsr_cyclic_ntt_context_create_large)");
+}
+
 static void ring_mul_device(const NttContext& c, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t b_rows, hipStream_t s) {
+    refuse_large(c);
     const bool shared_b = b_rows == 1 && batch > 1;
     std::lock_guard<std::mutex> lock(c.ring_mutex);
     const bool capturing = stream_is_capturing(s);
@@ -106,6 +111,7 @@ static void ring_mul_device(const NttContext& c, uint64_t* d_c, const uint64_t* 
 
 // host buffers through bounded device chunks on the context's work stream
 static void host_ring_mul(const NttContext& c, uint64_t* out, const uint64_t* a, const uint64_t* b, size_t batch, size_t b_rows) {
+    refuse_large(c);
     DeviceGuard guard(c.device);
     const size_t n = c.degree;
     const bool shared_b = b_rows == 1 && batch > 1;

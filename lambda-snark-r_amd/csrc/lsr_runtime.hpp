@@ -224,7 +224,10 @@ namespace lsr {
 
 NttContext* create_ntt_context(uint64_t q, uint32_t n, int device);
 // cyclic transform over F_q with the given primitive n-th root (0 = the reference's root for NTT_MODULUS)
-NttContext* create_cyclic_ntt_context(uint64_t q, uint32_t n, uint64_t omega, int device);
+// large: the ceiling is 2^22 instead of 2^17 (lsr_cyclic_ntt_context_create_large; above 2^17 only q = NTT_MODULUS); `where` names
+// the entry point in lsr_last_error
+NttContext* create_cyclic_ntt_context(uint64_t q, uint32_t n, uint64_t omega, int device, bool large = false,
+                                      const char* where = "lsr_cyclic_ntt_context_create");
 void destroy_ntt_context(NttContext* ctx);
 using NttContextPtr = std::unique_ptr<NttContext, HandleDeleter<NttContext, destroy_ntt_context>>;
 hipStream_t work_stream(const NttContext& ctx);
