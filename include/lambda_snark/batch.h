@@ -240,14 +240,33 @@ int lsr_fs_challenge(const uint64_t* public_inputs, size_t n_inputs, const LweCo
 int lsr_fs_challenge_batch_flat(const uint64_t* public_inputs, size_t n_inputs, const uint64_t* words,
                                 size_t words_per_commitment, size_t count, uint64_t modulus, uint64_t* alphas,
                                 uint8_t* hashes32, unsigned threads) LSR_NOEXCEPT;
-/* The same on device-resident arrays (8-byte aligned), one lane per transcript, asynchronous on `stream`: d_words
- * [count][words_per_commitment] (e.g. from lsr_lwe_commit_batch_flat_device), d_public_inputs [count][n_inputs] (may be a
- * previous call's d_alphas with n_inputs = 1: the second challenge of prove_r1cs, lib.rs:768), d_alphas [count],
- * d_hashes32 (optional) [count][32].  The kernel is launched on the calling thread's current HIP device (where the arrays
- * must live).  The cost is flat up to 65 536 transcripts (a wavefront per SIMD).  0 / -1. */
+/* alpha_i = derive(public_inputs_i, row_i), then beta_i = derive([alpha_i], row_i) — the pair every R1CS prover and verifier needs
+ * (lib.rs:761-768) — with both transcripts of a row hashed by the same pool thread.  betas [count] is required; hashes_alpha32 and
+ * hashes_beta32 (optional) [count][32].  Equal to two lsr_fs_challenge_batch_flat calls.  0 / -1. */
+int lsr_fs_challenge_chain_batch_flat(const uint64_t* public_inputs, size_t n_inputs, const uint64_t* words,
+                                      size_t words_per_commitment, size_t count, uint64_t modulus, uint64_t* alphas,
+                                      uint64_t* betas, uint8_t* hashes_alpha32, uint8_t* hashes_beta32, unsigned threads) LSR_NOEXCEPT;
+/* The same on device-resident arrays (8-byte aligned), asynchronous on `stream`: d_words [count][words_per_commitment] (e.g. from
+ * lsr_lwe_commit_batch_flat_device), d_public_inputs [count][n_inputs] (may be a previous call's d_alphas with n_inputs = 1),
+ * d_alphas [count], d_hashes32 (optional) [count][32].  One kernel launch on the calling thread's current HIP device (where the
+ * arrays must live): no allocation, no host synchronisation, capturable into a HIP graph.  Two kernels compute the same words:
+ * LANE gives every transcript one lane (a launch costs one transcript's time, flat up to 65 536 of them); WAVE gives it half a
+ * wavefront (several times faster for the batches the provers see).  This call picks by lsr_fs_transcript_path.  0 / -1. */
 int lsr_fs_challenge_batch_device(const uint64_t* d_public_inputs, size_t n_inputs, const uint64_t* d_words,
                                   size_t words_per_commitment, size_t count, uint64_t modulus, uint64_t* d_alphas,
                                   uint8_t* d_hashes32, void* stream) LSR_NOEXCEPT;
+enum { LSR_FS_PATH_AUTO = 0, LSR_FS_PATH_LANE = 1, LSR_FS_PATH_WAVE = 2 };
+/* lsr_fs_challenge_batch_device with the kernel chosen by the caller (an unknown `path` is -1). */
+int lsr_fs_challenge_batch_device_on(int path, const uint64_t* d_public_inputs, size_t n_inputs, const uint64_t* d_words,
+                                     size_t words_per_commitment, size_t count, uint64_t modulus, uint64_t* d_alphas,
+                                     uint8_t* d_hashes32, void* stream) LSR_NOEXCEPT;
+/* The chained pair on the device: d_alphas and d_betas [count] are both written, the digests are optional.  WAVE is ONE launch
+ * (the half-wavefront that found alpha goes on to hash [alpha] || row); LANE is the two launches a caller would chain. */
+int lsr_fs_challenge_chain_batch_device(int path, const uint64_t* d_public_inputs, size_t n_inputs, const uint64_t* d_words,
+                                        size_t words_per_commitment, size_t count, uint64_t modulus, uint64_t* d_alphas,
+                                        uint64_t* d_betas, uint8_t* d_hashes_alpha32, uint8_t* d_hashes_beta32, void* stream) LSR_NOEXCEPT;
+/* What AUTO picks for `count` transcripts of `words_per_commitment` words: LSR_FS_PATH_LANE or LSR_FS_PATH_WAVE (host only). */
+int lsr_fs_transcript_path(size_t count, size_t words_per_commitment) LSR_NOEXCEPT;
 
 /* ---------------- host-only number theory (usable without a GPU) ---------------- */
 uint64_t lsr_minimal_primitive_root(uint64_t q, uint32_t n) LSR_NOEXCEPT;   /* 0 if none */

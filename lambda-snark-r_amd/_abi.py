@@ -125,6 +125,10 @@ SIGNATURES = {
     "lsr_fs_challenge": (c_int, [vp, c_size, ctypes.POINTER(LweCommitment), u64, vp, vp]),
     "lsr_fs_challenge_batch_flat": (c_int, [vp, c_size, vp, c_size, c_size, u64, vp, vp, ctypes.c_uint]),
     "lsr_fs_challenge_batch_device": (c_int, [vp, c_size, vp, c_size, c_size, u64, vp, vp, vp]),
+    "lsr_fs_challenge_batch_device_on": (c_int, [c_int, vp, c_size, vp, c_size, c_size, u64, vp, vp, vp]),
+    "lsr_fs_challenge_chain_batch_device": (c_int, [c_int, vp, c_size, vp, c_size, c_size, u64, vp, vp, vp, vp, vp]),
+    "lsr_fs_challenge_chain_batch_flat": (c_int, [vp, c_size, vp, c_size, c_size, u64, vp, vp, vp, vp, ctypes.c_uint]),
+    "lsr_fs_transcript_path": (c_int, [c_size, c_size]),
     "lsr_lwe_commit_batch_flat_device": (c_int, [vp, vp, c_size, c_size, vp, vp]),
     "lsr_lwe_commit_keys": (c_int, [vp, vp, c_size, c_size, vp, vp]),
     "lsr_lwe_commit_keys_device": (c_int, [vp, vp, c_size, c_size, vp, vp, vp]),

@@ -1,5 +1,7 @@
-// Keccak-f[1600] (FIPS 202 §3) shared by the host transcript code (lsr_transcript.cpp) and the device kernel that hashes a
-// batch of transcripts, one lane per transcript (lsr_transcript_gpu.hip).
+// Keccak-f[1600] (FIPS 202 §3) with the whole state in one thread: shared by the host transcript code (lsr_transcript.cpp) and the
+// device kernel that gives every transcript of a large batch one lane (fs_challenge_rows_kernel, lsr_transcript_gpu.hip).  The
+// kernel for the batch sizes the provers see spreads one state over a half-wavefront instead: lsr_keccak_wave.hpp, which takes
+// its round constants from here.
 #pragma once
 
 #include <cstdint>

@@ -158,10 +158,9 @@ inline void r1cs_transcript(GatherPublicsKernel gather, const R1csSlots& v, cons
         hipLaunchKernelGGL(gather, dim3(grid), dim3(256), 0, s, d_z, n_vars, (uint32_t)n_public, v.publics, count * n_public);
     }
     LSR_HIP(hipGetLastError());
-    check_call(lsr_fs_challenge_batch_device(n_public ? v.publics : nullptr, n_public, d_rows, words, count, q, v.alphas,
-                                             reinterpret_cast<uint8_t*>(v.hash_a), s), "lsr_fs_challenge_batch_device");
-    check_call(lsr_fs_challenge_batch_device(v.alphas, 1, d_rows, words, count, q, v.betas, reinterpret_cast<uint8_t*>(v.hash_b), s),
-               "lsr_fs_challenge_batch_device");
+    check_call(lsr_fs_challenge_chain_batch_device(LSR_FS_PATH_AUTO, n_public ? v.publics : nullptr, n_public, d_rows, words, count, q, v.alphas, v.betas,
+                                                   reinterpret_cast<uint8_t*>(v.hash_a), reinterpret_cast<uint8_t*>(v.hash_b), s),
+               "lsr_fs_challenge_chain_batch_device");
 }
 
 // One batched call: host arrays (r1cs_prove_host) or device arrays (r1cs_prove_device); `seeds` is a host array either way.
@@ -239,13 +238,13 @@ void r1cs_prove_device(const R1csProverRef& r, const R1csProveCall& c, size_t ch
 
 // ---- verify_r1cs / verify_r1cs_zk, both R1CS paths: the two transcripts, then the path's per-proof check -----------------------------
 
-// on the host (transcripts on the host pool, lsr_fs_challenge_batch_flat): results[i] = check(proof i, alpha_i, beta_i)
+// on the host (transcripts on the host pool, lsr_fs_challenge_chain_batch_flat): results[i] = check(proof i, alpha_i, beta_i)
 template <class Check>
 void r1cs_verify_host(uint64_t q, const uint64_t* pub, size_t n_public, const uint64_t* rows, size_t words, const uint64_t* proofs, size_t batch,
                       int* results, Check&& check) {
     std::vector<uint64_t> alphas(batch), betas(batch);
-    check_call(lsr_fs_challenge_batch_flat(pub, n_public, rows, words, batch, q, alphas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
-    check_call(lsr_fs_challenge_batch_flat(alphas.data(), 1, rows, words, batch, q, betas.data(), nullptr, 0), "lsr_fs_challenge_batch_flat");
+    check_call(lsr_fs_challenge_chain_batch_flat(pub, n_public, rows, words, batch, q, alphas.data(), betas.data(), nullptr, nullptr, 0),
+               "lsr_fs_challenge_chain_batch_flat");
     for (size_t i = 0; i < batch; ++i) results[i] = check(proofs + i * 13, alphas[i], betas[i]);
 }
 
@@ -257,8 +256,8 @@ void r1cs_verify_device(uint64_t q, const uint64_t* d_pub, size_t n_public, cons
     uint64_t* d_ab = nullptr;
     LSR_HIP(hipMallocAsync(reinterpret_cast<void**>(&d_ab), 2 * batch * 8, s));
     try {
-        check_call(lsr_fs_challenge_batch_device(d_pub, n_public, d_rows, words, batch, q, d_ab, nullptr, s), "lsr_fs_challenge_batch_device");
-        check_call(lsr_fs_challenge_batch_device(d_ab, 1, d_rows, words, batch, q, d_ab + batch, nullptr, s), "lsr_fs_challenge_batch_device");
+        check_call(lsr_fs_challenge_chain_batch_device(LSR_FS_PATH_AUTO, d_pub, n_public, d_rows, words, batch, q, d_ab, d_ab + batch, nullptr, nullptr, s),
+                   "lsr_fs_challenge_chain_batch_device");
         launch_check(d_ab, d_ab + batch);
         LSR_HIP(hipGetLastError());
     } catch (...) {

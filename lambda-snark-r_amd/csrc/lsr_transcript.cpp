@@ -71,33 +71,60 @@ void derive(const uint64_t* public_inputs, size_t n_inputs, const uint64_t* word
     if (hash32) std::memcpy(hash32, digest, 32);
 }
 
+// rows [lo, hi) shared by a pool of host threads (SHA3 is sequential within a transcript, independent across them)
+template <class Row>
+void for_rows(size_t count, unsigned threads, Row&& row) {
+    unsigned workers = threads ? threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    workers = static_cast<unsigned>(std::min<size_t>(workers, count));
+    auto span = [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) row(i);
+    };
+    if (workers <= 1) {
+        span(0, count);
+        return;
+    }
+    std::vector<std::thread> pool;
+    const size_t per = (count + workers - 1) / workers;
+    for (unsigned w = 0; w < workers; ++w) {
+        const size_t lo = w * per, hi = std::min(count, lo + per);
+        if (lo < hi) pool.emplace_back(span, lo, hi);
+    }
+    for (std::thread& t : pool) t.join();
+}
+
 }  // namespace
 
 // `count` transcripts at once — the commitments as rows of one array (lsr_lwe_commit_batch_flat), the public inputs as
-// [count][n_inputs] — hashed by a pool of host threads (SHA3 is sequential within a transcript, independent across them).
+// [count][n_inputs] — hashed by a pool of host threads.
 extern "C" int lsr_fs_challenge_batch_flat(const uint64_t* public_inputs, size_t n_inputs, const uint64_t* words, size_t words_per_commitment,
                                            size_t count, uint64_t modulus, uint64_t* alphas, uint8_t* hashes32, unsigned threads) noexcept {
     if ((!public_inputs && n_inputs) || !words || words_per_commitment == 0 || modulus == 0 || !alphas) return -1;
     if (count == 0) return 0;
     try {
-        unsigned workers = threads ? threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-        workers = static_cast<unsigned>(std::min<size_t>(workers, count));
-        auto span = [&](size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; ++i)
-                derive(n_inputs ? public_inputs + i * n_inputs : nullptr, n_inputs, words + i * words_per_commitment, words_per_commitment, modulus,
-                       &alphas[i], hashes32 ? hashes32 + 32 * i : nullptr);
-        };
-        if (workers <= 1) {
-            span(0, count);
-            return 0;
-        }
-        std::vector<std::thread> pool;
-        const size_t per = (count + workers - 1) / workers;
-        for (unsigned w = 0; w < workers; ++w) {
-            const size_t lo = w * per, hi = std::min(count, lo + per);
-            if (lo < hi) pool.emplace_back(span, lo, hi);
-        }
-        for (std::thread& t : pool) t.join();
+        for_rows(count, threads, [&](size_t i) {
+            derive(n_inputs ? public_inputs + i * n_inputs : nullptr, n_inputs, words + i * words_per_commitment, words_per_commitment, modulus, &alphas[i],
+                   hashes32 ? hashes32 + 32 * i : nullptr);
+        });
+        return 0;
+    } catch (...) {
+        return -1;
+    }
+}
+
+// alpha = derive(public inputs, row), beta = derive([alpha], row) (lib.rs:761-768): both transcripts of a row on the same pool thread,
+// the row still warm in its cache for the second one.
+extern "C" int lsr_fs_challenge_chain_batch_flat(const uint64_t* public_inputs, size_t n_inputs, const uint64_t* words, size_t words_per_commitment,
+                                                 size_t count, uint64_t modulus, uint64_t* alphas, uint64_t* betas, uint8_t* hashes_alpha32,
+                                                 uint8_t* hashes_beta32, unsigned threads) noexcept {
+    if ((!public_inputs && n_inputs) || !words || words_per_commitment == 0 || modulus == 0 || !alphas || !betas) return -1;
+    if (count == 0) return 0;
+    try {
+        for_rows(count, threads, [&](size_t i) {
+            const uint64_t* row = words + i * words_per_commitment;
+            derive(n_inputs ? public_inputs + i * n_inputs : nullptr, n_inputs, row, words_per_commitment, modulus, &alphas[i],
+                   hashes_alpha32 ? hashes_alpha32 + 32 * i : nullptr);
+            derive(&alphas[i], 1, row, words_per_commitment, modulus, &betas[i], hashes_beta32 ? hashes_beta32 + 32 * i : nullptr);
+        });
         return 0;
     } catch (...) {
         return -1;
