@@ -166,6 +166,12 @@ struct ArithF64 {
     static constexpr bool needs_recentre(int stage_bits) {
         return R == 1 ? (stage_bits & 1) == 0 : (stage_bits & (3 << (R - 2))) == 0;
     }
+    // The first pass of a two-pass inverse may hand its last round's outputs over un-centred (exact integers of magnitude at most
+    // 32 q < 2^50, the all-sum class above) and leave the re-centring to the load side of the strided round.
+    static constexpr bool kDeferredRecentre = true;
+    // The LT = 12 tile pass of a two-pass transform reads the multipliers of its round on tile bits [8, 12) through scalar loads
+    // (lsr_ntt_kernels.hpp load_round_twiddles_uniform): 30 SGPRs.
+    static constexpr bool kScalarTopTwiddles = true;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -223,6 +229,8 @@ struct ArithU64 {
     }
     static __device__ __forceinline__ void end_of_inverse_round(elem&, const ModParams&) {}
     static constexpr bool kPartialRecentre = false;
+    static constexpr bool kDeferredRecentre = false;
+    static constexpr bool kScalarTopTwiddles = false;
     template <int R> static constexpr bool needs_recentre(int) { return true; }
 };
 
@@ -343,6 +351,8 @@ struct ArithGold {
     }
     static __device__ __forceinline__ void end_of_inverse_round(elem&, const ModParams&) {}
     static constexpr bool kPartialRecentre = false;
+    static constexpr bool kDeferredRecentre = false;
+    static constexpr bool kScalarTopTwiddles = false;
     template <int R> static constexpr bool needs_recentre(int) { return true; }
 };
 

@@ -226,9 +226,10 @@ static void tile_fwd(const NttContext& c, uint64_t* d, size_t total, hipStream_t
     const unsigned grid = static_cast<unsigned>((total + kTile - 1) / kTile);
     hipLaunchKernelGGL((ntt_tile_forward<A, LT, RAW_IN, RAW_OUT>), dim3(grid), dim3(kThreads), 0, s, d, total, c.mod, Flavour<A>::fwd(c), src);
 }
-template <class A, int LT, bool RAW_IN, bool RAW_OUT>
+template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool DEFER = false>
 static void tile_inv(const NttContext& c, uint64_t* d, size_t total, hipStream_t s, const uint64_t* add = nullptr, const uint64_t* pre = nullptr) {
     const unsigned grid = static_cast<unsigned>((total + kTile - 1) / kTile);
+    static_assert(!DEFER || !std::is_same_v<A, ArithGold>, "the pre-multiplied instantiation has no deferred form");
     if constexpr (std::is_same_v<A, ArithGold> && !RAW_IN) {   // the fused diagonal multiply exists for the prover's field only
         if (pre != nullptr) {
             hipLaunchKernelGGL((ntt_tile_inverse<A, LT, RAW_IN, RAW_OUT, true>), dim3(grid), dim3(kThreads), 0, s, d, total, c.mod, Flavour<A>::inv(c),
@@ -237,12 +238,18 @@ static void tile_inv(const NttContext& c, uint64_t* d, size_t total, hipStream_t
         }
     }
     if (pre != nullptr) throw std::runtime_error("pre-multiplied inverse transform: only for NTT_MODULUS contexts");
-    hipLaunchKernelGGL((ntt_tile_inverse<A, LT, RAW_IN, RAW_OUT>), dim3(grid), dim3(kThreads), 0, s, d, total, c.mod, Flavour<A>::inv(c),
+    hipLaunchKernelGGL((ntt_tile_inverse<A, LT, RAW_IN, RAW_OUT, false, DEFER>), dim3(grid), dim3(kThreads), 0, s, d, total, c.mod, Flavour<A>::inv(c),
                        Flavour<A>::consts(c), add);
 }
 
-template <class A, bool INVERSE, bool RAW_IN, bool RAW_OUT>
+// DEFERRED: the raw operands come from a tile pass that left its last round un-centred (run_ntt's two-pass inverse of a flavour with
+// A::kDeferredRecentre): the round re-centres on load — the one class of words that can exceed 2 q for four stages, every word for five
+// (lsr_ntt_kernels.hpp RECENTRE_IN, bounds in DESIGN.md §4; re-centring every word in the four-stage round measured the same,
+// profiles/r12_inverse_tile_ablation.txt).  The pipelines that bring raw intermediates of their own (commitment, opening, ring
+// multiply: launch_top_round_inverse, launch_strided_round) keep the plain instantiations.
+template <class A, bool INVERSE, bool RAW_IN, bool RAW_OUT, bool DEFERRED = false>
 static void strided(const NttContext& c, uint64_t* d, size_t total, int lo, int r, hipStream_t s, const uint64_t* add = nullptr) {
+    constexpr int kOnLoad4 = DEFERRED ? 1 : 0, kOnLoad5 = DEFERRED ? 2 : 0;
     const size_t groups = total >> r;
     const unsigned grid = static_cast<unsigned>((groups + kThreads - 1) / kThreads);
     const auto* tw = INVERSE ? Flavour<A>::inv(c) : Flavour<A>::fwd(c);
@@ -250,21 +257,21 @@ static void strided(const NttContext& c, uint64_t* d, size_t total, int lo, int 
     if constexpr (INVERSE && !RAW_OUT) {
         if (add != nullptr) {
             switch (r) {
-                case 1: hipLaunchKernelGGL((ntt_strided_round<A, 1, true, RAW_IN, false, true>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
-                case 2: hipLaunchKernelGGL((ntt_strided_round<A, 2, true, RAW_IN, false, true>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
-                case 3: hipLaunchKernelGGL((ntt_strided_round<A, 3, true, RAW_IN, false, true>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
-                case 4: hipLaunchKernelGGL((ntt_strided_round<A, 4, true, RAW_IN, false, true>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
-                default: hipLaunchKernelGGL((ntt_strided_round<A, 5, true, RAW_IN, false, true>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
+                case 1: hipLaunchKernelGGL((ntt_strided_round<A, 1, true, RAW_IN, false, true, kOnLoad4>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
+                case 2: hipLaunchKernelGGL((ntt_strided_round<A, 2, true, RAW_IN, false, true, kOnLoad4>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
+                case 3: hipLaunchKernelGGL((ntt_strided_round<A, 3, true, RAW_IN, false, true, kOnLoad4>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
+                case 4: hipLaunchKernelGGL((ntt_strided_round<A, 4, true, RAW_IN, false, true, kOnLoad4>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
+                default: hipLaunchKernelGGL((ntt_strided_round<A, 5, true, RAW_IN, false, true, kOnLoad5>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
             }
             return;
         }
     }
     switch (r) {
-        case 1: hipLaunchKernelGGL((ntt_strided_round<A, 1, INVERSE, RAW_IN, RAW_OUT, false>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
-        case 2: hipLaunchKernelGGL((ntt_strided_round<A, 2, INVERSE, RAW_IN, RAW_OUT, false>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
-        case 3: hipLaunchKernelGGL((ntt_strided_round<A, 3, INVERSE, RAW_IN, RAW_OUT, false>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
-        case 4: hipLaunchKernelGGL((ntt_strided_round<A, 4, INVERSE, RAW_IN, RAW_OUT, false>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
-        default: hipLaunchKernelGGL((ntt_strided_round<A, 5, INVERSE, RAW_IN, RAW_OUT, false>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
+        case 1: hipLaunchKernelGGL((ntt_strided_round<A, 1, INVERSE, RAW_IN, RAW_OUT, false, kOnLoad4>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
+        case 2: hipLaunchKernelGGL((ntt_strided_round<A, 2, INVERSE, RAW_IN, RAW_OUT, false, kOnLoad4>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
+        case 3: hipLaunchKernelGGL((ntt_strided_round<A, 3, INVERSE, RAW_IN, RAW_OUT, false, kOnLoad4>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
+        case 4: hipLaunchKernelGGL((ntt_strided_round<A, 4, INVERSE, RAW_IN, RAW_OUT, false, kOnLoad4>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
+        default: hipLaunchKernelGGL((ntt_strided_round<A, 5, INVERSE, RAW_IN, RAW_OUT, false, kOnLoad5>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add); break;
     }
 }
 
@@ -280,11 +287,12 @@ static void pass_forward(const NttContext& c, int lt, uint64_t* d, size_t total,
 }
 template <class A>
 static void pass_inverse(const NttContext& c, int lt, uint64_t* d, size_t total, hipStream_t s, const uint64_t* pre) {
+    constexpr bool kDefer = A::kDeferredRecentre;     // the strided round of run_ntt re-centres on load
     switch (lt) {
-        case 9: tile_inv<A, 9, false, true>(c, d, total, s, nullptr, pre); break;
-        case 10: tile_inv<A, 10, false, true>(c, d, total, s, nullptr, pre); break;
-        case 11: tile_inv<A, 11, false, true>(c, d, total, s, nullptr, pre); break;
-        default: tile_inv<A, 12, false, true>(c, d, total, s, nullptr, pre); break;
+        case 9: tile_inv<A, 9, false, true, kDefer>(c, d, total, s, nullptr, pre); break;
+        case 10: tile_inv<A, 10, false, true, kDefer>(c, d, total, s, nullptr, pre); break;
+        case 11: tile_inv<A, 11, false, true, kDefer>(c, d, total, s, nullptr, pre); break;
+        default: tile_inv<A, 12, false, true, kDefer>(c, d, total, s, nullptr, pre); break;
     }
 }
 
@@ -389,7 +397,7 @@ static void run_ntt(const NttContext& c, uint64_t* d, size_t batch, bool inverse
             if constexpr (std::is_same_v<A, ArithGold>) {
                 if (three) inner_round<A, true>(c, base, count, lt, ls.r_inner, cs);
             }
-            strided<A, true, true, false>(c, base, count, c.logn - r_top, r_top, cs, add ? add + (first << c.logn) : nullptr);
+            strided<A, true, true, false, A::kDeferredRecentre>(c, base, count, c.logn - r_top, r_top, cs, add ? add + (first << c.logn) : nullptr);
         }
     }
 }

@@ -111,6 +111,26 @@ __device__ __forceinline__ void load_round_twiddles(typename A::twid (&w)[kRound
     }
 }
 
+// The same slots for the round on tile bits [8, 12) of a 4096-residue block of a larger polynomial (the first forward / last inverse
+// round of the LT = 12 pass of a two-pass transform): every stage bit lies above the lane's 8 index bits, so the 15 multipliers depend on
+// the block's position alone — workgroup-uniform addresses, plain reads that become scalar loads (SGPR operands, no vector-memory
+// instruction, no VGPRs), as in the strided rounds.  profiles/r12_inverse_tile_ablation.txt: the vector twiddle loads own the
+// inverse tile pass's whole surplus over the fabric rate.
+template <class A, int LO, int R, bool INVERSE>
+__device__ __forceinline__ void load_round_twiddles_uniform(typename A::twid (&w)[kRoundTwiddles], uint32_t block_pos, int logn,
+                                                            const typename A::twid* __restrict__ tw) {
+    static_assert(LO == 8 && R == 4, "the lane index fills bits [0, 8): lane_base<8, 4>(t) = t");
+    static_for<0, R>([&](auto sc) {
+        constexpr int step = decltype(sc)::value;
+        constexpr int b = INVERSE ? LO + step : LO + R - 1 - step;
+        constexpr int count = 1 << (LO + R - 1 - b);
+        constexpr int before = INVERSE ? ((1 << R) - (1 << (R - step))) : ((1 << step) - 1);
+        const uint32_t tw_base = (1u << (logn - 1 - b)) + (block_pos >> (b + 1));     // block_pos is a multiple of 4096
+#pragma unroll
+        for (int u = 0; u < count; ++u) w[before + u] = A::load_tw(tw, tw_base + u);
+    });
+}
+
 // ---- butterflies of one round, forward (Cooley–Tukey, high bit first) -----------------------------
 // TOP: the round holds the transform's first stages (group index 0 above it).  Flavours with A::kUnitTopTwiddles (cyclic tables:
 // entry m + 0 of every stage is omega^0 = 1, lsr_host_math.cpp build_cyclic_twiddles) then skip the product of the u = 0 butterflies —
@@ -230,7 +250,8 @@ __device__ __forceinline__ void tile_forward_body(uint64_t* __restrict__ data, s
         uint64_t raw[kRegs];
 #pragma unroll
         for (int k = 0; k < kRegs; ++k) raw[k] = buf_load64<RAW_OUT ? 0 : kAuxStream>(from, base * 8u, reg_offset<LO, R>(k) * 8u);
-        load_round_twiddles<A, LO, R, false, false>(w[0], base, block_pos, nmask, p.logn, table);
+        if constexpr (A::kScalarTopTwiddles && LT == kTileLog && RAW_IN) load_round_twiddles_uniform<A, LO, R, false>(w[0], block_pos, p.logn, tw);
+        else load_round_twiddles<A, LO, R, false, false>(w[0], base, block_pos, nmask, p.logn, table);
         if constexpr (MODE == 0) {
 #pragma unroll
             for (int k = 0; k < kRegs; ++k) v[k] = RAW_IN ? elem_from_bits<A>(raw[k]) : A::load(raw[k], p);
@@ -367,10 +388,13 @@ __global__ void __launch_bounds__(kThreads) ntt_tile_forward_fused(uint64_t* __r
 // discrete-Gaussian blinding add of the commitment (u = INTT(...) + e1).
 // PRE: every input word is first multiplied by pre[its index within the polynomial] (canonical residues) — a diagonal
 // operator fused into the read-in (the coset twist of the prover's quotient pipeline, lsr_prover.hip).
-template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool PRE = false>
+// DEFER (first pass of a two-pass inverse, flavours with A::kDeferredRecentre): the last round's outputs are stored as they leave the
+// butterflies, |x| <= 32 q; the strided round that follows re-centres them on load (strided_round_body RECENTRE_IN), where the VALU idles.
+template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool PRE = false, bool DEFER = false>
 __device__ __forceinline__ void tile_inverse_body(uint64_t* __restrict__ data, size_t total, const ModParams& p,
                                                   const typename A::twid* __restrict__ tw, const RoundConsts<A>& cs,
                                                   const uint64_t* __restrict__ add, const uint64_t* __restrict__ pre, uint32_t vblock) {
+    static_assert(!DEFER || (RAW_OUT && A::kDeferredRecentre), "deferred re-centring: the raw hand-off of a flavour that re-centres");
     __shared__ uint64_t lds[kLdsWords];
     using elem = typename A::elem;
     using twid = typename A::twid;
@@ -428,7 +452,8 @@ __device__ __forceinline__ void tile_inverse_body(uint64_t* __restrict__ data, s
             constexpr int J1 = J - 1;
             constexpr int LO1 = TileRound<LT, J1>::LO, R1 = TileRound<LT, J1>::R;
             constexpr bool kNextFinal = (I + 1 == NR - 1) && !RAW_OUT;
-            load_round_twiddles<A, LO1, R1, true, kNextFinal>(w[(I + 1) & 1], lane_base<LO1, R1>(t), block_pos, nmask, p.logn, table);
+            if constexpr (A::kScalarTopTwiddles && LT == kTileLog && RAW_OUT && J1 == 0) load_round_twiddles_uniform<A, LO1, R1, true>(w[(I + 1) & 1], block_pos, p.logn, tw);
+            else load_round_twiddles<A, LO1, R1, true, kNextFinal>(w[(I + 1) & 1], lane_base<LO1, R1>(t), block_pos, nmask, p.logn, table);
         }
         uint64_t blind[(kLast && !RAW_OUT) ? kRegs : 1];
         if constexpr (kLast && !RAW_OUT) {   // request the blinding residues before the last round's arithmetic
@@ -439,9 +464,10 @@ __device__ __forceinline__ void tile_inverse_body(uint64_t* __restrict__ data, s
             }
         }
         inverse_round<A, LO, R, kFinal>(v, w[I & 1], p, cs);
-        if constexpr (!kFinal) {
+        if constexpr (!kFinal && !(DEFER && kLast)) {
             // inner rounds re-centre only the outputs that can exceed the next round's 2 q input bound (lsr_arith.hpp needs_recentre);
             // the last round of a first pass (RAW_OUT) re-centres everything: the strided round that follows runs up to five stages
+            // (DEFER: that round does it on load)
             constexpr bool kAll = kLast || !A::kPartialRecentre;
 #pragma unroll
             for (int k = 0; k < kRegs; ++k)
@@ -464,11 +490,11 @@ __device__ __forceinline__ void tile_inverse_body(uint64_t* __restrict__ data, s
         }
     });
 }
-template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool PRE = false>
+template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool PRE = false, bool DEFER = false>
 __global__ void __launch_bounds__(kThreads) ntt_tile_inverse(uint64_t* __restrict__ data, size_t total, ModParams p,
                                                                const typename A::twid* __restrict__ tw, RoundConsts<A> cs,
                                                                const uint64_t* __restrict__ add, const uint64_t* __restrict__ pre = nullptr) {
-    tile_inverse_body<A, LT, RAW_IN, RAW_OUT, PRE>(data, total, p, tw, cs, add, pre, blockIdx.x);
+    tile_inverse_body<A, LT, RAW_IN, RAW_OUT, PRE, DEFER>(data, total, p, tw, cs, add, pre, blockIdx.x);
 }
 
 // ---- ring multiply c = a b in the tile (lsr_ring_mul.hip) --------------------------------------------
@@ -638,7 +664,10 @@ __global__ void __launch_bounds__(kThreads) ntt_tile_ring_mul(uint64_t* c, const
 //            leaves them in bs.side as int8, one byte per row packed per column ([polynomial][column][2^R / 16] words: 1/16 of a
 //            polynomial pass); the inverse round reads that and samples rows [2^R / 2, 2^R) — the cipher work split over two passes.
 //            Needs table entries <= 127 (magnitudes fit a byte).
-template <class A, int R, bool INVERSE, bool RAW_IN, bool RAW_OUT, bool ADD, int SM>
+// RECENTRE_IN (last pass of run_ntt's two-pass inverse, whose tile pass ran with DEFER): the raw operands are the un-centred outputs
+// of the tile pass's last round, index bits [lo - 4, lo).  1: re-centre the words of the class that can exceed 2 q (needs_recentre:
+// index bits lo - 2 and lo - 1 clear — the same for a lane's 2^R words, and for a whole wavefront since lo >= 9); 2: re-centre all.
+template <class A, int R, bool INVERSE, bool RAW_IN, bool RAW_OUT, bool ADD, int SM, int RECENTRE_IN = 0>
 __device__ __forceinline__ void strided_round_body(uint64_t* __restrict__ data, size_t total, int lo, ModParams p,
                                                    const typename A::twid* __restrict__ tw, RoundConsts<A> cs,
                                                    const uint64_t* __restrict__ add, const BlindSampler& bs, uint32_t vblock = blockIdx.x,
@@ -649,6 +678,8 @@ __device__ __forceinline__ void strided_round_body(uint64_t* __restrict__ data, 
     static_assert(SM == 0 || R >= 4, "2^R / 16 blocks per lane and half");
     static_assert((SM != 1 && SM != 2) || ADD, "sampling replaces the read of the blinding residues");
     static_assert(SM != 3 || (!INVERSE && !ADD), "the forward round only prepares samples");
+    static_assert(RECENTRE_IN == 0 || (INVERSE && RAW_IN && !RAW_OUT && SM == 0 && A::kDeferredRecentre), "deferred re-centring: run_ntt's last inverse pass");
+    static_assert(RECENTRE_IN != 1 || R <= 4, "five stages need every operand re-centred (32 sums of 1.75 q pass 2^50 for q near 2^45)");
     using elem = typename A::elem;
     constexpr int N = 1 << R;
     const size_t group = (size_t)vblock * kThreads + vthread;
@@ -671,6 +702,12 @@ __device__ __forceinline__ void strided_round_body(uint64_t* __restrict__ data, 
         for (int k = 0; k < N; ++k) {
             const uint64_t raw = from[idx0 + ((size_t)k << lo)];
             v[k] = RAW_IN ? elem_from_bits<A>(raw) : A::load(raw, p);
+        }
+    }
+    if constexpr (RECENTRE_IN != 0) {
+        if (RECENTRE_IN == 2 || ((low >> (lo - 2)) & 3u) == 0) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) A::end_of_inverse_round(v[k], p);
         }
     }
     if constexpr (SM != 0) {
@@ -800,11 +837,11 @@ __device__ __forceinline__ void strided_round_body(uint64_t* __restrict__ data, 
     }
 }
 
-template <class A, int R, bool INVERSE, bool RAW_IN, bool RAW_OUT, bool ADD>
+template <class A, int R, bool INVERSE, bool RAW_IN, bool RAW_OUT, bool ADD, int RECENTRE_IN = 0>
 __global__ void __launch_bounds__(kThreads) ntt_strided_round(uint64_t* __restrict__ data, size_t total, int lo, ModParams p,
                                                                 const typename A::twid* __restrict__ tw, RoundConsts<A> cs,
                                                                 const uint64_t* __restrict__ add) {
-    strided_round_body<A, R, INVERSE, RAW_IN, RAW_OUT, ADD, 0>(data, total, lo, p, tw, cs, add, BlindSampler{});
+    strided_round_body<A, R, INVERSE, RAW_IN, RAW_OUT, ADD, 0, RECENTRE_IN>(data, total, lo, p, tw, cs, add, BlindSampler{});
 }
 
 // last pass of an inverse transform with the blinding residues sampled in place (dynamic LDS: table + sample tile); HALF: the first
