@@ -95,6 +95,30 @@ LweContext* lsr_lwe_context_create_seeded(const PublicParams* params, uint64_t k
  * refuses combinations whose centred coefficients sum beyond ~800 (noise budget); under the 60-bit prime the bound is ~2^25 and
  * the u64 Harvey/Shoup kernels run (about 1.5x the time per transform).  0 for an unsupported ring_degree. */
 uint64_t lsr_lwe_wide_modulus(uint32_t ring_degree) LSR_NOEXCEPT;
+/* Two-prime RNS context: the reference's lwe_linear_combine range (any coefficient below t, over any realistic number of terms) on
+ * the FP64 kernels.  The context commits under Q = q1 q2 (about 2^88) and keeps every commitment as its residues mod q1 and q2:
+ *   q1 = what a default context picks for ring_degree (17592169062401 up to 4096, else the largest 44-bit prime = 1 mod 2n),
+ *   q2 = the largest 44-bit prime = 1 (mod 2 ring_degree) other than q1;  t = lsr_plain_modulus(ring_degree), unchanged.
+ * params->modulus is IGNORED (as a default context ignores a modulus no transform can use).  Keys, context id and the per-commitment
+ * stream keys are derived exactly as by lsr_lwe_context_create_seeded (key_seed == 0: one draw of OS entropy); r, e1, e2 of a
+ * commitment are sampled once and are the same integers under both primes:
+ *   u_i = INTT_qi(A_i^T NTT_qi(r)) + e1,   v_i = INTT_qi(<b_i, NTT_qi(r)>) + e2 + (round(Q (m mod t) / t) mod q_i).
+ * Wire row (lsr_lwe_commitment_words = 6 + 2 (k + 1) n words): data[0] = payload bytes, then "LSRR0001", n | k<<32, q1, q2, t,
+ * u_1[k][n], v_1[n], u_2[k][n], v_2[n].  A single-prime context answers -1 to such a row and an RNS context -1 to a single-prime row.
+ * Opening: x_i = v_i - <s, u_i> mod q_i, x = CRT(x_1, x_2) in [0, Q), slot = floor((t x + Q/2) / Q) mod t, compared with the claimed
+ * words as given.  lwe_linear_combine enforces sum |c_i| (noise_unit + 1) < Q / 2t (c_i centred mod t), a bound of about 2^67.
+ * Served: lwe_commit, lwe_commit_batch, lsr_lwe_commit_batch_flat(_device), lsr_lwe_commit_keys(_device), lsr_lwe_commit_rows_device,
+ * lwe_verify_opening(_batch), lsr_lwe_verify_opening_batch_flat, lsr_lwe_verify_rows_device, lwe_linear_combine, the free calls and
+ * the size / rank getters; lsr_lwe_modulus returns q1; lsr_lwe_pipeline "rns-tile" (ring_degree 4096, rank <= 4, sigma <= ~6.9: one
+ * launch per batch, one workgroup per commitment or opening) or "rns-general".  Refused with -1 / NULL and a message in lsr_last_error:
+ * lsr_mlwe_matvec_batch_device, lsr_lwe_sample_blinding_device, lsr_lwe_public_matrix, lsr_lwe_ntt_context,
+ * lsr_lwe_context_replicate, every *_sharded call, and the provers / lsr_simple_verify_batch* when handed such a context.
+ * NULL (message in lsr_last_error) for any (ring_degree, module_rank, sigma) a default context refuses, and without a device. */
+LweContext* lsr_lwe_context_create_rns(const PublicParams* params, uint64_t key_seed, int device) LSR_NOEXCEPT;
+/* out = {q1, q2} of an RNS context, 0; -1 on any other context */
+int lsr_lwe_rns_moduli(const LweContext* ctx, uint64_t out[2]) LSR_NOEXCEPT;
+/* the same pair from the ring degree alone (host only, no device needed); -1 for an unsupported ring_degree */
+int lsr_rns_commit_moduli(uint32_t ring_degree, uint64_t out[2]) LSR_NOEXCEPT;
 uint64_t lsr_lwe_modulus(const LweContext* ctx) LSR_NOEXCEPT;         /* internal q actually used */
 uint64_t lsr_lwe_plain_modulus(const LweContext* ctx) LSR_NOEXCEPT;   /* t */
 uint32_t lsr_lwe_ring_degree(const LweContext* ctx) LSR_NOEXCEPT;
@@ -131,7 +155,7 @@ int lsr_lwe_commit_batch_flat_device(LweContext* ctx, const uint64_t* messages, 
  * flavour, rank <= 4, sigma <= ~6.9) run it as ONE launch with one workgroup per commitment: r, e1, e2 are sampled in the
  * lanes, transformed and multiplied in LDS, and only the finished row is written; ring_degree 2^16 / 2^17 sample inside the
  * strided transform rounds (three launches per chunk).  lsr_lwe_pipeline names the path a context takes: "tile", "fused",
- * "fused-matvec" (only the matrix-vector workload is fused), "general".
+ * "fused-matvec" (only the matrix-vector workload is fused), "general"; "rns-tile" / "rns-general" on an RNS context.
  * Calls on one context are ordered one behind the other (each waits for the previous call's last kernel), whatever streams the
  * caller passes; the synchronous entry points of the same context (lwe_commit, lwe_verify_opening, lwe_linear_combine, the batch
  * and sharded calls) and lwe_context_free wait for a pending asynchronous call before they touch the context's workspaces.

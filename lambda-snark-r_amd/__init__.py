@@ -172,6 +172,25 @@ class LweContext:
         if not self._h:
             raise CoreError("FfiError: lwe_context_create returned NULL")   # context.rs:46-48
 
+    @classmethod
+    def create_rns(cls, params, key_seed=None, device=-1):
+        """``lsr_lwe_context_create_rns``: a two-prime RNS context (``params.q`` is ignored) whose ``linear_combine`` takes any
+        coefficient below the plaintext modulus, as the reference does; commitments and openings go through the same wrappers."""
+        self = object.__new__(cls)
+        self._lib, self.params = _abi.lib(), params
+        ffi = params.to_ffi()
+        self._h = self._lib.lsr_lwe_context_create_rns(ctypes.byref(ffi), int(key_seed or 0), device)
+        if not self._h:
+            raise CoreError("FfiError: lsr_lwe_context_create_rns returned NULL: " + _abi.last_error())
+        return self
+
+    def rns_moduli(self):
+        """``lsr_lwe_rns_moduli``: (q1, q2) of an RNS context, None on any other context."""
+        out = (ctypes.c_uint64 * 2)()
+        if self._lib.lsr_lwe_rns_moduli(self._h, out) != 0:
+            return None
+        return int(out[0]), int(out[1])
+
     @property
     def handle(self):
         return self._h
@@ -427,6 +446,14 @@ class Commitment:
             self._p = None
 
     __del__ = free
+
+
+def rns_commit_moduli(ring_degree):
+    """``lsr_rns_commit_moduli``: the (q1, q2) an RNS context of this ring degree commits under (host only)."""
+    out = (ctypes.c_uint64 * 2)()
+    if _abi.lib().lsr_rns_commit_moduli(int(ring_degree), out) != 0:
+        raise ValueError("unsupported ring degree")
+    return int(out[0]), int(out[1])
 
 
 def wide_modulus(ring_degree):

@@ -136,6 +136,9 @@ SIGNATURES = {
     "lsr_lwe_verify_rows_device": (c_int, [vp, vp, vp, c_size, c_size, vp, vp]),
     "lsr_lwe_pipeline": (ctypes.c_char_p, [vp]),
     "lsr_lwe_wide_modulus": (ctypes.c_uint64, [ctypes.c_uint32]),
+    "lsr_lwe_context_create_rns": (vp, [ctypes.POINTER(PublicParams), u64, c_int]),
+    "lsr_lwe_rns_moduli": (c_int, [vp, vp]),
+    "lsr_rns_commit_moduli": (c_int, [u32, vp]),
     "lsr_minimal_primitive_root": (u64, [u64, u32]),
     # r1cs.h (SEAL/NTL-free shim, host only)
     "lambda_snark_r1cs_create": (c_int, [ctypes.POINTER(SparseMatrix), ctypes.POINTER(SparseMatrix), ctypes.POINTER(SparseMatrix), u64, ctypes.POINTER(vp)]),

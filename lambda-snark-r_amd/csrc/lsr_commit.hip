@@ -29,6 +29,7 @@
 #include "lsr_commit_fused.hpp"
 #include "lsr_commit_kernels.hpp"
 #include "lsr_commit_tile.hpp"
+#include "lsr_commit_rns.hpp"
 #include "lsr_commit_keys.hpp"
 #include "lsr_keys.hpp"
 #include "lsr_runtime.hpp"
@@ -99,6 +100,13 @@ struct LweContext {
     mutable lsr::PinnedBuffer<uint64_t> host_seeds{hipHostMallocPortable};
     mutable lsr::DeviceBuffer<uint64_t> ws_seeds;
     mutable lsr::Event ev_seeds;
+    // two-prime RNS context (lsr_commit_rns.hpp): this context holds prime q1 = q, `sib` the same keys under q2.  The
+    // sibling is never handed out: it is reached only through its owner, under the owner's mutex, and its workspaces serve the
+    // second prime's pass of the general kernels
+    bool rns = false;
+    bool rns_member = false;           // either half of an RNS pair: no n >= 2^16 fused pipelines (their RNS form does not exist)
+    LweContext* sib = nullptr;
+    lsr::RnsConsts rc{};
 };
 
 namespace lsr {
@@ -169,7 +177,7 @@ static void ensure_workspace(const LweContext& c, size_t batch) {
 
 // the fused pipeline exists for the FP64 flavour, two-pass degrees whose low pass is a full 4096-residue tile, ranks <= 4
 static bool fused_eligible(const LweContext& c) {
-    return c.tuning.fused && c.ntt->use_f64 && (c.logn == 16 || c.logn == 17) && c.k >= 1 && c.k <= 4;
+    return c.tuning.fused && !c.rns_member && c.ntt->use_f64 && (c.logn == 16 || c.logn == 17) && c.k >= 1 && c.k <= 4;
 }
 
 static bool env_flag(const char* name, bool fallback) {
@@ -183,7 +191,15 @@ static bool tile_eligible(const LweContext& c) {
     return c.tuning.fused && c.ntt->use_f64 && c.logn == 12 && c.k >= 1 && c.k <= 4 && c.cdf_entries <= 64;
 }
 
-static LweContext* create_lwe_context(const PublicParams* params, uint64_t key_seed, int device, const ContextKeys* replicate = nullptr) {
+// words of a wire row / of its body (everything behind the header) for this context's format
+static size_t header_words(const LweContext& c) { return c.rns ? kRnsHeaderWords : kHeaderWords; }
+static size_t body_words(const LweContext& c) { return (c.rns ? 2 : 1) * ((size_t)c.k + 1) * c.n; }
+static size_t row_words(const LweContext& c) { return header_words(c) + body_words(c); }
+// the modulus body word x lives under
+static uint64_t body_modulus(const LweContext& c, size_t x) { return c.rns && x >= ((size_t)c.k + 1) * c.n ? c.rc.q[1] : c.q; }
+
+static LweContext* create_lwe_context(const PublicParams* params, uint64_t key_seed, int device, const ContextKeys* replicate = nullptr,
+                                      bool rns_member = false) {
     if (!params) return nullptr;                                   // commitment.cpp:103
     uint32_t k = params->module_rank ? params->module_rank : 1;
     const uint32_t n = params->ring_degree;
@@ -203,6 +219,7 @@ static LweContext* create_lwe_context(const PublicParams* params, uint64_t key_s
     c->tuning.fused = env_flag("LAMBDA_SNARK_COMMIT_FUSED", true);
     c->tuning.mixed = env_flag("LAMBDA_SNARK_COMMIT_MIXED", true);
     c->params = *params;
+    c->rns_member = rns_member;
     c->q = q; c->t = t; c->delta = q / t; c->n = n; c->k = k; c->sigma = params->sigma;
     // Noise budget: opening decodes round(t/q (round(q m / t) + <e,r> - <s,e1> + e2)); the noise term is a sum of 2 k n products of
     // two sigma-Gaussians, standard deviation sigma^2 sqrt(2 k n); with an 8-sigma tail it must stay below Delta / 2.
@@ -264,8 +281,74 @@ static LweContext* create_lwe_context(const PublicParams* params, uint64_t key_s
     return c.release();
 }
 
+static void destroy_lwe_context(LweContext* c);
+// (q1, q2) of an RNS context for ring degree n: q1 = what a default context picks, q2 = the largest 44-bit prime = 1 (mod 2n) other than q1
+static bool rns_moduli_for(uint32_t n, uint64_t out[2]) {
+    const uint64_t q1 = select_commit_modulus(0, n);
+    if (!q1) return false;
+    uint64_t q2 = largest_prime_congruent_one(2ull * n, 44);
+    if (q2 == q1) {
+        for (q2 = q1 - 2ull * n; q2 > (1ull << 43) && !is_prime_u64(q2); q2 -= 2ull * n) {}
+        if (q2 <= (1ull << 43)) return false;
+    }
+    out[0] = q1;
+    out[1] = q2;
+    return q2 != 0;
+}
+// Two sibling single-prime contexts with the same keys.  params->modulus is ignored.
+static LweContext* create_rns_context(const PublicParams* params, uint64_t key_seed, int device) {
+    if (!params) {
+        set_last_error("lsr_lwe_context_create_rns: NULL params");
+        return nullptr;
+    }
+    PublicParams mine = *params;
+    mine.modulus = 0;                                                   // q1: the default selection
+    uint64_t q[2] = {0, 0};
+    if (!rns_moduli_for(params->ring_degree, q)) {
+        set_last_error("lsr_lwe_context_create_rns: ring_degree must be a power of two in [2, 131072]");
+        return nullptr;
+    }
+    const ContextKeys keys = derive_context_keys(key_seed);             // key_seed == 0: ONE draw of OS entropy for both siblings
+    LweContext* c = create_lwe_context(&mine, key_seed, device, &keys, true);   // NULL: the message of the default context's refusal stands
+    if (!c) return nullptr;
+    mine.modulus = q[1];
+    c->sib = create_lwe_context(&mine, key_seed, c->device, &keys, true);
+    if (!c->sib) {
+        const std::string why = last_error_cstr();
+        destroy_lwe_context(c);
+        set_last_error("lsr_lwe_context_create_rns: second prime: " + why);
+        return nullptr;
+    }
+    if (c->q != q[0] || c->sib->q != q[1]) {
+        destroy_lwe_context(c);
+        set_last_error("lsr_lwe_context_create_rns: the modulus selection did not honour the RNS pair (internal)");
+        return nullptr;
+    }
+    c->rns = true;
+    c->params = *params;
+    RnsConsts& rc = c->rc;
+    rc.q[0] = q[0]; rc.q[1] = q[1]; rc.t = c->t;
+    const u128 big = (u128)q[0] * q[1];
+    rc.qt = (uint64_t)(big % c->t);
+    rc.tinv[0] = invmod_prime(c->t % q[0], q[0]);
+    rc.tinv[1] = invmod_prime(c->t % q[1], q[1]);
+    rc.q1inv = invmod_prime(q[0] % q[1], q[1]);
+    rc.big_lo = (uint64_t)big; rc.big_hi = (uint64_t)(big >> 64);
+    rc.inv_q1 = 1.0 / (double)q[0]; rc.inv_q2 = 1.0 / (double)q[1];
+    return c;
+}
+
 static void destroy_lwe_context(LweContext* c) {
     if (!c) return;
+    if (c->sib) {
+        try {
+            DeviceGuard guard(c->device);
+            c->ev_last.sync();      // the sibling's workspaces serve the owner's asynchronous calls
+        } catch (...) {
+        }
+        destroy_lwe_context(c->sib);
+        c->sib = nullptr;
+    }
     try {
         DeviceGuard guard(c->device);
         try {
@@ -704,11 +787,67 @@ static void commit_rows_fused(const LweContext& c, const uint64_t* d_msgs, size_
     join_lanes(c, s, streams);
 }
 
+// ---- two-prime RNS rows (lsr_commit_rns.hpp) ----
+static RnsTilePrime rns_tile_prime(const LweContext& c, const double* mat) {
+    return RnsTilePrime{mat, c.ntt->mod, c.ntt->fwd_f64.ptr, c.ntt->inv_f64.ptr, RoundConsts<ArithF64>{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64}};
+}
+static bool rns_tile(const LweContext& c) { return c.rns && c.logn == 12 && c.ab_perm.ptr && c.sib->ab_perm.ptr && c.s_perm.ptr && c.sib->s_perm.ptr; }
+
+template <int K>
+static void launch_commit_rns_tile(const LweContext& c, const CommitRnsTileJob& job, hipStream_t s) {
+    hipLaunchKernelGGL((commit_rns_tile_kernel<K>), dim3(job.batch), dim3(kF8Threads), 0, s, job, rns_tile_prime(c, c.ab_perm.ptr),
+                       rns_tile_prime(*c.sib, c.sib->ab_perm.ptr));
+    LSR_HIP(hipGetLastError());
+}
+// "rns-tile": one launch, one workgroup per commitment, both primes
+static void commit_rows_rns_tile(const LweContext& c, const uint64_t* d_msgs, size_t msg_len, size_t batch, const uint64_t* d_keys, uint64_t* d_rows,
+                                 hipStream_t s) {
+    const size_t words = row_words(c);
+    for (size_t first = 0; first < batch; first += 0x40000000u) {            // grid limit: 2^30 workgroups per launch
+        const size_t now = std::min<size_t>(batch - first, 0x40000000u);
+        const CommitRnsTileJob job{d_rows + first * words, d_keys + 4 * first, d_msgs + first * msg_len, (uint64_t)msg_len,
+                                   (uint64_t)std::min<size_t>(msg_len, c.n), c.cdf.ptr, c.cdf_entries, (uint32_t)now, c.rc};
+        switch (c.k) {
+            case 1: launch_commit_rns_tile<1>(c, job, s); break;
+            case 2: launch_commit_rns_tile<2>(c, job, s); break;
+            case 3: launch_commit_rns_tile<3>(c, job, s); break;
+            default: launch_commit_rns_tile<4>(c, job, s); break;
+        }
+    }
+}
+// "rns-general": the general kernels once per prime from the same stream keys (so r, e1, e2 are the same integers under both), the
+// RNS message term, each prime's block packed into the rows
+static void commit_rows_rns_general(const LweContext& c, const uint64_t* d_msgs, size_t msg_len, size_t batch, const uint64_t* d_keys, uint64_t* d_rows,
+                                    hipStream_t s) {
+    const uint32_t n = c.n, k = c.k;
+    const size_t copy = std::min<size_t>(msg_len, n);
+    const uint64_t kn = (uint64_t)k * n, vcount = (uint64_t)batch * n;
+    for (int prime = 0; prime < 2; ++prime) {
+        const LweContext& ci = prime ? *c.sib : c;
+        ensure_workspace(ci, batch);
+        launch_gaussian3(GaussianJob{ci.ws_r.ptr, d_keys, 0, k, kDomR, n, batch * k, ci.q}, GaussianJob{ci.ws_e1.ptr, d_keys, 0, k, kDomE1, n, batch * k, ci.q},
+                         GaussianJob{ci.ws_e2.ptr, d_keys, 0, 1, kDomE2, n, batch, ci.q}, ci.cdf.ptr, ci.cdf_entries, s);
+        mlwe_matvec_device(ci, ci.ws_r.ptr, ci.ws_e1.ptr, ci.ws_u.ptr, batch, s);    // leaves r_hat in ws_r
+        matvec(ci, ci.ws_v.ptr, ci.b_hat.ptr, ci.ws_r.ptr, nullptr, 1, k, 0, 1, batch, s);
+        launch_ntt(*ci.ntt, ci.ws_v.ptr, batch, true, s);
+        hipLaunchKernelGGL(rns_finish_v_kernel, dim3(grid_for(vcount)), dim3(256), 0, s, ci.ws_v.ptr, ci.ws_e2.ptr, d_msgs, (uint64_t)msg_len, (uint64_t)copy,
+                           (uint32_t)c.logn, vcount, c.rc, prime, ci.ntt->mod);
+        hipLaunchKernelGGL(rns_pack_kernel, dim3(grid_for(batch * (kRnsHeaderWords + kn + n))), dim3(256), 0, s, d_rows, ci.ws_u.ptr, ci.ws_v.ptr, kn, (uint64_t)n,
+                           (uint64_t)batch, prime, c.rc, n | ((uint64_t)k << 32));
+        LSR_HIP(hipGetLastError());
+    }
+}
+
 // wire rows d_rows[batch][5 + (k + 1) n] of `batch` commitments from device-resident keys and messages, enqueued on `s` (caller
 // holds c.mutex): the reference's lwe_commit (commitment.cpp:138-164) for a whole batch without a byte of host traffic
 static void commit_rows_device(const LweContext& c, const uint64_t* d_msgs, size_t msg_len, size_t batch, const uint64_t* d_keys, uint64_t* d_rows,
                                hipStream_t s) {
     if (!batch) return;
+    if (c.rns) {
+        if (rns_tile(c)) commit_rows_rns_tile(c, d_msgs, msg_len, batch, d_keys, d_rows, s);
+        else commit_rows_rns_general(c, d_msgs, msg_len, batch, d_keys, d_rows, s);
+        return;
+    }
     if (c.ab_perm.ptr && c.logn == 12) commit_rows_tile(c, d_msgs, msg_len, batch, d_keys, d_rows, s);
     else if (c.a_perm.ptr && (c.ab_perm.ptr || c.b_perm.ptr)) commit_rows_fused(c, d_msgs, msg_len, batch, d_keys, d_rows, s);
     else commit_rows_general(c, d_msgs, msg_len, batch, d_keys, d_rows, s);
@@ -732,7 +871,7 @@ static void ensure_copy_stream(const LweContext& c) {
 // stream, chunk i + 1 is staged and computed (caller holds c.mutex)
 static void commit_batch_flat_host(const LweContext& c, const uint64_t* messages, size_t msg_len, size_t batch, const uint64_t* seeds, uint64_t* out_words,
                                    size_t chunk) {
-    const size_t words = kHeaderWords + ((size_t)c.k + 1) * c.n;
+    const size_t words = row_words(c);
     hipStream_t s = work_stream(*c.ntt);
     ensure_copy_stream(c);
     const size_t slot = std::min(chunk, batch) * words;
@@ -766,7 +905,7 @@ static void commit_batch_flat_host(const LweContext& c, const uint64_t* messages
 // out_words: host array (the rows come back in one copy) or, with `to_device`, device memory the rows are assembled in
 static void commit_chunk_flat(const LweContext& c, const uint64_t* messages, size_t msg_len, size_t batch, const uint64_t* seeds, uint64_t* out_words,
                               bool to_device) {
-    const size_t words = kHeaderWords + ((size_t)c.k + 1) * c.n;
+    const size_t words = row_words(c);
     hipStream_t s = work_stream(*c.ntt);
     StagedInputs in;
     stage_commit_inputs(c, messages, msg_len, batch, seeds, s, &in);
@@ -781,7 +920,7 @@ static void commit_chunk_flat(const LweContext& c, const uint64_t* messages, siz
 }
 
 static void commit_chunk(const LweContext& c, const uint64_t* messages, size_t msg_len, size_t batch, const uint64_t* seeds, LweCommitment** out) {
-    const size_t words = kHeaderWords + ((size_t)c.k + 1) * c.n;
+    const size_t words = row_words(c);
     hipStream_t s = work_stream(*c.ntt);
     StagedInputs in;
     stage_commit_inputs(c, messages, msg_len, batch, seeds, s, &in);
@@ -831,9 +970,15 @@ static bool parse_commitment(const LweContext& c, const LweCommitment* cm, const
     if (!cm || !cm->data || cm->len < 1) return false;
     const uint64_t byte_len = cm->data[0];
     if (byte_len == 0 || byte_len > (cm->len - 1) * 8) return false;       // commitment.cpp:71-75
-    const size_t words = kHeaderWords + (size_t)(c.k + 1) * c.n;
+    const size_t words = row_words(c);
     if (byte_len != 8ull * (words - 1)) return false;
     const uint64_t* d = cm->data;
+    if (c.rns) {
+        for (uint32_t w = 1; w < kRnsHeaderWords; ++w)
+            if (d[w] != rns_header_word(w, words, (uint64_t)c.n | ((uint64_t)c.k << 32), c.rc)) return false;
+        *body = d + kRnsHeaderWords;
+        return true;
+    }
     if (d[1] != kWireMagic || d[2] != ((uint64_t)c.n | ((uint64_t)c.k << 32)) || d[3] != c.q || d[4] != c.t) return false;
     *body = d + kHeaderWords;
     return true;
@@ -843,6 +988,44 @@ template <int K>
 static void launch_verify_tile(const LweContext& c, const VerifyTileJob& job, hipStream_t s) {
     hipLaunchKernelGGL((verify_tile_kernel<K>), dim3(job.count), dim3(kF8Threads), 0, s, job, c.s_perm.ptr, c.ntt->mod, c.ntt->fwd_f64.ptr, c.ntt->inv_f64.ptr,
                        RoundConsts<ArithF64>{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64});
+    LSR_HIP(hipGetLastError());
+}
+
+template <int K>
+static void launch_verify_rns_tile(const LweContext& c, const VerifyRnsTileJob& job, hipStream_t s) {
+    hipLaunchKernelGGL((verify_rns_tile_kernel<K>), dim3(job.count), dim3(kF8Threads), 0, s, job, rns_tile_prime(c, c.s_perm.ptr),
+                       rns_tile_prime(*c.sib, c.sib->s_perm.ptr));
+    LSR_HIP(hipGetLastError());
+}
+// openings of RNS rows (the verdict state c.ws_vflags / c.ws_vbad is cleared by the caller): w_p = v_p - <s, u_p> under each prime,
+// the CRT lift and the rounded decode in the sink (tile) or in an elementwise kernel (general)
+static void verify_rows_rns(const LweContext& c, const uint64_t* d_rows, const uint64_t* d_msgs, size_t msg_len, size_t count, hipStream_t s) {
+    const uint32_t n = c.n, k = c.k;
+    if (rns_tile(c)) {
+        const VerifyRnsTileJob job{d_rows, d_msgs, (uint64_t)msg_len, c.ws_vflags.ptr, c.ws_vbad, (uint32_t)count, c.rc};
+        switch (k) {
+            case 1: launch_verify_rns_tile<1>(c, job, s); break;
+            case 2: launch_verify_rns_tile<2>(c, job, s); break;
+            case 3: launch_verify_rns_tile<3>(c, job, s); break;
+            default: launch_verify_rns_tile<4>(c, job, s); break;
+        }
+        return;
+    }
+    const uint64_t kn = (uint64_t)k * n;
+    for (int prime = 0; prime < 2; ++prime) {
+        const LweContext& ci = prime ? *c.sib : c;
+        ensure_workspace(ci, count);
+        hipLaunchKernelGGL(rns_unpack_kernel, dim3(grid_for(count * (kRnsHeaderWords + kn + n))), dim3(256), 0, s, d_rows, ci.ws_u.ptr, ci.ws_v.ptr, c.ws_vbad, kn,
+                           (uint64_t)n, (uint64_t)count, prime, c.rc, (uint64_t)n | ((uint64_t)k << 32));
+        launch_ntt(*ci.ntt, ci.ws_u.ptr, count * k, false, s);
+        launch_ntt(*ci.ntt, ci.ws_v.ptr, count, false, s);
+        matvec(ci, ci.ws_e2.ptr, ci.s_hat.ptr, ci.ws_u.ptr, nullptr, 1, k, 0, 1, count, s);            // <s_hat, u_hat>
+        hipLaunchKernelGGL(rsub_mod_kernel, dim3(grid_for(count * n)), dim3(256), 0, s, ci.ws_e2.ptr, ci.ws_v.ptr, (uint64_t)count * n, ci.q);
+        launch_ntt(*ci.ntt, ci.ws_e2.ptr, count, true, s);
+    }
+    const uint64_t lanes = (uint64_t)count * msg_len;
+    hipLaunchKernelGGL(rns_decode_compare_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, c.ws_e2.ptr, c.sib->ws_e2.ptr, d_msgs,
+                       (uint64_t)msg_len, (uint32_t)c.logn, (uint64_t)count, c.rc, c.sib->ntt->mod, c.ws_vflags.ptr);
     LSR_HIP(hipGetLastError());
 }
 
@@ -858,6 +1041,10 @@ static void verify_rows_device(const LweContext& c, const uint64_t* d_rows, cons
     c.ws_vflags.reserve(state_words);
     c.ws_vbad = reinterpret_cast<uint32_t*>(c.ws_vflags.ptr + count);
     zero_words_async(reinterpret_cast<uint64_t*>(c.ws_vflags.ptr), state_words, s);
+    if (c.rns) {
+        verify_rows_rns(c, d_rows, d_msgs, msg_len, count, s);
+        return;
+    }
     if (c.s_perm.ptr && c.logn == 12) {     // one launch, one workgroup per opening: the row is read once (lsr_commit_tile.hpp)
         const VerifyTileJob job{d_rows, d_msgs, (uint64_t)msg_len, c.ws_vflags.ptr, c.ws_vbad, (uint32_t)count, c.q, c.t};
         switch (k) {
@@ -922,13 +1109,13 @@ static void verify_rows_device(const LweContext& c, const uint64_t* d_rows, cons
 
 // openings per device pass of the host-pointer entry points: about 1 GiB of rows and scratch
 static size_t verify_chunk(const LweContext& c, size_t count) {
-    const size_t per_opening = (4 * (size_t)c.k + 5) * c.n * 8;
+    const size_t per_opening = (c.rns ? 2 : 1) * (4 * (size_t)c.k + 5) * c.n * 8;
     return std::max<size_t>(1, std::min<size_t>(count, (1ull << 30) / per_opening));
 }
 
 // rows (host, back to back) and messages -> results, `chunk` openings per pass; rows may live in pageable or pinned memory
 static void verify_host_rows(const LweContext& c, const uint64_t* rows, const uint64_t* messages, size_t msg_len, size_t count, int* results, hipStream_t s) {
-    const size_t row = kHeaderWords + ((size_t)c.k + 1) * c.n;
+    const size_t row = row_words(c);
     const size_t chunk = verify_chunk(c, count);
     c.ws_rows.reserve(chunk * row);
     ensure_input_space(c, chunk);                            // ws_dm: chunk x n message slots (msg_len <= n here), no allocation per call
@@ -946,15 +1133,11 @@ static void verify_host_rows(const LweContext& c, const uint64_t* rows, const ui
     }
 }
 
+static int screen_opening(const LweContext& c, const uint64_t* body, size_t msg_len);
 static int verify_opening(const LweContext& c, const LweCommitment* cm, const uint64_t* message, size_t msg_len) {
     const uint64_t* body = nullptr;
     if (!parse_commitment(c, cm, &body)) return -1;
-    const size_t body_words = ((size_t)c.k + 1) * c.n;
-    if (msg_len == 0 || msg_len > c.n) {                                   // decided without the device
-        for (size_t i = 0; i < body_words; ++i)
-            if (body[i] >= c.q) return -1;                                  // not a canonical payload
-        return msg_len == 0 ? 1 : 0;                                        // commitment.cpp:219-221
-    }
+    if (msg_len == 0 || msg_len > c.n) return screen_opening(c, body, msg_len);   // decided without the device (commitment.cpp:219-221)
     DeviceGuard guard(c.device);
     std::lock_guard<std::mutex> lock(c.mutex);
     wait_for_async(c);
@@ -967,9 +1150,9 @@ static int verify_opening(const LweContext& c, const LweCommitment* cm, const ui
 
 // screening shared by the batched forms when the message length alone decides (0 or > n): -1 / 0 / 1 on the host
 static int screen_opening(const LweContext& c, const uint64_t* body, size_t msg_len) {
-    const size_t body_words = ((size_t)c.k + 1) * c.n;
-    for (size_t x = 0; x < body_words; ++x)
-        if (body[x] >= c.q) return -1;
+    const size_t count = body_words(c);
+    for (size_t x = 0; x < count; ++x)
+        if (body[x] >= body_modulus(c, x)) return -1;                       // not a canonical payload
     return msg_len == 0 ? 1 : 0;
 }
 
@@ -977,7 +1160,7 @@ static int screen_opening(const LweContext& c, const uint64_t* body, size_t msg_
 // commitments' words (cm->data is the wire row) are gathered in pinned memory a chunk at a time and go up in one copy.
 static void verify_opening_batch(const LweContext& c, const LweCommitment* const* cms, const uint64_t* messages, size_t msg_len, size_t count,
                                  int* results) {
-    const size_t row = kHeaderWords + ((size_t)c.k + 1) * c.n;
+    const size_t row = row_words(c);
     std::vector<size_t> live;           // indices that reach the device
     for (size_t i = 0; i < count; ++i) {
         const uint64_t* body = nullptr;
@@ -1024,7 +1207,7 @@ static void verify_opening_batch(const LweContext& c, const LweCommitment* const
 // the same for commitments stored back to back (rows of lsr_lwe_commit_batch_flat): the rows go up as they are, the header
 // and canonicity checks run on the device
 static void verify_opening_batch_flat(const LweContext& c, const uint64_t* words, const uint64_t* messages, size_t msg_len, size_t count, int* results) {
-    const size_t row = kHeaderWords + ((size_t)c.k + 1) * c.n;
+    const size_t row = row_words(c);
     if (msg_len == 0 || msg_len > c.n) {   // decided by the screening alone: host path
         for (size_t i = 0; i < count; ++i) {
             const LweCommitment view{const_cast<uint64_t*>(words + i * row), row};
@@ -1039,7 +1222,82 @@ static void verify_opening_batch_flat(const LweContext& c, const uint64_t* words
     verify_host_rows(c, words, messages, msg_len, count, results, work_stream(*c.ntt));
 }
 
+// RNS rows: the same sum under each prime (combine_kernel per residue block).  The budget is Q / 2t ~ 2^67: any coefficient below t
+// over any realistic number of terms — the reference's range (commitment.cpp:88-96,247-266)
+static LweCommitment* linear_combine_rns(const LweContext& c, const LweCommitment** cms, const uint64_t* coeffs, size_t count) {
+    const size_t block = ((size_t)c.k + 1) * c.n;
+    DeviceGuard guard(c.device);
+    std::lock_guard<std::mutex> lock(c.mutex);
+    wait_for_async(c);
+    hipStream_t s = work_stream(*c.ntt);
+    // sum_i |c'_i| (noise_unit + 1) < Q / 2t with c'_i the centred representative of c_i mod t.  Evaluated in long double: the weight
+    // is below count * t / 2 and the bound about 2^67, both far inside its range; nothing is multiplied in 64-bit integers
+    const auto centred_weight = [&](uint64_t coeff) {
+        const uint64_t cf = coeff % c.t;
+        return cf > c.t / 2 ? c.t - cf : cf;
+    };
+    long double weight = 0;
+    for (size_t i = 0; i < count; ++i)
+        if (cms[i]) weight += (long double)centred_weight(coeffs[i]);
+    const long double bound = (long double)c.rc.q[0] * (long double)c.rc.q[1] / (2.0L * (long double)c.t);
+    if (weight * ((long double)c.noise_unit + 1.0L) >= bound) {
+        set_last_error("lwe_linear_combine: coefficients exceed the noise budget Q/2t of this RNS context (sum of |c_i|, c_i centred mod t, too large)");
+        return nullptr;
+    }
+    // bodies are gathered `group` at a time (<= 64 MiB) in pinned memory, one block per prime, and folded in by one kernel per prime
+    const size_t group = std::max<size_t>(1, std::min<size_t>(count, (size_t(64) << 20) / (2 * block * 8)));
+    DeviceBuffer<uint64_t> acc(2 * block), terms(2 * group * block), d_coeffs(2 * group);
+    c.host_stage.reserve(2 * group * (block + 1));
+    uint64_t* const h_terms = c.host_stage.ptr;                             // [prime][group][block]
+    uint64_t* const h_coeffs = c.host_stage.ptr + 2 * group * block;        // [prime][group]
+    LSR_HIP(hipMemsetAsync(acc.ptr, 0, 2 * block * 8, s));
+    bool any = false;
+    size_t staged = 0;
+    auto flush = [&] {
+        if (!staged) return;
+        for (int prime = 0; prime < 2; ++prime) {      // only the staged terms of each prime's block travel
+            LSR_HIP(hipMemcpyAsync(terms.ptr + prime * group * block, h_terms + prime * group * block, staged * block * 8, hipMemcpyHostToDevice, s));
+            LSR_HIP(hipMemcpyAsync(d_coeffs.ptr + prime * group, h_coeffs + prime * group, staged * 8, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(combine_kernel, dim3(grid_for(block)), dim3(256), 0, s, acc.ptr + prime * block, terms.ptr + prime * group * block,
+                               d_coeffs.ptr + prime * group, (uint32_t)staged, (uint64_t)block, (prime ? c.sib : &c)->ntt->mod);
+        }
+        LSR_HIP(hipGetLastError());
+        LSR_HIP(hipStreamSynchronize(s));   // the staging is reused
+        staged = 0;
+    };
+    for (size_t i = 0; i < count; ++i) {
+        if (!cms[i]) continue;                                             // commitment.cpp:248-250
+        const uint64_t* body = nullptr;
+        if (!parse_commitment(c, cms[i], &body)) {
+            (void)hipStreamSynchronize(s);
+            return nullptr;                                                // commitment.cpp:253-255
+        }
+        const uint64_t cf = coeffs[i] % c.t;
+        for (int prime = 0; prime < 2; ++prime) {
+            std::memcpy(h_terms + (prime * group + staged) * block, body + prime * block, block * 8);
+            h_coeffs[prime * group + staged] = cf > c.t / 2 ? c.rc.q[prime] - (c.t - cf) : cf;     // c in (t/2, t) acts as c - t
+        }
+        any = true;
+        if (++staged == group) flush();
+    }
+    flush();
+    if (!any) return nullptr;                                              // commitment.cpp:268-270
+    const size_t words = row_words(c);
+    LweCommitment* out = new_commitment(words);
+    for (uint32_t w = 0; w < kRnsHeaderWords; ++w) out->data[w] = rns_header_word(w, words, (uint64_t)c.n | ((uint64_t)c.k << 32), c.rc);
+    try {
+        LSR_HIP(hipMemcpyAsync(out->data + kRnsHeaderWords, acc.ptr, 2 * block * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    } catch (...) {
+        delete[] out->data;
+        delete out;
+        throw;
+    }
+    return out;
+}
+
 static LweCommitment* linear_combine(const LweContext& c, const LweCommitment** cms, const uint64_t* coeffs, size_t count) {
+    if (c.rns) return linear_combine_rns(c, cms, coeffs, count);
     const size_t body_words = (size_t)(c.k + 1) * c.n;
     DeviceGuard guard(c.device);
     std::lock_guard<std::mutex> lock(c.mutex);
@@ -1193,6 +1451,49 @@ LweContext* lsr_lwe_context_create_seeded(const PublicParams* params, uint64_t k
     }
 }
 
+LweContext* lsr_lwe_context_create_rns(const PublicParams* params, uint64_t key_seed, int device) noexcept {
+    try {
+        return lsr::create_rns_context(params, key_seed, device);
+    } catch (const std::exception& e) {
+        lsr::set_last_error(std::string("lsr_lwe_context_create_rns: ") + e.what());
+        std::fprintf(stderr, "lwe_context_create error: %s\n", e.what());
+        return nullptr;
+    } catch (...) {
+        return nullptr;
+    }
+}
+
+int lsr_lwe_rns_moduli(const LweContext* ctx, uint64_t out[2]) noexcept {
+    if (!ctx || !ctx->rns || !out) return -1;
+    out[0] = ctx->rc.q[0];
+    out[1] = ctx->rc.q[1];
+    return 0;
+}
+int lsr_rns_commit_moduli(uint32_t ring_degree, uint64_t out[2]) noexcept {
+    try {
+        return out && lsr::rns_moduli_for(ring_degree, out) ? 0 : -1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+// entry points that have no RNS form yet: refused before any device work
+static bool refuse_rns(const char* where, const LweContext* ctx) noexcept {
+    if (!ctx || !ctx->rns) return false;
+    try {
+        lsr::set_last_error(std::string(where) + ": not available on an RNS context (lsr_lwe_context_create_rns): it serves commitments, openings and "
+                                                 "linear combinations only");
+    } catch (...) {
+    }
+    return true;
+}
+static bool refuse_rns_shards(const char* where, LweContext* const* ctxs, int shards) noexcept {
+    if (!ctxs) return false;
+    for (int g = 0; g < shards; ++g)
+        if (refuse_rns(where, ctxs[g])) return true;
+    return false;
+}
+
 void lwe_context_free(LweContext* ctx) noexcept { lsr::destroy_lwe_context(ctx); }
 
 uint64_t lsr_lwe_wide_modulus(uint32_t ring_degree) noexcept {
@@ -1203,11 +1504,15 @@ uint64_t lsr_lwe_modulus(const LweContext* ctx) noexcept { return ctx ? ctx->q :
 uint64_t lsr_lwe_plain_modulus(const LweContext* ctx) noexcept { return ctx ? ctx->t : 0; }
 uint32_t lsr_lwe_ring_degree(const LweContext* ctx) noexcept { return ctx ? ctx->n : 0; }
 uint32_t lsr_lwe_module_rank(const LweContext* ctx) noexcept { return ctx ? ctx->k : 0; }
-size_t lsr_lwe_commitment_words(const LweContext* ctx) noexcept { return ctx ? lsr::kHeaderWords + (size_t)(ctx->k + 1) * ctx->n : 0; }
-const NttContext* lsr_lwe_ntt_context(const LweContext* ctx) noexcept { return ctx ? ctx->ntt.get() : nullptr; }
+size_t lsr_lwe_commitment_words(const LweContext* ctx) noexcept { return ctx ? lsr::row_words(*ctx) : 0; }
+const NttContext* lsr_lwe_ntt_context(const LweContext* ctx) noexcept {
+    if (refuse_rns("lsr_lwe_ntt_context", ctx)) return nullptr;     // two transforms, not one
+    return ctx ? ctx->ntt.get() : nullptr;
+}
 
 int lsr_lwe_public_matrix(const LweContext* ctx, uint64_t* a_hat) noexcept {
     if (!ctx || !a_hat) return -1;
+    if (refuse_rns("lsr_lwe_public_matrix", ctx)) return -1;
     try {
         lsr::DeviceGuard guard(ctx->device);
         LSR_HIP(hipMemcpy(a_hat, ctx->a_hat.ptr, ctx->a_hat.count * 8, hipMemcpyDeviceToHost));
@@ -1225,7 +1530,7 @@ int lwe_commit_batch(LweContext* ctx, const uint64_t* messages, size_t msg_len, 
         lsr::DeviceGuard guard(ctx->device);
         std::lock_guard<std::mutex> lock(ctx->mutex);
         lsr::wait_for_async(*ctx);
-        const size_t per_commit = (3 * (size_t)ctx->k + 3) * ctx->n * 8;
+        const size_t per_commit = (ctx->rns ? 2 : 1) * (3 * (size_t)ctx->k + 3) * ctx->n * 8;
         const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, (1ull << 30) / per_commit));
         size_t done = 0;
         try {
@@ -1254,8 +1559,8 @@ static int commit_batch_flat(const char* where, LweContext* ctx, const uint64_t*
         lsr::DeviceGuard guard(ctx->device);
         std::lock_guard<std::mutex> lock(ctx->mutex);
         lsr::wait_for_async(*ctx);
-        const size_t words = lsr::kHeaderWords + ((size_t)ctx->k + 1) * ctx->n;
-        const size_t per_commit = (4 * (size_t)ctx->k + 5) * ctx->n * 8;
+        const size_t words = lsr::row_words(*ctx);
+        const size_t per_commit = (ctx->rns ? 2 : 1) * (4 * (size_t)ctx->k + 5) * ctx->n * 8;
         const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, (1ull << 30) / per_commit));
         if (!to_device) {
             // host array: pieces of about 32 MiB of rows, so that the copy of one piece (57 GB/s over PCIe: the long pole) runs under
@@ -1395,6 +1700,7 @@ int lsr_lwe_verify_rows_device(const LweContext* ctx, const uint64_t* d_rows, co
 
 const char* lsr_lwe_pipeline(const LweContext* ctx) noexcept {
     if (!ctx) return "";
+    if (ctx->rns) return lsr::rns_tile(*ctx) ? "rns-tile" : "rns-general";
     if (ctx->ab_perm.ptr && ctx->logn == 12) return "tile";
     if (ctx->a_perm.ptr) return (ctx->ab_perm.ptr || ctx->b_perm.ptr) ? "fused" : "fused-matvec";
     return "general";
@@ -1502,6 +1808,7 @@ size_t lsr_words_to_limbs(const uint64_t* words, size_t count, unsigned limb_bit
 
 LweContext* lsr_lwe_context_replicate(const LweContext* ctx, int device) noexcept {
     if (!ctx) return nullptr;
+    if (refuse_rns("lsr_lwe_context_replicate", ctx)) return nullptr;
     try {
         return lsr::create_lwe_context(&ctx->params, ctx->key_seed, device, &ctx->keys);   // same keys => same A_hat, s, b_hat
     } catch (const std::exception& e) {
@@ -1514,6 +1821,7 @@ LweContext* lsr_lwe_context_replicate(const LweContext* ctx, int device) noexcep
 
 int lsr_lwe_commit_batch_flat_sharded(LweContext* const* ctxs, int shards, const uint64_t* messages, size_t msg_len, size_t batch, const uint64_t* seeds,
                                       uint64_t* out_words) noexcept {
+    if (refuse_rns_shards("lsr_lwe_commit_batch_flat_sharded", ctxs, shards)) return -1;
     if (!shards_compatible(ctxs, shards) || !messages || !out_words) return -1;
     if (batch == 0) return 0;
     const size_t words = lsr::kHeaderWords + ((size_t)ctxs[0]->k + 1) * ctxs[0]->n;
@@ -1574,15 +1882,18 @@ static int mlwe_matvec_batch_sharded(LweContext* const* ctxs, int shards, uint64
 }
 int lsr_mlwe_matvec_batch_sharded(LweContext* const* ctxs, int shards, uint64_t* const* d_r, const uint64_t* const* d_e1, size_t batch, uint64_t* host_u,
                                   double* seconds) noexcept {
+    if (refuse_rns_shards("lsr_mlwe_matvec_batch_sharded", ctxs, shards)) return -1;
     return mlwe_matvec_batch_sharded(ctxs, shards, d_r, d_e1, batch, host_u, seconds, nullptr);
 }
 int lsr_mlwe_matvec_batch_sharded_stats(LweContext* const* ctxs, int shards, uint64_t* const* d_r, const uint64_t* const* d_e1, size_t batch, uint64_t* host_u,
                                         double* per_shard) noexcept {
+    if (refuse_rns_shards("lsr_mlwe_matvec_batch_sharded_stats", ctxs, shards)) return -1;
     return mlwe_matvec_batch_sharded(ctxs, shards, d_r, d_e1, batch, host_u, nullptr, per_shard);
 }
 
 int lsr_lwe_sample_blinding_device(const LweContext* ctx, uint64_t* d_e1, size_t batch, const uint64_t* seeds, void* stream) noexcept {
     if (!ctx || !d_e1 || !seeds) return -1;
+    if (refuse_rns("lsr_lwe_sample_blinding_device", ctx)) return -1;
     if (batch == 0) return 0;
     try {
         lsr::DeviceGuard guard(ctx->device);
@@ -1607,6 +1918,7 @@ int lsr_mlwe_matvec_batch_device(const LweContext* ctx, uint64_t* d_r, const uin
                                  void* stream) noexcept {
     if (!ctx || !d_r || !d_u) return -1;
     if (!d_e1 && !seeds) return -1;
+    if (refuse_rns("lsr_mlwe_matvec_batch_device", ctx)) return -1;
     if (batch == 0) return 0;
     try {
         lsr::DeviceGuard guard(ctx->device);

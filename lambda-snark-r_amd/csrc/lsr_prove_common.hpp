@@ -18,6 +18,14 @@ inline void check_call(int rc, const char* what) {
     if (rc != 0) throw std::runtime_error(std::string(what) + ": " + lsr_last_error());
 }
 
+// The provers and their verifiers commit and open under ONE modulus: a two-prime RNS context (batch.h, lsr_lwe_context_create_rns)
+// is refused by their argument checks.  `lwe` non-NULL.
+inline int refuse_rns_context(const char* where, const LweContext* lwe) {
+    uint64_t moduli[2];
+    if (lsr_lwe_rns_moduli(lwe, moduli) != 0) return 0;
+    return abi_refuse(where, "RNS contexts (lsr_lwe_context_create_rns) are not supported by the provers and their verifiers");
+}
+
 // keys and rows of `count` commitments to the device messages d_msg [count][msg_len], all on `s`.  host_keys: derive the keys on
 // the host (seed 0 = fresh entropy) from the messages copied back; else on the device.
 inline void commit_messages(LweContext* lwe, const uint64_t* d_msg, size_t msg_len, size_t count, const uint64_t* seeds, uint64_t* d_keys,

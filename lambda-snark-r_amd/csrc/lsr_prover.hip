@@ -726,6 +726,7 @@ static int prove_checks(const char* where, const LsrR1csProver* prover, const Lw
     if (!w || !seeds || !rows || !proofs || !status) return abi_refuse(where, "NULL witnesses, seeds, rows, proofs or status");
     if (n_public > prover->n_vars) return abi_refuse(where, "n_public exceeds the circuit's variable count");
     if (commit_modulus <= 1) return abi_refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
+    if (lsr::refuse_rns_context(where, lwe)) return -1;
     const NttContext* ntt = lsr_lwe_ntt_context(lwe);
     if (!ntt || ntt->device != prover->device()) return abi_refuse(where, "the prover and the LWE context live on different devices");
     return 0;

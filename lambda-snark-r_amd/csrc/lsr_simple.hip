@@ -295,6 +295,7 @@ static int prove_args(const char* where, const LsrSimpleProver* p, const LweCont
     if ((mode != LSR_SIMPLE_SIMULATE && !w) || (!pub && n_public) || !seeds || !rows || !coeffs || !proofs)
         return abi_refuse(where, "NULL witnesses, public inputs, seeds or output");
     if (commit_modulus <= 1) return abi_refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
+    if (lsr::refuse_rns_context(where, lwe)) return -1;
     const NttContext* ntt = lsr_lwe_ntt_context(lwe);
     if (!ntt || ntt->device != p->device) return abi_refuse(where, "the prover and the LWE context live on different devices");
     return 0;
@@ -308,6 +309,7 @@ static int verify_args(const char* where, uint64_t q, const void* pub, size_t n_
     if (len > 0xffffffffull) return abi_refuse(where, "len must be below 2^32");
     if (lwe) {
         if (commit_modulus <= 1) return abi_refuse(where, "commit_modulus must be LweContext::modulus() (> 1)");
+        if (lsr::refuse_rns_context(where, lwe)) return -1;
         if (words != lsr_lwe_commitment_words(lwe)) return abi_refuse(where, "words_per_row must be the context's commitment words");
     }
     return 0;
