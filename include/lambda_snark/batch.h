@@ -176,6 +176,40 @@ int lsr_lwe_verify_rows_device(const LweContext* ctx, const uint64_t* d_rows, co
                                size_t count, int* d_results, void* stream) LSR_NOEXCEPT;
 const char* lsr_lwe_pipeline(const LweContext* ctx) LSR_NOEXCEPT;
 
+/* ---------------- commitment: decoding rows, with the measured noise ----------------
+ * What a row opens to, and how much decoding headroom it has left — for callers that fold rows with lwe_linear_combine and would
+ * otherwise recompute the expected message on the side, and for combinations of already combined rows, whose depth the budget
+ * check of lwe_linear_combine cannot see (it assumes fresh inputs; the wire row carries no weight).
+ * Definitions.  x_i = the i-th coefficient of v - <s, u> mod q (RNS context: the CRT lift of the two residues into [0, Q); read
+ * Q for q below).  With h = floor(q/2):
+ *   N_i   = t x_i + h = s_i q + rem_i,   0 <= rem_i < q,   s_i in [0, t]
+ *   slot  = (s_i == t ? 0 : s_i)                    bit for bit the value lwe_verify_opening compares with the claimed word
+ *   rho_i = |rem_i - h| = |t x_i - s_i q| <= h      t times the distance of x_i from the nearest plaintext lattice point, exact
+ *   noise_bits = bitlen(max_i rho_i) over ALL ring_degree coefficients (0 when the maximum is 0)
+ * A row stops decoding to its message when noise_bits reaches lsr_lwe_noise_capacity_bits = bitlen(h); the headroom of a row is
+ * the capacity minus its noise_bits.  Scaling a row by 2^e adds e to its noise_bits.  Fresh commitments at ring_degree 4096, rank 2,
+ * sigma 3.19 measure 32 or 33 bits, of a capacity of 43 (default context) or 87 (RNS context).
+ *
+ * lsr_lwe_decode_rows_device: d_messages[count][slots] = the first `slots` decoded plaintext slots of each device-resident row
+ * (1 <= slots <= ring_degree); d_status[count] = 1 (well-formed, decoded) or -1 (wrong header for this context, a residue word >=
+ * its modulus, a row of the other kind of context — the screening of lsr_lwe_verify_rows_device): messages and noise of such a row
+ * are unspecified, its neighbours are unaffected.  d_noise_bits (may be NULL) [count].  Without it only the first `slots`
+ * coefficients of a row are divided; with it all ring_degree are.  Asynchronous on `stream`; ordering behind other calls on the
+ * context, workspaces and graph capture exactly as lsr_lwe_verify_rows_device.  Every pipeline lsr_lwe_pipeline names is served.
+ * lsr_lwe_decode_batch_flat: the same for host rows words[count][lsr_lwe_commitment_words], staged in the chunks the flat verify uses;
+ * returns when the outputs are complete.
+ * lsr_lwe_decode: one LweCommitment; returns the status (1 / -1).
+ * NULL context or buffer (noise_bits excepted), slots == 0 or > ring_degree: -1 and a message in lsr_last_error, before any device
+ * work (without a device there is no context to pass).  count == 0: no-op, 0.  Otherwise 0 / -1.
+ * Decoding reveals the message by design; nothing here is meant to be constant-time. */
+int lsr_lwe_decode_rows_device(const LweContext* ctx, const uint64_t* d_rows, size_t count, size_t slots,
+                               uint64_t* d_messages, int* d_status, uint32_t* d_noise_bits, void* stream) LSR_NOEXCEPT;
+int lsr_lwe_decode_batch_flat(const LweContext* ctx, const uint64_t* words, size_t count, size_t slots,
+                              uint64_t* messages, int* status, uint32_t* noise_bits) LSR_NOEXCEPT;
+int lsr_lwe_decode(const LweContext* ctx, const LweCommitment* cm, uint64_t* message, size_t slots, uint32_t* noise_bits) LSR_NOEXCEPT;
+/* bit length of floor(q/2) (RNS: floor(Q/2)); 0 for a NULL context */
+uint32_t lsr_lwe_noise_capacity_bits(const LweContext* ctx) LSR_NOEXCEPT;
+
 /* `count` openings in one device pass.  messages = [count][msg_len]; results[i] = 1 / 0 / -1 with the meaning of
  * lwe_verify_opening (cpp-core/src/commitment.cpp:200-232) for (commitments[i], messages[i]); NULL entries => -1.
  * Returns 0, or -1 if the call itself failed. */

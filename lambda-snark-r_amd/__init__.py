@@ -255,6 +255,33 @@ class LweContext:
         if self._lib.lsr_lwe_verify_rows_device(self._h, d_rows, d_messages, msg_len, count, d_results, stream) != 0:
             raise CoreError("VerificationFailed: " + _abi.last_error())
 
+    @property
+    def noise_capacity_bits(self):
+        """``lsr_lwe_noise_capacity_bits``: a row stops decoding to its message when its ``noise_bits`` reaches this."""
+        return self._lib.lsr_lwe_noise_capacity_bits(self._h)
+
+    def decode_rows_device(self, d_rows, count, slots, d_messages, d_status, d_noise_bits, stream):
+        """``lsr_lwe_decode_rows_device``: device pointers (ints) in; the first `slots` plaintext slots of every row, int32 status
+        (1 / -1) and, unless `d_noise_bits` is None, uint32 noise bit lengths out; asynchronous on `stream`."""
+        if self._lib.lsr_lwe_decode_rows_device(self._h, d_rows, count, slots, d_messages, d_status, d_noise_bits, stream) != 0:
+            raise CoreError("DecodeFailed: " + _abi.last_error())
+
+    def decode_rows(self, rows, slots=None, noise=False):
+        """``lsr_lwe_decode_batch_flat``: rows [count][words] (host) -> (messages [count][slots], status [count]) and, with `noise`,
+        noise_bits [count]; `slots` defaults to the ring degree."""
+        rows = _u64_array(rows, "rows")
+        if rows.ndim != 2 or rows.shape[1] != self.commitment_words:
+            raise ValueError("rows must be [count][commitment_words]")
+        slots = self.ring_degree if slots is None else int(slots)
+        count = rows.shape[0]
+        messages = np.zeros((count, max(slots, 0)), dtype=np.uint64)
+        status = np.zeros(count, dtype=np.int32)
+        bits = np.zeros(count, dtype=np.uint32)
+        if self._lib.lsr_lwe_decode_batch_flat(self._h, rows.ctypes.data, count, slots, messages.ctypes.data, status.ctypes.data,
+                                               bits.ctypes.data if noise else None) != 0:
+            raise CoreError("DecodeFailed: " + _abi.last_error())
+        return (messages, status, bits) if noise else (messages, status)
+
     def public_matrix(self):
         k, n = self.module_rank, self.ring_degree
         a = np.zeros((k, k, n), dtype=np.uint64)
@@ -422,6 +449,17 @@ class Commitment:
         if not p:
             raise CoreError("CommitmentFailed")   # commitment.rs:80-82
         return Commitment(ctx, _raw=p)
+
+    def decode(self, ctx, slots=None, noise=False):
+        """``lsr_lwe_decode``: the first `slots` plaintext slots this commitment opens to under `ctx` (default: all of them), with
+        `noise` also its noise bit length; raises when the commitment is not a canonical row of `ctx`."""
+        slots = ctx.ring_degree if slots is None else int(slots)
+        message = np.zeros(max(slots, 1), dtype=np.uint64)
+        bits = ctypes.c_uint32(0)
+        if self._lib.lsr_lwe_decode(ctx.handle, self._p, message.ctypes.data, slots, ctypes.byref(bits) if noise else None) != 1:
+            raise CoreError("DecodeFailed: " + _abi.last_error())
+        message = message[:slots]
+        return (message, int(bits.value)) if noise else message
 
     def as_words(self):
         """commitment.rs:88-93: the flat u64 words (hashed word-by-word by the Fiat–Shamir transcript)."""

@@ -135,6 +135,10 @@ SIGNATURES = {
     "lsr_lwe_commit_rows_device": (c_int, [vp, vp, c_size, c_size, vp, vp, vp]),
     "lsr_lwe_verify_rows_device": (c_int, [vp, vp, vp, c_size, c_size, vp, vp]),
     "lsr_lwe_pipeline": (ctypes.c_char_p, [vp]),
+    "lsr_lwe_decode_rows_device": (c_int, [vp, vp, c_size, c_size, vp, vp, vp, vp]),
+    "lsr_lwe_decode_batch_flat": (c_int, [vp, vp, c_size, c_size, vp, vp, vp]),
+    "lsr_lwe_decode": (c_int, [vp, ctypes.POINTER(LweCommitment), vp, c_size, vp]),
+    "lsr_lwe_noise_capacity_bits": (u32, [vp]),
     "lsr_lwe_wide_modulus": (ctypes.c_uint64, [ctypes.c_uint32]),
     "lsr_lwe_context_create_rns": (vp, [ctypes.POINTER(PublicParams), u64, c_int]),
     "lsr_lwe_rns_moduli": (c_int, [vp, vp]),

@@ -1222,6 +1222,168 @@ static void verify_opening_batch_flat(const LweContext& c, const uint64_t* words
     verify_host_rows(c, words, messages, msg_len, count, results, work_stream(*c.ntt));
 }
 
+// ---- decoding rows: the opening's pipelines with a storing sink ------------------------------------------------------
+template <int K>
+static void launch_decode_tile(const LweContext& c, const DecodeTileJob& job, bool noise, hipStream_t s) {
+    const RoundConsts<ArithF64> cs{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64};
+    if (noise)
+        hipLaunchKernelGGL((decode_tile_kernel<K, true>), dim3(job.count), dim3(kF8Threads), 0, s, job, c.s_perm.ptr, c.ntt->mod, c.ntt->fwd_f64.ptr,
+                           c.ntt->inv_f64.ptr, cs);
+    else
+        hipLaunchKernelGGL((decode_tile_kernel<K, false>), dim3(job.count), dim3(kF8Threads), 0, s, job, c.s_perm.ptr, c.ntt->mod, c.ntt->fwd_f64.ptr,
+                           c.ntt->inv_f64.ptr, cs);
+    LSR_HIP(hipGetLastError());
+}
+template <int K>
+static void launch_decode_rns_tile(const LweContext& c, const DecodeRnsTileJob& job, bool noise, hipStream_t s) {
+    const RnsTilePrime a = rns_tile_prime(c, c.s_perm.ptr), b = rns_tile_prime(*c.sib, c.sib->s_perm.ptr);
+    if (noise) hipLaunchKernelGGL((decode_rns_tile_kernel<K, true>), dim3(job.count), dim3(kF8Threads), 0, s, job, a, b);
+    else hipLaunchKernelGGL((decode_rns_tile_kernel<K, false>), dim3(job.count), dim3(kF8Threads), 0, s, job, a, b);
+    LSR_HIP(hipGetLastError());
+}
+template <int R>
+static void launch_decode_top_inverse(const LweContext& c, const DecodeTopJob& job, unsigned grid, bool noise, hipStream_t s) {
+    const RoundConsts<ArithF64> cs{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64};
+    if (noise) hipLaunchKernelGGL((decode_top_inverse_kernel<R, true>), dim3(grid), dim3(256), 0, s, job, 12, c.ntt->mod, c.ntt->inv_f64.ptr, cs);
+    else hipLaunchKernelGGL((decode_top_inverse_kernel<R, false>), dim3(grid), dim3(256), 0, s, job, 12, c.ntt->mod, c.ntt->inv_f64.ptr, cs);
+}
+// lanes of the elementwise decoding kernels: every coefficient with the noise, the first `slots` of each row without
+static unsigned decode_store_grid(const LweContext& c, size_t count, size_t slots, bool noise) {
+    return (unsigned)(((uint64_t)count * (noise ? (size_t)c.n : slots) + 255) / 256);
+}
+
+// `count` device-resident wire rows -> d_out[count][slots] (1 <= slots <= n), enqueued on `s`; caller holds c.mutex.  The same state as
+// verify_rows_device leaves: the per-row "not a canonical commitment of this context" mark in c.ws_vbad, and in c.ws_vflags, instead
+// of the compare flags, the per-row maximum of bitlen(rho) (noise only).  Pipeline selection, screening, chunking, chunk lanes and
+// workspaces are those of verify_rows_device; only the last stage differs.
+static void decode_rows_device(const LweContext& c, const uint64_t* d_rows, size_t count, size_t slots, uint64_t* d_out, bool noise, hipStream_t s) {
+    const uint32_t n = c.n, k = c.k;
+    const size_t state_words = count + (count + 1) / 2;
+    c.ws_vflags.reserve(state_words);
+    c.ws_vbad = reinterpret_cast<uint32_t*>(c.ws_vflags.ptr + count);
+    zero_words_async(reinterpret_cast<uint64_t*>(c.ws_vflags.ptr), state_words, s);
+    if (c.rns) {
+        if (rns_tile(c)) {
+            const DecodeRnsTileJob job{d_rows, d_out, (uint64_t)slots, c.ws_vflags.ptr, c.ws_vbad, (uint32_t)count, c.rc};
+            switch (k) {
+                case 1: launch_decode_rns_tile<1>(c, job, noise, s); break;
+                case 2: launch_decode_rns_tile<2>(c, job, noise, s); break;
+                case 3: launch_decode_rns_tile<3>(c, job, noise, s); break;
+                default: launch_decode_rns_tile<4>(c, job, noise, s); break;
+            }
+            return;
+        }
+        const uint64_t kn = (uint64_t)k * n;
+        for (int prime = 0; prime < 2; ++prime) {
+            const LweContext& ci = prime ? *c.sib : c;
+            ensure_workspace(ci, count);
+            hipLaunchKernelGGL(rns_unpack_kernel, dim3(grid_for(count * (kRnsHeaderWords + kn + n))), dim3(256), 0, s, d_rows, ci.ws_u.ptr, ci.ws_v.ptr, c.ws_vbad, kn,
+                               (uint64_t)n, (uint64_t)count, prime, c.rc, (uint64_t)n | ((uint64_t)k << 32));
+            launch_ntt(*ci.ntt, ci.ws_u.ptr, count * k, false, s);
+            launch_ntt(*ci.ntt, ci.ws_v.ptr, count, false, s);
+            matvec(ci, ci.ws_e2.ptr, ci.s_hat.ptr, ci.ws_u.ptr, nullptr, 1, k, 0, 1, count, s);            // <s_hat, u_hat>
+            hipLaunchKernelGGL(rsub_mod_kernel, dim3(grid_for(count * n)), dim3(256), 0, s, ci.ws_e2.ptr, ci.ws_v.ptr, (uint64_t)count * n, ci.q);
+            launch_ntt(*ci.ntt, ci.ws_e2.ptr, count, true, s);
+        }
+        const unsigned grid = decode_store_grid(c, count, slots, noise);
+        if (noise)
+            hipLaunchKernelGGL(rns_decode_store_kernel<true>, dim3(grid), dim3(256), 0, s, c.ws_e2.ptr, c.sib->ws_e2.ptr, d_out, (uint64_t)slots, (uint32_t)c.logn,
+                               (uint64_t)count, c.rc, c.sib->ntt->mod, c.ws_vflags.ptr);
+        else
+            hipLaunchKernelGGL(rns_decode_store_kernel<false>, dim3(grid), dim3(256), 0, s, c.ws_e2.ptr, c.sib->ws_e2.ptr, d_out, (uint64_t)slots, (uint32_t)c.logn,
+                               (uint64_t)count, c.rc, c.sib->ntt->mod, c.ws_vflags.ptr);
+        LSR_HIP(hipGetLastError());
+        return;
+    }
+    const size_t kn = (size_t)k * n, row = kHeaderWords + kn + n;
+    if (c.s_perm.ptr && c.logn == 12) {
+        const DecodeTileJob job{d_rows, d_out, (uint64_t)slots, c.ws_vflags.ptr, c.ws_vbad, (uint32_t)count, c.q, c.t};
+        switch (k) {
+            case 1: launch_decode_tile<1>(c, job, noise, s); break;
+            case 2: launch_decode_tile<2>(c, job, noise, s); break;
+            case 3: launch_decode_tile<3>(c, job, noise, s); break;
+            default: launch_decode_tile<4>(c, job, noise, s); break;
+        }
+        return;
+    }
+    if (c.s_perm.ptr && c.a_perm.ptr) {     // n = 2^16 / 2^17: the chunks, chunk lanes and workspace of verify_rows_device
+        const size_t vec_words = (size_t)k << c.logn;
+        const size_t chunk = std::max<size_t>(1, kVerifyChunkBytes / (vec_words * 8));
+        const size_t slot = std::min(chunk, count);
+        const int streams = static_cast<int>(std::min<size_t>((size_t)kVerifyStreams, (count + chunk - 1) / chunk));
+        ensure_side_streams(c, streams);
+        const size_t slot_words = slot * (vec_words + n);
+        c.ws_mid.reserve(slot_words * streams);
+        const int r = c.logn - 12, lo = 12;
+        fork_lanes(c, s, streams);
+        size_t index = 0;
+        for (size_t first = 0; first < count; first += chunk, ++index) {
+            const size_t now = std::min(chunk, count - first);
+            hipStream_t st = index % streams == 0 ? s : c.side[index % streams - 1];
+            uint64_t* const ws = c.ws_mid.ptr + (index % streams) * slot_words;
+            uint64_t* const ws_out = ws + slot * vec_words;
+            const VerifyTopJob fwd{d_rows + first * row, ws, ws_out, nullptr, 0, (uint64_t)row, c.ws_vflags.ptr + first, c.ws_vbad + first, (uint32_t)now, k, c.q,
+                                   c.t};
+            const DecodeTopJob inv{d_rows + first * row, ws_out, d_out + first * slots, (uint64_t)slots, (uint64_t)row, c.ws_vflags.ptr + first,
+                                   c.ws_vbad + first, (uint32_t)now, k, c.q, c.t};
+            const unsigned grid_f = static_cast<unsigned>((now * k << c.logn) >> (r + 8)), grid_i = static_cast<unsigned>((now << c.logn) >> (r + 8));
+            if (r == 4) hipLaunchKernelGGL((verify_top_forward_kernel<4>), dim3(grid_f), dim3(256), 0, st, fwd, lo, c.ntt->mod, c.ntt->fwd_f64.ptr);
+            else hipLaunchKernelGGL((verify_top_forward_kernel<5>), dim3(grid_f), dim3(256), 0, st, fwd, lo, c.ntt->mod, c.ntt->fwd_f64.ptr);
+            switch (k) {
+                case 1: launch_mid_general<1, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
+                case 2: launch_mid_general<2, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
+                case 3: launch_mid_general<3, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
+                default: launch_mid_general<4, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
+            }
+            if (r == 4) launch_decode_top_inverse<4>(c, inv, grid_i, noise, st);
+            else launch_decode_top_inverse<5>(c, inv, grid_i, noise, st);
+            LSR_HIP(hipGetLastError());
+        }
+        join_lanes(c, s, streams);
+        return;
+    }
+    ensure_workspace(c, count);
+    hipLaunchKernelGGL(unpack_commitments_kernel, dim3(grid_for(count * row)), dim3(256), 0, s, d_rows, c.ws_u.ptr, c.ws_v.ptr, c.ws_vbad, (uint64_t)kn,
+                       (uint64_t)n, (uint64_t)count, c.q, c.t, (uint64_t)n | ((uint64_t)k << 32));
+    launch_ntt(*c.ntt, c.ws_u.ptr, count * k, false, s);
+    launch_ntt(*c.ntt, c.ws_v.ptr, count, false, s);
+    matvec(c, c.ws_e2.ptr, c.s_hat.ptr, c.ws_u.ptr, nullptr, 1, k, 0, 1, count, s);            // <s_hat, u_hat>
+    hipLaunchKernelGGL(rsub_mod_kernel, dim3(grid_for(count * n)), dim3(256), 0, s, c.ws_e2.ptr, c.ws_v.ptr, (uint64_t)count * n, c.q);
+    launch_ntt(*c.ntt, c.ws_e2.ptr, count, true, s);
+    const unsigned grid = decode_store_grid(c, count, slots, noise);
+    if (noise)
+        hipLaunchKernelGGL(decode_store_batch_kernel<true>, dim3(grid), dim3(256), 0, s, c.ws_e2.ptr, d_out, (uint64_t)slots, (uint32_t)c.logn, (uint64_t)count, c.t,
+                           c.ntt->mod, c.ws_vflags.ptr);
+    else
+        hipLaunchKernelGGL(decode_store_batch_kernel<false>, dim3(grid), dim3(256), 0, s, c.ws_e2.ptr, d_out, (uint64_t)slots, (uint32_t)c.logn, (uint64_t)count, c.t,
+                           c.ntt->mod, c.ws_vflags.ptr);
+    LSR_HIP(hipGetLastError());
+}
+
+// rows (host, back to back) -> messages[count][slots], status[count], noise_bits[count] (optional), verify_chunk() rows per pass
+static void decode_host_rows(const LweContext& c, const uint64_t* rows, size_t count, size_t slots, uint64_t* messages, int* status, uint32_t* noise_bits,
+                             hipStream_t s) {
+    const size_t row = row_words(c);
+    const size_t chunk = verify_chunk(c, count);
+    c.ws_rows.reserve(chunk * row);
+    ensure_input_space(c, chunk);                            // ws_dm: chunk x n slots (slots <= n)
+    uint64_t* const d_out = c.ws_dm.ptr;
+    std::vector<unsigned long long> state(chunk + (chunk + 1) / 2);
+    for (size_t first = 0; first < count; first += chunk) {
+        const size_t now = std::min(chunk, count - first);
+        LSR_HIP(hipMemcpyAsync(c.ws_rows.ptr, rows + first * row, now * row * 8, hipMemcpyHostToDevice, s));
+        decode_rows_device(c, c.ws_rows.ptr, now, slots, d_out, noise_bits != nullptr, s);
+        LSR_HIP(hipMemcpyAsync(messages + first * slots, d_out, now * slots * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(state.data(), c.ws_vflags.ptr, (now + (now + 1) / 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+        const uint32_t* const host_bad = reinterpret_cast<const uint32_t*>(state.data() + now);
+        for (size_t j = 0; j < now; ++j) {
+            status[first + j] = host_bad[j] ? -1 : 1;
+            if (noise_bits) noise_bits[first + j] = (uint32_t)state[j];
+        }
+    }
+}
+
 // RNS rows: the same sum under each prime (combine_kernel per residue block).  The budget is Q / 2t ~ 2^67: any coefficient below t
 // over any realistic number of terms — the reference's range (commitment.cpp:88-96,247-266)
 static LweCommitment* linear_combine_rns(const LweContext& c, const LweCommitment** cms, const uint64_t* coeffs, size_t count) {
@@ -1696,6 +1858,91 @@ int lsr_lwe_verify_rows_device(const LweContext* ctx, const uint64_t* d_rows, co
     } catch (...) {
         return -1;
     }
+}
+
+// argument screening shared by the decoding entry points: false (and a message) for what is refused before any device work
+// (a process without a device has no context to pass: the NULL-context refusal is also the no-device one)
+static bool decode_arguments_ok(const char* where, const LweContext* ctx, const void* rows, size_t slots, const void* messages, const void* status) {
+    const char* why = nullptr;
+    if (!ctx) why = "NULL context (no context exists without a HIP device)";
+    else if (!rows || !messages || !status) why = "NULL buffer";
+    else if (slots == 0 || slots > ctx->n) why = "slots must lie in 1 .. ring_degree";
+    if (why) lsr::set_last_error(std::string(where) + ": " + why);
+    return why == nullptr;
+}
+
+int lsr_lwe_decode_rows_device(const LweContext* ctx, const uint64_t* d_rows, size_t count, size_t slots, uint64_t* d_messages, int* d_status,
+                               uint32_t* d_noise_bits, void* stream) noexcept {
+    if (!decode_arguments_ok("lsr_lwe_decode_rows_device", ctx, d_rows, slots, d_messages, d_status)) return -1;
+    if (count == 0) return 0;
+    if (count > 0x7fffffffull) {
+        lsr::set_last_error("lsr_lwe_decode_rows_device: count exceeds one launch (2^31 - 1 rows)");
+        return -1;
+    }
+    try {
+        lsr::DeviceGuard guard(ctx->device);
+        std::lock_guard<std::mutex> lock(ctx->mutex);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        lsr::begin_async(*ctx, s);
+        lsr::decode_rows_device(*ctx, d_rows, count, slots, d_messages, d_noise_bits != nullptr, s);
+        hipLaunchKernelGGL(lsr::decode_status_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, ctx->ws_vflags.ptr, ctx->ws_vbad, d_status, d_noise_bits,
+                           (uint64_t)count);
+        LSR_HIP(hipGetLastError());
+        lsr::end_async(*ctx, s);
+        return 0;
+    } catch (const std::exception& e) {
+        lsr::set_last_error(std::string("lsr_lwe_decode_rows_device: ") + e.what());
+        return -1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int lsr_lwe_decode_batch_flat(const LweContext* ctx, const uint64_t* words, size_t count, size_t slots, uint64_t* messages, int* status,
+                              uint32_t* noise_bits) noexcept {
+    if (!decode_arguments_ok("lsr_lwe_decode_batch_flat", ctx, words, slots, messages, status)) return -1;
+    if (count == 0) return 0;
+    try {
+        lsr::DeviceGuard guard(ctx->device);
+        std::lock_guard<std::mutex> lock(ctx->mutex);
+        lsr::wait_for_async(*ctx);
+        lsr::decode_host_rows(*ctx, words, count, slots, messages, status, noise_bits, lsr::work_stream(*ctx->ntt));
+        return 0;
+    } catch (const std::exception& e) {
+        lsr::set_last_error(std::string("lsr_lwe_decode_batch_flat: ") + e.what());
+        return -1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int lsr_lwe_decode(const LweContext* ctx, const LweCommitment* cm, uint64_t* message, size_t slots, uint32_t* noise_bits) noexcept {
+    int status = -1;
+    if (!decode_arguments_ok("lsr_lwe_decode", ctx, cm, slots, message, &status)) return -1;
+    try {
+        const uint64_t* body = nullptr;
+        if (lsr::parse_commitment(*ctx, cm, &body)) {                  // otherwise the row never reaches the device
+            lsr::DeviceGuard guard(ctx->device);
+            std::lock_guard<std::mutex> lock(ctx->mutex);
+            lsr::wait_for_async(*ctx);
+            lsr::decode_host_rows(*ctx, cm->data, 1, slots, message, &status, noise_bits, lsr::work_stream(*ctx->ntt));
+        }
+        if (status != 1) lsr::set_last_error("lsr_lwe_decode: not a canonical commitment of this context");
+        return status;
+    } catch (const std::exception& e) {
+        lsr::set_last_error(std::string("lsr_lwe_decode: ") + e.what());
+        return -1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+uint32_t lsr_lwe_noise_capacity_bits(const LweContext* ctx) noexcept {
+    if (!ctx) return 0;
+    if (!ctx->rns) return 64u - (uint32_t)__builtin_clzll(ctx->q >> 1);
+    const unsigned __int128 half = ((((unsigned __int128)ctx->rc.big_hi) << 64) | ctx->rc.big_lo) >> 1;
+    const uint64_t hi = (uint64_t)(half >> 64);
+    return hi ? 128u - (uint32_t)__builtin_clzll(hi) : 64u - (uint32_t)__builtin_clzll((uint64_t)half);
 }
 
 const char* lsr_lwe_pipeline(const LweContext* ctx) noexcept {

@@ -195,6 +195,31 @@ __global__ void __launch_bounds__(256) decode_compare_batch_kernel(const uint64_
     if (diff) atomicOr(&flags[j], (unsigned long long)diff);
 }
 
+// the decoding twin: out[j][i] = decode(w[j][i]) for i < slots.  One lane per (j, i < slots); NOISE: one lane per
+// (j, i < n), each also folding bitlen(rho) of its coefficient into noise[j] (n >= 64: a wavefront serves one row)
+template <bool NOISE>
+__global__ void __launch_bounds__(256) decode_store_batch_kernel(const uint64_t* __restrict__ w, uint64_t* __restrict__ out, uint64_t slots, uint32_t logn,
+                                                                   uint64_t count, uint64_t t, ModParams p, unsigned long long* __restrict__ noise) {
+    const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if constexpr (NOISE) {
+        const uint64_t j = gid >> logn, i = gid & ((1ull << logn) - 1);
+        const bool live = j < count;
+        uint32_t bits = 0;
+        if (live) {
+            uint64_t rho;
+            const uint64_t slot = decode_slot_noise(w[gid], t, p, &rho);
+            bits = bitlen64(rho);
+            if (i < slots) out[j * slots + i] = slot;
+        }
+        if (logn >= 6) row_noise_max(&noise[live ? j : 0], bits);         // a dead wavefront adds 0 to row 0
+        else if (live) atomicMax(&noise[j], (unsigned long long)bits);
+    } else {
+        if (gid >= count * slots) return;
+        const uint64_t j = gid / slots, i = gid - j * slots;
+        out[gid] = decode_slot(w[(j << logn) + i], t, p);
+    }
+}
+
 static unsigned grid_for(uint64_t work, unsigned cap = 256 * 16) {
     const uint64_t blocks = (work + 255) / 256;
     return static_cast<unsigned>(std::min<uint64_t>(blocks, cap));
@@ -240,6 +265,15 @@ __global__ void __launch_bounds__(256) opening_verdict_kernel(const unsigned lon
                                                                int* __restrict__ results, uint64_t count) {
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (j < count) results[j] = bad[j] ? -1 : (flags[j] == 0 ? 1 : 0);
+}
+
+// the decoding twin: bad[j] -> status[j] = -1 / 1, and the row's accumulated bit length -> noise_bits[j] (optional)
+__global__ void __launch_bounds__(256) decode_status_kernel(const unsigned long long* __restrict__ noise, const uint32_t* __restrict__ bad,
+                                                             int* __restrict__ status, uint32_t* __restrict__ noise_bits, uint64_t count) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= count) return;
+    status[j] = bad[j] ? -1 : 1;
+    if (noise_bits) noise_bits[j] = (uint32_t)noise[j];
 }
 
 }  // namespace lsr

@@ -93,6 +93,37 @@ __device__ __forceinline__ uint64_t rns_decode_slot(uint64_t x1, uint64_t x2, co
     }
     return s == rc.t ? 0 : s;
 }
+// rns_decode_slot with the measured noise: after the fix-ups rem = N - s Q lies in [0, Q), and
+// rho = |rem - (Q - 1) / 2| = |t x - s Q| <= (Q - 1) / 2 < 2^87 — its bit length comes from the two halves
+__device__ __forceinline__ uint64_t rns_decode_slot_noise(uint64_t x1, uint64_t x2, const RnsConsts& rc, const ModParams& p2, uint32_t* rho_bits) {
+    const uint64_t x1r = x1 >= rc.q[1] ? x1 - rc.q[1] : x1;
+    const uint64_t diff = x2 >= x1r ? x2 - x1r : x2 + rc.q[1] - x1r;
+    const uint64_t y = mulmod_barrett128(diff, rc.q1inv, p2);
+    const unsigned __int128 big = ((unsigned __int128)rc.big_hi << 64) | rc.big_lo;
+    const unsigned __int128 x = (unsigned __int128)rc.q[0] * y + x1;
+    const unsigned __int128 num = x * rc.t + (big >> 1);
+    const double est = (double)rc.t * (((double)y + (double)x1 * rc.inv_q1) * rc.inv_q2) + 0.5;
+    uint64_t s = (uint64_t)(long long)__builtin_floor(est);
+    s = s > rc.t ? rc.t : s;
+    __int128 rem = (__int128)num - (__int128)((unsigned __int128)s * big);
+#pragma unroll
+    for (int fix = 0; fix < 2; ++fix) {
+        const bool under = rem < 0;
+        rem += under ? (__int128)big : (__int128)0;
+        s -= under ? 1 : 0;
+    }
+#pragma unroll
+    for (int fix = 0; fix < 2; ++fix) {
+        const bool over = rem >= (__int128)big;
+        rem -= over ? (__int128)big : (__int128)0;
+        s += over ? 1 : 0;
+    }
+    const __int128 off = rem - (__int128)(big >> 1);
+    const unsigned __int128 rho = (unsigned __int128)(off < 0 ? -off : off);
+    const uint64_t rho_hi = (uint64_t)(rho >> 64), rho_lo = (uint64_t)rho;
+    *rho_bits = rho_hi ? 64u + bitlen64(rho_hi) : bitlen64(rho_lo);
+    return s == rc.t ? 0 : s;
+}
 
 // ---- elementwise kernels of "rns-general" ---------------------------------------------------------------------------------------
 // v[j][x] = (v[j][x] + e2[j][x] + round(Q (msg[j][x] mod t) / t)) mod q_i for x < copy: the scalar component's epilogue under prime i
@@ -160,6 +191,28 @@ __global__ void __launch_bounds__(256) rns_decode_compare_kernel(const uint64_t*
     const uint64_t j = gid / msg_len, i = gid - j * msg_len;
     const uint64_t diff = rns_decode_slot(w1[(j << logn) + i], w2[(j << logn) + i], rc, p2) ^ msgs[gid];
     if (diff) atomicOr(&flags[j], (unsigned long long)diff);
+}
+// the decoding twin, lanes as decode_store_batch_kernel: out[j][i] = decode(w1[j][i], w2[j][i]) for i < slots
+template <bool NOISE>
+__global__ void __launch_bounds__(256) rns_decode_store_kernel(const uint64_t* __restrict__ w1, const uint64_t* __restrict__ w2, uint64_t* __restrict__ out,
+                                                                 uint64_t slots, uint32_t logn, uint64_t count, RnsConsts rc, ModParams p2,
+                                                                 unsigned long long* __restrict__ noise) {
+    const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if constexpr (NOISE) {
+        const uint64_t j = gid >> logn, i = gid & ((1ull << logn) - 1);
+        const bool live = j < count;
+        uint32_t bits = 0;
+        if (live) {
+            const uint64_t slot = rns_decode_slot_noise(w1[gid], w2[gid], rc, p2, &bits);
+            if (i < slots) out[j * slots + i] = slot;
+        }
+        if (logn >= 6) row_noise_max(&noise[live ? j : 0], bits);
+        else if (live) atomicMax(&noise[j], (unsigned long long)bits);
+    } else {
+        if (gid >= count * slots) return;
+        const uint64_t j = gid / slots, i = gid - j * slots;
+        out[gid] = rns_decode_slot(w1[(j << logn) + i], w2[(j << logn) + i], rc, p2);
+    }
 }
 
 // ---- "rns-tile" -----------------------------------------------------------------------------------------------------------------
@@ -373,6 +426,78 @@ __global__ void __launch_bounds__(kF8Threads, 4) verify_rns_tile_kernel(VerifyRn
         VerifyRnsTileSource src{block, &job.bad[j], job.rc.q[1]};
         VerifyRnsTileSink<K, 1> sink{job, block + ((size_t)K << 12), msg, &job.flags[j], &job.bad[j], b.p, w1};
         f8_tile_pipeline<K, 1, true, VerifyRnsTileSource, VerifyRnsTileSink<K, 1>, true>(0u, src, sink, b.mat, b.p, b.fwd_tw, b.inv_tw, b.cs, tile_lds, tw_lds);
+    }
+}
+
+// ---- decoding -------------------------------------------------------------------------------------------------------
+struct DecodeRnsTileJob {
+    const uint64_t* rows;        // [count][6 + 2 (k + 1) n]
+    uint64_t* out;               // [count][slots] decoded plaintext slots
+    uint64_t slots;              // 1 .. n
+    unsigned long long* noise;   // [count]: max over the row's coefficients of bitlen(rho) (NOISE only)
+    uint32_t* bad;
+    uint32_t count;
+    RnsConsts rc;
+};
+// as VerifyRnsTileSink: the first pass leaves w_1 in registers, the second lifts, decodes and stores the slots
+template <int K, int PRIME, bool NOISE>
+struct DecodeRnsTileSink {
+    const DecodeRnsTileJob& job;
+    const uint64_t* vsrc;        // v of this prime's block
+    uint64_t* out;
+    unsigned long long* noise;
+    uint32_t* bad;
+    const ModParams& p;
+    double (&w1)[kF8Regs];
+    __device__ __forceinline__ void store(int, const double (&x)[kF8Regs]) const {
+        uint32_t bits = 0;
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < kF8Regs; ++k) {
+            const uint32_t idx = threadIdx.x + 512u * (uint32_t)k;
+            const uint64_t raw = vsrc[idx];
+            ok = ok && raw < p.q;
+            const double w = canonical_f64(f64_from_u52(raw) - x[k], p.qd, p.inv_qd);
+            if constexpr (PRIME == 0) {
+                w1[k] = w;
+            } else if constexpr (NOISE) {
+                uint32_t b;
+                const uint64_t slot = rns_decode_slot_noise(u52_from_f64(w1[k]), u52_from_f64(w), job.rc, p, &b);
+                bits = b > bits ? b : bits;
+                if (idx < job.slots) out[idx] = slot;
+            } else {
+                if (idx < job.slots) out[idx] = rns_decode_slot(u52_from_f64(w1[k]), u52_from_f64(w), job.rc, p);
+            }
+        }
+        if (!ok) atomicOr(bad, 1u);
+        if constexpr (PRIME == 1 && NOISE) row_noise_max(noise, bits);
+    }
+};
+
+template <int K, bool NOISE>
+__global__ void __launch_bounds__(kF8Threads, 4) decode_rns_tile_kernel(DecodeRnsTileJob job, RnsTilePrime a, RnsTilePrime b) {
+    __shared__ double tile_lds[kF8TileWords];
+    __shared__ double tw_lds[kF8TwShared];
+    const uint32_t j = blockIdx.x;
+    if (j >= job.count) return;
+    constexpr size_t block_words = (size_t)(K + 1) << 12, row_words = kRnsHeaderWords + 2 * block_words;
+    const uint64_t* const row = job.rows + (size_t)j * row_words;
+    if (threadIdx.x < kRnsHeaderWords && row[threadIdx.x] != rns_header_word(threadIdx.x, row_words, 4096ull | ((uint64_t)K << 32), job.rc))
+        atomicOr(&job.bad[j], 1u);
+    uint64_t* const out = job.out + (size_t)j * job.slots;
+    double w1[kF8Regs];
+    {
+        const uint64_t* const block = row + kRnsHeaderWords;
+        VerifyRnsTileSource src{block, &job.bad[j], job.rc.q[0]};
+        DecodeRnsTileSink<K, 0, NOISE> sink{job, block + ((size_t)K << 12), out, &job.noise[j], &job.bad[j], a.p, w1};
+        f8_tile_pipeline<K, 1, true, VerifyRnsTileSource, DecodeRnsTileSink<K, 0, NOISE>, true>(0u, src, sink, a.mat, a.p, a.fwd_tw, a.inv_tw, a.cs, tile_lds, tw_lds);
+    }
+    __syncthreads();
+    {
+        const uint64_t* const block = row + kRnsHeaderWords + block_words;
+        VerifyRnsTileSource src{block, &job.bad[j], job.rc.q[1]};
+        DecodeRnsTileSink<K, 1, NOISE> sink{job, block + ((size_t)K << 12), out, &job.noise[j], &job.bad[j], b.p, w1};
+        f8_tile_pipeline<K, 1, true, VerifyRnsTileSource, DecodeRnsTileSink<K, 1, NOISE>, true>(0u, src, sink, b.mat, b.p, b.fwd_tw, b.inv_tw, b.cs, tile_lds, tw_lds);
     }
 }
 

@@ -51,6 +51,52 @@ __device__ __forceinline__ uint64_t decode_slot(uint64_t w, uint64_t t, const Mo
     return d == t ? 0 : d;
 }
 
+// ---- decoding with the measured noise ----
+// div128_by_q with the remainder kept: (hi:lo) = quot q + *rem, 0 <= *rem < q.  The same estimate and the same three fix-ups; before
+// them the true remainder is below 4 q < 2^63, so its low word `lo - quot q` IS the remainder.
+__device__ __forceinline__ uint64_t div128_by_q_rem(uint64_t hi, uint64_t lo, const ModParams& p, uint64_t* rem_out) {
+    const uint64_t c1 = __umul64hi(lo, p.barrett_lo);
+    const uint64_t m1_lo = lo * p.barrett_hi, m1_hi = __umul64hi(lo, p.barrett_hi);
+    const uint64_t m2_lo = hi * p.barrett_lo, m2_hi = __umul64hi(hi, p.barrett_lo);
+    uint64_t s = c1 + m1_lo;
+    uint64_t carry = s < c1;
+    const uint64_t s2 = s + m2_lo;
+    carry += s2 < s;
+    uint64_t quot = hi * p.barrett_hi + m1_hi + m2_hi + carry;
+    uint64_t rem = lo - quot * p.q;
+#pragma unroll
+    for (int fix = 0; fix < 3; ++fix) {
+        const bool over = rem >= p.q;
+        rem -= over ? p.q : 0;
+        quot += over ? 1 : 0;
+    }
+    *rem_out = rem;
+    return quot;
+}
+// decode_slot and rho = |t w - s q| = |rem - floor(q/2)| for N = t w + floor(q/2) = s q + rem: t times the distance of w from the
+// nearest plaintext lattice point, an exact integer <= floor(q/2)
+__device__ __forceinline__ uint64_t decode_slot_noise(uint64_t w, uint64_t t, const ModParams& p, uint64_t* rho) {
+    const uint64_t half = p.q >> 1;
+    const uint64_t lo0 = w * t, hi0 = __umul64hi(w, t);
+    const uint64_t lo = lo0 + half;
+    const uint64_t hi = hi0 + (lo < lo0);
+    uint64_t rem;
+    const uint64_t d = div128_by_q_rem(hi, lo, p, &rem);
+    *rho = rem >= half ? rem - half : half - rem;
+    return d == t ? 0 : d;
+}
+__device__ __forceinline__ uint32_t bitlen64(uint64_t x) { return x ? 64u - (uint32_t)__builtin_clzll(x) : 0u; }
+// noise[row] = max(noise[row], bits) from every lane of a wavefront whose lanes all serve the same row: bitlen is monotone, so the
+// maximum of the lanes' bit lengths is the bit length of the row's largest rho.  One atomic per wavefront.
+__device__ __forceinline__ void row_noise_max(unsigned long long* noise, uint32_t bits) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)bits, d, 64);
+        bits = other > bits ? other : bits;
+    }
+    if ((threadIdx.x & 63u) == 0) atomicMax(noise, (unsigned long long)bits);
+}
+
 // The message term of the scalar component: round(q (m mod t) / t) = floor((q m' + t/2) / t) for any 64-bit word m and t < 2^21,
 // in FP64 (a 64-bit integer division costs hundreds of instructions; the embed sits in the same lanes as the transforms).
 // Why not floor(q/t) m': with q = Delta t + rho a sum of commitments carries Delta M for the INTEGER M = sum c_i m_i, and
@@ -273,6 +319,73 @@ __global__ void __launch_bounds__(kF8Threads, LSR_VERIFY_TILE_WAVES) verify_tile
     f8_tile_pipeline<K, 1, true, VerifyTileSource<K>, VerifyTileSink<K>, LSR_VERIFY_TILE_TW_REGS != 0>(0u, src, sink, s_perm, p, fwd_tw, inv_tw, cs, tile_lds, tw_lds);
 }
 
+// ---- decoding: the opening's pipeline with a sink that keeps the decoded slots instead of comparing them ----
+struct DecodeTileJob {
+    const uint64_t* rows;        // [count][5 + (k + 1) n] wire rows, device
+    uint64_t* out;               // [count][slots] decoded plaintext slots
+    uint64_t slots;              // 1 .. n
+    unsigned long long* noise;   // [count]: max over the row's coefficients of bitlen(rho) (NOISE only)
+    uint32_t* bad;               // [count]: != 0 when the row is not a canonical commitment of this context
+    uint32_t count;
+    uint64_t q, t;
+};
+// w = v - INTT(<s_hat, u_hat>) as VerifyTileSink forms it; the slot is stored where verify compares it.  NOISE: every coefficient
+// goes through the division (its remainder is the measurement); otherwise only the first `slots`
+template <int K, bool NOISE>
+struct DecodeTileSink {
+    const DecodeTileJob& job;
+    const uint64_t* row;
+    uint64_t* out;
+    unsigned long long* noise;
+    uint32_t* bad;
+    const ModParams& p;
+    __device__ __forceinline__ void store(int, const double (&x)[kF8Regs]) const {
+        const uint64_t* const vsrc = row + kRowHeaderWords + ((size_t)K << 12);
+        uint32_t bits = 0;
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < kF8Regs; ++k) {
+            const uint32_t idx = threadIdx.x + 512u * (uint32_t)k;
+            const uint64_t raw = vsrc[idx];
+            ok = ok && raw < job.q;
+            if (NOISE || idx < job.slots) {
+                const uint64_t w = u52_from_f64(canonical_f64(f64_from_u52(raw) - x[k], p.qd, p.inv_qd));
+                if constexpr (NOISE) {
+                    uint64_t rho;
+                    const uint64_t slot = decode_slot_noise(w, job.t, p, &rho);
+                    const uint32_t b = bitlen64(rho);
+                    bits = b > bits ? b : bits;
+                    if (idx < job.slots) out[idx] = slot;
+                } else {
+                    out[idx] = decode_slot(w, job.t, p);
+                }
+            }
+        }
+        if (!ok) atomicOr(bad, 1u);
+        if constexpr (NOISE) row_noise_max(noise, bits);
+    }
+};
+template <int K, bool NOISE>
+__global__ void __launch_bounds__(kF8Threads, LSR_VERIFY_TILE_WAVES) decode_tile_kernel(DecodeTileJob job, const double* __restrict__ s_perm, ModParams p,
+                                                                                         const double* __restrict__ fwd_tw, const double* __restrict__ inv_tw,
+                                                                                         RoundConsts<ArithF64> cs) {
+    __shared__ double tile_lds[kF8TileWords];
+    __shared__ double tw_lds[kF8TwShared + (LSR_VERIFY_TILE_TW_REGS ? 0 : kF8TwPrivate)];
+    const uint32_t j = blockIdx.x;
+    if (j >= job.count) return;
+    const size_t row_words = kRowHeaderWords + ((size_t)(K + 1) << 12);
+    const uint64_t* const row = job.rows + (size_t)j * row_words;
+    if (threadIdx.x < kRowHeaderWords) {
+        const uint32_t w = threadIdx.x;
+        const uint64_t want = w == 0 ? 8ull * (row_words - 1) : (w == 1 ? kRowMagic : (w == 2 ? (4096ull | ((uint64_t)K << 32)) : (w == 3 ? job.q : job.t)));
+        if (row[w] != want) atomicOr(&job.bad[j], 1u);
+    }
+    VerifyTileSource<K> src{row, &job.bad[j], job.q};
+    DecodeTileSink<K, NOISE> sink{job, row, job.out + (size_t)j * job.slots, &job.noise[j], &job.bad[j], p};
+    f8_tile_pipeline<K, 1, true, VerifyTileSource<K>, DecodeTileSink<K, NOISE>, LSR_VERIFY_TILE_TW_REGS != 0>(0u, src, sink, s_perm, p, fwd_tw, inv_tw, cs, tile_lds,
+                                                                                                             tw_lds);
+}
+
 // =================================================================================================================================
 // The same two operations at n = 2^16 / 2^17 (a polynomial is 16 / 32 tiles): three launches per chunk of commitments,
 //     commit_top_forward  — r_i SAMPLED where the top forward round wants its operands (no array of r exists), raw elements out
@@ -474,6 +587,56 @@ __global__ void __launch_bounds__(256) verify_top_inverse_kernel(VerifyTopJob jo
     }
     if (!ok) atomicOr(&job.bad[j], 1u);
     if (diff) atomicOr(&job.flags[j], (unsigned long long)diff);
+}
+
+// ---- decoding at n = 2^16 / 2^17: verify_top_forward_kernel and the middle stage as they are, then this sink ----
+struct DecodeTopJob {
+    const uint64_t* rows;        // [count][row_words]
+    const uint64_t* ws_out;      // [count][n] raw: middle stage -> inverse round
+    uint64_t* out;               // [count][slots]
+    uint64_t slots, row_words;
+    unsigned long long* noise;   // [count] (NOISE only)
+    uint32_t* bad;
+    uint32_t count, k;
+    uint64_t q, t;
+};
+template <int R, bool NOISE>
+__global__ void __launch_bounds__(256) decode_top_inverse_kernel(DecodeTopJob job, int lo, ModParams p, const double* __restrict__ tw, RoundConsts<ArithF64> cs) {
+    constexpr int N = 1 << R;
+    const size_t g0 = (size_t)blockIdx.x * 256u;
+    const uint32_t j = (uint32_t)(g0 >> lo), low0 = (uint32_t)(g0 & (((size_t)1 << lo) - 1));
+    if (j >= job.count) return;
+    const uint64_t* const data = job.ws_out + ((size_t)j << (lo + R)) + low0 + threadIdx.x;
+    const uint64_t* const vsrc = job.rows + (size_t)j * job.row_words + kRowHeaderWords + ((size_t)job.k << (lo + R)) + low0 + threadIdx.x;
+    uint64_t* const out = job.out + (size_t)j * job.slots;
+    double v[N];
+    uint64_t vraw[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = __longlong_as_double((long long)__builtin_nontemporal_load(data + ((size_t)k << lo)));
+#pragma unroll
+    for (int k = 0; k < N; ++k) vraw[k] = __builtin_nontemporal_load(vsrc + ((size_t)k << lo));
+    top_round_inverse<R>(v, tw, cs, p);
+    uint32_t bits = 0;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const uint32_t x = ((uint32_t)k << lo) + low0 + threadIdx.x;
+        ok = ok && vraw[k] < job.q;
+        if (NOISE || x < job.slots) {
+            const uint64_t w = u52_from_f64(canonical_f64(f64_from_u52(vraw[k]) - v[k], p.qd, p.inv_qd));
+            if constexpr (NOISE) {
+                uint64_t rho;
+                const uint64_t slot = decode_slot_noise(w, job.t, p, &rho);
+                const uint32_t b = bitlen64(rho);
+                bits = b > bits ? b : bits;
+                if (x < job.slots) out[x] = slot;
+            } else {
+                out[x] = decode_slot(w, job.t, p);
+            }
+        }
+    }
+    if (!ok) atomicOr(&job.bad[j], 1u);
+    if constexpr (NOISE) row_noise_max(&job.noise[j], bits);
 }
 
 }  // namespace lsr
