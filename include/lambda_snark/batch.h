@@ -210,6 +210,40 @@ int lsr_lwe_decode(const LweContext* ctx, const LweCommitment* cm, uint64_t* mes
 /* bit length of floor(q/2) (RNS: floor(Q/2)); 0 for a NULL context */
 uint32_t lsr_lwe_noise_capacity_bits(const LweContext* ctx) LSR_NOEXCEPT;
 
+/* ---------------- commitment: batched linear combination of device-resident rows ----------------
+ * lwe_linear_combine for a whole batch, without a host round trip.  With W = lsr_lwe_commitment_words(ctx), output j < outputs is
+ *   out_j = sum_{i < terms} c'_{j,i} * row[j * term_stride + i]
+ * over the (k + 1) n body residues mod q (RNS context: over both residue blocks, each under its own prime), where c'_{j,i} is the
+ * centred representative of d_coeffs[j * terms + i] mod t: a value in (t/2, t) acts as c - t, exactly as in lwe_linear_combine.
+ * d_rows holds (outputs - 1) * term_stride + terms rows of W words and is only read.  term_stride = 0 combines one shared set of
+ * terms with `outputs` coefficient vectors; term_stride = terms folds disjoint consecutive groups; any other stride is allowed.
+ * d_out_rows[outputs][W] must not overlap d_rows.  d_coeffs[outputs][terms] is DEVICE memory (d_alphas of
+ * lsr_fs_challenge_batch_device can be passed as it is); coefficients are any 64-bit words, reduced mod t as given.
+ * An output row with status 1 is word for word the `data` lwe_linear_combine returns for the same terms and coefficients (header
+ * and canonical body residues).
+ * d_status[j] =  1  combined;
+ *                0  refused for the noise budget: sum_i |c'_{j,i}| exceeds the largest integer weight the comparison of
+ *                   lwe_linear_combine accepts on this context (weight (noise_unit + 1) < Delta / 2 in double; RNS: < Q / 2t in long
+ *                   double), computed once per call on the host and compared with the kernel's exact integer sum — the decision of
+ *                   lwe_linear_combine for that coefficient vector;
+ *               -1  some term row of this output is not a canonical row of this context (wrong header, a row of the other kind of
+ *                   context, a body residue >= its modulus — the screening of lsr_lwe_verify_rows_device), whatever its coefficient.
+ * Rows with status 0 or -1 are unspecified; their neighbours are unaffected.
+ * Asynchronous on `stream`; uses no workspace of the context and allocates nothing, so a call can be captured into a HIP graph from
+ * the first call on (the status is written by a kernel).  Ordered behind other asynchronous calls on the context exactly as
+ * lsr_lwe_verify_rows_device, and waited for by the synchronous entry points.  Every kind of context is served (FP64, u64, RNS).
+ * lsr_lwe_combine_batch_flat: the same for host arrays, staged in the bounded chunks the flat verify uses (the terms of one output
+ * are never split); returns when the outputs are complete.
+ * NULL context or buffer, terms == 0, terms >= 2^32, outputs >= 2^31, a term_stride whose row count overflows: -1 and a message
+ * naming the entry point in lsr_last_error, before any device work.  outputs == 0: no-op, 0.  Otherwise 0 / -1.
+ * The FP64 kernel canonicalises its accumulators every LSR_COMBINE_TERMS terms; a workgroup serves LSR_COMBINE_OUTPUTS outputs. */
+#define LSR_COMBINE_TERMS 32
+#define LSR_COMBINE_OUTPUTS 8
+int lsr_lwe_combine_rows_device(const LweContext* ctx, const uint64_t* d_rows, size_t terms, size_t term_stride,
+                                const uint64_t* d_coeffs, size_t outputs, uint64_t* d_out_rows, int* d_status, void* stream) LSR_NOEXCEPT;
+int lsr_lwe_combine_batch_flat(const LweContext* ctx, const uint64_t* rows, size_t terms, size_t term_stride,
+                               const uint64_t* coeffs, size_t outputs, uint64_t* out_rows, int* status) LSR_NOEXCEPT;
+
 /* `count` openings in one device pass.  messages = [count][msg_len]; results[i] = 1 / 0 / -1 with the meaning of
  * lwe_verify_opening (cpp-core/src/commitment.cpp:200-232) for (commitments[i], messages[i]); NULL entries => -1.
  * Returns 0, or -1 if the call itself failed. */

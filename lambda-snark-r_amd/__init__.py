@@ -5,6 +5,8 @@ C-ABI are mirrored here in Python with the same names, argument meaning and erro
 
 * ``LweContext``  <-> rust-api/lambda-snark/src/context.rs:14-76   (``LweContext::new`` -> ``lwe_context_create``)
 * ``Commitment``  <-> rust-api/lambda-snark/src/commitment.rs:31-121 (``new``, ``clone``, ``linear_combine``, ``as_bytes``)
+* ``LweContext.combine_rows_device`` / ``LweContext.combine_rows`` <-> ``Commitment::linear_combine`` (commitment.rs:48-84) for a
+  batch of device-resident (or host) wire rows: ``lsr_lwe_combine_rows_device`` / ``lsr_lwe_combine_batch_flat``
 * ``verify_opening_with_context`` <-> rust-api/lambda-snark/src/opening.rs:160-222
 * ``NttContext``  <-> the ``ntt_*`` symbols (only exercised by cpp-core/tests/test_ntt.cpp in the reference)
 * ``CyclicNtt`` / ``QuotientPlan`` <-> rust-api/lambda-snark/src/ntt.rs:117-233 and r1cs.rs:474-506 (prover path)
@@ -281,6 +283,31 @@ class LweContext:
                                                bits.ctypes.data if noise else None) != 0:
             raise CoreError("DecodeFailed: " + _abi.last_error())
         return (messages, status, bits) if noise else (messages, status)
+
+    def combine_rows_device(self, d_rows, terms, d_coeffs, outputs, d_out_rows, d_status, term_stride=0, stream=None):
+        """``lsr_lwe_combine_rows_device``: device pointers (ints) in; out_j = sum_i c'_{j,i} row[j * term_stride + i] for j < outputs
+        and int32 status (1 combined / 0 over the noise budget / -1 a malformed term row) out; asynchronous on `stream`."""
+        if self._lib.lsr_lwe_combine_rows_device(self._h, d_rows, terms, term_stride, d_coeffs, outputs, d_out_rows, d_status, stream) != 0:
+            raise CoreError("CombineFailed: " + _abi.last_error())
+
+    def combine_rows(self, rows, coeffs, term_stride=0):
+        """``lsr_lwe_combine_batch_flat``: rows [(outputs - 1) * term_stride + terms][words] and coeffs [outputs][terms] (host) ->
+        (out_rows [outputs][words], status [outputs])."""
+        rows = _u64_array(rows, "rows")
+        coeffs = _u64_array(coeffs, "coeffs")
+        if rows.ndim != 2 or rows.shape[1] != self.commitment_words:
+            raise ValueError("rows must be [count][commitment_words]")
+        if coeffs.ndim != 2:
+            raise ValueError("coeffs must be [outputs][terms]")
+        outputs, terms = coeffs.shape
+        if outputs and rows.shape[0] != (outputs - 1) * int(term_stride) + terms:
+            raise ValueError("rows must hold (outputs - 1) * term_stride + terms rows")
+        out = np.zeros((outputs, rows.shape[1]), dtype=np.uint64)
+        status = np.zeros(outputs, dtype=np.int32)
+        if self._lib.lsr_lwe_combine_batch_flat(self._h, rows.ctypes.data, terms, int(term_stride), coeffs.ctypes.data, outputs, out.ctypes.data,
+                                                status.ctypes.data) != 0:
+            raise CoreError("CombineFailed: " + _abi.last_error())
+        return out, status
 
     def public_matrix(self):
         k, n = self.module_rank, self.ring_degree

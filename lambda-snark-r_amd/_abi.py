@@ -58,6 +58,10 @@ class R1CSWitness(ctypes.Structure):
 
 
 PROFILE_SCALAR_A = 0
+# batch.h LSR_COMBINE_TERMS / LSR_COMBINE_OUTPUTS: the combine kernel canonicalises its FP64 accumulators every COMBINE_TERMS terms,
+# and a workgroup serves COMBINE_OUTPUTS outputs
+COMBINE_TERMS = 32
+COMBINE_OUTPUTS = 8
 PROFILE_RING_B = 1
 
 # every symbol declared in include/lambda_snark/*.h: name -> (restype, argtypes)
@@ -139,6 +143,8 @@ SIGNATURES = {
     "lsr_lwe_decode_batch_flat": (c_int, [vp, vp, c_size, c_size, vp, vp, vp]),
     "lsr_lwe_decode": (c_int, [vp, ctypes.POINTER(LweCommitment), vp, c_size, vp]),
     "lsr_lwe_noise_capacity_bits": (u32, [vp]),
+    "lsr_lwe_combine_rows_device": (c_int, [vp, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
+    "lsr_lwe_combine_batch_flat": (c_int, [vp, vp, c_size, c_size, vp, c_size, vp, vp]),
     "lsr_lwe_wide_modulus": (ctypes.c_uint64, [ctypes.c_uint32]),
     "lsr_lwe_context_create_rns": (vp, [ctypes.POINTER(PublicParams), u64, c_int]),
     "lsr_lwe_rns_moduli": (c_int, [vp, vp]),

@@ -30,6 +30,7 @@
 #include "lsr_commit_kernels.hpp"
 #include "lsr_commit_tile.hpp"
 #include "lsr_commit_rns.hpp"
+#include "lsr_commit_combine.hpp"
 #include "lsr_commit_keys.hpp"
 #include "lsr_keys.hpp"
 #include "lsr_runtime.hpp"
@@ -1539,6 +1540,90 @@ static LweCommitment* linear_combine(const LweContext& c, const LweCommitment** 
     return out;
 }
 
+// ---- batched, device-resident combination (lsr_commit_combine.hpp) ----------------------------------------------------
+// The largest integer weight sum |c'_i| that the comparison of linear_combine / linear_combine_rns above accepts on this context.  Both
+// comparisons are monotone in the weight, and the weights in question (< 2^32 * t/2 < 2^53) are exact in either floating type, so the
+// kernel's exact integer `weight <= max` decides what the host loop decides.
+static_assert(kCombineTerms == LSR_COMBINE_TERMS && kCombineOutputs == LSR_COMBINE_OUTPUTS, "batch.h states the kernel's tile");
+template <typename Real>
+static uint64_t largest_accepted_weight(Real unit, Real bound) {
+    constexpr uint64_t cap = 1ull << 62;
+    const auto accepted = [&](uint64_t w) { return !(static_cast<Real>(w) * unit >= bound); };
+    const Real guess = bound / unit;
+    uint64_t w = guess >= static_cast<Real>(cap) ? cap : static_cast<uint64_t>(guess);
+    while (w < cap && accepted(w + 1)) ++w;
+    while (w > 0 && !accepted(w)) --w;
+    return w;
+}
+static uint64_t combine_max_weight(const LweContext& c) {
+    if (c.rns)
+        return largest_accepted_weight<long double>((long double)c.noise_unit + 1.0L,
+                                                    (long double)c.rc.q[0] * (long double)c.rc.q[1] / (2.0L * (long double)c.t));
+    return largest_accepted_weight<double>(c.noise_unit + 1.0, 0.5 * static_cast<double>(c.delta));
+}
+
+// enqueued on `s`, no workspace, nothing allocated (caller holds c.mutex): the prologue (header screening, budget, status, output
+// headers), then the body tiles
+static void combine_rows_device(const LweContext& c, const uint64_t* d_rows, size_t terms, size_t term_stride, const uint64_t* d_coeffs, size_t outputs,
+                                uint64_t* d_out, int* d_status, hipStream_t s) {
+    CombineJob job{};
+    job.rows = d_rows; job.coeffs = d_coeffs; job.out = d_out; job.status = d_status;
+    job.terms = terms; job.term_stride = term_stride; job.outputs = outputs;
+    job.row_words = row_words(c);
+    job.header_words = (uint32_t)header_words(c);
+    job.body_words = (uint32_t)body_words(c);
+    job.block_words = (uint32_t)(((size_t)c.k + 1) * c.n);
+    const uint64_t shape = (uint64_t)c.n | ((uint64_t)c.k << 32);
+    for (uint32_t w = 0; w < job.header_words; ++w)
+        job.header[w] = c.rns ? rns_header_word(w, job.row_words, shape, c.rc)
+                              : (w == 0 ? 8ull * (job.row_words - 1) : (w == 1 ? kWireMagic : (w == 2 ? shape : (w == 3 ? c.q : c.t))));
+    job.t = c.t;
+    job.max_weight = combine_max_weight(c);
+    job.plain = make_plain_scale(c.q, c.t);
+    const ModParams p0 = c.ntt->mod, p1 = c.rns ? c.sib->ntt->mod : c.ntt->mod;
+    hipLaunchKernelGGL(combine_prologue_kernel, dim3((unsigned)outputs), dim3(256), 0, s, job);
+    // output tiles on x (neighbouring workgroups share their term words when term_stride == 0), word tiles on y (at most 2^15)
+    const dim3 grid((unsigned)((outputs + kCombineOutputs - 1) / kCombineOutputs), (job.body_words + kCombineThreads - 1) / kCombineThreads);
+    const bool f64 = c.ntt->use_f64 && (!c.rns || c.sib->ntt->use_f64), shared = term_stride == 0;
+    if (f64) {
+        if (shared) hipLaunchKernelGGL((combine_body_kernel<true, true>), grid, dim3(kCombineThreads), 0, s, job, p0, p1);
+        else hipLaunchKernelGGL((combine_body_kernel<true, false>), grid, dim3(kCombineThreads), 0, s, job, p0, p1);
+    } else {
+        if (shared) hipLaunchKernelGGL((combine_body_kernel<false, true>), grid, dim3(kCombineThreads), 0, s, job, p0, p1);
+        else hipLaunchKernelGGL((combine_body_kernel<false, false>), grid, dim3(kCombineThreads), 0, s, job, p0, p1);
+    }
+    LSR_HIP(hipGetLastError());
+}
+
+// host arrays: outputs are staged `now` at a time so that the term rows and output rows of a pass stay within the rows of one
+// verify_chunk() pass and its coefficients within 1 GiB (one output is never split: its terms go up whole)
+static void combine_host_rows(const LweContext& c, const uint64_t* rows, size_t terms, size_t term_stride, const uint64_t* coeffs, size_t outputs,
+                              uint64_t* out_rows, int* status, hipStream_t s) {
+    const size_t row = row_words(c);
+    const size_t cap = verify_chunk(c, ~size_t(0));
+    size_t chunk = 1;
+    if (outputs > 1 && terms + 1 < cap) chunk = std::max<size_t>(1, (cap - terms + term_stride) / (term_stride + 1));
+    chunk = std::min(chunk, std::max<size_t>(1, (size_t(1) << 27) / terms));
+    chunk = std::min(chunk, outputs);
+    const size_t term_rows = (chunk - 1) * term_stride + terms;
+    c.ws_rows.reserve((term_rows + chunk) * row);
+    c.ws_dm.reserve(chunk * terms);
+    c.ws_vflags.reserve((chunk + 1) / 2);
+    uint64_t* const d_terms = c.ws_rows.ptr;
+    uint64_t* const d_out = c.ws_rows.ptr + term_rows * row;
+    int* const d_status = reinterpret_cast<int*>(c.ws_vflags.ptr);
+    for (size_t first = 0; first < outputs; first += chunk) {
+        const size_t now = std::min(chunk, outputs - first);
+        if (first == 0 || term_stride != 0)      // shared terms go up once
+            LSR_HIP(hipMemcpyAsync(d_terms, rows + first * term_stride * row, ((now - 1) * term_stride + terms) * row * 8, hipMemcpyHostToDevice, s));
+        LSR_HIP(hipMemcpyAsync(c.ws_dm.ptr, coeffs + first * terms, now * terms * 8, hipMemcpyHostToDevice, s));
+        combine_rows_device(c, d_terms, terms, term_stride, c.ws_dm.ptr, now, d_out, d_status, s);
+        LSR_HIP(hipMemcpyAsync(out_rows + first * row, d_out, now * row * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(status + first, d_status, now * sizeof(int), hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
 }  // namespace lsr
 
 // one host thread per shard; body(g, first, count) runs with the shard's device current
@@ -1931,6 +2016,61 @@ int lsr_lwe_decode(const LweContext* ctx, const LweCommitment* cm, uint64_t* mes
         return status;
     } catch (const std::exception& e) {
         lsr::set_last_error(std::string("lsr_lwe_decode: ") + e.what());
+        return -1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+// argument screening shared by the combining entry points: false (and a message) for what is refused before any device work
+static bool combine_arguments_ok(const char* where, const LweContext* ctx, const void* rows, size_t terms, size_t term_stride, const void* coeffs,
+                                 size_t outputs, const void* out_rows, const void* status) {
+    const char* why = nullptr;
+    size_t span = 0, total = 0, bytes = 0;
+    if (!ctx) why = "NULL context (no context exists without a HIP device)";
+    else if (!rows || !coeffs || !out_rows || !status) why = "NULL buffer";
+    else if (terms == 0) why = "terms must be at least 1";
+    else if (terms >= (1ull << 32)) why = "terms must stay below 2^32 (the weight sum is kept in 64 bits)";
+    else if (outputs > 0x7fffffffull) why = "outputs exceed one launch (2^31 - 1 rows)";
+    else if (outputs > 1 && (__builtin_mul_overflow(outputs - 1, term_stride, &span) || __builtin_add_overflow(span, terms, &total) ||
+                             __builtin_mul_overflow(total, lsr::row_words(*ctx) * 8, &bytes)))
+        why = "term_stride overflows the row count";
+    if (why) lsr::set_last_error(std::string(where) + ": " + why);
+    return why == nullptr;
+}
+
+int lsr_lwe_combine_rows_device(const LweContext* ctx, const uint64_t* d_rows, size_t terms, size_t term_stride, const uint64_t* d_coeffs, size_t outputs,
+                                uint64_t* d_out_rows, int* d_status, void* stream) noexcept {
+    if (!combine_arguments_ok("lsr_lwe_combine_rows_device", ctx, d_rows, terms, term_stride, d_coeffs, outputs, d_out_rows, d_status)) return -1;
+    if (outputs == 0) return 0;
+    try {
+        lsr::DeviceGuard guard(ctx->device);
+        std::lock_guard<std::mutex> lock(ctx->mutex);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        lsr::begin_async(*ctx, s);
+        lsr::combine_rows_device(*ctx, d_rows, terms, term_stride, d_coeffs, outputs, d_out_rows, d_status, s);
+        lsr::end_async(*ctx, s);
+        return 0;
+    } catch (const std::exception& e) {
+        lsr::set_last_error(std::string("lsr_lwe_combine_rows_device: ") + e.what());
+        return -1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int lsr_lwe_combine_batch_flat(const LweContext* ctx, const uint64_t* rows, size_t terms, size_t term_stride, const uint64_t* coeffs, size_t outputs,
+                               uint64_t* out_rows, int* status) noexcept {
+    if (!combine_arguments_ok("lsr_lwe_combine_batch_flat", ctx, rows, terms, term_stride, coeffs, outputs, out_rows, status)) return -1;
+    if (outputs == 0) return 0;
+    try {
+        lsr::DeviceGuard guard(ctx->device);
+        std::lock_guard<std::mutex> lock(ctx->mutex);
+        lsr::wait_for_async(*ctx);
+        lsr::combine_host_rows(*ctx, rows, terms, term_stride, coeffs, outputs, out_rows, status, lsr::work_stream(*ctx->ntt));
+        return 0;
+    } catch (const std::exception& e) {
+        lsr::set_last_error(std::string("lsr_lwe_combine_batch_flat: ") + e.what());
         return -1;
     } catch (...) {
         return -1;
