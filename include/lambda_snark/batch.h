@@ -75,6 +75,37 @@ int lsr_ntt_ring_mul_batch(const NttContext* ctx, uint64_t* c, const uint64_t* a
 int lsr_ntt_ring_mul_batch_device(const NttContext* ctx, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b,
                                   size_t batch, size_t b_rows, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: batched ring inner product ---------------- */
+/* c_j = sum_{i < terms} a_{j,i} * b_{j,i} in the ring of the context (as lsr_ntt_ring_mul_batch: X^n + 1 on negacyclic contexts,
+ * X^n - 1 on cyclic ones): a row of A s, <b, r>, a long product split into blocks.  Natural coefficient order in and out, inputs
+ * in [0,q), outputs canonical.  a: [batch][terms][n]; b: [b_rows][terms][n] with b_rows == batch (one vector b per output) or
+ * b_rows == 1 (the same vector b for every output); c: [batch][n].  terms == 1 gives lsr_ntt_ring_mul_batch's output word for word.
+ * The products are summed in registers and the inverse transform runs once per output: one fused pass at n <= 4096 (16 terms + 8
+ * bytes of memory traffic per output residue, 8 terms + 8 with a shared b), three passes per chunk above.
+ *
+ * Refusals (-1 and lsr_last_error, before any device work), in this order: NULL context or buffer; b_rows not in {1, batch};
+ * terms == 0.  Then batch == 0 is a no-op that returns 0.  Then: a context above n = 131072; terms above LSR_RING_DOT_MAX_TERMS
+ * (the terms of one output tile are addressed through one 32-bit buffer range); c overlapping a or b in address range (the output
+ * has another shape than the operands: there is no aliasing form); no visible device.
+ *
+ * lsr_ntt_ring_dot_batch: host buffers, staged through bounded device chunks; returns when c is complete.
+ * lsr_ntt_ring_dot_batch_device: device buffers on the context's device, asynchronous on `stream` (enqueues only).
+ *
+ * Workspace, ordering and graph capture: the contract of lsr_ntt_ring_mul_batch above.  n > 4096, and b_rows == 1 with batch > 1, use
+ * a workspace owned by the context whose size depends on n alone (never on batch or terms: the batch and, where they do not fit, the
+ * terms are taken in chunks); the first eager call that needs it allocates it, it is never resized, a capturing call that would have
+ * to allocate it returns -1.  Calls on one context are ordered by the same event as its ring multiplies, so the two kinds are
+ * ordered against each other too; ntt_context_free waits for pending work.
+ *
+ * FP64-flavour contexts (q < 2^45) re-centre the running sum every LSR_RING_DOT_F64_RECENTRE_PERIOD products, which keeps it an
+ * exact integer in a double for any number of terms. */
+#define LSR_RING_DOT_MAX_TERMS 65536
+#define LSR_RING_DOT_F64_RECENTRE_PERIOD 32
+int lsr_ntt_ring_dot_batch(const NttContext* ctx, uint64_t* c, const uint64_t* a, const uint64_t* b,
+                           size_t batch, size_t terms, size_t b_rows) LSR_NOEXCEPT;
+int lsr_ntt_ring_dot_batch_device(const NttContext* ctx, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b,
+                                  size_t batch, size_t terms, size_t b_rows, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

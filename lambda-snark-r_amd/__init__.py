@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -55,6 +55,35 @@ def _ring_mul(lib, handle, n, a, b):
 def _ring_mul_device(lib, handle, d_c, d_a, d_b, batch, b_rows, stream):
     if lib.lsr_ntt_ring_mul_batch_device(handle, d_c, d_a, d_b, batch, b_rows, stream) != 0:
         raise CoreError("lsr_ntt_ring_mul_batch_device failed: " + _abi.last_error())
+
+
+# FP64-flavour contexts re-centre the running sum of a ring inner product after this many products (batch.h
+# LSR_RING_DOT_F64_RECENTRE_PERIOD); the largest number of terms is LSR_RING_DOT_MAX_TERMS
+RING_DOT_F64_RECENTRE_PERIOD = 32
+RING_DOT_MAX_TERMS = 65536
+
+
+def _ring_dot(lib, handle, n, a, b):
+    """c = sum_i a_i * b_i in the context's ring (host arrays): a is [terms, n] (one output) or [batch, terms, n]; b is [terms, n] (one
+    vector b for every output) or [batch, terms, n].  Returns [n] for a 2-d a, else [batch, n]."""
+    a_in = _u64_array(a)
+    if a_in.ndim < 2 or a_in.shape[-1] != n:
+        raise ValueError("a must be [terms, n] or [batch, terms, n]")
+    terms = a_in.shape[-2]
+    if terms == 0:
+        raise ValueError("terms must be at least 1")
+    a3 = np.ascontiguousarray(a_in.reshape(-1, terms, n))
+    b3 = np.ascontiguousarray(_u64_array(b).reshape(-1, terms, n))
+    batch, b_rows = a3.shape[0], b3.shape[0]
+    out = np.empty((batch, n), dtype=np.uint64)
+    if lib.lsr_ntt_ring_dot_batch(handle, out.ctypes.data, a3.ctypes.data, b3.ctypes.data, batch, terms, b_rows) != 0:
+        raise CoreError("lsr_ntt_ring_dot_batch failed: " + _abi.last_error())
+    return out[0] if a_in.ndim == 2 else out
+
+
+def _ring_dot_device(lib, handle, d_c, d_a, d_b, batch, terms, b_rows, stream):
+    if lib.lsr_ntt_ring_dot_batch_device(handle, d_c, d_a, d_b, batch, terms, b_rows, stream) != 0:
+        raise CoreError("lsr_ntt_ring_dot_batch_device failed: " + _abi.last_error())
 
 
 class NttContext:
@@ -145,6 +174,16 @@ class NttContext:
     def ring_mul_device(self, d_c, d_a, d_b, batch, b_rows, stream=0):
         """Device buffers [batch][n] (b: [b_rows][n], b_rows 1 or batch), asynchronous on `stream`."""
         _ring_mul_device(self._lib, self._h, d_c, d_a, d_b, batch, b_rows, stream)
+
+    # --- ring inner product in Z_q[X]/(X^n + 1) ---
+    def ring_dot(self, a, b):
+        """sum_i a_i * b_i mod (X^n + 1, q): a is [terms, n] or [batch, terms, n], b is [terms, n] (shared by every output) or
+        [batch, terms, n]; numpy in and out ([n] or [batch, n])."""
+        return _ring_dot(self._lib, self._h, self.n, a, b)
+
+    def ring_dot_device(self, d_c, d_a, d_b, batch, terms, b_rows, stream=0):
+        """Device buffers: c [batch][n], a [batch][terms][n], b [b_rows][terms][n] (b_rows 1 or batch), asynchronous on `stream`."""
+        _ring_dot_device(self._lib, self._h, d_c, d_a, d_b, batch, terms, b_rows, stream)
 
 
 class Params:
@@ -648,6 +687,13 @@ class CyclicNtt:
 
     def ring_mul_device(self, d_c, d_a, d_b, batch, b_rows, stream=0):
         _ring_mul_device(self._lib, self._h, d_c, d_a, d_b, batch, b_rows, stream)
+
+    def ring_dot(self, a, b):
+        """Sum of cyclic convolutions sum_i a_i * b_i mod (X^n - 1, modulus); shapes as NttContext.ring_dot."""
+        return _ring_dot(self._lib, self._h, self.n, a, b)
+
+    def ring_dot_device(self, d_c, d_a, d_b, batch, terms, b_rows, stream=0):
+        _ring_dot_device(self._lib, self._h, d_c, d_a, d_b, batch, terms, b_rows, stream)
 
     def close(self):
         if self._h:

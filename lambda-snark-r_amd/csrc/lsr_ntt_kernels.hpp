@@ -649,6 +649,228 @@ __global__ void __launch_bounds__(kThreads) ntt_tile_ring_mul(uint64_t* c, const
     });
 }
 
+// ---- ring inner product c = sum_i a_i b_i in the tile (lsr_ring_dot.hip) ------------------------------
+// ntt_tile_ring_mul with a loop over the terms around its forward half: per term the forward rounds of the tile of a_i, the
+// forward rounds of the tile of b_i (or b-hat_i read at the last-round positions), the product added into a register accumulator
+// that sits at the last-forward / first-inverse mapping; after the last term the inverse rounds run from the accumulator.
+//
+// Operand addressing.  The words of term i that belong to ONE output are n contiguous words; consecutive outputs' term-i polynomials
+// are `os` words apart (os = terms n for a [batch][terms][n] operand).  n = 4096 and MID: the tile is one run of 4096 words.  n < 4096
+// (kStrided): tile index idx = output (idx >> LT) | coefficient (idx & (n - 1)) lies at (idx & (n - 1)) + (idx >> LT) os.  Every
+// mapping writes idx as lane part | register part over disjoint bits, so both terms split into one lane offset plus one
+// workgroup-uniform register offset, as in the contiguous kernels.
+// Accumulator contract: F64 — a product is |r| <= 0.875 q, the accumulator is re-centred to |acc| <= q/2 + 1 after
+// every kRingDotF64Period products and after the last one, so |acc| <= (0.5 + 0.875 * 32) q + 1 < 29 q < 2^50: every sum is an exact
+// integer in a double and inside recentre_f64's domain, and the inverse rounds receive |x| <= q/2 + 1 <= 2 q.  U64: canonical
+// products, one conditional subtraction per addition (sums stay below 2 q < 2^62).  Goldilocks: gold_add.
+constexpr uint32_t kRingDotF64Period = 32;
+constexpr uint32_t kRingDotFirst = 1u, kRingDotLast = 2u;
+constexpr uint32_t kRingDotOutOfRange = 0x80000000u;   // a lane offset beyond every operand range (ranges stay below 2^31 bytes)
+
+template <class A> __device__ __forceinline__ typename A::elem ring_accumulate(typename A::elem acc, typename A::elem r, const ModParams& p);
+template <> __device__ __forceinline__ double ring_accumulate<ArithF64>(double acc, double r, const ModParams&) { return acc + r; }
+template <> __device__ __forceinline__ uint64_t ring_accumulate<ArithU64>(uint64_t acc, uint64_t r, const ModParams& p) {
+    const uint64_t s = acc + r;
+    return s >= p.q ? s - p.q : s;
+}
+template <> __device__ __forceinline__ uint64_t ring_accumulate<ArithGold>(uint64_t acc, uint64_t r, const ModParams&) { return gold_add(acc, r); }
+
+// ring_forward_tile with the operand words fetched by `load(k)` (the raw word of register k in round 0's mapping) instead of read from
+// one contiguous tile.
+template <class A, int LT, bool RAW, int S, bool PRELOADED, class Load, class After>
+__device__ __forceinline__ void ring_forward_tile_from(typename A::elem (&v)[kRegs], typename A::twid (&w)[2][kRoundTwiddles], uint64_t* lds, Load&& load,
+                                                       rsrc_t table, uint32_t block_pos, uint32_t nmask, const ModParams& p, After&& after) {
+    constexpr int NR = TileRound<LT, 0>::kCount;
+    const uint32_t t = threadIdx.x;
+    {
+        constexpr int LO = TileRound<LT, 0>::LO, R = TileRound<LT, 0>::R;
+        uint64_t raw[kRegs];
+#pragma unroll
+        for (int k = 0; k < kRegs; ++k) raw[k] = load(k);
+        if constexpr (!PRELOADED) load_round_twiddles<A, LO, R, false, false>(w[S & 1], lane_base<LO, R>(t), block_pos, nmask, p.logn, table);
+#pragma unroll
+        for (int k = 0; k < kRegs; ++k) v[k] = RAW ? elem_from_bits<A>(raw[k]) : A::load(raw[k], p);
+    }
+    static_for<0, NR>([&](auto ic) {
+        constexpr int I = decltype(ic)::value;
+        constexpr int LO = TileRound<LT, I>::LO, R = TileRound<LT, I>::R;
+        if constexpr (I + 1 < NR) {
+            constexpr int LO1 = TileRound<LT, I + 1>::LO, R1 = TileRound<LT, I + 1>::R;
+            load_round_twiddles<A, LO1, R1, false, false>(w[(S + I + 1) & 1], lane_base<LO1, R1>(t), block_pos, nmask, p.logn, table);
+        } else {
+            after(w[(S + NR) & 1]);
+        }
+        forward_round<A, LO, R, I == 0 && !RAW && (LO + R == LT)>(v, w[(S + I) & 1], p);
+        if constexpr (I + 1 < NR) {
+            uint64_t* const row = lds + lds_slot(lane_base<LO, R>(t));
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) row[lds_slot(reg_offset<LO, R>(k))] = elem_bits<A>(v[k]);
+            __syncthreads();
+            constexpr int LO1 = TileRound<LT, I + 1>::LO, R1 = TileRound<LT, I + 1>::R;
+            const uint64_t* const row1 = lds + lds_slot(lane_base<LO1, R1>(t));
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) v[k] = elem_from_bits<A>(row1[lds_slot(reg_offset<LO1, R1>(k))]);
+        }
+    });
+}
+
+// c: [outputs][n], `total` words.  a: term i of output j at a + j a_os + i n; b likewise with b_os — or, BHAT, the transforms of the
+// `nterms` polynomials of ONE shared b ([nterms][n], canonical, the order launch_ntt writes).  MID: a and b hold raw elements left
+// by the strided forward rounds, c receives raw elements for the strided inverse round.
+// flags: kRingDotFirst — the accumulator starts at zero (else: at the raw accumulator an earlier launch left in c);
+//        kRingDotLast  — inverse rounds and the final store (else: the re-centred raw accumulator goes to c at the last-round positions
+//                        for the launch that takes the next terms).  A launch sequence over groups of terms keeps its tiling, so every
+//                        workgroup reads back what it wrote itself.
+template <class A, int LT, bool MID, bool BHAT>
+__global__ void __launch_bounds__(kThreads) ntt_tile_ring_dot(uint64_t* c, const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, size_t total,
+                                                                uint32_t nterms, size_t a_os, size_t b_os, uint32_t flags, ModParams p,
+                                                                const typename A::twid* __restrict__ fwd, const typename A::twid* __restrict__ inv,
+                                                                RoundConsts<A> cs) {
+    __shared__ uint64_t lds[kLdsWords];
+    using elem = typename A::elem;
+    using twid = typename A::twid;
+    constexpr int NR = TileRound<LT, 0>::kCount;
+    constexpr int LO0 = TileRound<LT, 0>::LO, R0 = TileRound<LT, 0>::R;               // the mapping the operands are read in
+    constexpr int LOL = TileRound<LT, NR - 1>::LO, RL = TileRound<LT, NR - 1>::R;    // the shared last-forward / first-inverse mapping
+    constexpr bool kStrided = !MID && LT < kTileLog;                                 // several outputs per tile
+    constexpr uint32_t kMask = kStrided ? (1u << LT) - 1u : 0xFFFFFFFFu;
+    const uint32_t t = threadIdx.x;
+    const size_t tile_base = (size_t)blockIdx.x * kTile;
+    const uint32_t n = 1u << p.logn;
+    const uint32_t nmask = n - 1u;
+    const uint32_t block_pos = (uint32_t)(tile_base & nmask);
+    const size_t left = total - tile_base;
+    const uint32_t tile_words = left >= kTile ? kTile : (uint32_t)left;
+    const size_t first_output = tile_base >> p.logn;
+    const uint32_t outputs = kStrided ? tile_words >> LT : 1u;                        // (total is a multiple of n)
+    const rsrc_t out = make_rsrc(c + tile_base, tile_words * 8u);
+    const rsrc_t ftab = make_rsrc(fwd, (uint32_t)sizeof(twid) << p.logn);
+    const rsrc_t itab = make_rsrc(inv, (uint32_t)sizeof(twid) << p.logn);
+    const uint32_t lbase = lane_base<LOL, RL>(t);
+    const uint32_t base0 = lane_base<LO0, R0>(t);
+
+    // byte offset of tile index part `idx` (a lane part or a register part) in an operand whose outputs are `os` words apart
+    auto operand_bytes = [&](uint32_t idx, uint32_t os) -> uint32_t {
+        return kStrided ? ((idx & kMask) + (idx >> LT) * os) * 8u : idx * 8u;
+    };
+    // Word k of round 0 from the operand tile at `tile` (os: as above).  A partial last tile (fewer than 4096 / n outputs) is clipped
+    // twice: by the range of the buffer resource, and — the outputs being far apart — by an out-of-range lane offset for every word
+    // of an output the tile does not have.
+    auto operand_words = [&](uint32_t os) -> uint32_t { return kStrided ? (outputs - 1u) * os + n : tile_words; };
+    auto operand_word = [&](rsrc_t r, uint32_t os, int k) -> uint64_t {
+        const uint32_t reg = reg_offset<LO0, R0>(k);
+        const bool present = !kStrided || (base0 >> LT) + (reg >> LT) < outputs;
+        return buf_load64<MID ? 0 : kAuxStream>(r, present ? operand_bytes(base0, os) : kRingDotOutOfRange, operand_bytes(reg, os));
+    };
+    const uint32_t a_step = (uint32_t)a_os, b_step = (uint32_t)b_os;                  // used when kStrided only: terms n <= 2^27 there
+    // first inverse round's twiddles; SKIP_TOP when that round is also the transform's last stage
+    auto inverse_first = [&](twid (&slot)[kRoundTwiddles]) {
+        load_round_twiddles<A, LOL, RL, true, (NR == 1) && !MID>(slot, lbase, block_pos, nmask, p.logn, itab);
+    };
+    const uint64_t* a_tile = a + first_output * a_os + block_pos;
+    const uint64_t* b_tile = BHAT ? b : b + first_output * b_os + block_pos;
+
+    elem v[kRegs], acc[kRegs];
+    twid w[2][kRoundTwiddles];
+    constexpr int S1 = BHAT ? NR & 1 : 0;   // twiddle slot of the first inverse round: (S + NR) & 1 of the last forward transform
+    if (flags & kRingDotFirst) {
+#pragma unroll
+        for (int k = 0; k < kRegs; ++k) acc[k] = elem_from_bits<A>(0);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kRegs; ++k) acc[k] = elem_from_bits<A>(buf_load64(out, lbase * 8u, reg_offset<LOL, RL>(k) * 8u));
+    }
+
+    for (uint32_t i = 0; i < nterms; ++i, a_tile += n, b_tile += n) {
+        const bool last_term = i + 1 == nterms;
+        if constexpr (NR > 1) {
+            if (i) __syncthreads();                  // the previous term's last LDS reads before this term's first LDS writes
+        }
+        const rsrc_t ra = make_rsrc(a_tile, operand_words(a_step) * 8u);
+        if constexpr (BHAT) {
+            ring_forward_tile_from<A, LT, MID, 0, false>(v, w, lds, [&](int k) { return operand_word(ra, a_step, k); }, ftab, block_pos, nmask, p,
+                                                         [&](twid (&slot)[kRoundTwiddles]) {
+                                                             if (last_term) inverse_first(slot);
+                                                         });
+            // b-hat_i at this lane's last-round positions within the polynomial
+            const rsrc_t rb = make_rsrc(b_tile, 8u << p.logn);
+            const uint32_t lane_off = MID ? block_pos + lbase : (lbase & kMask);
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) {
+                const elem bh = A::load(buf_load64(rb, lane_off * 8u, (reg_offset<LOL, RL>(k) & kMask) * 8u), p);
+                acc[k] = ring_accumulate<A>(acc[k], ring_product<A>(v[k], bh, p), p);
+            }
+        } else {
+            elem ah[kRegs];
+            // a's last round prefetches b's first-round twiddles (round 0 of the same table) into the free slot
+            ring_forward_tile_from<A, LT, MID, 0, false>(v, w, lds, [&](int k) { return operand_word(ra, a_step, k); }, ftab, block_pos, nmask, p,
+                                                         [&](twid (&slot)[kRoundTwiddles]) {
+                                                             load_round_twiddles<A, LO0, R0, false, false>(slot, base0, block_pos, nmask, p.logn, ftab);
+                                                         });
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) ah[k] = v[k];
+            if constexpr (NR > 1) __syncthreads();   // a's last LDS reads before b's first LDS writes
+            const rsrc_t rb = make_rsrc(b_tile, operand_words(b_step) * 8u);
+            ring_forward_tile_from<A, LT, MID, NR & 1, true>(v, w, lds, [&](int k) { return operand_word(rb, b_step, k); }, ftab, block_pos, nmask, p,
+                                                             [&](twid (&slot)[kRoundTwiddles]) {
+                                                                 if (last_term) inverse_first(slot);
+                                                             });
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) acc[k] = ring_accumulate<A>(acc[k], ring_product<A>(ah[k], v[k], p), p);
+        }
+        if constexpr (std::is_same_v<A, ArithF64>) {
+            if ((i & (kRingDotF64Period - 1u)) == kRingDotF64Period - 1u || last_term) {
+#pragma unroll
+                for (int k = 0; k < kRegs; ++k) acc[k] = recentre_f64(acc[k], p.qd, p.inv_qd);
+            }
+        }
+    }
+
+    if (!(flags & kRingDotLast)) {
+#pragma unroll
+        for (int k = 0; k < kRegs; ++k) buf_store64(out, lbase * 8u, reg_offset<LOL, RL>(k) * 8u, elem_bits<A>(acc[k]));
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < kRegs; ++k) v[k] = acc[k];
+
+    // inverse rounds (ntt_tile_ring_mul's schedule), the first one straight from registers
+    static_for<0, NR>([&](auto ic) {
+        constexpr int I = decltype(ic)::value;
+        constexpr int J = NR - 1 - I;
+        constexpr int LO = TileRound<LT, J>::LO, R = TileRound<LT, J>::R;
+        constexpr bool kLast = (I == NR - 1);
+        constexpr bool kFinal = kLast && !MID;
+        const uint32_t base = lane_base<LO, R>(t);
+        uint64_t* const row = lds + lds_slot(base);
+        if constexpr (I > 0) {
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) v[k] = elem_from_bits<A>(row[lds_slot(reg_offset<LO, R>(k))]);
+        }
+        if constexpr (!kLast) {
+            constexpr int LO1 = TileRound<LT, J - 1>::LO, R1 = TileRound<LT, J - 1>::R;
+            load_round_twiddles<A, LO1, R1, true, (I + 1 == NR - 1) && !MID>(w[(S1 + I + 1) & 1], lane_base<LO1, R1>(t), block_pos, nmask, p.logn, itab);
+        }
+        inverse_round<A, LO, R, kFinal>(v, w[(S1 + I) & 1], p, cs);
+        if constexpr (!kFinal) {
+            constexpr bool kAll = kLast || !A::kPartialRecentre;
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k)
+                if (kAll || A::template needs_recentre<R>(k & ((1 << R) - 1))) A::end_of_inverse_round(v[k], p);
+        }
+        if constexpr (kLast) {
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k)
+                buf_store64<MID ? 0 : kAuxStream>(out, base * 8u, reg_offset<LO, R>(k) * 8u, MID ? elem_bits<A>(v[k]) : A::store_reduced(v[k], p));
+        } else {
+            // (I = 0: these are the slots this lane read in the last forward round — no barrier needed before the store)
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) row[lds_slot(reg_offset<LO, R>(k))] = elem_bits<A>(v[k]);
+            __syncthreads();
+        }
+    });
+}
+
 // ---- strided round kernel (the TOP R index bits: lo + R == log n) ------------------------------------
 // Its butterfly groups are indexed by the polynomial only, so stage j (register bit j) uses the table entries
 // 2^(R-1-j) + u for every lane of every polynomial: compile-time indices, scalar loads, no VGPRs for twiddles.

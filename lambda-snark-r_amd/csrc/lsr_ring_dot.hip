@@ -1,0 +1,228 @@
+// Batched ring inner product c_j = sum_{i < terms} a_{j,i} b_{j,i} in Z_q[X]/(X^n + 1) (negacyclic contexts) or Z_q[X]/(X^n - 1) (cyclic
+// contexts): the rank-`terms` case of lsr_ring_mul.hip, with the products summed in registers and ONE inverse transform per output.
+//   n <= 4096: ONE launch (ntt_tile_ring_dot): per output tile and term both forward transforms, the product added into a register
+//              accumulator; the inverse after the last term — 16 terms + 8 bytes of HBM traffic per output residue.
+//   n > 4096:  per chunk the strided forward rounds of the chunk's a and b terms into the workspace, the tile kernel as middle pass
+//              (reads the raw tiles term by term, accumulates, runs its inverse rounds, writes raw elements to c), one strided inverse
+//              round on c.
+//   b_rows == 1 (one vector b for every output): b is transformed once per call (launch_ntt) into the workspace and the tile kernel
+//              reads b-hat_i at its last-round positions instead of transforming b.
+// The workspace holds a fixed number of polynomials (ring_dot_chunk_polys: a function of n and the process-wide chunk size).  More
+// terms than fit are taken in groups, one launch sequence per group; between groups the raw accumulator waits in c
+// (kRingDotFirst / kRingDotLast, lsr_ntt_kernels.hpp).
+#include <algorithm>
+#include <cstring>
+
+#include "lambda_snark/batch.h"
+#include "lsr_flavour.hpp"
+#include "lsr_ntt_kernels.hpp"
+#include "lsr_runtime.hpp"
+
+static_assert(LSR_RING_DOT_F64_RECENTRE_PERIOD == (int)lsr::kRingDotF64Period, "batch.h documents the kernel's re-centring period");
+
+namespace lsr {
+
+// the terms (and, n <= 4096, terms n words of one output) are addressed through 32-bit buffer offsets: 4096 terms words stay below 2^31 bytes
+static_assert((uint64_t)LSR_RING_DOT_MAX_TERMS * kTile * 8 <= (1ull << 31), "operand ranges of one tile must fit a buffer resource");
+
+struct DotOperands {
+    uint64_t* c;
+    const uint64_t *a, *b;
+    size_t total;        // words of c
+    uint32_t nterms;
+    size_t a_os, b_os;   // words between consecutive outputs' term-i polynomials
+    uint32_t flags;
+};
+
+template <class A, int LT, bool MID, bool BHAT>
+static void dot_tile(const NttContext& c, const DotOperands& o, hipStream_t s) {
+    const unsigned grid = static_cast<unsigned>((o.total + kTile - 1) / kTile);
+    hipLaunchKernelGGL((ntt_tile_ring_dot<A, LT, MID, BHAT>), dim3(grid), dim3(kThreads), 0, s, o.c, o.a, o.b, o.total, o.nterms, o.a_os, o.b_os, o.flags,
+                       c.mod, Flavour<A>::fwd(c), Flavour<A>::inv(c), Flavour<A>::consts(c));
+}
+
+#define LSR_DOT_CASE(LT) case LT: dot_tile<A, LT, MID, BHAT>(c, o, s); break;
+template <class A, bool MID, bool BHAT>
+static void dot_tile_lt(const NttContext& c, int lt, const DotOperands& o, hipStream_t s) {
+    if constexpr (MID) {   // the low lt = log n - 4 (n = 2^17: - 5) bits of a two-pass transform
+        switch (lt) {
+            LSR_DOT_CASE(9) LSR_DOT_CASE(10) LSR_DOT_CASE(11)
+            default: dot_tile<A, 12, MID, BHAT>(c, o, s); break;
+        }
+    } else {
+        switch (lt) {
+            LSR_DOT_CASE(1) LSR_DOT_CASE(2) LSR_DOT_CASE(3) LSR_DOT_CASE(4) LSR_DOT_CASE(5) LSR_DOT_CASE(6)
+            LSR_DOT_CASE(7) LSR_DOT_CASE(8) LSR_DOT_CASE(9) LSR_DOT_CASE(10) LSR_DOT_CASE(11)
+            default: dot_tile<A, 12, MID, BHAT>(c, o, s); break;
+        }
+    }
+}
+#undef LSR_DOT_CASE
+
+// Polynomials per workspace array.  n > 4096: three arrays are live between the passes of a chunk (the transformed a terms, the
+// transformed b terms, the c chunk), so each gets a third of the Infinity Cache budget of a two-pass transform (ntt_chunk_bytes():
+// 256 MiB -> 170 polynomials at n = 2^16).  n <= 4096: the same budget bounds the b-hat rows of a shared b, at most 4096 of them.
+static size_t ring_dot_chunk_polys(const NttContext& c) {
+    const size_t polys = std::max<size_t>(1, (ntt_chunk_bytes() / 3) >> (c.logn + 3));
+    return c.logn > kTileLog ? polys : std::min<size_t>(polys, 4096);
+}
+// Workspace words: n > 4096 — the a terms and the b terms (or b-hat rows) of one chunk; n <= 4096 — the b-hat rows.  A function of n
+// (and of the process-wide chunk size) only, never of the batch or the terms.
+static size_t ring_dot_scratch_words(const NttContext& c) {
+    return (c.logn > kTileLog ? 2 : 1) * ring_dot_chunk_polys(c) * c.degree;
+}
+
+// first / last: this call starts / finishes the sums (the host variant stages long sums in groups of terms, as this function does)
+template <class A>
+static void ring_dot_enqueue(const NttContext& c, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms, bool shared_b,
+                             bool first, bool last, hipStream_t s) {
+    const size_t n = c.degree, polys = ring_dot_chunk_polys(c);
+    uint64_t* const ws = c.ring_dot_scratch.ptr;
+    auto flags_of = [&](size_t i0, size_t group) -> uint32_t {
+        return (first && i0 == 0 ? kRingDotFirst : 0u) | (last && i0 + group == terms ? kRingDotLast : 0u);
+    };
+    if (c.logn <= kTileLog) {
+        if (!shared_b) {
+            dot_tile_lt<A, false, false>(c, c.logn, {d_c, d_a, d_b, batch * n, (uint32_t)terms, terms * n, terms * n, flags_of(0, terms)}, s);
+            return;
+        }
+        for (size_t i0 = 0; i0 < terms; i0 += polys) {
+            const size_t group = std::min(polys, terms - i0);
+            launch_ntt(c, ws, group, false, s, nullptr, nullptr, d_b + i0 * n);
+            dot_tile_lt<A, false, true>(c, c.logn, {d_c, d_a + i0 * n, ws, batch * n, (uint32_t)group, terms * n, 0, flags_of(i0, group)}, s);
+        }
+        return;
+    }
+    const int lt = c.logn - std::max(c.logn - kTileLog, 4);
+    uint64_t* const wa = ws;
+    uint64_t* const wb = ws + polys * n;
+    // all terms fit: chunks of whole outputs; else one output at a time, its terms in groups.  Either way the (output, term)
+    // polynomials of one chunk and group are contiguous in a and b.
+    const size_t group_max = std::min(terms, polys), chunk = group_max == terms ? polys / terms : 1;
+    for (size_t i0 = 0; i0 < terms; i0 += group_max) {
+        const size_t group = std::min(group_max, terms - i0);
+        const uint32_t flags = flags_of(i0, group);
+        if (shared_b) launch_ntt(c, wb, group, false, s, nullptr, nullptr, d_b + i0 * n);
+        for (size_t j0 = 0; j0 < batch; j0 += chunk) {
+            const size_t now = std::min(chunk, batch - j0), off = (j0 * terms + i0) * n;
+            launch_strided_round(c, wa, d_a + off, now * group, false, s);
+            if (!shared_b) launch_strided_round(c, wb, d_b + off, now * group, false, s);
+            const DotOperands o{d_c + j0 * n, wa, wb, now * n, (uint32_t)group, group * n, group * n, flags};
+            if (shared_b) dot_tile_lt<A, true, true>(c, lt, o, s);
+            else dot_tile_lt<A, true, false>(c, lt, o, s);
+            if (flags & kRingDotLast) launch_strided_round(c, d_c + j0 * n, nullptr, now, true, s);
+        }
+    }
+}
+
+static void refuse_large(const NttContext& c) {   // the middle pass above assumes ONE strided round on either side
+    if (c.logn > kTwoPassMaxLog2) throw std::runtime_error("ring inner product on a context above n = 131072 is not supported (lsr_cyclic_ntt_context_create_large)");
+}
+
+// One call on the device (caller validated the arguments): workspace, ordering brackets, launches.
+static void ring_dot_device(const NttContext& c, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms, size_t b_rows,
+                            hipStream_t s, bool first = true, bool last = true) {
+    const bool shared_b = b_rows == 1 && batch > 1;
+    std::lock_guard<std::mutex> lock(c.ring_mutex);
+    const bool capturing = stream_is_capturing(s);
+    if ((c.logn > kTileLog || shared_b) && !c.ring_dot_scratch.ptr) {
+        // allocated once and never resized, as the ring multiply's workspace (lsr_ring_mul.hip)
+        if (capturing)
+            throw std::runtime_error("this call needs the context's workspace, which the first such call allocates: make one eager (uncaptured) "
+                                     "call on this context before capturing");
+        c.ring_dot_scratch.allocate(ring_dot_scratch_words(c));
+    }
+    // (a capturing stream: no brackets — lsr_runtime.hpp, stream_is_capturing)
+    if (!capturing) c.ring_event.wait(s);
+    if (c.gold) ring_dot_enqueue<ArithGold>(c, d_c, d_a, d_b, batch, terms, shared_b, first, last, s);
+    else if (c.use_f64) ring_dot_enqueue<ArithF64>(c, d_c, d_a, d_b, batch, terms, shared_b, first, last, s);
+    else ring_dot_enqueue<ArithU64>(c, d_c, d_a, d_b, batch, terms, shared_b, first, last, s);
+    LSR_HIP(hipGetLastError());
+    if (!capturing) c.ring_event.record(s);
+}
+
+// host buffers through bounded device chunks on the context's work stream: whole outputs while one output's terms fit the staging
+// bound, else one output at a time with its terms in groups (the accumulator stays on the device between groups)
+static void host_ring_dot(const NttContext& c, uint64_t* out, const uint64_t* a, const uint64_t* b, size_t batch, size_t terms, size_t b_rows) {
+    DeviceGuard guard(c.device);
+    const size_t n = c.degree;
+    const bool shared_b = b_rows == 1 && batch > 1;
+    const size_t bound = std::max<size_t>(1, (256ull << 20) / (n * 8));          // polynomials per staged operand
+    const size_t group_max = std::min(terms, bound), chunk = group_max == terms ? std::max<size_t>(1, std::min(batch, bound / terms)) : 1;
+    DeviceBuffer<uint64_t> da(chunk * group_max * n), db((shared_b ? 1 : chunk) * group_max * n), dc(chunk * n);
+    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
+    hipStream_t s = work_stream(c);
+    for (size_t j0 = 0; j0 < batch; j0 += chunk) {
+        const size_t now = std::min(chunk, batch - j0);
+        for (size_t i0 = 0; i0 < terms; i0 += group_max) {
+            const size_t group = std::min(group_max, terms - i0), off = (j0 * terms + i0) * n;
+            LSR_HIP(hipMemcpyAsync(da.ptr, a + off, now * group * n * 8, hipMemcpyHostToDevice, s));
+            if (!shared_b) LSR_HIP(hipMemcpyAsync(db.ptr, b + off, now * group * n * 8, hipMemcpyHostToDevice, s));
+            else if (j0 == 0 || group != terms) LSR_HIP(hipMemcpyAsync(db.ptr, b + i0 * n, group * n * 8, hipMemcpyHostToDevice, s));
+            ring_dot_device(c, dc.ptr, da.ptr, db.ptr, now, group, shared_b ? 1 : now, s, i0 == 0, i0 + group == terms);
+        }
+        LSR_HIP(hipMemcpyAsync(out + j0 * n, dc.ptr, now * n * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+}  // namespace lsr
+
+// ------------------------------------------------------------------------------------------------
+// C-ABI
+// ------------------------------------------------------------------------------------------------
+// Argument checks that need no device (and no dereference of ctx), in the documented order: -1 and a message, or 0 to go on.
+static int ring_dot_check(const char* where, const NttContext* ctx, const void* c, const void* a, const void* b, size_t batch, size_t terms,
+                          size_t b_rows) {
+    if (!ctx || !c || !a || !b) return lsr::abi_refuse(where, "NULL context or buffer");
+    if (b_rows != 1 && b_rows != batch)
+        return lsr::abi_refuse(where, "b_rows must be 1 or batch (" + std::to_string(batch) + "), got " + std::to_string(b_rows));
+    if (terms == 0) return lsr::abi_refuse(where, "terms must be at least 1");
+    return 0;
+}
+
+// The checks of a non-empty call that read the context, still before any device work.
+static void ring_dot_validate(const NttContext& ctx, const uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t terms, size_t b_rows) {
+    lsr::refuse_large(ctx);
+    if (terms > LSR_RING_DOT_MAX_TERMS)
+        throw std::runtime_error("terms = " + std::to_string(terms) + " is above LSR_RING_DOT_MAX_TERMS (" + std::to_string(LSR_RING_DOT_MAX_TERMS) + ")");
+    const size_t n = ctx.degree;
+    auto overlaps = [&](const uint64_t* x, size_t polys) {
+        const uintptr_t c0 = reinterpret_cast<uintptr_t>(c), c1 = c0 + batch * n * 8;
+        const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), x1 = x0 + polys * n * 8;
+        return c0 < x1 && x0 < c1;
+    };
+    if (overlaps(a, batch * terms)) throw std::runtime_error("c overlaps a: the output must not share memory with an operand");
+    if (overlaps(b, b_rows * terms)) throw std::runtime_error("c overlaps b: the output must not share memory with an operand");
+}
+
+static void require_device() {
+    if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
+}
+
+extern "C" {
+
+int lsr_ntt_ring_dot_batch(const NttContext* ctx, uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t terms,
+                           size_t b_rows) noexcept {
+    if (ring_dot_check("lsr_ntt_ring_dot_batch", ctx, c, a, b, batch, terms, b_rows) != 0) return -1;
+    if (batch == 0) return 0;
+    return lsr::abi_guarded("lsr_ntt_ring_dot_batch", [&] {
+        ring_dot_validate(*ctx, c, a, b, batch, terms, b_rows);
+        require_device();
+        lsr::host_ring_dot(*ctx, c, a, b, batch, terms, b_rows);
+    });
+}
+
+int lsr_ntt_ring_dot_batch_device(const NttContext* ctx, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms,
+                                  size_t b_rows, void* stream) noexcept {
+    if (ring_dot_check("lsr_ntt_ring_dot_batch_device", ctx, d_c, d_a, d_b, batch, terms, b_rows) != 0) return -1;
+    if (batch == 0) return 0;
+    return lsr::abi_guarded("lsr_ntt_ring_dot_batch_device", [&] {
+        ring_dot_validate(*ctx, d_c, d_a, d_b, batch, terms, b_rows);
+        require_device();
+        lsr::DeviceGuard guard(ctx->device);
+        lsr::ring_dot_device(*ctx, d_c, d_a, d_b, batch, terms, b_rows, static_cast<hipStream_t>(stream));
+    });
+}
+
+}  // extern "C"

@@ -218,6 +218,9 @@ struct NttContext {
     mutable std::mutex ring_mutex;
     mutable lsr::DeviceBuffer<uint64_t> ring_scratch;
     mutable lsr::Event ring_event;
+    // workspace of lsr_ntt_ring_dot_batch(_device) (lsr_ring_dot.hip), under the same rules and the same mutex and event: a buffer of
+    // its own, because neither workspace is ever resized and the two calls need different sizes
+    mutable lsr::DeviceBuffer<uint64_t> ring_dot_scratch;
 };
 
 namespace lsr {
