@@ -275,6 +275,42 @@ int lsr_lwe_combine_rows_device(const LweContext* ctx, const uint64_t* d_rows, s
 int lsr_lwe_combine_batch_flat(const LweContext* ctx, const uint64_t* rows, size_t terms, size_t term_stride,
                                const uint64_t* coeffs, size_t outputs, uint64_t* out_rows, int* status) LSR_NOEXCEPT;
 
+/* ---------------- commitment: ring-element linear combination of device-resident rows ----------------
+ * Folding rows with ring-valued challenges.  With W = lsr_lwe_commitment_words(ctx) and n the ring degree, output j < outputs is
+ *   out_j = sum_{i < terms} p'_{j,i}(X) * row[j * term_stride + i]
+ * component by component over the k + 1 body polynomials in Z_q[X]/(X^n + 1) (RNS context: over both residue blocks, each under its
+ * own prime, with the same integer polynomial p').  d_polys[outputs][terms][n] is DEVICE memory, natural coefficient order; every
+ * word is any 64-bit value, reduced mod t as given and centred: c <= (t - 1)/2 acts as c, otherwise as c - t (the rule of
+ * lsr_lwe_combine_rows_device per coefficient).  d_rows is only read; term_stride means what it means for
+ * lsr_lwe_combine_rows_device (0: shared terms; terms: disjoint groups; anything else allowed).  d_out_rows[outputs][W] must not
+ * overlap d_rows or d_polys.  Output rows carry the context's header and canonical body residues.
+ * d_status[j] =  1  combined.  The row opens to sum_i p'_{j,i} m_i mod (X^n + 1, t), m_i = the n decoded slots of the term rows;
+ *                0  weight_j = sum_i sum_x |p'_{j,i,x}| (an exact integer below 2^52) exceeds lsr_lwe_combine_max_weight(ctx), the
+ *                   weight the scalar combine compares against: |(p e)_x| <= ||p||_1 ||e||_inf, and the rounding of round(q m / t)
+ *                   adds at most ||p||_1 / 2 (the "+ 1" of noise_unit + 1);
+ *               -1  some term row of this output is not a canonical row of this context (the screening of
+ *                   lsr_lwe_verify_rows_device).
+ * Rows with status 0 or -1 are unspecified; their neighbours are unaffected.  When every polynomial of a call is constant, the call
+ * gives the rows and statuses of lsr_lwe_combine_rows_device for the same constants, word for word.
+ * Asynchronous on `stream`, ordered behind other asynchronous calls on the context exactly as lsr_lwe_verify_rows_device; the
+ * synchronous entry points and lwe_context_free wait for it.  The call needs a workspace for the transformed polynomials, owned by
+ * the context: its size depends on (n, k, kind of context) and the process-wide chunk size only, the first eager call that needs it
+ * allocates it, and it is never resized.  A CAPTURING call (HIP graph) that would have to allocate the workspace returns -1: make
+ * one eager call on the context first (n > 4096: that call also allocates the ring inner product's workspace).  Outputs, and terms
+ * where they do not fit, are taken in chunks; between groups of terms the re-centred raw accumulator waits in the output row.
+ * lsr_lwe_ring_combine_batch_flat: the same for host arrays, staged in the bounded chunks lsr_lwe_combine_batch_flat uses (the terms
+ * of one output go up whole and are split on the device only, in the group form above); returns when the outputs are complete.
+ * Every kind of context is served (FP64, u64 wide modulus, RNS; every ring degree a context accepts).
+ * NULL context or buffer, terms == 0, terms > LSR_RING_COMBINE_MAX_TERMS, outputs >= 2^31, a row count that overflows, an output
+ * overlapping an input: -1 and a message naming the entry point in lsr_last_error, before any device work.  outputs == 0: no-op, 0.
+ * lsr_lwe_combine_max_weight: the largest weight either combine accepts on this context; 0 for NULL. */
+#define LSR_RING_COMBINE_MAX_TERMS 65536
+int lsr_lwe_ring_combine_rows_device(const LweContext* ctx, const uint64_t* d_rows, size_t terms, size_t term_stride,
+                                     const uint64_t* d_polys, size_t outputs, uint64_t* d_out_rows, int* d_status, void* stream) LSR_NOEXCEPT;
+int lsr_lwe_ring_combine_batch_flat(const LweContext* ctx, const uint64_t* rows, size_t terms, size_t term_stride,
+                                    const uint64_t* polys, size_t outputs, uint64_t* out_rows, int* status) LSR_NOEXCEPT;
+uint64_t lsr_lwe_combine_max_weight(const LweContext* ctx) LSR_NOEXCEPT;
+
 /* `count` openings in one device pass.  messages = [count][msg_len]; results[i] = 1 / 0 / -1 with the meaning of
  * lwe_verify_opening (cpp-core/src/commitment.cpp:200-232) for (commitments[i], messages[i]); NULL entries => -1.
  * Returns 0, or -1 if the call itself failed. */

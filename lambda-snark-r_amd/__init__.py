@@ -348,6 +348,38 @@ class LweContext:
             raise CoreError("CombineFailed: " + _abi.last_error())
         return out, status
 
+    @property
+    def combine_max_weight(self):
+        """``lsr_lwe_combine_max_weight``: the largest weight (sum of |c'|, for ring elements over every coefficient) that
+        ``combine_rows`` and ``ring_combine_rows`` accept on this context."""
+        return self._lib.lsr_lwe_combine_max_weight(self._h)
+
+    def ring_combine_rows_device(self, d_rows, terms, d_polys, outputs, d_out_rows, d_status, term_stride=0, stream=None):
+        """``lsr_lwe_ring_combine_rows_device``: device pointers (ints) in; out_j = sum_i p'_{j,i}(X) row[j * term_stride + i] in
+        Z_q[X]/(X^n + 1) for j < outputs, d_polys = [outputs][terms][n] coefficient words (reduced mod t and centred), and int32 status
+        (1 combined / 0 over the noise budget / -1 a malformed term row) out; asynchronous on `stream`."""
+        if self._lib.lsr_lwe_ring_combine_rows_device(self._h, d_rows, terms, term_stride, d_polys, outputs, d_out_rows, d_status, stream) != 0:
+            raise CoreError("RingCombineFailed: " + _abi.last_error())
+
+    def ring_combine_rows(self, rows, polys, term_stride=0):
+        """``lsr_lwe_ring_combine_batch_flat``: rows [(outputs - 1) * term_stride + terms][words] and polys [outputs][terms][n] (host) ->
+        (out_rows [outputs][words], status [outputs])."""
+        rows = _u64_array(rows, "rows")
+        polys = _u64_array(polys, "polys")
+        if rows.ndim != 2 or rows.shape[1] != self.commitment_words:
+            raise ValueError("rows must be [count][commitment_words]")
+        if polys.ndim != 3 or polys.shape[2] != self.ring_degree:
+            raise ValueError("polys must be [outputs][terms][ring_degree]")
+        outputs, terms = polys.shape[:2]
+        if outputs and rows.shape[0] != (outputs - 1) * int(term_stride) + terms:
+            raise ValueError("rows must hold (outputs - 1) * term_stride + terms rows")
+        out = np.zeros((outputs, rows.shape[1]), dtype=np.uint64)
+        status = np.zeros(outputs, dtype=np.int32)
+        if self._lib.lsr_lwe_ring_combine_batch_flat(self._h, rows.ctypes.data, terms, int(term_stride), polys.ctypes.data, outputs, out.ctypes.data,
+                                                     status.ctypes.data) != 0:
+            raise CoreError("RingCombineFailed: " + _abi.last_error())
+        return out, status
+
     def public_matrix(self):
         k, n = self.module_rank, self.ring_degree
         a = np.zeros((k, k, n), dtype=np.uint64)

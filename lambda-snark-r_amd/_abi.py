@@ -62,6 +62,8 @@ PROFILE_SCALAR_A = 0
 # and a workgroup serves COMBINE_OUTPUTS outputs
 COMBINE_TERMS = 32
 COMBINE_OUTPUTS = 8
+# batch.h LSR_RING_COMBINE_MAX_TERMS: the most terms one output of the ring-element combination takes
+RING_COMBINE_MAX_TERMS = 65536
 PROFILE_RING_B = 1
 
 # every symbol declared in include/lambda_snark/*.h: name -> (restype, argtypes)
@@ -147,6 +149,9 @@ SIGNATURES = {
     "lsr_lwe_noise_capacity_bits": (u32, [vp]),
     "lsr_lwe_combine_rows_device": (c_int, [vp, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
     "lsr_lwe_combine_batch_flat": (c_int, [vp, vp, c_size, c_size, vp, c_size, vp, vp]),
+    "lsr_lwe_ring_combine_rows_device": (c_int, [vp, vp, c_size, c_size, vp, c_size, vp, vp, vp]),
+    "lsr_lwe_ring_combine_batch_flat": (c_int, [vp, vp, c_size, c_size, vp, c_size, vp, vp]),
+    "lsr_lwe_combine_max_weight": (ctypes.c_uint64, [vp]),
     "lsr_lwe_wide_modulus": (ctypes.c_uint64, [ctypes.c_uint32]),
     "lsr_lwe_context_create_rns": (vp, [ctypes.POINTER(PublicParams), u64, c_int]),
     "lsr_lwe_rns_moduli": (c_int, [vp, vp]),

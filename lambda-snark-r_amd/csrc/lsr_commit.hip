@@ -31,7 +31,9 @@
 #include "lsr_commit_tile.hpp"
 #include "lsr_commit_rns.hpp"
 #include "lsr_commit_combine.hpp"
+#include "lsr_commit_ring_combine.hpp"
 #include "lsr_commit_keys.hpp"
+#include "lsr_flavour.hpp"
 #include "lsr_keys.hpp"
 #include "lsr_runtime.hpp"
 #include "lsr_sampler.hpp"
@@ -108,6 +110,10 @@ struct LweContext {
     bool rns_member = false;           // either half of an RNS pair: no n >= 2^16 fused pipelines (their RNS form does not exist)
     LweContext* sib = nullptr;
     lsr::RnsConsts rc{};
+    // lsr_lwe_ring_combine_rows_device: the transformed polynomials of a chunk (n > 4096: the unpacked components, the
+    // lifted polynomials and one partial result).  Allocated by the first eager call at a size fixed by (n, k, kind of context) and
+    // the process-wide chunk size, never resized; ws_ring_polys stages the polynomials of the host-array entry point
+    mutable lsr::DeviceBuffer<uint64_t> ws_ring, ws_ring_polys;
 };
 
 namespace lsr {
@@ -1624,6 +1630,173 @@ static void combine_host_rows(const LweContext& c, const uint64_t* rows, size_t 
     }
 }
 
+// ---- ring-element combination (lsr_commit_ring_combine.hpp) -------------------------------------------------------------
+static_assert(LSR_RING_COMBINE_MAX_TERMS <= LSR_RING_DOT_MAX_TERMS, "the composed form hands a group of terms to the ring inner product");
+static_assert((uint64_t)LSR_RING_COMBINE_MAX_TERMS << (17 + 19) <= 1ull << 52, "the weight sum stays exact");
+
+// n <= 4096: polynomials per prime of one chunk of transformed polynomials; n > 4096: terms per group of the composed form
+static size_t ring_combine_polys(const LweContext& c) {
+    const size_t per_poly = ntt_chunk_bytes() >> (c.logn + 3);
+    if (c.logn <= kTileLog) return std::max<size_t>(1, per_poly / (c.rns ? 2 : 1));
+    return std::min<size_t>(LSR_RING_COMBINE_MAX_TERMS, std::max<size_t>(1, per_poly / ((size_t)c.k + 2)));
+}
+static size_t ring_combine_workspace_words(const LweContext& c) {
+    const size_t polys = ring_combine_polys(c), kp1 = (size_t)c.k + 1;
+    if (c.logn <= kTileLog) return (c.rns ? 2 : 1) * polys * c.n;
+    return (kp1 * polys + polys + kp1) * c.n;          // components [k + 1][group][n], lifted polynomials [group][n], one partial result
+}
+
+static unsigned ring_combine_grid(uint64_t words) { return (unsigned)std::min<uint64_t>((words + 255) / 256, 1u << 20); }
+
+template <class A>
+static RingCombinePrime<A> ring_combine_prime(const NttContext& ntt, const uint64_t* phat, uint64_t block_off) {
+    return RingCombinePrime<A>{ntt.mod, Flavour<A>::fwd(ntt), Flavour<A>::inv(ntt), Flavour<A>::consts(ntt), phat, block_off};
+}
+
+template <class A, int LT>
+static void ring_combine_tile_launch(const RingCombineTile& job, const RingCombinePrime<A>& pr, hipStream_t s) {
+    const unsigned tiles = (unsigned)((((uint64_t)job.polys << LT) + kTile - 1) / kTile);
+    hipLaunchKernelGGL((ring_combine_tile<A, LT>), dim3(tiles), dim3(kThreads), 0, s, job, pr);
+}
+#define LSR_RING_COMBINE_CASE(LT) case LT: ring_combine_tile_launch<A, LT>(job, pr, s); break;
+template <class A>
+static void ring_combine_tile_lt(int lt, const RingCombineTile& job, const RingCombinePrime<A>& pr, hipStream_t s) {
+    switch (lt) {
+        LSR_RING_COMBINE_CASE(1) LSR_RING_COMBINE_CASE(2) LSR_RING_COMBINE_CASE(3) LSR_RING_COMBINE_CASE(4) LSR_RING_COMBINE_CASE(5)
+        LSR_RING_COMBINE_CASE(6) LSR_RING_COMBINE_CASE(7) LSR_RING_COMBINE_CASE(8) LSR_RING_COMBINE_CASE(9) LSR_RING_COMBINE_CASE(10)
+        LSR_RING_COMBINE_CASE(11)
+        default: ring_combine_tile_launch<A, 12>(job, pr, s); break;
+    }
+}
+#undef LSR_RING_COMBINE_CASE
+
+// the fused launch of one chunk and group under one prime of the context, in that prime's flavour
+static void ring_combine_tile_prime(const LweContext& c, const RingCombineTile& job, const NttContext& ntt, const uint64_t* phat, uint64_t block,
+                                    hipStream_t s) {
+    if (ntt.use_f64) ring_combine_tile_lt<ArithF64>(c.logn, job, ring_combine_prime<ArithF64>(ntt, phat, block), s);
+    else ring_combine_tile_lt<ArithU64>(c.logn, job, ring_combine_prime<ArithU64>(ntt, phat, block), s);
+}
+
+// enqueued on `s` (caller holds c.mutex): the prologue for all outputs, then per chunk the lift, the forward transforms and the
+// fused tile launch (n <= 4096) or, per output, the composed form through the ring inner product (n > 4096)
+static void ring_combine_rows_device(const LweContext& c, const uint64_t* d_rows, size_t terms, size_t term_stride, const uint64_t* d_polys,
+                                     size_t outputs, uint64_t* d_out, int* d_status, hipStream_t s) {
+    if (!c.ws_ring.ptr) {
+        if (stream_is_capturing(s))
+            throw std::runtime_error("this call needs the context's workspace, which the first such call allocates: make one eager (uncaptured) "
+                                     "call on this context before capturing");
+        c.ws_ring.allocate(ring_combine_workspace_words(c));
+    }
+    const size_t n = c.n, row = row_words(c), kp1 = (size_t)c.k + 1;
+    RingCombineJob job{};
+    job.rows = d_rows; job.polys = d_polys; job.out = d_out; job.status = d_status;
+    job.terms = terms; job.term_stride = term_stride; job.outputs = outputs;
+    job.row_words = row;
+    job.header_words = (uint32_t)header_words(c);
+    job.logn = (uint32_t)c.logn;
+    const uint64_t shape = (uint64_t)c.n | ((uint64_t)c.k << 32);
+    for (uint32_t w = 0; w < job.header_words; ++w)
+        job.header[w] = c.rns ? rns_header_word(w, row, shape, c.rc)
+                              : (w == 0 ? 8ull * (row - 1) : (w == 1 ? kWireMagic : (w == 2 ? shape : (w == 3 ? c.q : c.t))));
+    job.max_weight = combine_max_weight(c);
+    job.plain = make_plain_scale(c.q, c.t);
+    hipLaunchKernelGGL(ring_combine_prologue_kernel, dim3((unsigned)outputs), dim3(256), 0, s, job);
+    LSR_HIP(hipGetLastError());
+
+    const int primes = c.rns ? 2 : 1;
+    const NttContext* const ntt[2] = {c.ntt.get(), c.rns ? c.sib->ntt.get() : c.ntt.get()};
+    const uint64_t block[2] = {job.header_words, job.header_words + kp1 * n};
+    const size_t polys = ring_combine_polys(c);
+    if (c.logn <= kTileLog) {
+        // all terms fit: chunks of whole outputs; else one output at a time, its terms in groups with the raw accumulator in the output row
+        const size_t group_max = std::min(terms, polys), chunk = group_max == terms ? std::min(outputs, polys / terms) : 1;
+        const uint64_t* const phat[2] = {c.ws_ring.ptr, c.ws_ring.ptr + polys * n};
+        for (size_t j0 = 0; j0 < outputs; j0 += chunk) {
+            const size_t now = std::min(chunk, outputs - j0);
+            for (size_t i0 = 0; i0 < terms; i0 += group_max) {
+                const size_t group = std::min(group_max, terms - i0);
+                for (int pr = 0; pr < primes; ++pr) {
+                    uint64_t* const ph = c.ws_ring.ptr + pr * polys * n;
+                    hipLaunchKernelGGL(ring_combine_lift_kernel, dim3(ring_combine_grid(now * group * n)), dim3(256), 0, s, ph,
+                                       d_polys + (j0 * terms + i0) * n, (uint64_t)(terms * n), (uint64_t)now, (uint64_t)(group * n), ntt[pr]->modulus,
+                                       job.plain);
+                    LSR_HIP(hipGetLastError());
+                    launch_ntt(*ntt[pr], ph, now * group, false, s);
+                }
+                RingCombineTile tile{};
+                tile.rows = d_rows + (j0 * term_stride + i0) * row;
+                tile.out = d_out + j0 * row;
+                tile.status = d_status + j0;
+                tile.stride_words = term_stride * row;
+                tile.row_words = row;
+                tile.kp1 = (uint32_t)kp1;
+                tile.nterms = (uint32_t)group;
+                tile.polys = (uint32_t)(now * kp1);
+                tile.flags = (i0 == 0 ? kRingDotFirst : 0u) | (i0 + group == terms ? kRingDotLast : 0u);
+                for (int pr = 0; pr < primes; ++pr) ring_combine_tile_prime(c, tile, *ntt[pr], phat[pr], block[pr], s);
+                LSR_HIP(hipGetLastError());
+            }
+        }
+        return;
+    }
+    // n > 4096, the composed form: per output and prime the components of a group of terms as [k + 1][group][n], the lifted
+    // polynomials [group][n], the ring inner product with one shared b straight into the output row's block (a later group: into
+    // the partial result, then added)
+    uint64_t* const comps = c.ws_ring.ptr;
+    uint64_t* const lifted = comps + kp1 * polys * n;
+    uint64_t* const partial = lifted + polys * n;
+    for (size_t j = 0; j < outputs; ++j) {
+        for (int pr = 0; pr < primes; ++pr) {
+            const uint64_t q = ntt[pr]->modulus;
+            uint64_t* const dst = d_out + j * row + block[pr];
+            for (size_t i0 = 0; i0 < terms; i0 += polys) {
+                const size_t group = std::min(polys, terms - i0);
+                hipLaunchKernelGGL(ring_combine_unpack_kernel, dim3(ring_combine_grid(kp1 * group * n)), dim3(256), 0, s, comps,
+                                   d_rows + (j * term_stride + i0) * row, (uint64_t)row, block[pr], (uint32_t)kp1, (uint64_t)group, (uint32_t)c.logn, q,
+                                   d_status + j);
+                hipLaunchKernelGGL(ring_combine_lift_kernel, dim3(ring_combine_grid(group * n)), dim3(256), 0, s, lifted, d_polys + (j * terms + i0) * n,
+                                   (uint64_t)0, (uint64_t)1, (uint64_t)(group * n), q, job.plain);
+                LSR_HIP(hipGetLastError());
+                if (lsr_ntt_ring_dot_batch_device(ntt[pr], i0 == 0 ? dst : partial, comps, lifted, kp1, group, 1, s) != 0)
+                    throw std::runtime_error(std::string("ring inner product pass failed: ") + lsr_last_error());
+                if (i0 != 0) {
+                    hipLaunchKernelGGL(ring_combine_add_kernel, dim3(ring_combine_grid(kp1 * n)), dim3(256), 0, s, dst, partial, (uint64_t)(kp1 * n), q);
+                    LSR_HIP(hipGetLastError());
+                }
+            }
+        }
+    }
+}
+
+// host arrays: outputs are staged `now` at a time within the rows of one verify_chunk() pass and 1 GiB of polynomial words (one
+// output is never split on the host side: its terms and polynomials go up whole; the device call splits them into groups)
+static void ring_combine_host_rows(const LweContext& c, const uint64_t* rows, size_t terms, size_t term_stride, const uint64_t* polys, size_t outputs,
+                                   uint64_t* out_rows, int* status, hipStream_t s) {
+    const size_t row = row_words(c), poly_words = terms * c.n;
+    const size_t cap = verify_chunk(c, ~size_t(0));
+    size_t chunk = 1;
+    if (outputs > 1 && terms + 1 < cap) chunk = std::max<size_t>(1, (cap - terms + term_stride) / (term_stride + 1));
+    chunk = std::min(chunk, std::max<size_t>(1, (size_t(1) << 27) / poly_words));
+    chunk = std::min(chunk, outputs);
+    const size_t term_rows = (chunk - 1) * term_stride + terms;
+    c.ws_rows.reserve((term_rows + chunk) * row);
+    c.ws_ring_polys.reserve(chunk * poly_words);
+    c.ws_vflags.reserve((chunk + 1) / 2);
+    uint64_t* const d_terms = c.ws_rows.ptr;
+    uint64_t* const d_out = c.ws_rows.ptr + term_rows * row;
+    int* const d_status = reinterpret_cast<int*>(c.ws_vflags.ptr);
+    for (size_t first = 0; first < outputs; first += chunk) {
+        const size_t now = std::min(chunk, outputs - first);
+        if (first == 0 || term_stride != 0)      // shared terms go up once
+            LSR_HIP(hipMemcpyAsync(d_terms, rows + first * term_stride * row, ((now - 1) * term_stride + terms) * row * 8, hipMemcpyHostToDevice, s));
+        LSR_HIP(hipMemcpyAsync(c.ws_ring_polys.ptr, polys + first * poly_words, now * poly_words * 8, hipMemcpyHostToDevice, s));
+        ring_combine_rows_device(c, d_terms, terms, term_stride, c.ws_ring_polys.ptr, now, d_out, d_status, s);
+        LSR_HIP(hipMemcpyAsync(out_rows + first * row, d_out, now * row * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(status + first, d_status, now * sizeof(int), hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
 }  // namespace lsr
 
 // one host thread per shard; body(g, first, count) runs with the shard's device current
@@ -2074,6 +2247,75 @@ int lsr_lwe_combine_batch_flat(const LweContext* ctx, const uint64_t* rows, size
         return -1;
     } catch (...) {
         return -1;
+    }
+}
+
+// argument screening of the ring-element combination: false (and a message) for what is refused before any device work
+static bool ring_combine_arguments_ok(const char* where, const LweContext* ctx, const void* rows, size_t terms, size_t term_stride, const void* polys,
+                                      size_t outputs, const void* out_rows, const void* status) {
+    const char* why = nullptr;
+    size_t span = 0, total = terms, row_bytes = 0, poly_count = 0, poly_bytes = 0, out_bytes = 0;
+    if (!ctx) why = "NULL context (no context exists without a HIP device)";
+    else if (!rows || !polys || !out_rows || !status) why = "NULL buffer";
+    else if (terms == 0) why = "terms must be at least 1";
+    else if (terms > LSR_RING_COMBINE_MAX_TERMS) why = "terms exceed LSR_RING_COMBINE_MAX_TERMS (65536)";
+    else if (outputs > 0x7fffffffull) why = "outputs exceed one launch (2^31 - 1 rows)";
+    else if ((outputs > 1 && (__builtin_mul_overflow(outputs - 1, term_stride, &span) || __builtin_add_overflow(span, terms, &total))) ||
+             __builtin_mul_overflow(total, lsr::row_words(*ctx) * 8, &row_bytes) || __builtin_mul_overflow(outputs, terms, &poly_count) ||
+             __builtin_mul_overflow(poly_count, (size_t)ctx->n * 8, &poly_bytes) || __builtin_mul_overflow(outputs, lsr::row_words(*ctx) * 8, &out_bytes))
+        why = "term_stride overflows the row count";
+    else if (outputs != 0) {
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_rows), o1 = o0 + out_bytes;
+        const uintptr_t r0 = reinterpret_cast<uintptr_t>(rows), p0 = reinterpret_cast<uintptr_t>(polys);
+        if ((o0 < r0 + row_bytes && r0 < o1) || (o0 < p0 + poly_bytes && p0 < o1)) why = "the output rows overlap an input (rows or polynomials)";
+    }
+    if (why) lsr::set_last_error(std::string(where) + ": " + why);
+    return why == nullptr;
+}
+
+int lsr_lwe_ring_combine_rows_device(const LweContext* ctx, const uint64_t* d_rows, size_t terms, size_t term_stride, const uint64_t* d_polys,
+                                     size_t outputs, uint64_t* d_out_rows, int* d_status, void* stream) noexcept {
+    if (!ring_combine_arguments_ok("lsr_lwe_ring_combine_rows_device", ctx, d_rows, terms, term_stride, d_polys, outputs, d_out_rows, d_status)) return -1;
+    if (outputs == 0) return 0;
+    try {
+        lsr::DeviceGuard guard(ctx->device);
+        std::lock_guard<std::mutex> lock(ctx->mutex);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        lsr::begin_async(*ctx, s);
+        lsr::ring_combine_rows_device(*ctx, d_rows, terms, term_stride, d_polys, outputs, d_out_rows, d_status, s);
+        lsr::end_async(*ctx, s);
+        return 0;
+    } catch (const std::exception& e) {
+        lsr::set_last_error(std::string("lsr_lwe_ring_combine_rows_device: ") + e.what());
+        return -1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+int lsr_lwe_ring_combine_batch_flat(const LweContext* ctx, const uint64_t* rows, size_t terms, size_t term_stride, const uint64_t* polys, size_t outputs,
+                                    uint64_t* out_rows, int* status) noexcept {
+    if (!ring_combine_arguments_ok("lsr_lwe_ring_combine_batch_flat", ctx, rows, terms, term_stride, polys, outputs, out_rows, status)) return -1;
+    if (outputs == 0) return 0;
+    try {
+        lsr::DeviceGuard guard(ctx->device);
+        std::lock_guard<std::mutex> lock(ctx->mutex);
+        lsr::wait_for_async(*ctx);
+        lsr::ring_combine_host_rows(*ctx, rows, terms, term_stride, polys, outputs, out_rows, status, lsr::work_stream(*ctx->ntt));
+        return 0;
+    } catch (const std::exception& e) {
+        lsr::set_last_error(std::string("lsr_lwe_ring_combine_batch_flat: ") + e.what());
+        return -1;
+    } catch (...) {
+        return -1;
+    }
+}
+
+uint64_t lsr_lwe_combine_max_weight(const LweContext* ctx) noexcept {
+    try {
+        return ctx ? lsr::combine_max_weight(*ctx) : 0;
+    } catch (...) {
+        return 0;
     }
 }
 
