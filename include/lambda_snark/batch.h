@@ -35,6 +35,12 @@ int      lsr_ntt_context_device(const NttContext* ctx) LSR_NOEXCEPT;
 uint64_t lsr_ntt_context_root(const NttContext* ctx) LSR_NOEXCEPT;   /* psi */
 /* 1 if the context computes with the exact FP64-FMA Barrett kernels (q < 2^45), 0 for u64 Shoup */
 int      lsr_ntt_context_uses_f64(const NttContext* ctx) LSR_NOEXCEPT;
+/* bytes per residue of the private intermediate between the two passes of an n > 4096 transform: 6 when the FP64 kernels' hand-off words
+ * fit 48 bits (q < 2^47 / 4.5 for n <= 65536, q < 2^47 / 5.375 for n = 131072) and the context was not created under
+ * LAMBDA_SNARK_NTT_HANDOFF=8, else 8 (also for n <= 4096, where there is no hand-off).  Results are the same words either way for
+ * inputs in [0, q), which every transform entry point requires.  The library does not check them: words >= q, which the 8-byte path
+ * happened to carry exactly up to 2^50, wrap at 48 bits on the 6-byte path and give wrong results without an error. */
+int      lsr_ntt_handoff_bytes(const NttContext* ctx) LSR_NOEXCEPT;
 /* force the arithmetic flavour of FUTURE contexts: 0 auto, 1 u64 Shoup always (testing) */
 void     lsr_set_arith_mode(int mode) LSR_NOEXCEPT;
 

@@ -108,6 +108,11 @@ class NttContext:
     def uses_f64(self):
         return bool(self._lib.lsr_ntt_context_uses_f64(self._h))
 
+    @property
+    def handoff_bytes(self):
+        """Bytes per residue of the intermediate between the two passes of an n > 4096 transform (6 or 8; batch.h)."""
+        return self._lib.lsr_ntt_handoff_bytes(self._h)
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.ntt_context_free(self._h)

@@ -92,6 +92,7 @@ SIGNATURES = {
     "lsr_ntt_context_device": (c_int, [vp]),
     "lsr_ntt_context_root": (u64, [vp]),
     "lsr_ntt_context_uses_f64": (c_int, [vp]),
+    "lsr_ntt_handoff_bytes": (c_int, [vp]),
     "lsr_set_arith_mode": (None, [c_int]),
     "ntt_forward_batch": (c_int, [vp, vp, c_size]),
     "ntt_inverse_batch": (c_int, [vp, vp, c_size]),

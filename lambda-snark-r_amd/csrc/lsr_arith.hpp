@@ -38,6 +38,30 @@ __device__ __forceinline__ uint64_t u52_from_f64(double v) {   // v an integer i
     return (uint64_t)__double_as_longlong(v + 4503599627370496.0) & 0x000FFFFFFFFFFFFFull;
 }
 
+// ---------------------------------------------------------------------------------------------
+// 6-byte hand-off word of the two-pass FP64 transform (lsr_ntt_kernels.hpp PACKED): an exact integer |x| < 2^47 travels as the low 48
+// bits of its two's complement, a dword and a halfword.  One FP64 add each way and no integer conversion instruction:
+//   pack:   y = x + 1.5 * 2^52 has exponent 52 (|x| < 2^51), so its mantissa field is 2^51 + x and the low 48 bits of its bit pattern
+//           are x mod 2^48; the high dword is 0x43380000 + floor(x / 2^32), whose low 16 bits go out as the halfword h;
+//   unpack: floor(x / 2^32) lies in [-2^15, 2^15), so it is sext16(h): high dword = 0x43380000 + sext16(h), low dword as stored, and
+//           subtracting 1.5 * 2^52 returns x exactly.
+// Who may use it (decided on the host, lsr_ntt.hip handoff_is_packed).  Forward: the strided round takes canonical words [0, q) through
+// r_top Cooley-Tukey stages, each adding a product of magnitude <= 0.875 q: |x| <= q + r_top * 0.875 q (4.5 q for four stages, 5.375 q
+// for five).  Inverse: the tile pass re-centres its last round itself, |x| <= q / 2 + 1 <= 2 q (the deferred form hands over up to
+// 32 q < 2^50 and cannot ride along).  Both must stay below 2^47: (8 + 7 r_top) q < 2^50, i.e. q < 2^47 / 4.5 for r_top = 4.
+// ---------------------------------------------------------------------------------------------
+constexpr double kPackBias = 0x1.8p52;             // 1.5 * 2^52
+constexpr uint32_t kPackBiasHigh = 0x43380000u;    // high dword of kPackBias
+__device__ __forceinline__ void pack48_from_f64(double x, uint32_t& lo, uint16_t& hi) {
+    const uint64_t bits = (uint64_t)__double_as_longlong(x + kPackBias);
+    lo = (uint32_t)bits;
+    hi = (uint16_t)(bits >> 32);
+}
+__device__ __forceinline__ double f64_from_pack48(uint32_t lo, int16_t hi) {   // hi: the halfword, sign-extended by the load
+    const uint32_t high = kPackBiasHigh + (uint32_t)(int32_t)hi;
+    return __longlong_as_double((long long)(((uint64_t)high << 32) | lo)) - kPackBias;
+}
+
 __device__ __forceinline__ double mulmod_f64(double x, double w, double q, double inv_q) {
     const double h = x * w;
     const double l = __builtin_fma(x, w, -h);
@@ -97,6 +121,24 @@ __device__ __forceinline__ void buf_store64(rsrc_t r, uint32_t lane_bytes, uint3
     v.x = (uint32_t)x;
     v.y = (uint32_t)(x >> 32);
     __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)lane_bytes, (int)const_bytes, AUX);
+}
+
+// 32-bit and sign-extending 16-bit accesses for the 6-byte hand-off (vector memory instructions like the rest)
+template <int AUX = 0>
+__device__ __forceinline__ uint32_t buf_load32(rsrc_t r, uint32_t lane_bytes, uint32_t const_bytes) {
+    return __builtin_amdgcn_raw_buffer_load_b32(r, (int)lane_bytes, (int)const_bytes, AUX);
+}
+template <int AUX = 0>
+__device__ __forceinline__ int16_t buf_load16s(rsrc_t r, uint32_t lane_bytes, uint32_t const_bytes) {
+    return (int16_t)__builtin_amdgcn_raw_buffer_load_b16(r, (int)lane_bytes, (int)const_bytes, AUX);
+}
+template <int AUX = 0>
+__device__ __forceinline__ void buf_store32(rsrc_t r, uint32_t lane_bytes, uint32_t const_bytes, uint32_t x) {
+    __builtin_amdgcn_raw_buffer_store_b32(x, r, (int)lane_bytes, (int)const_bytes, AUX);
+}
+template <int AUX = 0>
+__device__ __forceinline__ void buf_store16(rsrc_t r, uint32_t lane_bytes, uint32_t const_bytes, uint16_t x) {
+    __builtin_amdgcn_raw_buffer_store_b16(x, r, (int)lane_bytes, (int)const_bytes, AUX);
 }
 
 struct ArithF64 {

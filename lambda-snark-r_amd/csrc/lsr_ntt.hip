@@ -113,6 +113,19 @@ int resolve_device(const char* where, int device, bool announce) {
     return device;
 }
 
+// Whether run_ntt's two-pass FP64 transform may hand its intermediate over in 6 bytes per residue (lsr_arith.hpp pack48_from_f64): the
+// forward hand-off is bounded by q + r_top * 0.875 q, the re-centred inverse one by 2 q, and both must stay below 2^47, i.e.
+// (8 + 7 r_top) q < 2^50 — q < 2^47 / 4.5 for the four-stage round of n <= 2^16, q < 2^47 / 5.375 for the five stages of n = 2^17.
+// LAMBDA_SNARK_NTT_HANDOFF=8, read when the context is created, keeps the 8-byte hand-off.
+static bool handoff_is_packed(uint64_t q, int logn, bool use_f64) {
+    if (!use_f64 || logn <= kTileLog || logn > kTwoPassMaxLog2) return false;
+    if (const char* e = std::getenv("LAMBDA_SNARK_NTT_HANDOFF")) {
+        if (std::strcmp(e, "8") == 0) return false;
+    }
+    const uint64_t r_top = static_cast<uint64_t>(std::max(logn - kTileLog, 4));
+    return static_cast<u128>(q) * (8 + 7 * r_top) < (static_cast<u128>(1) << 50);
+}
+
 static NttContext* build_context(const char* where, uint64_t q, uint32_t n, int logn, int device, const TwiddleTables& tw, bool cyclic) {
     device = resolve_device(where, device, true);
     if (device < 0) return nullptr;
@@ -128,6 +141,7 @@ static NttContext* build_context(const char* where, uint64_t q, uint32_t n, int 
         ctx->gold = (q == kProverModulus);
         ctx->mod = make_mod_params(q, logn);
         ctx->use_f64 = !ctx->gold && (q < (1ull << 45)) && arith_mode() != 1;
+        ctx->handoff_bytes = handoff_is_packed(q, logn, ctx->use_f64) ? 6 : 8;
         const uint64_t w_last_scaled = mulmod(tw.inv[n > 1 ? 1 : 0], tw.n_inv, q);
         if (ctx->gold) {   // multipliers in Montgomery form (gold_mul_mont)
             std::vector<uint64_t> f(n), g(n);
@@ -221,12 +235,12 @@ void destroy_ntt_context(NttContext* ctx) {
 // ------------------------------------------------------------------------------------------------
 // dispatch
 // ------------------------------------------------------------------------------------------------
-template <class A, int LT, bool RAW_IN, bool RAW_OUT>
+template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool PACKED = false>
 static void tile_fwd(const NttContext& c, uint64_t* d, size_t total, hipStream_t s, const uint64_t* src = nullptr) {
     const unsigned grid = static_cast<unsigned>((total + kTile - 1) / kTile);
-    hipLaunchKernelGGL((ntt_tile_forward<A, LT, RAW_IN, RAW_OUT>), dim3(grid), dim3(kThreads), 0, s, d, total, c.mod, Flavour<A>::fwd(c), src);
+    hipLaunchKernelGGL((ntt_tile_forward<A, LT, RAW_IN, RAW_OUT, PACKED>), dim3(grid), dim3(kThreads), 0, s, d, total, c.mod, Flavour<A>::fwd(c), src);
 }
-template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool DEFER = false>
+template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool DEFER = false, bool PACKED = false>
 static void tile_inv(const NttContext& c, uint64_t* d, size_t total, hipStream_t s, const uint64_t* add = nullptr, const uint64_t* pre = nullptr) {
     const unsigned grid = static_cast<unsigned>((total + kTile - 1) / kTile);
     static_assert(!DEFER || !std::is_same_v<A, ArithGold>, "the pre-multiplied instantiation has no deferred form");
@@ -238,7 +252,7 @@ static void tile_inv(const NttContext& c, uint64_t* d, size_t total, hipStream_t
         }
     }
     if (pre != nullptr) throw std::runtime_error("pre-multiplied inverse transform: only for NTT_MODULUS contexts");
-    hipLaunchKernelGGL((ntt_tile_inverse<A, LT, RAW_IN, RAW_OUT, false, DEFER>), dim3(grid), dim3(kThreads), 0, s, d, total, c.mod, Flavour<A>::inv(c),
+    hipLaunchKernelGGL((ntt_tile_inverse<A, LT, RAW_IN, RAW_OUT, false, DEFER, PACKED>), dim3(grid), dim3(kThreads), 0, s, d, total, c.mod, Flavour<A>::inv(c),
                        Flavour<A>::consts(c), add);
 }
 
@@ -247,13 +261,28 @@ static void tile_inv(const NttContext& c, uint64_t* d, size_t total, hipStream_t
 // (lsr_ntt_kernels.hpp RECENTRE_IN, bounds in DESIGN.md §4; re-centring every word in the four-stage round measured the same,
 // profiles/r12_inverse_tile_ablation.txt).  The pipelines that bring raw intermediates of their own (commitment, opening, ring
 // multiply: launch_top_round_inverse, launch_strided_round) keep the plain instantiations.
-template <class A, bool INVERSE, bool RAW_IN, bool RAW_OUT, bool DEFERRED = false>
+// PACKED: the raw side is the 6-byte hand-off of run_ntt<ArithF64> (a two-pass transform's top round has four or five stages).
+template <class A, bool INVERSE, bool RAW_IN, bool RAW_OUT, bool DEFERRED = false, bool PACKED = false>
 static void strided(const NttContext& c, uint64_t* d, size_t total, int lo, int r, hipStream_t s, const uint64_t* add = nullptr) {
     constexpr int kOnLoad4 = DEFERRED ? 1 : 0, kOnLoad5 = DEFERRED ? 2 : 0;
     const size_t groups = total >> r;
     const unsigned grid = static_cast<unsigned>((groups + kThreads - 1) / kThreads);
     const auto* tw = INVERSE ? Flavour<A>::inv(c) : Flavour<A>::fwd(c);
     const auto cs = Flavour<A>::consts(c);
+    if constexpr (PACKED) {
+        static_assert(!DEFERRED, "the packed hand-off is re-centred by the tile pass");
+        if (r != 4 && r != 5) throw std::runtime_error("packed hand-off: top rounds of four or five stages only");
+        if constexpr (INVERSE) {
+            if (add != nullptr) {
+                if (r == 4) hipLaunchKernelGGL((ntt_strided_round<A, 4, true, true, false, true, 0, true>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add);
+                else hipLaunchKernelGGL((ntt_strided_round<A, 5, true, true, false, true, 0, true>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add);
+                return;
+            }
+        }
+        if (r == 4) hipLaunchKernelGGL((ntt_strided_round<A, 4, INVERSE, RAW_IN, RAW_OUT, false, 0, true>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add);
+        else hipLaunchKernelGGL((ntt_strided_round<A, 5, INVERSE, RAW_IN, RAW_OUT, false, 0, true>), dim3(grid), dim3(kThreads), 0, s, d, total, lo, c.mod, tw, cs, add);
+        return;
+    }
     if constexpr (INVERSE && !RAW_OUT) {
         if (add != nullptr) {
             switch (r) {
@@ -276,23 +305,24 @@ static void strided(const NttContext& c, uint64_t* d, size_t total, int lo, int 
 }
 
 // tile pass of a two-pass transform (n > 4096): LT low bits, raw element hand-off on the other side
-template <class A>
+template <class A, bool PACKED = false>
 static void pass_forward(const NttContext& c, int lt, uint64_t* d, size_t total, hipStream_t s) {
     switch (lt) {
-        case 9: tile_fwd<A, 9, true, false>(c, d, total, s); break;
-        case 10: tile_fwd<A, 10, true, false>(c, d, total, s); break;
-        case 11: tile_fwd<A, 11, true, false>(c, d, total, s); break;
-        default: tile_fwd<A, 12, true, false>(c, d, total, s); break;
+        case 9: tile_fwd<A, 9, true, false, PACKED>(c, d, total, s); break;
+        case 10: tile_fwd<A, 10, true, false, PACKED>(c, d, total, s); break;
+        case 11: tile_fwd<A, 11, true, false, PACKED>(c, d, total, s); break;
+        default: tile_fwd<A, 12, true, false, PACKED>(c, d, total, s); break;
     }
 }
-template <class A>
+template <class A, bool PACKED = false>
 static void pass_inverse(const NttContext& c, int lt, uint64_t* d, size_t total, hipStream_t s, const uint64_t* pre) {
-    constexpr bool kDefer = A::kDeferredRecentre;     // the strided round of run_ntt re-centres on load
+    // the strided round of run_ntt re-centres on load — unless the hand-off is packed: 6 bytes hold the re-centred words only
+    constexpr bool kDefer = A::kDeferredRecentre && !PACKED;
     switch (lt) {
-        case 9: tile_inv<A, 9, false, true, kDefer>(c, d, total, s, nullptr, pre); break;
-        case 10: tile_inv<A, 10, false, true, kDefer>(c, d, total, s, nullptr, pre); break;
-        case 11: tile_inv<A, 11, false, true, kDefer>(c, d, total, s, nullptr, pre); break;
-        default: tile_inv<A, 12, false, true, kDefer>(c, d, total, s, nullptr, pre); break;
+        case 9: tile_inv<A, 9, false, true, kDefer, PACKED>(c, d, total, s, nullptr, pre); break;
+        case 10: tile_inv<A, 10, false, true, kDefer, PACKED>(c, d, total, s, nullptr, pre); break;
+        case 11: tile_inv<A, 11, false, true, kDefer, PACKED>(c, d, total, s, nullptr, pre); break;
+        default: tile_inv<A, 12, false, true, kDefer, PACKED>(c, d, total, s, nullptr, pre); break;
     }
 }
 
@@ -386,6 +416,18 @@ static void run_ntt(const NttContext& c, uint64_t* d, size_t batch, bool inverse
         uint64_t* base = d + (first << c.logn);
         const size_t count = now << c.logn;
         hipStream_t cs = s;
+        if constexpr (std::is_same_v<A, ArithF64>) {
+            if (c.handoff_bytes == 6) {   // the same two passes with the intermediate in 6 bytes per residue (build_context decided)
+                if (!inverse) {
+                    strided<A, false, false, true, false, true>(c, base, count, c.logn - r_top, r_top, cs, src ? src + (first << c.logn) : nullptr);
+                    pass_forward<A, true>(c, lt, base, count, cs);
+                } else {
+                    pass_inverse<A, true>(c, lt, base, count, cs, pre);
+                    strided<A, true, true, false, false, true>(c, base, count, c.logn - r_top, r_top, cs, add ? add + (first << c.logn) : nullptr);
+                }
+                continue;
+            }
+        }
         if (!inverse) {
             strided<A, false, false, true>(c, base, count, c.logn - r_top, r_top, cs, src ? src + (first << c.logn) : nullptr);
             if constexpr (std::is_same_v<A, ArithGold>) {
@@ -617,6 +659,7 @@ void ntt_context_free(NttContext* ctx) noexcept { lsr::destroy_ntt_context(ctx);
 int lsr_ntt_context_device(const NttContext* ctx) noexcept { return ctx ? ctx->device : -1; }
 uint64_t lsr_ntt_context_root(const NttContext* ctx) noexcept { return ctx ? ctx->psi : 0; }
 int lsr_ntt_context_uses_f64(const NttContext* ctx) noexcept { return ctx && ctx->use_f64 ? 1 : 0; }
+int lsr_ntt_handoff_bytes(const NttContext* ctx) noexcept { return ctx ? ctx->handoff_bytes : -1; }
 
 int ntt_forward(const NttContext* ctx, uint64_t* coeffs, uint32_t n) noexcept {
     if (!ctx || !coeffs || n != ctx->degree) return -1;   // ntt.cpp:81

@@ -47,6 +47,19 @@ struct RoundConsts {
 // lds_slot(lane) + lds_slot(constant), so every access is one lane address plus an immediate offset.
 __host__ __device__ constexpr uint32_t lds_slot(uint32_t idx) { return idx + (idx >> 4); }
 
+// ---- 6-byte hand-off of the two-pass FP64 transform (PACKED; conversion and bounds: lsr_arith.hpp pack48_from_f64) ----------------
+// The private intermediate between the strided round and the tile pass, in place in the caller's array: the 64 consecutive residues
+// a wavefront touches in one register row own their 512 bytes — [0, 256) the 64 low dwords, [256, 384) the 64 high halfwords,
+// [384, 512) never touched — so every access is whole 128-byte lines and a quarter of the hand-off's bytes stays off the fabric.
+// Residue i lives at dword (i & ~63) * 8 + (i & 63) * 4 and halfword (i & ~63) * 8 + 256 + (i & 63) * 2: every index bit has a fixed
+// weight, so for i = lane part | register part over disjoint bits both offsets split into one lane offset plus a constant.
+// In place without a barrier: the strided rounds read and write a cell from the same wavefront (lane -> consecutive index, 2^lo a
+// multiple of 64), and a wavefront's loads have all returned before its first store because every output of the round depends on every
+// input; the tile passes own whole cells and put a workgroup barrier between their global loads and stores anyway.
+constexpr uint32_t kPackedHalfwords = 256;     // byte offset of a cell's halfwords
+template <class T> __host__ __device__ constexpr T packed_lo_bytes(T i) { return ((i & ~(T)63) << 3) + ((i & (T)63) << 2); }
+template <class T> __host__ __device__ constexpr T packed_hi_bytes(T i) { return ((i & ~(T)63) << 3) + ((i & (T)63) << 1); }   // + kPackedHalfwords
+
 template <class A> __device__ __forceinline__ uint64_t elem_bits(typename A::elem v);
 template <> __device__ __forceinline__ uint64_t elem_bits<ArithF64>(double v) { return (uint64_t)__double_as_longlong(v); }
 template <> __device__ __forceinline__ uint64_t elem_bits<ArithU64>(uint64_t v) { return v; }
@@ -224,10 +237,12 @@ struct FuseIn {
     uint64_t* quotient = nullptr;         // [instances][m], natural order
     uint32_t* top = nullptr;              // [instances]: 1 + highest non-zero index
 };
-template <class A, int LT, bool RAW_IN, bool RAW_OUT, int MODE = 0>
+// PACKED (RAW_IN, FP64): the raw operands arrive in the 6-byte hand-off layout above.
+template <class A, int LT, bool RAW_IN, bool RAW_OUT, int MODE = 0, bool PACKED = false>
 __device__ __forceinline__ void tile_forward_body(uint64_t* __restrict__ data, size_t total, const ModParams& p,
                                                   const typename A::twid* __restrict__ tw, const uint64_t* __restrict__ src, uint32_t vblock,
                                                   const FuseIn& fuse = FuseIn{}) {
+    static_assert(!PACKED || (RAW_IN && !RAW_OUT && MODE == 0 && std::is_same_v<A, ArithF64>), "6-byte hand-off: second pass of the FP64 forward transform");
     __shared__ uint64_t lds[kLdsWords];
     using elem = typename A::elem;
     using twid = typename A::twid;
@@ -247,12 +262,26 @@ __device__ __forceinline__ void tile_forward_body(uint64_t* __restrict__ data, s
     {   // first round: operands straight from global memory in the round's own mapping
         constexpr int LO = TileRound<LT, 0>::LO, R = TileRound<LT, 0>::R;
         const uint32_t base = lane_base<LO, R>(t);
-        uint64_t raw[kRegs];
+        uint64_t raw[PACKED ? 1 : kRegs];
+        uint32_t low[PACKED ? kRegs : 1];
+        int16_t high[PACKED ? kRegs : 1];
+        if constexpr (PACKED) {
+            const uint32_t lane_lo = packed_lo_bytes(base), lane_hi = packed_hi_bytes(base);
 #pragma unroll
-        for (int k = 0; k < kRegs; ++k) raw[k] = buf_load64<RAW_OUT ? 0 : kAuxStream>(from, base * 8u, reg_offset<LO, R>(k) * 8u);
+            for (int k = 0; k < kRegs; ++k) {
+                low[k] = buf_load32<kAuxStream>(from, lane_lo, packed_lo_bytes(reg_offset<LO, R>(k)));
+                high[k] = buf_load16s<kAuxStream>(from, lane_hi, packed_hi_bytes(reg_offset<LO, R>(k)) + kPackedHalfwords);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) raw[k] = buf_load64<RAW_OUT ? 0 : kAuxStream>(from, base * 8u, reg_offset<LO, R>(k) * 8u);
+        }
         if constexpr (A::kScalarTopTwiddles && LT == kTileLog && RAW_IN) load_round_twiddles_uniform<A, LO, R, false>(w[0], block_pos, p.logn, tw);
         else load_round_twiddles<A, LO, R, false, false>(w[0], base, block_pos, nmask, p.logn, table);
-        if constexpr (MODE == 0) {
+        if constexpr (PACKED) {
+#pragma unroll
+            for (int k = 0; k < kRegs; ++k) v[k] = f64_from_pack48(low[k], high[k]);
+        } else if constexpr (MODE == 0) {
 #pragma unroll
             for (int k = 0; k < kRegs; ++k) v[k] = RAW_IN ? elem_from_bits<A>(raw[k]) : A::load(raw[k], p);
         } else {
@@ -373,10 +402,10 @@ __device__ __forceinline__ void tile_forward_body(uint64_t* __restrict__ data, s
         buf_store64<RAW_OUT ? 0 : kAuxStream>(tile, t * 8u, (uint32_t)k * kThreads * 8u, RAW_OUT ? bits : A::store_canonical(elem_from_bits<A>(bits), p));
     }
 }
-template <class A, int LT, bool RAW_IN, bool RAW_OUT>
+template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool PACKED = false>
 __global__ void __launch_bounds__(kThreads) ntt_tile_forward(uint64_t* __restrict__ data, size_t total, ModParams p,
                                                                const typename A::twid* __restrict__ tw, const uint64_t* __restrict__ src = nullptr) {
-    tile_forward_body<A, LT, RAW_IN, RAW_OUT>(data, total, p, tw, src, blockIdx.x);
+    tile_forward_body<A, LT, RAW_IN, RAW_OUT, 0, PACKED>(data, total, p, tw, src, blockIdx.x);
 }
 template <class A, int LT, int MODE>
 __global__ void __launch_bounds__(kThreads) ntt_tile_forward_fused(uint64_t* __restrict__ data, size_t total, ModParams p,
@@ -390,11 +419,14 @@ __global__ void __launch_bounds__(kThreads) ntt_tile_forward_fused(uint64_t* __r
 // operator fused into the read-in (the coset twist of the prover's quotient pipeline, lsr_prover.hip).
 // DEFER (first pass of a two-pass inverse, flavours with A::kDeferredRecentre): the last round's outputs are stored as they leave the
 // butterflies, |x| <= 32 q; the strided round that follows re-centres them on load (strided_round_body RECENTRE_IN), where the VALU idles.
-template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool PRE = false, bool DEFER = false>
+// PACKED (RAW_OUT, FP64, never with DEFER: the un-centred words need 50 bits): the last round re-centres its outputs, |x| <= q / 2 + 1,
+// and stores them in the 6-byte hand-off layout.
+template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool PRE = false, bool DEFER = false, bool PACKED = false>
 __device__ __forceinline__ void tile_inverse_body(uint64_t* __restrict__ data, size_t total, const ModParams& p,
                                                   const typename A::twid* __restrict__ tw, const RoundConsts<A>& cs,
                                                   const uint64_t* __restrict__ add, const uint64_t* __restrict__ pre, uint32_t vblock) {
     static_assert(!DEFER || (RAW_OUT && A::kDeferredRecentre), "deferred re-centring: the raw hand-off of a flavour that re-centres");
+    static_assert(!PACKED || (RAW_OUT && !RAW_IN && !DEFER && std::is_same_v<A, ArithF64>), "6-byte hand-off: first pass of the FP64 inverse transform, re-centred");
     __shared__ uint64_t lds[kLdsWords];
     using elem = typename A::elem;
     using twid = typename A::twid;
@@ -478,6 +510,16 @@ __device__ __forceinline__ void tile_inverse_body(uint64_t* __restrict__ data, s
 #pragma unroll
                 for (int k = 0; k < kRegs; ++k)
                     buf_store64<kAuxStream>(tile, base * 8u, reg_offset<LO, R>(k) * 8u, A::store_reduced_plus(v[k], blind[k], p));
+            } else if constexpr (PACKED) {
+                const uint32_t lane_lo = packed_lo_bytes(base), lane_hi = packed_hi_bytes(base);
+#pragma unroll
+                for (int k = 0; k < kRegs; ++k) {
+                    uint32_t low;
+                    uint16_t high;
+                    pack48_from_f64(v[k], low, high);
+                    buf_store32(tile, lane_lo, packed_lo_bytes(reg_offset<LO, R>(k)), low);
+                    buf_store16(tile, lane_hi, packed_hi_bytes(reg_offset<LO, R>(k)) + kPackedHalfwords, high);
+                }
             } else {
 #pragma unroll
                 for (int k = 0; k < kRegs; ++k)
@@ -490,11 +532,11 @@ __device__ __forceinline__ void tile_inverse_body(uint64_t* __restrict__ data, s
         }
     });
 }
-template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool PRE = false, bool DEFER = false>
+template <class A, int LT, bool RAW_IN, bool RAW_OUT, bool PRE = false, bool DEFER = false, bool PACKED = false>
 __global__ void __launch_bounds__(kThreads) ntt_tile_inverse(uint64_t* __restrict__ data, size_t total, ModParams p,
                                                                const typename A::twid* __restrict__ tw, RoundConsts<A> cs,
                                                                const uint64_t* __restrict__ add, const uint64_t* __restrict__ pre = nullptr) {
-    tile_inverse_body<A, LT, RAW_IN, RAW_OUT, PRE, DEFER>(data, total, p, tw, cs, add, pre, blockIdx.x);
+    tile_inverse_body<A, LT, RAW_IN, RAW_OUT, PRE, DEFER, PACKED>(data, total, p, tw, cs, add, pre, blockIdx.x);
 }
 
 // ---- ring multiply c = a b in the tile (lsr_ring_mul.hip) --------------------------------------------
@@ -889,7 +931,9 @@ __global__ void __launch_bounds__(kThreads) ntt_tile_ring_dot(uint64_t* c, const
 // RECENTRE_IN (last pass of run_ntt's two-pass inverse, whose tile pass ran with DEFER): the raw operands are the un-centred outputs
 // of the tile pass's last round, index bits [lo - 4, lo).  1: re-centre the words of the class that can exceed 2 q (needs_recentre:
 // index bits lo - 2 and lo - 1 clear — the same for a lane's 2^R words, and for a whole wavefront since lo >= 9); 2: re-centre all.
-template <class A, int R, bool INVERSE, bool RAW_IN, bool RAW_OUT, bool ADD, int SM, int RECENTRE_IN = 0>
+// PACKED (run_ntt's FP64 two-pass transform when the context allows it): the raw side of the round — the outputs of a forward round, the
+// operands of an inverse one — is in the 6-byte hand-off layout (top of this file); the canonical side is unchanged.
+template <class A, int R, bool INVERSE, bool RAW_IN, bool RAW_OUT, bool ADD, int SM, int RECENTRE_IN = 0, bool PACKED = false>
 __device__ __forceinline__ void strided_round_body(uint64_t* __restrict__ data, size_t total, int lo, ModParams p,
                                                    const typename A::twid* __restrict__ tw, RoundConsts<A> cs,
                                                    const uint64_t* __restrict__ add, const BlindSampler& bs, uint32_t vblock = blockIdx.x,
@@ -902,6 +946,8 @@ __device__ __forceinline__ void strided_round_body(uint64_t* __restrict__ data, 
     static_assert(SM != 3 || (!INVERSE && !ADD), "the forward round only prepares samples");
     static_assert(RECENTRE_IN == 0 || (INVERSE && RAW_IN && !RAW_OUT && SM == 0 && A::kDeferredRecentre), "deferred re-centring: run_ntt's last inverse pass");
     static_assert(RECENTRE_IN != 1 || R <= 4, "five stages need every operand re-centred (32 sums of 1.75 q pass 2^50 for q near 2^45)");
+    static_assert(!PACKED || (std::is_same_v<A, ArithF64> && SM == 0 && RECENTRE_IN == 0 && RAW_IN == INVERSE && RAW_OUT == !INVERSE),
+                  "6-byte hand-off: the two strided rounds of run_ntt<ArithF64>, re-centred operands");
     using elem = typename A::elem;
     constexpr int N = 1 << R;
     const size_t group = (size_t)vblock * kThreads + vthread;
@@ -913,7 +959,24 @@ __device__ __forceinline__ void strided_round_body(uint64_t* __restrict__ data, 
     const uint64_t* const from = (!INVERSE && add != nullptr) ? add : data;
     // streaming policy: the last pass of an inverse transform, and operands read out of place (the caller's array is read once)
     const bool stream_in = (LSR_NT_LAST_PASS && INVERSE && !RAW_OUT) || (LSR_NT_COMMIT_INPUTS && !INVERSE && add != nullptr);
-    if (stream_in) {
+    // (PACKED: row k of a lane's words starts k << lo residues = (k << lo) * 8 bytes further on — 2^lo is a multiple of the 64-residue cell)
+    // In place the same bytes are read as uint64_t and written as uint32_t / uint16_t (forward; the inverse round the other way round),
+    // types that type-based alias analysis treats as disjoint, so the compiler is NOT held to program order by the addresses.  What holds
+    // it — and, in the hardware, what makes every load of the wavefront return before its first store issues — is data dependence alone:
+    // each stored value is a function of all 2^R loaded ones (R full butterfly stages).  A variant of this round whose outputs did not
+    // depend on every input (a partial round, a copy-through row) would need an explicit fence between its loads and its stores.
+    char* const cell_lo = reinterpret_cast<char*>(data) + packed_lo_bytes(idx0);
+    char* const cell_hi = reinterpret_cast<char*>(data) + packed_hi_bytes(idx0) + kPackedHalfwords;
+    if constexpr (PACKED && RAW_IN) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const uint32_t* const pl = reinterpret_cast<const uint32_t*>(cell_lo + ((size_t)k << (lo + 3)));
+            const int16_t* const ph = reinterpret_cast<const int16_t*>(cell_hi + ((size_t)k << (lo + 3)));
+            const uint32_t low = stream_in ? __builtin_nontemporal_load(pl) : *pl;
+            const int16_t high = stream_in ? __builtin_nontemporal_load(ph) : *ph;
+            v[k] = f64_from_pack48(low, high);
+        }
+    } else if (stream_in) {
 #pragma unroll
         for (int k = 0; k < N; ++k) {
             const uint64_t raw = __builtin_nontemporal_load(from + idx0 + ((size_t)k << lo));
@@ -1047,6 +1110,17 @@ __device__ __forceinline__ void strided_round_body(uint64_t* __restrict__ data, 
             for (int k = 0; k < N; ++k) A::end_of_inverse_round(v[k], p);
         }
     }
+    if constexpr (PACKED && RAW_OUT) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            uint32_t low;
+            uint16_t high;
+            pack48_from_f64(v[k], low, high);
+            *reinterpret_cast<uint32_t*>(cell_lo + ((size_t)k << (lo + 3))) = low;
+            *reinterpret_cast<uint16_t*>(cell_hi + ((size_t)k << (lo + 3))) = high;
+        }
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         const size_t gi = idx0 + ((size_t)k << lo);
@@ -1059,11 +1133,11 @@ __device__ __forceinline__ void strided_round_body(uint64_t* __restrict__ data, 
     }
 }
 
-template <class A, int R, bool INVERSE, bool RAW_IN, bool RAW_OUT, bool ADD, int RECENTRE_IN = 0>
+template <class A, int R, bool INVERSE, bool RAW_IN, bool RAW_OUT, bool ADD, int RECENTRE_IN = 0, bool PACKED = false>
 __global__ void __launch_bounds__(kThreads) ntt_strided_round(uint64_t* __restrict__ data, size_t total, int lo, ModParams p,
                                                                 const typename A::twid* __restrict__ tw, RoundConsts<A> cs,
                                                                 const uint64_t* __restrict__ add) {
-    strided_round_body<A, R, INVERSE, RAW_IN, RAW_OUT, ADD, 0, RECENTRE_IN>(data, total, lo, p, tw, cs, add, BlindSampler{});
+    strided_round_body<A, R, INVERSE, RAW_IN, RAW_OUT, ADD, 0, RECENTRE_IN, PACKED>(data, total, lo, p, tw, cs, add, BlindSampler{});
 }
 
 // last pass of an inverse transform with the blinding residues sampled in place (dynamic LDS: table + sample tile); HALF: the first

@@ -193,6 +193,8 @@ struct NttContext {
     int logn = 0;
     int device = 0;
     bool use_f64 = false;
+    int handoff_bytes = 8;   // bytes per residue of the private intermediate between the two passes of run_ntt (n > 4096): 8, or 6 when the
+                             // FP64 flavour's hand-off words fit 48 bits (lsr_ntt.hip handoff_is_packed)
     bool gold = false;       // modulus = NTT_MODULUS (2^64 - 2^32 + 1): ArithGold kernels
     bool cyclic = false;     // cyclic twiddle tables (prover path) instead of negacyclic; psi then holds omega
     uint64_t psi = 0;

@@ -98,6 +98,76 @@ __global__ void __launch_bounds__(256) pass1_deep(uint64_t* __restrict__ d, size
     for (int k = 0; k < ROWS; ++k) d[idx0 + ((size_t)k << SH)] = v[k];
 }
 
+// round 18: the intermediate between the two passes stored as 4 + 2 bytes per residue IN PLACE (the fake values keep 48 bits).
+// LAYOUT 1, wave cells: the 64 consecutive residues a wavefront touches in one register row own 512 B — bytes [0, 256) the 64 low
+//   dwords, [256, 384) the 64 high halfwords, [384, 512) untouched; every access is whole 128-byte lines.  Writers and readers of a cell
+//   are one wavefront, so no barrier: in place this is safe because a wavefront's 16 loads have all returned before its first store —
+//   every output depends on every input (the sum `s` below keeps that dependence of the real butterflies in the fake arithmetic).
+// LAYOUT 2, workgroup cells: the same per 2 KiB row segment of a 256-lane workgroup (1 KiB dwords, 512 B halfwords, 512 B hole); other
+//   wavefronts' dwords land on bytes this wavefront reads, so one __syncthreads() separates the loads from the stores.
+template <int LAYOUT> __device__ __forceinline__ size_t packed_lo(size_t i) {
+    return LAYOUT == 1 ? ((i >> 6) << 9) + ((i & 63) << 2) : ((i >> 8) << 11) + ((i & 255) << 2);
+}
+template <int LAYOUT> __device__ __forceinline__ size_t packed_hi(size_t i) {
+    return LAYOUT == 1 ? ((i >> 6) << 9) + 256 + ((i & 63) << 1) : ((i >> 8) << 11) + 1024 + ((i & 255) << 1);
+}
+template <int LAYOUT, bool NT> __device__ __forceinline__ uint64_t ld_packed(const uint64_t* d, size_t i) {
+    const char* const b = reinterpret_cast<const char*>(d);
+    const uint32_t* const pl = reinterpret_cast<const uint32_t*>(b + packed_lo<LAYOUT>(i));
+    const int16_t* const ph = reinterpret_cast<const int16_t*>(b + packed_hi<LAYOUT>(i));
+    const uint32_t lo = NT ? __builtin_nontemporal_load(pl) : *pl;
+    const int16_t hi = NT ? __builtin_nontemporal_load(ph) : *ph;
+    return (uint64_t)lo | ((uint64_t)(int64_t)hi << 32);
+}
+template <int LAYOUT> __device__ __forceinline__ void st_packed(uint64_t* d, size_t i, uint64_t v) {
+    char* const b = reinterpret_cast<char*>(d);
+    *reinterpret_cast<uint32_t*>(b + packed_lo<LAYOUT>(i)) = (uint32_t)v;
+    *reinterpret_cast<uint16_t*>(b + packed_hi<LAYOUT>(i)) = (uint16_t)(v >> 32);
+}
+// pass 1 (strided rows, plain u64 loads as the library's first pass) writing the packed intermediate over its own operands
+template <int LAYOUT>
+__global__ void __launch_bounds__(256) pass1_packed(uint64_t* d, size_t total) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= total / 16) return;                         // whole workgroups (total / 16 is a multiple of 256)
+    const size_t idx0 = ((g >> 12) << 16) | (g & 4095);
+    uint64_t v[16], s = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = d[idx0 + ((size_t)k << 12)];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s += v[k];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = v[k] * 3 + s;
+    if (LAYOUT == 2) __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) st_packed<LAYOUT>(d, idx0 + ((size_t)k << 12), v[k]);
+}
+// pass 2 (contiguous tiles) reading the packed intermediate with streaming loads, writing u64 with streaming stores
+template <int LAYOUT>
+__global__ void __launch_bounds__(256) pass2_packed(uint64_t* d, size_t total) {
+    const size_t base = (size_t)blockIdx.x * 4096 + threadIdx.x;
+    uint64_t v[16], s = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = ld_packed<LAYOUT, true>(d, base + (size_t)k * 256);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) s += v[k];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = v[k] * 5 + s;
+    if (LAYOUT == 2) __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) __builtin_nontemporal_store(v[k], d + base + (size_t)k * 256);
+}
+
+struct Spread { float lo, med, hi; };
+template <class F> static Spread timed_spread(F&& launch, hipEvent_t a, hipEvent_t b) {
+    std::vector<float> ms;
+    for (int rep = 0; rep < 9; ++rep) {
+        hipEventRecord(a); launch(); hipEventRecord(b); hipEventSynchronize(b);
+        float t; hipEventElapsedTime(&t, a, b); ms.push_back(t);
+    }
+    std::sort(ms.begin(), ms.end());
+    return {ms.front(), ms[ms.size() / 2], ms.back()};
+}
+
 template <class F> static float timed(F&& launch, hipEvent_t a, hipEvent_t b) {
     std::vector<float> ms;
     for (int rep = 0; rep < 7; ++rep) {
@@ -161,5 +231,19 @@ int main() {
     printf("pass1 strided 2^4 rows per lane        %.3f\n", RUND(4));
     printf("pass1 strided 2^5 rows per lane        %.3f\n", RUND(5));
     printf("pass1 strided 2^6 rows per lane        %.3f\n", RUND(6));
+    // round 18: packed in-place hand-off against the 8-byte one, three interleaved rounds of 9 repeats each (min / median / max)
+#define RUNP(LAYOUT) timed_spread([&] { for (size_t c = 0; c < polys; c += chunk_polys) { \
+        hipLaunchKernelGGL((pass1_packed<LAYOUT>), dim3((unsigned)(chunk / 16 / 256)), dim3(256), 0, 0, data + c * n, chunk); \
+        hipLaunchKernelGGL((pass2_packed<LAYOUT>), dim3((unsigned)(chunk / 4096)), dim3(256), 0, 0, data + c * n, chunk); } }, a, b)
+#define RUNB9(W1, L1, S1, W2, L2, S2) timed_spread([&] { for (size_t c = 0; c < polys; c += chunk_polys) { \
+        hipLaunchKernelGGL((pass1<W1, L1, S1>), dim3((unsigned)(chunk / 16 / 256 / W1)), dim3(256), 0, 0, data + c * n, chunk); \
+        hipLaunchKernelGGL((pass2<W2, L2, S2>), dim3((unsigned)(chunk / 4096)), dim3(256), 0, 0, data + c * n, chunk); } }, a, b)
+    for (int round = 0; round < 3; ++round) {
+        const Spread u = RUNB9(1, false, false, 1, true, true), w = RUNP(1), g = RUNP(2);
+        printf("round %d  both 8B plain / 8B nt-load+store, in place     min %.3f  median %.3f  max %.3f\n", round, u.lo, u.med, u.hi);
+        printf("round %d  both 6B wave cells (4 B + 2 B), in place       min %.3f  median %.3f  max %.3f\n", round, w.lo, w.med, w.hi);
+        printf("round %d  both 6B workgroup cells (4 B + 2 B), in place  min %.3f  median %.3f  max %.3f\n", round, g.lo, g.med, g.hi);
+    }
+    CK(hipDeviceSynchronize());
     return 0;
 }
