@@ -112,6 +112,56 @@ int lsr_ntt_ring_dot_batch(const NttContext* ctx, uint64_t* c, const uint64_t* a
 int lsr_ntt_ring_dot_batch_device(const NttContext* ctx, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b,
                                   size_t batch, size_t terms, size_t b_rows, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: batched ring matrix-vector product with a resident matrix ---------------- */
+/* y_j = M x_j over the ring of the context (as lsr_ntt_ring_mul_batch: X^n + 1 on negacyclic contexts, X^n - 1 on cyclic ones):
+ * y[j][r] = sum_{c < cols} M[r][c] * x[j][c] — a module-SIS / Ajtai commitment, a fold of many rows by a matrix of ring-valued
+ * challenges.  m: [rows][cols][n]; x: [batch][cols][n]; y: [batch][rows][n].  Natural coefficient order in and out; m and x under
+ * the operand contract of lsr_ntt_ring_dot_batch's b and a (inputs in [0,q)); outputs canonical, equal word for word to
+ * lsr_ntt_ring_dot_batch(ctx, ., x, M[r], batch, cols, 1) row by row.
+ *
+ * The matrix handle.  lsr_ntt_ring_matrix_create(_device) copies M to the context's device and keeps it there in the form the
+ * product reads: at n <= 4096 the forward transform of every entry, computed once; above, M as given.  The handle owns that copy:
+ * the caller's buffer may be changed or freed once lsr_ntt_ring_matrix_create returns (host pointer m) — for
+ * lsr_ntt_ring_matrix_create_device (device pointer d_m, asynchronous on `stream`) once the work enqueued on `stream` up to that
+ * point is done; products on any stream start behind it.  The handle is immutable after creation: products on one matrix may be
+ * issued from several threads and on several streams.  The context must outlive the matrix: free every matrix of a context
+ * (lsr_ntt_ring_matrix_free, NULL-safe, waits for products still reading the matrix) before ntt_context_free.
+ * lsr_ntt_ring_matrix_rows / _cols: the dimensions; _row_block: the number of rows one workgroup of the n <= 4096 kernel keeps in
+ * registers (a property of the context's arithmetic flavour; 1 above n = 4096) — all three 0 on NULL.
+ *
+ * Limits: rows in [1, LSR_RING_MATVEC_MAX_ROWS], cols in [1, LSR_RING_DOT_MAX_TERMS] (the x words and the y words of one tile are
+ * each addressed through one 32-bit buffer range, which these two caps keep below 2^31 bytes: every cols within the cap goes through
+ * one launch, there are no column groups), rows * cols * n * 8 <= LSR_RING_MATVEC_MAX_MATRIX_BYTES (the device copy; the kernel
+ * addresses M one polynomial at a time from a 64-bit pointer).
+ *
+ * Refusals of create (NULL and lsr_last_error, before any device work), in this order: NULL ctx or m; rows == 0; cols == 0; rows
+ * above LSR_RING_MATVEC_MAX_ROWS; cols above LSR_RING_DOT_MAX_TERMS; rows * cols * 16 above LSR_RING_MATVEC_MAX_MATRIX_BYTES (over
+ * the cap at any n) — all of these without reading the context; then a context above n = 131072 (as lsr_ntt_ring_dot_batch);
+ * rows * cols * n * 8 above the cap; no visible device.
+ * Refusals of the product (-1 and lsr_last_error, before any device work): NULL mat, y or x.  Then batch == 0 is a no-op that
+ * returns 0.  Then: y overlapping x in address range; no visible device.
+ *
+ * lsr_ntt_ring_matvec_batch: host buffers, staged through bounded device chunks; returns when y is complete.
+ * lsr_ntt_ring_matvec_batch_device: device buffers on the context's device, asynchronous on `stream` (enqueues only).
+ *
+ * n <= 4096: one launch per call, no workspace, no ordering against other calls beyond the streams' own.  n > 4096: one ring inner
+ * product per row and chunk of the batch plus a strided copy, through lsr_ntt_ring_dot_batch_device's workspace and a dense chunk
+ * the first create on the context allocates (sizes fixed by n alone); ordering and graph capture are lsr_ntt_ring_dot_batch's — same
+ * mutex, same event, one eager product before capturing. */
+#define LSR_RING_MATVEC_MAX_ROWS 32768
+#define LSR_RING_MATVEC_MAX_MATRIX_BYTES 1073741824
+typedef struct LsrRingMatrix LsrRingMatrix;
+LsrRingMatrix* lsr_ntt_ring_matrix_create(const NttContext* ctx, const uint64_t* m, size_t rows, size_t cols) LSR_NOEXCEPT;
+LsrRingMatrix* lsr_ntt_ring_matrix_create_device(const NttContext* ctx, const uint64_t* d_m, size_t rows, size_t cols,
+                                                 void* stream) LSR_NOEXCEPT;
+void lsr_ntt_ring_matrix_free(LsrRingMatrix* mat) LSR_NOEXCEPT;
+size_t lsr_ntt_ring_matrix_rows(const LsrRingMatrix* mat) LSR_NOEXCEPT;
+size_t lsr_ntt_ring_matrix_cols(const LsrRingMatrix* mat) LSR_NOEXCEPT;
+size_t lsr_ntt_ring_matrix_row_block(const LsrRingMatrix* mat) LSR_NOEXCEPT;
+int lsr_ntt_ring_matvec_batch(const LsrRingMatrix* mat, uint64_t* y, const uint64_t* x, size_t batch) LSR_NOEXCEPT;
+int lsr_ntt_ring_matvec_batch_device(const LsrRingMatrix* mat, uint64_t* d_y, const uint64_t* d_x, size_t batch,
+                                     void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -84,6 +84,89 @@ def _ring_dot(lib, handle, n, a, b):
 def _ring_dot_device(lib, handle, d_c, d_a, d_b, batch, terms, b_rows, stream):
     if lib.lsr_ntt_ring_dot_batch_device(handle, d_c, d_a, d_b, batch, terms, b_rows, stream) != 0:
         raise CoreError("lsr_ntt_ring_dot_batch_device failed: " + _abi.last_error())
+
+
+# batch.h LSR_RING_MATVEC_MAX_ROWS / LSR_RING_MATVEC_MAX_MATRIX_BYTES: the caps on a RingMatrix (cols is capped by RING_DOT_MAX_TERMS)
+RING_MATVEC_MAX_ROWS = 32768
+RING_MATVEC_MAX_MATRIX_BYTES = 1 << 30
+
+
+class RingMatrix:
+    """A rows x cols matrix of ring elements resident on a context's device (``LsrRingMatrix*``, batch.h): ``matvec`` computes
+    y_j = M x_j in the context's ring.  Made by ``NttContext.ring_matrix`` / ``CyclicNtt.ring_matrix`` (host array) or
+    ``ring_matrix_device`` (device pointer).  Holds a reference to its context, which must stay open for every ``matvec``; ``close()`` itself does not read the context,
+    so closing (or collecting) the matrix after its context is safe."""
+
+    def __init__(self, ctx, handle):
+        self._ctx, self._lib, self._h, self.n = ctx, ctx._lib, handle, ctx.n
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def rows(self):
+        return self._lib.lsr_ntt_ring_matrix_rows(self._h)
+
+    @property
+    def cols(self):
+        return self._lib.lsr_ntt_ring_matrix_cols(self._h)
+
+    @property
+    def row_block(self):
+        """Rows of M one workgroup of the n <= 4096 kernel keeps in registers (1 above n = 4096)."""
+        return self._lib.lsr_ntt_ring_matrix_row_block(self._h)
+
+    def matvec(self, x):
+        """x is [cols, n] (one vector, returns [rows, n]) or [batch, cols, n] (returns [batch, rows, n]); numpy in and out."""
+        x_in = _u64_array(x)
+        if x_in.ndim not in (2, 3) or x_in.shape[-2:] != (self.cols, self.n):
+            raise ValueError("x must be [cols, n] or [batch, cols, n]")
+        x3 = np.ascontiguousarray(x_in.reshape(-1, self.cols, self.n))
+        out = np.empty((x3.shape[0], self.rows, self.n), dtype=np.uint64)
+        if self._lib.lsr_ntt_ring_matvec_batch(self._h, out.ctypes.data, x3.ctypes.data, x3.shape[0]) != 0:
+            raise CoreError("lsr_ntt_ring_matvec_batch failed: " + _abi.last_error())
+        return out[0] if x_in.ndim == 2 else out
+
+    def matvec_device(self, d_y, d_x, batch, stream=0):
+        """Device buffers: y [batch][rows][n], x [batch][cols][n], asynchronous on `stream`."""
+        if self._lib.lsr_ntt_ring_matvec_batch_device(self._h, d_y, d_x, batch, stream) != 0:
+            raise CoreError("lsr_ntt_ring_matvec_batch_device failed: " + _abi.last_error())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.lsr_ntt_ring_matrix_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _ring_matrix(ctx, m):
+    m_in = _u64_array(m)
+    if m_in.ndim != 3 or m_in.shape[-1] != ctx.n:
+        raise ValueError("m must be [rows, cols, n]")
+    m3 = np.ascontiguousarray(m_in)
+    handle = ctx._lib.lsr_ntt_ring_matrix_create(ctx._h, m3.ctypes.data, m3.shape[0], m3.shape[1])
+    if not handle:
+        raise CoreError("lsr_ntt_ring_matrix_create failed: " + _abi.last_error())
+    return RingMatrix(ctx, handle)
+
+
+def _ring_matrix_device(ctx, d_m, rows, cols, stream):
+    handle = ctx._lib.lsr_ntt_ring_matrix_create_device(ctx._h, d_m, rows, cols, stream)
+    if not handle:
+        raise CoreError("lsr_ntt_ring_matrix_create_device failed: " + _abi.last_error())
+    return RingMatrix(ctx, handle)
 
 
 class NttContext:
@@ -189,6 +272,15 @@ class NttContext:
     def ring_dot_device(self, d_c, d_a, d_b, batch, terms, b_rows, stream=0):
         """Device buffers: c [batch][n], a [batch][terms][n], b [b_rows][terms][n] (b_rows 1 or batch), asynchronous on `stream`."""
         _ring_dot_device(self._lib, self._h, d_c, d_a, d_b, batch, terms, b_rows, stream)
+
+    # --- ring matrix-vector product y = M x with a matrix resident on the device ---
+    def ring_matrix(self, m):
+        """A RingMatrix of m [rows, cols, n] (host array; copied and, at n <= 4096, transformed once)."""
+        return _ring_matrix(self, m)
+
+    def ring_matrix_device(self, d_m, rows, cols, stream=0):
+        """A RingMatrix of the device buffer d_m [rows][cols][n], asynchronous on `stream`."""
+        return _ring_matrix_device(self, d_m, rows, cols, stream)
 
 
 class Params:
@@ -731,6 +823,13 @@ class CyclicNtt:
 
     def ring_dot_device(self, d_c, d_a, d_b, batch, terms, b_rows, stream=0):
         _ring_dot_device(self._lib, self._h, d_c, d_a, d_b, batch, terms, b_rows, stream)
+
+    def ring_matrix(self, m):
+        """A RingMatrix of m [rows, cols, n] over Z_q[X]/(X^n - 1); as NttContext.ring_matrix."""
+        return _ring_matrix(self, m)
+
+    def ring_matrix_device(self, d_m, rows, cols, stream=0):
+        return _ring_matrix_device(self, d_m, rows, cols, stream)
 
     def close(self):
         if self._h:

@@ -223,6 +223,12 @@ struct NttContext {
     // workspace of lsr_ntt_ring_dot_batch(_device) (lsr_ring_dot.hip), under the same rules and the same mutex and event: a buffer of
     // its own, because neither workspace is ever resized and the two calls need different sizes
     mutable lsr::DeviceBuffer<uint64_t> ring_dot_scratch;
+    // n > 4096 route of lsr_ntt_ring_matvec_batch(_device) (lsr_ring_matvec.hip): one dense chunk of ring_dot outputs on its way to
+    // the strided rows of y.  Allocated by the first lsr_ntt_ring_matrix_create(_device) on the context at a size fixed by n alone,
+    // never resized.  ring_matvec_mutex is held for a whole call (taken before ring_mutex, never the other way round); the call
+    // records ring_event after its last copy out of the buffer, so the next ring call starts behind it.
+    mutable std::mutex ring_matvec_mutex;
+    mutable lsr::DeviceBuffer<uint64_t> ring_matvec_scratch;
 };
 
 namespace lsr {
