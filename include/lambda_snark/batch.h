@@ -162,6 +162,56 @@ int lsr_ntt_ring_matvec_batch(const LsrRingMatrix* mat, uint64_t* y, const uint6
 int lsr_ntt_ring_matvec_batch_device(const LsrRingMatrix* mat, uint64_t* d_y, const uint64_t* d_x, size_t batch,
                                      void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: gadget decomposition, norm check and the fused product y = M G^-1(x) ---------------- */
+/* An Ajtai commitment y = M x binds only when x is short.  These calls write arbitrary ring elements in small balanced digits, check
+ * that an opened vector is short, and commit to the digits without materialising them.
+ *
+ * Parameters: b = base_log2, B = 2^b, D = digits, off = (B/2) (B^D - 1) / (B - 1) — B/2 in every digit position.
+ * (b, D) is ADMISSIBLE for q when 2 <= b <= 32, D >= 1, b D <= 64; B/2 <= floor(q/2) (every digit is its own centred representative);
+ * floor((q - 1)/2) <= off; floor(q/2) <= B^D - 1 - off.
+ * lsr_ring_gadget_min_digits(q, base_log2): the smallest admissible D, 0 when there is none (e.g. every b for q = 2^64 - 2^32 + 1,
+ * so cyclic Goldilocks contexts are refused by the rule itself).  Host only, no device needed.
+ *
+ * Digits.  For x in [0, q): v = x if x <= floor(q/2), else x - q; u = v + off, so 0 <= u < B^D <= 2^64 and wrapping 64-bit arithmetic
+ * is exact.  Digit d is z_d = ((u >> b d) & (B - 1)) - B/2 in [-B/2, B/2 - 1], stored as the canonical residue (z_d, or q + z_d when
+ * negative); sum_d z_d B^d = v exactly.  There is no carry chain: digit d is a function of the word and d alone.
+ * G^-1 of a vector x [batch][xcols][n] is [batch][xcols D][n] with column c D + d = digit d of x[.][c], coefficient by coefficient.
+ *
+ * lsr_ntt_ring_decompose_batch(_device): x [count][n] in [0, q) -> out [count][digits][n].  Every ring degree and arithmetic flavour a
+ *   context has; no workspace, so a device call can be captured into a HIP graph from the first call.  out must not overlap x.
+ * lsr_ntt_ring_recompose_batch(_device): out[j] = sum_d B^d z[j][d] mod q for ANY canonical z [count][digits][n], short or not — the
+ *   gadget product G z.  Needs only 2 <= b <= 32, D >= 1, b (D - 1) <= 64, not admissibility.  out must not overlap z.
+ * lsr_ntt_ring_linf_batch(_device): linf[j] = max over the n coefficients of |centred x[j]|, x [count][n]; UINT64_MAX when some word of
+ *   element j is >= q (a verifier passes untrusted data: the case is defined, and the other elements are unaffected).  The l2 norm is
+ *   not offered: n (q/2)^2 does not fit 64 bits.
+ * lsr_ntt_ring_matvec_gadget_batch(_device): x [batch][xcols][n] with xcols * digits == lsr_ntt_ring_matrix_cols(mat) ->
+ *   y [batch][rows][n] = lsr_ntt_ring_matvec_batch(mat, G^-1(x)) word for word.  n <= 4096: one launch, no workspace (the digits are
+ *   extracted as the tile kernel loads x).  n > 4096 is refused: there lsr_ntt_ring_matvec_batch is itself a composed route, so
+ *   decompose into a temporary and call it.
+ * The plain forms take host buffers, staged through bounded device chunks, and return when the output is complete; the _device forms
+ * take device buffers on the context's device and are asynchronous on `stream` (enqueue only).
+ *
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL handle or buffer; (2) the
+ * rules that do not read the context: b outside [2, 32], D == 0, b D > 64 (recompose: b (D - 1) > 64); (3) decompose and the fused
+ * product: (b, D) not admissible for the context's q; (4) fused product: cols % digits != 0.  (5) Then count == 0 / batch == 0 is a
+ * no-op that returns 0.  Then (6) the output overlapping the operand in address range; (7) fused product: n above 4096; (8) no
+ * visible device. */
+uint64_t lsr_ring_gadget_min_digits(uint64_t q, unsigned base_log2) LSR_NOEXCEPT;
+int lsr_ntt_ring_decompose_batch(const NttContext* ctx, uint64_t* out, const uint64_t* x, size_t count, unsigned base_log2,
+                                 size_t digits) LSR_NOEXCEPT;
+int lsr_ntt_ring_decompose_batch_device(const NttContext* ctx, uint64_t* d_out, const uint64_t* d_x, size_t count, unsigned base_log2,
+                                        size_t digits, void* stream) LSR_NOEXCEPT;
+int lsr_ntt_ring_recompose_batch(const NttContext* ctx, uint64_t* out, const uint64_t* z, size_t count, unsigned base_log2,
+                                 size_t digits) LSR_NOEXCEPT;
+int lsr_ntt_ring_recompose_batch_device(const NttContext* ctx, uint64_t* d_out, const uint64_t* d_z, size_t count, unsigned base_log2,
+                                        size_t digits, void* stream) LSR_NOEXCEPT;
+int lsr_ntt_ring_linf_batch(const NttContext* ctx, const uint64_t* x, size_t count, uint64_t* linf) LSR_NOEXCEPT;
+int lsr_ntt_ring_linf_batch_device(const NttContext* ctx, const uint64_t* d_x, size_t count, uint64_t* d_linf, void* stream) LSR_NOEXCEPT;
+int lsr_ntt_ring_matvec_gadget_batch(const LsrRingMatrix* mat, uint64_t* y, const uint64_t* x, size_t batch, unsigned base_log2,
+                                     size_t digits) LSR_NOEXCEPT;
+int lsr_ntt_ring_matvec_gadget_batch_device(const LsrRingMatrix* mat, uint64_t* d_y, const uint64_t* d_x, size_t batch,
+                                            unsigned base_log2, size_t digits, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -133,6 +133,23 @@ class RingMatrix:
         if self._lib.lsr_ntt_ring_matvec_batch_device(self._h, d_y, d_x, batch, stream) != 0:
             raise CoreError("lsr_ntt_ring_matvec_batch_device failed: " + _abi.last_error())
 
+    def matvec_gadget(self, x, base_log2, digits):
+        """y = M G^-1(x) without the decomposed vector (n <= 4096): x is [xcols, n] or [batch, xcols, n] with xcols * digits == cols;
+        equal to ``matvec(ctx.ring_decompose(x, base_log2, digits))`` word for word."""
+        x_in = _u64_array(x)
+        if x_in.ndim not in (2, 3) or x_in.shape[-1] != self.n or x_in.shape[-2] * int(digits) != self.cols:
+            raise ValueError("x must be [xcols, n] or [batch, xcols, n] with xcols * digits == cols")
+        x3 = np.ascontiguousarray(x_in.reshape(-1, x_in.shape[-2], self.n))
+        out = np.empty((x3.shape[0], self.rows, self.n), dtype=np.uint64)
+        if self._lib.lsr_ntt_ring_matvec_gadget_batch(self._h, out.ctypes.data, x3.ctypes.data, x3.shape[0], base_log2, digits) != 0:
+            raise CoreError("lsr_ntt_ring_matvec_gadget_batch failed: " + _abi.last_error())
+        return out[0] if x_in.ndim == 2 else out
+
+    def matvec_gadget_device(self, d_y, d_x, batch, base_log2, digits, stream=0):
+        """Device buffers: y [batch][rows][n], x [batch][cols / digits][n], asynchronous on `stream`."""
+        if self._lib.lsr_ntt_ring_matvec_gadget_batch_device(self._h, d_y, d_x, batch, base_log2, digits, stream) != 0:
+            raise CoreError("lsr_ntt_ring_matvec_gadget_batch_device failed: " + _abi.last_error())
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.lsr_ntt_ring_matrix_free(self._h)
@@ -169,7 +186,69 @@ def _ring_matrix_device(ctx, d_m, rows, cols, stream):
     return RingMatrix(ctx, handle)
 
 
-class NttContext:
+def ring_gadget_min_digits(q, base_log2):
+    """The smallest admissible digit count of the balanced base-2^base_log2 decomposition under q (batch.h), 0 when there is none.
+    Host only."""
+    return _abi.lib().lsr_ring_gadget_min_digits(int(q), int(base_log2))
+
+
+def _check(rc, name):
+    if rc != 0:
+        raise CoreError(name + " failed: " + _abi.last_error())
+
+
+class _RingGadget:
+    """Gadget decomposition on a context (``NttContext`` and ``CyclicNtt``; batch.h "gadget decomposition")."""
+
+    def ring_decompose(self, x, base_log2, digits):
+        """x [n] or [count, n] in [0, q) -> its balanced base-2^base_log2 digits [digits, n] or [count, digits, n], canonical residues."""
+        x_in = _u64_array(x)
+        if x_in.ndim not in (1, 2) or x_in.shape[-1] != self.n:
+            raise ValueError("x must be [n] or [count, n]")
+        x2 = np.ascontiguousarray(x_in.reshape(-1, self.n))
+        out = np.empty((x2.shape[0], int(digits), self.n), dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_decompose_batch(self._h, out.ctypes.data, x2.ctypes.data, x2.shape[0], base_log2, digits),
+               "lsr_ntt_ring_decompose_batch")
+        return out[0] if x_in.ndim == 1 else out
+
+    def ring_decompose_device(self, d_out, d_x, count, base_log2, digits, stream=0):
+        """Device buffers: out [count][digits][n], x [count][n], asynchronous on `stream`."""
+        _check(self._lib.lsr_ntt_ring_decompose_batch_device(self._h, d_out, d_x, count, base_log2, digits, stream),
+               "lsr_ntt_ring_decompose_batch_device")
+
+    def ring_recompose(self, z, base_log2):
+        """z [digits, n] or [count, digits, n], any canonical residues -> sum_d 2^(base_log2 d) z[d] mod q, [n] or [count, n]."""
+        z_in = _u64_array(z)
+        if z_in.ndim not in (2, 3) or z_in.shape[-1] != self.n:
+            raise ValueError("z must be [digits, n] or [count, digits, n]")
+        digits = z_in.shape[-2]
+        z3 = np.ascontiguousarray(z_in.reshape(-1, digits, self.n))
+        out = np.empty((z3.shape[0], self.n), dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_recompose_batch(self._h, out.ctypes.data, z3.ctypes.data, z3.shape[0], base_log2, digits),
+               "lsr_ntt_ring_recompose_batch")
+        return out[0] if z_in.ndim == 2 else out
+
+    def ring_recompose_device(self, d_out, d_z, count, base_log2, digits, stream=0):
+        """Device buffers: out [count][n], z [count][digits][n], asynchronous on `stream`."""
+        _check(self._lib.lsr_ntt_ring_recompose_batch_device(self._h, d_out, d_z, count, base_log2, digits, stream),
+               "lsr_ntt_ring_recompose_batch_device")
+
+    def ring_linf(self, x):
+        """max |centred coefficient| of every element of x [..., n] (shape x.shape[:-1]); 2^64 - 1 for an element with a word >= q."""
+        x_in = _u64_array(x)
+        if x_in.shape[-1] != self.n:
+            raise ValueError("x must be [..., n]")
+        x2 = np.ascontiguousarray(x_in.reshape(-1, self.n))
+        out = np.empty(x2.shape[0], dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_linf_batch(self._h, x2.ctypes.data, x2.shape[0], out.ctypes.data), "lsr_ntt_ring_linf_batch")
+        return out.reshape(x_in.shape[:-1])
+
+    def ring_linf_device(self, d_x, count, d_linf, stream=0):
+        """Device buffers: x [count][n], linf [count], asynchronous on `stream`."""
+        _check(self._lib.lsr_ntt_ring_linf_batch_device(self._h, d_x, count, d_linf, stream), "lsr_ntt_ring_linf_batch_device")
+
+
+class NttContext(_RingGadget):
     """RAII handle over ``NttContext*`` (cpp-core/include/lambda_snark/ntt.h:25-41)."""
 
     def __init__(self, q, n, device=-1):
@@ -775,7 +854,7 @@ def prover_max_log2_size():
     return int(_abi.lib().lsr_prover_max_log2_size())
 
 
-class CyclicNtt:
+class CyclicNtt(_RingGadget):
     """The transform pair of rust-api/lambda-snark/src/ntt.rs: ``forward(coeffs)`` = ``ntt_forward(coeffs, modulus, omega)``
     (natural order in and out), ``inverse(evals)`` = ``ntt_inverse``.  One handle per (modulus, n, omega).  n above 2^17 (up to 2^22,
     NTT_MODULUS only) goes through ``lsr_cyclic_ntt_context_create_large``."""

@@ -112,6 +112,15 @@ SIGNATURES = {
     "lsr_ntt_ring_matrix_row_block": (c_size, [vp]),
     "lsr_ntt_ring_matvec_batch": (c_int, [vp, vp, vp, c_size]),
     "lsr_ntt_ring_matvec_batch_device": (c_int, [vp, vp, vp, c_size, vp]),
+    "lsr_ring_gadget_min_digits": (u64, [u64, ctypes.c_uint]),
+    "lsr_ntt_ring_decompose_batch": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size]),
+    "lsr_ntt_ring_decompose_batch_device": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size, vp]),
+    "lsr_ntt_ring_recompose_batch": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size]),
+    "lsr_ntt_ring_recompose_batch_device": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size, vp]),
+    "lsr_ntt_ring_linf_batch": (c_int, [vp, vp, c_size, vp]),
+    "lsr_ntt_ring_linf_batch_device": (c_int, [vp, vp, c_size, vp, vp]),
+    "lsr_ntt_ring_matvec_gadget_batch": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size]),
+    "lsr_ntt_ring_matvec_gadget_batch_device": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size, vp]),
     "lsr_sample_gaussian_seeded": (c_int, [vp, c_size, c_double, u64, u32, u64]),
     "lsr_gaussian_cdf": (c_size, [c_double, vp, c_size]),
     "lsr_lwe_context_create_seeded": (vp, [ctypes.POINTER(PublicParams), u64, c_int]),

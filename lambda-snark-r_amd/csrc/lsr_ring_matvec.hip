@@ -10,27 +10,11 @@
 
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
+#include "lsr_ring_matrix.hpp"
 #include "lsr_ring_matvec_kernels.hpp"
 #include "lsr_runtime.hpp"
 
-// The opaque C-ABI handle.  Immutable after creation: calls on one matrix may come from several threads and streams.
-struct LsrRingMatrix {
-    const NttContext* ctx = nullptr;
-    int device = 0;                     // ctx->device, kept here so that freeing the matrix never reads the context
-    size_t rows = 0, cols = 0;
-    lsr::DeviceBuffer<uint64_t> data;   // [rows][cols][n]: M-hat (n <= 4096) or M (n > 4096)
-    lsr::Event ready;                   // recorded by the device form of create: calls on other streams start behind it
-};
-
 namespace lsr {
-
-// Rows per workgroup, per flavour, from the compiler's resource report (profiles/r19_ring_matvec_resource_usage.txt).  The rule: the
-// largest block that keeps two waves per SIMD at LT = 12 (n = 4096) and has no scratch at any tile size.  Six smaller tile sizes
-// (F64 LT 10, Gold LT 8-11, U64 LT 4) then use 3-8 AGPRs beyond 256 VGPRs and run at one wave per SIMD: accepted, not measured.
-template <class A> struct MatvecRowBlock;
-template <> struct MatvecRowBlock<ArithF64> { static constexpr int value = 4; };
-template <> struct MatvecRowBlock<ArithGold> { static constexpr int value = 4; };
-template <> struct MatvecRowBlock<ArithU64> { static constexpr int value = 2; };
 
 // one tile's x and y ranges are addressed through 32-bit buffer offsets: 4096 cols (rows) words stay below 2^31 bytes
 static_assert((uint64_t)LSR_RING_DOT_MAX_TERMS * kTile * 8 <= (1ull << 31), "the x range of one tile must fit a buffer resource");
