@@ -9,6 +9,8 @@ import sys
 import numpy as np
 import pytest
 
+from ring_tile_model import schoolbook_dot as _schoolbook_dot
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,33 +27,6 @@ def _rand(rng, q, shape):
 
 def _to_u64(values):
     return np.array([int(x) for x in np.ravel(values)], dtype=np.uint64).reshape(np.shape(values))
-
-
-def _schoolbook(a, b, q, sign):
-    """a * b mod (X^n - sign, q) for lists of Python integers (sign = -1: negacyclic)."""
-    n = len(a)
-    r = [0] * n
-    for i, x in enumerate(a):
-        for j, y in enumerate(b):
-            k = i + j
-            if k < n:
-                r[k] = (r[k] + x * y) % q
-            else:
-                r[k - n] = (r[k - n] + sign * x * y) % q
-    return r
-
-
-def _schoolbook_dot(a, b, q, sign):
-    """a: [batch][terms][n]; b: [batch][terms][n] or [terms][n]."""
-    out = []
-    for j in range(a.shape[0]):
-        bj = b if b.ndim == 2 else b[j]
-        acc = [0] * a.shape[2]
-        for i in range(a.shape[1]):
-            prod = _schoolbook([int(x) for x in a[j, i]], [int(x) for x in bj[i]], q, sign)
-            acc = [(x + y) % q for x, y in zip(acc, prod)]
-        out.append(acc)
-    return out
 
 
 def _oracle_dot(oracle, q, n, a, b):

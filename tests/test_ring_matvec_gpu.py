@@ -5,6 +5,8 @@ and at the accumulator's worst case (identical entries: every product of one sig
 import numpy as np
 import pytest
 
+from ring_tile_model import schoolbook_matvec as _schoolbook_matvec
+
 pytestmark = pytest.mark.gpu
 
 Q44 = 17592180539393           # 44-bit prime, 2^18 | q - 1: every n up to 2^17 (FP64 kernels)
@@ -19,35 +21,6 @@ def _rand(rng, q, shape):
 
 def _to_u64(values):
     return np.array([int(x) for x in np.ravel(values)], dtype=np.uint64).reshape(np.shape(values))
-
-
-def _schoolbook(a, b, q, sign):
-    """a * b mod (X^n - sign, q) for lists of Python integers (sign = -1: negacyclic)."""
-    n = len(a)
-    r = [0] * n
-    for i, x in enumerate(a):
-        for j, y in enumerate(b):
-            k = i + j
-            if k < n:
-                r[k] = (r[k] + x * y) % q
-            else:
-                r[k - n] = (r[k - n] + sign * x * y) % q
-    return r
-
-
-def _schoolbook_matvec(m, x, q, sign):
-    """m: [rows][cols][n]; x: [batch][cols][n] -> [batch][rows][n] as nested lists."""
-    out = []
-    for j in range(x.shape[0]):
-        vec = []
-        for r in range(m.shape[0]):
-            acc = [0] * m.shape[2]
-            for c in range(m.shape[1]):
-                prod = _schoolbook([int(v) for v in m[r, c]], [int(v) for v in x[j, c]], q, sign)
-                acc = [(s + t) % q for s, t in zip(acc, prod)]
-            vec.append(acc)
-        out.append(vec)
-    return out
 
 
 def _by_ring_dot(ctx, m, x):
