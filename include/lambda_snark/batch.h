@@ -212,6 +212,65 @@ int lsr_ntt_ring_matvec_gadget_batch(const LsrRingMatrix* mat, uint64_t* y, cons
 int lsr_ntt_ring_matvec_gadget_batch_device(const LsrRingMatrix* mat, uint64_t* d_y, const uint64_t* d_x, size_t batch,
                                             unsigned base_log2, size_t digits, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: seeded ring sampling on the device and seed-expanded ring matrices ---------------- */
+/* Exact sampling of ring elements from ChaCha20 streams: the public matrix of an Ajtai commitment from a
+ * seed, short masking vectors and ternary secrets, and ring-valued challenges keyed by transcript digests that never leave the
+ * device.  Integer code that reads only q and n of the context: every context (negacyclic, cyclic, large cyclic) and every
+ * arithmetic flavour is served by one path.  out: [count][n], canonical residues, natural coefficient order.
+ *
+ * Streams.  A stream is (256-bit key, domain, 64-bit index).  Its 64-bit word w is ChaCha20 block w / 8 (the 32-bit block
+ * counter), 32-bit words 2 (w % 8) (low half) and 2 (w % 8) + 1 (high half); the nonce is {domain, index_lo, index_hi}.  A key is
+ * four little-endian 64-bit words; the 32 bytes of a SHA3 digest, in their own byte order, are a valid key.
+ * Element e < count uses key keys[4 (e / components) ..] and stream index index_base + (e % components): ceil(count / components)
+ * keys are read, the last group may be ragged.
+ *
+ * The one rejection primitive draw(m; w_0, w_1, ...; U) for m >= 2: L = bitlen(m - 1), F = floor(U / L); the candidates of a word
+ * are its F low fields (w >> f L) & (2^L - 1), f = 0 .. F-1; words are scanned in order and fields in order within a word; the
+ * result is the first candidate below m.  After LSR_RING_SAMPLE_MAX_WORDS words without an accepted candidate the result is field
+ * 0 of the last word reduced mod m (probability at most 2^-64; defined so that the function is total).  m = 1 gives 0 and consumes
+ * nothing.
+ *
+ * Kinds.
+ *   LSR_RING_SAMPLE_UNIFORM (param must be 0): coefficient i = draw(q; word a n + i for a = 0, 1, ...; U = 64) — exactly uniform
+ *     on [0, q).
+ *   LSR_RING_SAMPLE_BOUNDED (param beta, 1 <= beta <= (q - 1) / 2): r = draw(2 beta + 1; the same words; U = 64), v = r - beta,
+ *     stored as the canonical residue (v, or q + v) — exactly uniform on [-beta, beta].
+ *   LSR_RING_SAMPLE_BALL (param kappa, 1 <= kappa <= n): exactly kappa coefficients +-1, the rest 0, uniform over that set
+ *     (Dilithium's SampleInBall).  c = 0; for s = 0 .. kappa-1: i = n - kappa + s, j = draw(i + 1; word a kappa + s for a = 0, 1,
+ *     ...; U = 63); c[i] = c[j]; then c[j] = (bit 63 of word s) ? q - 1 : 1.
+ * All word indices stay below 2^28, so the block counter never wraps.
+ * Sampling is NOT constant-time: the pattern of rejections depends on the stream.  Rejected candidates are independent of the
+ * accepted values (each candidate is a fresh field of the stream), so the timing reveals nothing about the values drawn.
+ *
+ * lsr_ring_sample_key_from_seed: the key {seed_lo, seed_hi, "LSR1", "STRM", 0, 0, 0, 0} of a raw 64-bit seed (reproducible test
+ *   streams, as lsr_sample_gaussian_seeded; only as secret as the seed).  Host only.
+ * lsr_ntt_ring_sample_batch: host buffers (out and keys), staged through bounded device chunks; complete on return.
+ * lsr_ntt_ring_sample_batch_device: d_out and d_keys are device memory on the context's device (d_keys 8-byte aligned; it may be
+ *   the d_hashes32 of lsr_fs_challenge_batch_device); enqueues only, allocates nothing, can be captured into a HIP graph from the
+ *   first call.
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL context, buffer or
+ * keys; (2) an unknown kind, components == 0; (3) the rules that read the context: UNIFORM with param != 0, BOUNDED with beta == 0
+ * or beta > (q - 1) / 2, BALL with kappa == 0 or kappa > n.  (4) Then count == 0 is a no-op that returns 0.  Then (5) index_base +
+ * components overflowing 64 bits; no visible device.
+ *
+ * lsr_ntt_ring_matrix_create_seeded: the matrix whose entry M[r][c] is the UNIFORM element with stream index index_base + r cols +
+ *   c under the one key, sampled straight into the handle's buffer on the device and, at n <= 4096, transformed in place: the
+ *   matrix never crosses PCIe and never exists on the host.  Complete on return.  The handle is indistinguishable from
+ *   lsr_ntt_ring_matrix_create_device of the sampled words.  Limits and refusal order of lsr_ntt_ring_matrix_create with key in the
+ *   place of m; index_base + rows cols overflowing 64 bits is refused just before the visible-device check. */
+#define LSR_RING_SAMPLE_UNIFORM 0
+#define LSR_RING_SAMPLE_BOUNDED 1
+#define LSR_RING_SAMPLE_BALL 2
+#define LSR_RING_SAMPLE_MAX_WORDS 64
+void lsr_ring_sample_key_from_seed(uint64_t seed, uint64_t key[4]) LSR_NOEXCEPT;
+int lsr_ntt_ring_sample_batch(const NttContext* ctx, uint64_t* out, size_t count, int kind, uint64_t param, const uint64_t* keys,
+                              size_t components, uint32_t domain, uint64_t index_base) LSR_NOEXCEPT;
+int lsr_ntt_ring_sample_batch_device(const NttContext* ctx, uint64_t* d_out, size_t count, int kind, uint64_t param,
+                                     const uint64_t* d_keys, size_t components, uint32_t domain, uint64_t index_base,
+                                     void* stream) LSR_NOEXCEPT;
+LsrRingMatrix* lsr_ntt_ring_matrix_create_seeded(const NttContext* ctx, const uint64_t key[4], uint32_t domain, uint64_t index_base,
+                                                 size_t rows, size_t cols) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

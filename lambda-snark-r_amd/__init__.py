@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -248,7 +248,73 @@ class _RingGadget:
         _check(self._lib.lsr_ntt_ring_linf_batch_device(self._h, d_x, count, d_linf, stream), "lsr_ntt_ring_linf_batch_device")
 
 
-class NttContext(_RingGadget):
+# batch.h LSR_RING_SAMPLE_*: the kinds of ring_sample and the attempt cap of its rejection primitive
+RING_SAMPLE_UNIFORM, RING_SAMPLE_BOUNDED, RING_SAMPLE_BALL = 0, 1, 2
+RING_SAMPLE_MAX_WORDS = 64
+
+
+def ring_sample_key(seed):
+    """The 256-bit stream key {seed_lo, seed_hi, "LSR1", "STRM", 0, 0, 0, 0} of a raw 64-bit seed as four uint64 words (batch.h
+    lsr_ring_sample_key_from_seed): reproducible test streams, only as secret as the seed.  Host only."""
+    key = np.zeros(4, dtype=np.uint64)
+    _abi.lib().lsr_ring_sample_key_from_seed(int(seed), key.ctypes.data)
+    return key
+
+
+def _ring_keys(keys):
+    """Keys as [groups, 4] uint64 words: a uint64 array of 4 words per key, or bytes / a uint8 array of 32 bytes per key (a digest)."""
+    if isinstance(keys, (bytes, bytearray)):
+        keys = np.frombuffer(bytes(keys), dtype=np.uint8)
+    arr = np.asarray(keys)
+    if arr.dtype == np.uint8:
+        if arr.size == 0 or arr.size % 32:
+            raise ValueError("byte keys must be 32 bytes each")
+        return np.ascontiguousarray(arr).reshape(-1, 32).view("<u8")
+    arr = _u64_array(keys, "keys")
+    if arr.size == 0 or arr.size % 4:
+        raise ValueError("keys must be four 64-bit words each")
+    return np.ascontiguousarray(arr.reshape(-1, 4))
+
+
+class _RingSample:
+    """Seeded ring sampling on a context (``NttContext`` and ``CyclicNtt``; batch.h "seeded ring sampling")."""
+
+    def ring_sample(self, count, kind, param, keys, components=None, domain=16, index_base=0):
+        """[count, n] canonical ring elements of `kind` (RING_SAMPLE_UNIFORM with param 0, _BOUNDED with param beta, _BALL with param
+        kappa).  Element e uses key e // components and stream index index_base + e % components; keys is [groups, 4] uint64 (or 32
+        bytes per key) with groups >= ceil(count / components).  components=None spreads the elements evenly over the keys given:
+        ceil(count / groups) — one key: all elements under it; count keys: one element each."""
+        k2 = _ring_keys(keys)
+        count = int(count)
+        if components is None:
+            components = max(1, -(-count // k2.shape[0]))
+        components = int(components)
+        if components > 0 and k2.shape[0] < -(-count // components):
+            raise ValueError("keys must hold ceil(count / components) keys")
+        out = np.empty((count, self.n), dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_sample_batch(self._h, out.ctypes.data, count, kind, param, k2.ctypes.data, components, domain, index_base),
+               "lsr_ntt_ring_sample_batch")
+        return out
+
+    def ring_sample_device(self, d_out, count, kind, param, d_keys, components, domain=16, index_base=0, stream=0):
+        """Device buffers: out [count][n]; d_keys [ceil(count / components)][4] words (8-byte aligned; transcript digests are valid
+        keys).  Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ntt_ring_sample_batch_device(self._h, d_out, count, kind, param, d_keys, components, domain, index_base, stream),
+               "lsr_ntt_ring_sample_batch_device")
+
+    def ring_matrix_seeded(self, key, rows, cols, domain=16, index_base=0):
+        """The RingMatrix whose entry [r][c] is the UNIFORM element of stream index index_base + r cols + c under `key` (four uint64
+        words or 32 bytes), sampled on the device: equal to ring_matrix(ring_sample(rows cols, RING_SAMPLE_UNIFORM, 0, key))."""
+        k2 = _ring_keys(key)
+        if k2.shape[0] != 1:
+            raise ValueError("key must be one 256-bit key")
+        handle = self._lib.lsr_ntt_ring_matrix_create_seeded(self._h, k2.ctypes.data, domain, index_base, rows, cols)
+        if not handle:
+            raise CoreError("lsr_ntt_ring_matrix_create_seeded failed: " + _abi.last_error())
+        return RingMatrix(self, handle)
+
+
+class NttContext(_RingGadget, _RingSample):
     """RAII handle over ``NttContext*`` (cpp-core/include/lambda_snark/ntt.h:25-41)."""
 
     def __init__(self, q, n, device=-1):
@@ -854,7 +920,7 @@ def prover_max_log2_size():
     return int(_abi.lib().lsr_prover_max_log2_size())
 
 
-class CyclicNtt(_RingGadget):
+class CyclicNtt(_RingGadget, _RingSample):
     """The transform pair of rust-api/lambda-snark/src/ntt.rs: ``forward(coeffs)`` = ``ntt_forward(coeffs, modulus, omega)``
     (natural order in and out), ``inverse(evals)`` = ``ntt_inverse``.  One handle per (modulus, n, omega).  n above 2^17 (up to 2^22,
     NTT_MODULUS only) goes through ``lsr_cyclic_ntt_context_create_large``."""

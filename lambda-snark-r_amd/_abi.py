@@ -121,6 +121,10 @@ SIGNATURES = {
     "lsr_ntt_ring_linf_batch_device": (c_int, [vp, vp, c_size, vp, vp]),
     "lsr_ntt_ring_matvec_gadget_batch": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size]),
     "lsr_ntt_ring_matvec_gadget_batch_device": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size, vp]),
+    "lsr_ring_sample_key_from_seed": (None, [u64, vp]),
+    "lsr_ntt_ring_sample_batch": (c_int, [vp, vp, c_size, c_int, u64, vp, c_size, u32, u64]),
+    "lsr_ntt_ring_sample_batch_device": (c_int, [vp, vp, c_size, c_int, u64, vp, c_size, u32, u64, vp]),
+    "lsr_ntt_ring_matrix_create_seeded": (vp, [vp, vp, u32, u64, c_size, c_size]),
     "lsr_sample_gaussian_seeded": (c_int, [vp, c_size, c_double, u64, u32, u64]),
     "lsr_gaussian_cdf": (c_size, [c_double, vp, c_size]),
     "lsr_lwe_context_create_seeded": (vp, [ctypes.POINTER(PublicParams), u64, c_int]),

@@ -2,6 +2,8 @@
 // creates it and computes y = M x, lsr_ring_gadget.hip computes y = M G^-1(x) from the same M-hat.
 #pragma once
 
+#include <functional>
+
 #include "lsr_ntt_kernels.hpp"
 #include "lsr_runtime.hpp"
 
@@ -23,5 +25,13 @@ template <class A> struct MatvecRowBlock;
 template <> struct MatvecRowBlock<ArithF64> { static constexpr int value = 4; };
 template <> struct MatvecRowBlock<ArithGold> { static constexpr int value = 4; };
 template <> struct MatvecRowBlock<ArithU64> { static constexpr int value = 2; };
+
+// lsr_ntt_ring_matrix_create with the matrix words produced on the device (lsr_ring_sample.hip): the same checks in the same order
+// with `key` in the place of m, then precheck() (throws to refuse) just before the visible-device check, then fill(d_m, s) enqueues
+// the kernels that write M [rows][cols][n] in natural order into the handle's buffer on the context's work stream; at n <= 4096 the
+// words are transformed in place behind it.  Complete on return; NULL and lsr_last_error on refusal.
+using MatrixFill = std::function<void(uint64_t* d_m, hipStream_t s)>;
+LsrRingMatrix* matrix_create_filled(const char* where, const NttContext* ctx, const void* key, size_t rows, size_t cols,
+                                    const std::function<void()>& precheck, const MatrixFill& fill) noexcept;
 
 }  // namespace lsr

@@ -108,8 +108,10 @@ static void host_matvec(const LsrRingMatrix& m, uint64_t* y, const uint64_t* x, 
     }
 }
 
-// device: m is a device pointer, the work is enqueued on `s`; else m is a host pointer and the matrix is complete on return
-static LsrRingMatrix* matrix_create(const NttContext& c, const uint64_t* m, size_t rows, size_t cols, bool device, hipStream_t s) {
+// device: m is a device pointer, the work is enqueued on `s`; else m is a host pointer and the matrix is complete on return (with
+// `fill`: m is not read, the words are written by the kernels fill enqueues)
+static LsrRingMatrix* matrix_create(const NttContext& c, const uint64_t* m, size_t rows, size_t cols, bool device, hipStream_t s,
+                                    const MatrixFill* fill = nullptr) {
     DeviceGuard guard(c.device);
     const size_t n = c.degree, polys = rows * cols;
     auto mat = std::make_unique<LsrRingMatrix>();
@@ -126,7 +128,8 @@ static LsrRingMatrix* matrix_create(const NttContext& c, const uint64_t* m, size
     if (!device) {
         staging = std::unique_lock<std::mutex>(c.staging_mutex);   // serialises use of work_stream(c)
         s = work_stream(c);
-        LSR_HIP(hipMemcpyAsync(mat->data.ptr, m, polys * n * 8, hipMemcpyHostToDevice, s));
+        if (fill) (*fill)(mat->data.ptr, s);
+        else LSR_HIP(hipMemcpyAsync(mat->data.ptr, m, polys * n * 8, hipMemcpyHostToDevice, s));
         if (c.logn <= kTileLog) launch_ntt(c, mat->data.ptr, polys, false, s);
         LSR_HIP(hipStreamSynchronize(s));
     } else {
@@ -158,7 +161,8 @@ static int matrix_check(const char* where, const NttContext* ctx, const void* m,
 }
 
 static LsrRingMatrix* matrix_create_guarded(const char* where, const NttContext* ctx, const uint64_t* m, size_t rows, size_t cols, bool device,
-                                            void* stream) noexcept {
+                                            void* stream, const std::function<void()>* precheck = nullptr,
+                                            const lsr::MatrixFill* fill = nullptr) noexcept {
     if (matrix_check(where, ctx, m, rows, cols) != 0) return nullptr;
     LsrRingMatrix* mat = nullptr;
     lsr::abi_guarded(where, [&] {
@@ -167,10 +171,16 @@ static LsrRingMatrix* matrix_create_guarded(const char* where, const NttContext*
         if (rows * cols * ctx->degree * 8 > LSR_RING_MATVEC_MAX_MATRIX_BYTES)
             throw std::runtime_error("rows * cols * n * 8 = " + std::to_string(rows * cols * ctx->degree * 8) + " bytes are above LSR_RING_MATVEC_MAX_MATRIX_BYTES (" +
                                      std::to_string(LSR_RING_MATVEC_MAX_MATRIX_BYTES) + ")");
+        if (precheck) (*precheck)();
         if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
-        mat = lsr::matrix_create(*ctx, m, rows, cols, device, static_cast<hipStream_t>(stream));
+        mat = lsr::matrix_create(*ctx, m, rows, cols, device, static_cast<hipStream_t>(stream), fill);
     });
     return mat;
+}
+
+LsrRingMatrix* lsr::matrix_create_filled(const char* where, const NttContext* ctx, const void* key, size_t rows, size_t cols,
+                                         const std::function<void()>& precheck, const MatrixFill& fill) noexcept {
+    return matrix_create_guarded(where, ctx, static_cast<const uint64_t*>(key), rows, cols, false, nullptr, &precheck, &fill);
 }
 
 // 0: go on; 1: nothing to do; -1: refused
