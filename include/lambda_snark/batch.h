@@ -271,6 +271,40 @@ int lsr_ntt_ring_sample_batch_device(const NttContext* ctx, uint64_t* d_out, siz
 LsrRingMatrix* lsr_ntt_ring_matrix_create_seeded(const NttContext* ctx, const uint64_t key[4], uint32_t domain, uint64_t index_base,
                                                  size_t rows, size_t cols) LSR_NOEXCEPT;
 
+/* ---------------- NTT: batched fold of ring vectors by ring-valued challenges ---------------- */
+/* out[j][c] = sum_{i < terms} p[j][i] * v[j term_stride + i][c] in the ring of the context (as lsr_ntt_ring_mul_batch: X^n + 1 on
+ * negacyclic contexts, X^n - 1 on cyclic ones): the folded witness z_j = sum_i c_{j,i} x_{j,i} of a folding or Sigma protocol over
+ * Ajtai commitments, and — applied to the commitments — the folded commitment.
+ * v: [vectors][width][n] with vectors = (outputs - 1) term_stride + terms; p: [outputs][terms][n]; out: [outputs][width][n].  Words
+ * are canonical ([0,q) in, canonical out) in natural coefficient order, as lsr_ntt_ring_dot_batch; a challenge's -1 is q - 1, which is
+ * what LSR_RING_SAMPLE_BALL writes.  term_stride as lsr_lwe_ring_combine_rows_device: 0 — every output folds the same `terms`
+ * vectors; terms — disjoint groups; any other value is allowed (overlapping or spaced groups).
+ * out[j][c] equals lsr_ntt_ring_dot_batch on the gathered operands a[(j,c)][i] = v[j term_stride + i][c], b[(j,c)][i] = p[j][i]
+ * word for word, in every arithmetic flavour and at every n from 2 to 131072.  The transform of a challenge is shared by the `width`
+ * components it multiplies: one fused pass at n <= 4096 behind one transform of the challenges, three passes per chunk above.
+ *
+ * Limits: terms <= LSR_RING_DOT_MAX_TERMS, width <= LSR_RING_FOLD_MAX_WIDTH.
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL context or buffer;
+ * (2) terms == 0.  (3) Then outputs == 0 or width == 0 is a no-op that returns 0 (as batch == 0 of lsr_ntt_ring_dot_batch).  Then
+ * (4) terms above LSR_RING_DOT_MAX_TERMS; (5) width above LSR_RING_FOLD_MAX_WIDTH; (6) a size that overflows size_t: vectors,
+ * vectors * width, outputs * terms, outputs * width, or one of the last three times 16 bytes (a polynomial of the smallest ring) —
+ * all of these without reading the context.  Then (7) a context above n = 131072; (8) the byte size of v, p or out overflowing
+ * size_t at the context's n; (9) out overlapping v, then p, in address range (there is no aliasing form); (10) no visible device.
+ *
+ * lsr_ntt_ring_fold_batch: host buffers, staged through bounded device chunks; returns when out is complete.
+ * lsr_ntt_ring_fold_batch_device: device buffers on the context's device, asynchronous on `stream` (enqueues only).
+ *
+ * Workspace, ordering and graph capture: the contract of lsr_ntt_ring_dot_batch above, and its workspace — no other.  Every call
+ * uses it (its size depends on n alone; outputs, components and terms that do not fit are taken in chunks and groups); the first
+ * eager ring inner product or fold on the context allocates it, a capturing call that would have to allocate it returns -1: make one
+ * eager call first.  Calls are ordered by the context's ring event against each other and against the ring multiplies and inner
+ * products of the context.  FP64-flavour contexts re-centre the running sum every LSR_RING_DOT_F64_RECENTRE_PERIOD products. */
+#define LSR_RING_FOLD_MAX_WIDTH 65536
+int lsr_ntt_ring_fold_batch(const NttContext* ctx, uint64_t* out, const uint64_t* v, const uint64_t* p,
+                            size_t outputs, size_t terms, size_t term_stride, size_t width) LSR_NOEXCEPT;
+int lsr_ntt_ring_fold_batch_device(const NttContext* ctx, uint64_t* d_out, const uint64_t* d_v, const uint64_t* d_p,
+                                   size_t outputs, size_t terms, size_t term_stride, size_t width, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

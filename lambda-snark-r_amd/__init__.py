@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -61,6 +61,8 @@ def _ring_mul_device(lib, handle, d_c, d_a, d_b, batch, b_rows, stream):
 # LSR_RING_DOT_F64_RECENTRE_PERIOD); the largest number of terms is LSR_RING_DOT_MAX_TERMS
 RING_DOT_F64_RECENTRE_PERIOD = 32
 RING_DOT_MAX_TERMS = 65536
+# the largest width of a ring fold (batch.h LSR_RING_FOLD_MAX_WIDTH)
+RING_FOLD_MAX_WIDTH = 65536
 
 
 def _ring_dot(lib, handle, n, a, b):
@@ -314,7 +316,39 @@ class _RingSample:
         return RingMatrix(self, handle)
 
 
-class NttContext(_RingGadget, _RingSample):
+class _RingFold:
+    """Fold of ring vectors by ring-valued challenges on a context (``NttContext`` and ``CyclicNtt``; batch.h)."""
+
+    def ring_fold(self, v, p, term_stride=0):
+        """out[j][c] = sum_i p[j][i] * v[j term_stride + i][c] in the context's ring (host arrays): v is [vectors, width, n], p is
+        [outputs, terms, n] (or [terms, n]: one output) with vectors >= (outputs - 1) term_stride + terms.  Returns
+        [outputs, width, n] ([width, n] for a 2-d p)."""
+        n = self.n
+        v_in, p_in = _u64_array(v, "v"), _u64_array(p, "p")
+        if v_in.ndim != 3 or v_in.shape[-1] != n:
+            raise ValueError("v must be [vectors, width, n]")
+        if p_in.ndim not in (2, 3) or p_in.shape[-1] != n:
+            raise ValueError("p must be [terms, n] or [outputs, terms, n]")
+        terms, term_stride = p_in.shape[-2], int(term_stride)
+        if terms == 0:
+            raise ValueError("terms must be at least 1")
+        v3, p3 = np.ascontiguousarray(v_in), np.ascontiguousarray(p_in.reshape(-1, terms, n))
+        outputs, width = p3.shape[0], v3.shape[1]
+        if term_stride < 0 or (outputs and v3.shape[0] < (outputs - 1) * term_stride + terms):
+            raise ValueError("v must hold (outputs - 1) * term_stride + terms vectors")
+        out = np.empty((outputs, width, n), dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_fold_batch(self._h, out.ctypes.data, v3.ctypes.data, p3.ctypes.data, outputs, terms, term_stride, width),
+               "lsr_ntt_ring_fold_batch")
+        return out[0] if p_in.ndim == 2 else out
+
+    def ring_fold_device(self, d_out, d_v, d_p, outputs, terms, term_stride, width, stream=0):
+        """Device buffers: out [outputs][width][n], v [(outputs - 1) term_stride + terms][width][n], p [outputs][terms][n].
+        Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ntt_ring_fold_batch_device(self._h, d_out, d_v, d_p, outputs, terms, term_stride, width, stream),
+               "lsr_ntt_ring_fold_batch_device")
+
+
+class NttContext(_RingGadget, _RingSample, _RingFold):
     """RAII handle over ``NttContext*`` (cpp-core/include/lambda_snark/ntt.h:25-41)."""
 
     def __init__(self, q, n, device=-1):
@@ -920,7 +954,7 @@ def prover_max_log2_size():
     return int(_abi.lib().lsr_prover_max_log2_size())
 
 
-class CyclicNtt(_RingGadget, _RingSample):
+class CyclicNtt(_RingGadget, _RingSample, _RingFold):
     """The transform pair of rust-api/lambda-snark/src/ntt.rs: ``forward(coeffs)`` = ``ntt_forward(coeffs, modulus, omega)``
     (natural order in and out), ``inverse(evals)`` = ``ntt_inverse``.  One handle per (modulus, n, omega).  n above 2^17 (up to 2^22,
     NTT_MODULUS only) goes through ``lsr_cyclic_ntt_context_create_large``."""

@@ -104,6 +104,8 @@ SIGNATURES = {
     "lsr_ntt_ring_mul_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, vp]),
     "lsr_ntt_ring_dot_batch": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size]),
     "lsr_ntt_ring_dot_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, vp]),
+    "lsr_ntt_ring_fold_batch": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, c_size]),
+    "lsr_ntt_ring_fold_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, c_size, vp]),
     "lsr_ntt_ring_matrix_create": (vp, [vp, vp, c_size, c_size]),
     "lsr_ntt_ring_matrix_create_device": (vp, [vp, vp, c_size, c_size, vp]),
     "lsr_ntt_ring_matrix_free": (None, [vp]),

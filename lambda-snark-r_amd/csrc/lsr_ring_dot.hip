@@ -16,6 +16,7 @@
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
 #include "lsr_ntt_kernels.hpp"
+#include "lsr_ring_workspace.hpp"
 #include "lsr_runtime.hpp"
 
 static_assert(LSR_RING_DOT_F64_RECENTRE_PERIOD == (int)lsr::kRingDotF64Period, "batch.h documents the kernel's re-centring period");
@@ -59,18 +60,7 @@ static void dot_tile_lt(const NttContext& c, int lt, const DotOperands& o, hipSt
 }
 #undef LSR_DOT_CASE
 
-// Polynomials per workspace array.  n > 4096: three arrays are live between the passes of a chunk (the transformed a terms, the
-// transformed b terms, the c chunk), so each gets a third of the Infinity Cache budget of a two-pass transform (ntt_chunk_bytes():
-// 256 MiB -> 170 polynomials at n = 2^16).  n <= 4096: the same budget bounds the b-hat rows of a shared b, at most 4096 of them.
-static size_t ring_dot_chunk_polys(const NttContext& c) {
-    const size_t polys = std::max<size_t>(1, (ntt_chunk_bytes() / 3) >> (c.logn + 3));
-    return c.logn > kTileLog ? polys : std::min<size_t>(polys, 4096);
-}
-// Workspace words: n > 4096 — the a terms and the b terms (or b-hat rows) of one chunk; n <= 4096 — the b-hat rows.  A function of n
-// (and of the process-wide chunk size) only, never of the batch or the terms.
-static size_t ring_dot_scratch_words(const NttContext& c) {
-    return (c.logn > kTileLog ? 2 : 1) * ring_dot_chunk_polys(c) * c.degree;
-}
+// (workspace sizing — ring_dot_chunk_polys, ring_dot_scratch_words: lsr_ring_workspace.hpp, shared with lsr_ring_fold.hip)
 
 // first / last: this call starts / finishes the sums (the host variant stages long sums in groups of terms, as this function does)
 template <class A>
