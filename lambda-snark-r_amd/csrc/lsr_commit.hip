@@ -35,6 +35,7 @@
 #include "lsr_commit_keys.hpp"
 #include "lsr_flavour.hpp"
 #include "lsr_keys.hpp"
+#include "lsr_ring_call.hpp"
 #include "lsr_runtime.hpp"
 #include "lsr_sampler.hpp"
 
@@ -1658,17 +1659,10 @@ static void ring_combine_tile_launch(const RingCombineTile& job, const RingCombi
     const unsigned tiles = (unsigned)((((uint64_t)job.polys << LT) + kTile - 1) / kTile);
     hipLaunchKernelGGL((ring_combine_tile<A, LT>), dim3(tiles), dim3(kThreads), 0, s, job, pr);
 }
-#define LSR_RING_COMBINE_CASE(LT) case LT: ring_combine_tile_launch<A, LT>(job, pr, s); break;
 template <class A>
 static void ring_combine_tile_lt(int lt, const RingCombineTile& job, const RingCombinePrime<A>& pr, hipStream_t s) {
-    switch (lt) {
-        LSR_RING_COMBINE_CASE(1) LSR_RING_COMBINE_CASE(2) LSR_RING_COMBINE_CASE(3) LSR_RING_COMBINE_CASE(4) LSR_RING_COMBINE_CASE(5)
-        LSR_RING_COMBINE_CASE(6) LSR_RING_COMBINE_CASE(7) LSR_RING_COMBINE_CASE(8) LSR_RING_COMBINE_CASE(9) LSR_RING_COMBINE_CASE(10)
-        LSR_RING_COMBINE_CASE(11)
-        default: ring_combine_tile_launch<A, 12>(job, pr, s); break;
-    }
+    for_tile_log<1, 12>(lt, [&](auto t) { ring_combine_tile_launch<A, decltype(t)::value>(job, pr, s); });
 }
-#undef LSR_RING_COMBINE_CASE
 
 // the fused launch of one chunk and group under one prime of the context, in that prime's flavour
 static void ring_combine_tile_prime(const LweContext& c, const RingCombineTile& job, const NttContext& ntt, const uint64_t* phat, uint64_t block,

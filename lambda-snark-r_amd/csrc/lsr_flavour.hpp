@@ -1,5 +1,5 @@
 // Per-flavour views of an NttContext for kernel launches (twiddle tables, round constants), shared by the dispatching translation
-// units (lsr_ntt.hip, lsr_ring_mul.hip).
+// units (lsr_ntt.hip, lsr_ring_mul.hip, lsr_ring_dot.hip, lsr_ring_fold.hip, lsr_ring_matvec.hip, lsr_ring_gadget.hip, lsr_commit.hip).
 #pragma once
 
 #include "lsr_ntt_kernels.hpp"

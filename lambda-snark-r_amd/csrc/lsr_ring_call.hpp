@@ -1,0 +1,96 @@
+// The host call path shared by the fused ring operations (lsr_ring_mul.hip, lsr_ring_dot.hip, lsr_ring_fold.hip, lsr_ring_matvec.hip,
+// lsr_ring_gadget.hip, lsr_ring_sample.hip and the ring combination of lsr_commit.hip): the dispatch from a context to a kernel
+// instantiation, the bracket that keeps the context's workspaces safe across streams and threads, the argument checks
+// the entry points have in common and the staging of host buffers.  Host code only.
+#pragma once
+#include <algorithm>
+#include <type_traits>
+
+#include "lsr_ntt_kernels.hpp"
+#include "lsr_runtime.hpp"
+
+namespace lsr {
+
+// f(std::integral_constant<int, LT>{}) for LT = lt in [LO, HI]; any other lt goes to HI.  <1, 12>: every tile size; <9, 12>: the
+// middle pass of a two-pass transform (mid_tile_log).
+template <int LO, int HI, class F>
+void for_tile_log(int lt, F&& f) {
+    if constexpr (LO < HI) {
+        if (lt == LO) f(std::integral_constant<int, LO>{});
+        else for_tile_log<LO + 1, HI>(lt, f);
+    } else {
+        f(std::integral_constant<int, HI>{});
+    }
+}
+
+// f(A{}) for the arithmetic flavour A of the context's kernels
+template <class F>
+decltype(auto) for_flavour(const NttContext& c, F&& f) {
+    if (c.gold) return f(ArithGold{});
+    if (c.use_f64) return f(ArithF64{});
+    return f(ArithU64{});
+}
+
+// n > 4096: the tile size of the middle pass, the low log n - 4 (n = 2^17: - 5) bits of a two-pass transform
+inline int mid_tile_log(const NttContext& c) { return c.logn - std::max(c.logn - kTileLog, 4); }
+
+// The bracket of one ring call on the device (caller validated the arguments): under ring_mutex, `workspace` allocated at
+// `workspace_words` by the first call that needs it, the launches of `enqueue` on `s` behind the context's previous ring call, and
+// ring_event recorded behind them for the next one.  A capturing stream: no brackets (lsr_runtime.hpp, stream_is_capturing).
+template <class Enqueue>
+void ring_call(const NttContext& c, DeviceBuffer<uint64_t>& workspace, size_t workspace_words, bool needs_workspace, hipStream_t s,
+               Enqueue&& enqueue) {
+    std::lock_guard<std::mutex> lock(c.ring_mutex);
+    const bool capturing = stream_is_capturing(s);
+    if (needs_workspace && !workspace.ptr) {
+        // the workspace is allocated once and never resized, so a graph captured after one eager call keeps valid pointers; an
+        // allocation inside the capture would not be part of the graph
+        if (capturing)
+            throw std::runtime_error("this call needs the context's workspace, which the first such call allocates: make one eager (uncaptured) "
+                                     "call on this context before capturing");
+        workspace.allocate(workspace_words);
+    }
+    if (!capturing) c.ring_event.wait(s);
+    enqueue();
+    LSR_HIP(hipGetLastError());
+    if (!capturing) c.ring_event.record(s);
+}
+
+inline void require_device() {
+    if (visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
+}
+
+// `message` when [out, out + out_bytes) and [in, in + in_bytes) share memory
+inline void require_apart(const void* out, size_t out_bytes, const void* in, size_t in_bytes, const char* message) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + out_bytes;
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + in_bytes;
+    if (o0 < i1 && i0 < o1) throw std::runtime_error(message);
+}
+
+// the middle pass of a fused ring operation assumes ONE strided round on either side
+inline void refuse_above_two_pass(const NttContext& c, const char* message) {
+    if (c.logn > kTwoPassMaxLog2) throw std::runtime_error(message);
+}
+
+// bytes of device memory one host-pointer call stages at a time
+constexpr size_t kStagingBytes = 256ull << 20;
+
+// Host buffers through bounded device chunks on the context's work stream: `in_words` words go up and `out_words` words come back
+// per item, `run(d_out, d_in, now, s)` enqueues the work of `now` items.
+template <class Run>
+void host_staged(const NttContext& c, uint64_t* out, const uint64_t* in, size_t count, size_t out_words, size_t in_words, Run&& run) {
+    DeviceGuard guard(c.device);
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(count, (kStagingBytes / 8) / (in_words + out_words)));
+    DeviceBuffer<uint64_t> din(chunk * in_words), dout(chunk * out_words);
+    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
+    hipStream_t s = work_stream(c);
+    for (size_t j0 = 0; j0 < count; j0 += chunk) {
+        const size_t now = std::min(chunk, count - j0);
+        LSR_HIP(hipMemcpyAsync(din.ptr, in + j0 * in_words, now * in_words * 8, hipMemcpyHostToDevice, s));
+        run(dout.ptr, din.ptr, now, s);
+        LSR_HIP(hipMemcpyAsync(out + j0 * out_words, dout.ptr, now * out_words * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+}  // namespace lsr

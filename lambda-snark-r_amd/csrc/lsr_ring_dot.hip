@@ -16,6 +16,7 @@
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
 #include "lsr_ntt_kernels.hpp"
+#include "lsr_ring_call.hpp"
 #include "lsr_ring_workspace.hpp"
 #include "lsr_runtime.hpp"
 
@@ -42,23 +43,10 @@ static void dot_tile(const NttContext& c, const DotOperands& o, hipStream_t s) {
                        c.mod, Flavour<A>::fwd(c), Flavour<A>::inv(c), Flavour<A>::consts(c));
 }
 
-#define LSR_DOT_CASE(LT) case LT: dot_tile<A, LT, MID, BHAT>(c, o, s); break;
 template <class A, bool MID, bool BHAT>
 static void dot_tile_lt(const NttContext& c, int lt, const DotOperands& o, hipStream_t s) {
-    if constexpr (MID) {   // the low lt = log n - 4 (n = 2^17: - 5) bits of a two-pass transform
-        switch (lt) {
-            LSR_DOT_CASE(9) LSR_DOT_CASE(10) LSR_DOT_CASE(11)
-            default: dot_tile<A, 12, MID, BHAT>(c, o, s); break;
-        }
-    } else {
-        switch (lt) {
-            LSR_DOT_CASE(1) LSR_DOT_CASE(2) LSR_DOT_CASE(3) LSR_DOT_CASE(4) LSR_DOT_CASE(5) LSR_DOT_CASE(6)
-            LSR_DOT_CASE(7) LSR_DOT_CASE(8) LSR_DOT_CASE(9) LSR_DOT_CASE(10) LSR_DOT_CASE(11)
-            default: dot_tile<A, 12, MID, BHAT>(c, o, s); break;
-        }
-    }
+    for_tile_log<MID ? 9 : 1, 12>(lt, [&](auto t) { dot_tile<A, decltype(t)::value, MID, BHAT>(c, o, s); });
 }
-#undef LSR_DOT_CASE
 
 // (workspace sizing — ring_dot_chunk_polys, ring_dot_scratch_words: lsr_ring_workspace.hpp, shared with lsr_ring_fold.hip)
 
@@ -68,9 +56,7 @@ static void ring_dot_enqueue(const NttContext& c, uint64_t* d_c, const uint64_t*
                              bool first, bool last, hipStream_t s) {
     const size_t n = c.degree, polys = ring_dot_chunk_polys(c);
     uint64_t* const ws = c.ring_dot_scratch.ptr;
-    auto flags_of = [&](size_t i0, size_t group) -> uint32_t {
-        return (first && i0 == 0 ? kRingDotFirst : 0u) | (last && i0 + group == terms ? kRingDotLast : 0u);
-    };
+    auto flags_of = [&](size_t i0, size_t group) { return ring_dot_flags(first && i0 == 0, last && i0 + group == terms); };
     if (c.logn <= kTileLog) {
         if (!shared_b) {
             dot_tile_lt<A, false, false>(c, c.logn, {d_c, d_a, d_b, batch * n, (uint32_t)terms, terms * n, terms * n, flags_of(0, terms)}, s);
@@ -83,7 +69,7 @@ static void ring_dot_enqueue(const NttContext& c, uint64_t* d_c, const uint64_t*
         }
         return;
     }
-    const int lt = c.logn - std::max(c.logn - kTileLog, 4);
+    const int lt = mid_tile_log(c);
     uint64_t* const wa = ws;
     uint64_t* const wb = ws + polys * n;
     // all terms fit: chunks of whole outputs; else one output at a time, its terms in groups.  Either way the (output, term)
@@ -105,30 +91,13 @@ static void ring_dot_enqueue(const NttContext& c, uint64_t* d_c, const uint64_t*
     }
 }
 
-static void refuse_large(const NttContext& c) {   // the middle pass above assumes ONE strided round on either side
-    if (c.logn > kTwoPassMaxLog2) throw std::runtime_error("ring inner product on a context above n = 131072 is not supported (lsr_cyclic_ntt_context_create_large)");
-}
-
 // One call on the device (caller validated the arguments): workspace, ordering brackets, launches.
 static void ring_dot_device(const NttContext& c, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms, size_t b_rows,
                             hipStream_t s, bool first = true, bool last = true) {
     const bool shared_b = b_rows == 1 && batch > 1;
-    std::lock_guard<std::mutex> lock(c.ring_mutex);
-    const bool capturing = stream_is_capturing(s);
-    if ((c.logn > kTileLog || shared_b) && !c.ring_dot_scratch.ptr) {
-        // allocated once and never resized, as the ring multiply's workspace (lsr_ring_mul.hip)
-        if (capturing)
-            throw std::runtime_error("this call needs the context's workspace, which the first such call allocates: make one eager (uncaptured) "
-                                     "call on this context before capturing");
-        c.ring_dot_scratch.allocate(ring_dot_scratch_words(c));
-    }
-    // (a capturing stream: no brackets — lsr_runtime.hpp, stream_is_capturing)
-    if (!capturing) c.ring_event.wait(s);
-    if (c.gold) ring_dot_enqueue<ArithGold>(c, d_c, d_a, d_b, batch, terms, shared_b, first, last, s);
-    else if (c.use_f64) ring_dot_enqueue<ArithF64>(c, d_c, d_a, d_b, batch, terms, shared_b, first, last, s);
-    else ring_dot_enqueue<ArithU64>(c, d_c, d_a, d_b, batch, terms, shared_b, first, last, s);
-    LSR_HIP(hipGetLastError());
-    if (!capturing) c.ring_event.record(s);
+    ring_call(c, c.ring_dot_scratch, ring_dot_scratch_words(c), c.logn > kTileLog || shared_b, s, [&] {
+        for_flavour(c, [&](auto a) { ring_dot_enqueue<decltype(a)>(c, d_c, d_a, d_b, batch, terms, shared_b, first, last, s); });
+    });
 }
 
 // host buffers through bounded device chunks on the context's work stream: whole outputs while one output's terms fit the staging
@@ -137,7 +106,7 @@ static void host_ring_dot(const NttContext& c, uint64_t* out, const uint64_t* a,
     DeviceGuard guard(c.device);
     const size_t n = c.degree;
     const bool shared_b = b_rows == 1 && batch > 1;
-    const size_t bound = std::max<size_t>(1, (256ull << 20) / (n * 8));          // polynomials per staged operand
+    const size_t bound = std::max<size_t>(1, kStagingBytes / (n * 8));          // polynomials per staged operand
     const size_t group_max = std::min(terms, bound), chunk = group_max == terms ? std::max<size_t>(1, std::min(batch, bound / terms)) : 1;
     DeviceBuffer<uint64_t> da(chunk * group_max * n), db((shared_b ? 1 : chunk) * group_max * n), dc(chunk * n);
     std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
@@ -173,21 +142,12 @@ static int ring_dot_check(const char* where, const NttContext* ctx, const void* 
 
 // The checks of a non-empty call that read the context, still before any device work.
 static void ring_dot_validate(const NttContext& ctx, const uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t terms, size_t b_rows) {
-    lsr::refuse_large(ctx);
+    lsr::refuse_above_two_pass(ctx, "ring inner product on a context above n = 131072 is not supported (lsr_cyclic_ntt_context_create_large)");
     if (terms > LSR_RING_DOT_MAX_TERMS)
         throw std::runtime_error("terms = " + std::to_string(terms) + " is above LSR_RING_DOT_MAX_TERMS (" + std::to_string(LSR_RING_DOT_MAX_TERMS) + ")");
-    const size_t n = ctx.degree;
-    auto overlaps = [&](const uint64_t* x, size_t polys) {
-        const uintptr_t c0 = reinterpret_cast<uintptr_t>(c), c1 = c0 + batch * n * 8;
-        const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), x1 = x0 + polys * n * 8;
-        return c0 < x1 && x0 < c1;
-    };
-    if (overlaps(a, batch * terms)) throw std::runtime_error("c overlaps a: the output must not share memory with an operand");
-    if (overlaps(b, b_rows * terms)) throw std::runtime_error("c overlaps b: the output must not share memory with an operand");
-}
-
-static void require_device() {
-    if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
+    const size_t poly_bytes = (size_t)ctx.degree * 8;
+    lsr::require_apart(c, batch * poly_bytes, a, batch * terms * poly_bytes, "c overlaps a: the output must not share memory with an operand");
+    lsr::require_apart(c, batch * poly_bytes, b, b_rows * terms * poly_bytes, "c overlaps b: the output must not share memory with an operand");
 }
 
 extern "C" {
@@ -198,7 +158,7 @@ int lsr_ntt_ring_dot_batch(const NttContext* ctx, uint64_t* c, const uint64_t* a
     if (batch == 0) return 0;
     return lsr::abi_guarded("lsr_ntt_ring_dot_batch", [&] {
         ring_dot_validate(*ctx, c, a, b, batch, terms, b_rows);
-        require_device();
+        lsr::require_device();
         lsr::host_ring_dot(*ctx, c, a, b, batch, terms, b_rows);
     });
 }
@@ -209,7 +169,7 @@ int lsr_ntt_ring_dot_batch_device(const NttContext* ctx, uint64_t* d_c, const ui
     if (batch == 0) return 0;
     return lsr::abi_guarded("lsr_ntt_ring_dot_batch_device", [&] {
         ring_dot_validate(*ctx, d_c, d_a, d_b, batch, terms, b_rows);
-        require_device();
+        lsr::require_device();
         lsr::DeviceGuard guard(ctx->device);
         lsr::ring_dot_device(*ctx, d_c, d_a, d_b, batch, terms, b_rows, static_cast<hipStream_t>(stream));
     });

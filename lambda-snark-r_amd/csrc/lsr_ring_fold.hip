@@ -14,6 +14,7 @@
 
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
+#include "lsr_ring_call.hpp"
 #include "lsr_ring_fold_kernels.hpp"
 #include "lsr_ring_workspace.hpp"
 #include "lsr_runtime.hpp"
@@ -39,23 +40,10 @@ static void fold_tile(const NttContext& c, const FoldOperands& o, hipStream_t s)
                        Flavour<A>::fwd(c), Flavour<A>::inv(c), Flavour<A>::consts(c));
 }
 
-#define LSR_FOLD_CASE(LT) case LT: fold_tile<A, LT, MID>(c, o, s); break;
 template <class A, bool MID>
 static void fold_tile_lt(const NttContext& c, int lt, const FoldOperands& o, hipStream_t s) {
-    if constexpr (MID) {   // the low lt = log n - 4 (n = 2^17: - 5) bits of a two-pass transform
-        switch (lt) {
-            LSR_FOLD_CASE(9) LSR_FOLD_CASE(10) LSR_FOLD_CASE(11)
-            default: fold_tile<A, 12, MID>(c, o, s); break;
-        }
-    } else {
-        switch (lt) {
-            LSR_FOLD_CASE(1) LSR_FOLD_CASE(2) LSR_FOLD_CASE(3) LSR_FOLD_CASE(4) LSR_FOLD_CASE(5) LSR_FOLD_CASE(6)
-            LSR_FOLD_CASE(7) LSR_FOLD_CASE(8) LSR_FOLD_CASE(9) LSR_FOLD_CASE(10) LSR_FOLD_CASE(11)
-            default: fold_tile<A, 12, MID>(c, o, s); break;
-        }
-    }
+    for_tile_log<MID ? 9 : 1, 12>(lt, [&](auto t) { fold_tile<A, decltype(t)::value, MID>(c, o, s); });
 }
-#undef LSR_FOLD_CASE
 
 // first / last: this call starts / finishes the sums (the host variant stages long sums in groups of terms, as this function does)
 template <class A>
@@ -63,9 +51,7 @@ static void ring_fold_enqueue(const NttContext& c, uint64_t* d_out, const uint64
                               size_t width, bool first, bool last, hipStream_t s) {
     const size_t n = c.degree, polys = ring_dot_chunk_polys(c), vec = width * n;
     uint64_t* const ws = c.ring_dot_scratch.ptr;
-    auto flags_of = [&](size_t i0, size_t group) -> uint32_t {
-        return (first && i0 == 0 ? kRingDotFirst : 0u) | (last && i0 + group == terms ? kRingDotLast : 0u);
-    };
+    auto flags_of = [&](size_t i0, size_t group) { return ring_dot_flags(first && i0 == 0, last && i0 + group == terms); };
     if (c.logn <= kTileLog) {
         if (terms <= polys) {       // chunks of whole outputs: their challenges are contiguous in p
             const size_t chunk = std::min(polys / terms, kFoldMaxGridY);
@@ -84,7 +70,7 @@ static void ring_fold_enqueue(const NttContext& c, uint64_t* d_out, const uint64
             }
         return;
     }
-    const int lt = c.logn - std::max(c.logn - kTileLog, 4);
+    const int lt = mid_tile_log(c);
     uint64_t* const wa = ws;
     uint64_t* const wb = ws + polys * n;
     if (width <= polys && terms <= polys / width) {
@@ -128,22 +114,10 @@ static void ring_fold_enqueue(const NttContext& c, uint64_t* d_out, const uint64
 // One call on the device (caller validated the arguments): workspace, ordering brackets, launches.
 static void ring_fold_device(const NttContext& c, uint64_t* d_out, const uint64_t* d_v, const uint64_t* d_p, size_t outputs, size_t terms, size_t ts,
                              size_t width, hipStream_t s, bool first = true, bool last = true) {
-    std::lock_guard<std::mutex> lock(c.ring_mutex);
-    const bool capturing = stream_is_capturing(s);
-    if (!c.ring_dot_scratch.ptr) {
-        // the ring inner product's workspace: allocated once and never resized
-        if (capturing)
-            throw std::runtime_error("this call needs the context's workspace, which the first such call allocates: make one eager (uncaptured) "
-                                     "call on this context before capturing");
-        c.ring_dot_scratch.allocate(ring_dot_scratch_words(c));
-    }
-    // (a capturing stream: no brackets — lsr_runtime.hpp, stream_is_capturing)
-    if (!capturing) c.ring_event.wait(s);
-    if (c.gold) ring_fold_enqueue<ArithGold>(c, d_out, d_v, d_p, outputs, terms, ts, width, first, last, s);
-    else if (c.use_f64) ring_fold_enqueue<ArithF64>(c, d_out, d_v, d_p, outputs, terms, ts, width, first, last, s);
-    else ring_fold_enqueue<ArithU64>(c, d_out, d_v, d_p, outputs, terms, ts, width, first, last, s);
-    LSR_HIP(hipGetLastError());
-    if (!capturing) c.ring_event.record(s);
+    // the ring inner product's workspace, which every fold needs: the challenges are transformed into it at every n
+    ring_call(c, c.ring_dot_scratch, ring_dot_scratch_words(c), true, s, [&] {
+        for_flavour(c, [&](auto a) { ring_fold_enqueue<decltype(a)>(c, d_out, d_v, d_p, outputs, terms, ts, width, first, last, s); });
+    });
 }
 
 // host buffers through bounded device chunks on the context's work stream: chunks of whole outputs (with the span of vectors they
@@ -153,7 +127,7 @@ static void host_ring_fold(const NttContext& c, uint64_t* out, const uint64_t* v
                            size_t width) {
     DeviceGuard guard(c.device);
     const size_t n = c.degree, vec = width * n;
-    const size_t bound = std::max<size_t>(1, (256ull << 20) / (n * 8));          // polynomials per staged operand
+    const size_t bound = std::max<size_t>(1, kStagingBytes / (n * 8));          // polynomials per staged operand
     std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
     hipStream_t s = work_stream(c);
     if (width <= bound && terms <= bound / width) {
@@ -224,21 +198,15 @@ int ring_fold_check(const char* where, const NttContext* ctx, const void* out, c
 
 // The checks of a non-empty call that read the context, still before any device work.
 void ring_fold_validate(const NttContext& ctx, const uint64_t* out, const uint64_t* v, const uint64_t* p, const FoldCounts& k) {
-    if (ctx.logn > lsr::kTwoPassMaxLog2)
-        throw std::runtime_error("ring fold on a context above n = 131072 is not supported (lsr_cyclic_ntt_context_create_large)");
+    lsr::refuse_above_two_pass(ctx, "ring fold on a context above n = 131072 is not supported (lsr_cyclic_ntt_context_create_large)");
     const size_t poly_bytes = (size_t)ctx.degree * 8;
     size_t bytes = 0;
     if (__builtin_mul_overflow(k.v_polys, poly_bytes, &bytes) || __builtin_mul_overflow(k.p_polys, poly_bytes, &bytes) ||
         __builtin_mul_overflow(k.out_polys, poly_bytes, &bytes))
         throw std::runtime_error("the sizes of v, p or out overflow size_t at this ring degree");
-    auto overlaps = [&](const uint64_t* x, size_t polys) {
-        const uintptr_t c0 = reinterpret_cast<uintptr_t>(out), c1 = c0 + k.out_polys * poly_bytes;
-        const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), x1 = x0 + polys * poly_bytes;
-        return c0 < x1 && x0 < c1;
-    };
-    if (overlaps(v, k.v_polys)) throw std::runtime_error("out overlaps v: the output must not share memory with an operand");
-    if (overlaps(p, k.p_polys)) throw std::runtime_error("out overlaps p: the output must not share memory with an operand");
-    if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
+    lsr::require_apart(out, k.out_polys * poly_bytes, v, k.v_polys * poly_bytes, "out overlaps v: the output must not share memory with an operand");
+    lsr::require_apart(out, k.out_polys * poly_bytes, p, k.p_polys * poly_bytes, "out overlaps p: the output must not share memory with an operand");
+    lsr::require_device();
 }
 
 }  // namespace

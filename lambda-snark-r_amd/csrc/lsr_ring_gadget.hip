@@ -6,6 +6,7 @@
 
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
+#include "lsr_ring_call.hpp"
 #include "lsr_ring_gadget_kernels.hpp"
 #include "lsr_ring_matrix.hpp"
 #include "lsr_runtime.hpp"
@@ -75,45 +76,21 @@ static void gadget_tile(const LsrRingMatrix& m, uint64_t* d_y, const uint64_t* d
                        (uint32_t)(m.cols / g.digits), g, c.mod, Flavour<A>::fwd(c), Flavour<A>::inv(c), Flavour<A>::consts(c));
 }
 
-#define LSR_GADGET_CASE(LT) case LT: gadget_tile<A, LT>(m, d_y, d_x, batch, g, s); break;
 template <class A>
 static void gadget_tile_lt(const LsrRingMatrix& m, uint64_t* d_y, const uint64_t* d_x, size_t batch, const GadgetParams& g, hipStream_t s) {
-    switch (m.ctx->logn) {
-        LSR_GADGET_CASE(1) LSR_GADGET_CASE(2) LSR_GADGET_CASE(3) LSR_GADGET_CASE(4) LSR_GADGET_CASE(5) LSR_GADGET_CASE(6)
-        LSR_GADGET_CASE(7) LSR_GADGET_CASE(8) LSR_GADGET_CASE(9) LSR_GADGET_CASE(10) LSR_GADGET_CASE(11)
-        default: gadget_tile<A, 12>(m, d_y, d_x, batch, g, s); break;
-    }
+    for_tile_log<1, 12>(m.ctx->logn, [&](auto t) { gadget_tile<A, decltype(t)::value>(m, d_y, d_x, batch, g, s); });
 }
-#undef LSR_GADGET_CASE
 
 // n <= 4096 (caller validated the arguments)
 static void matvec_gadget_device(const LsrRingMatrix& m, uint64_t* d_y, const uint64_t* d_x, size_t batch, unsigned b, uint64_t digits, hipStream_t s) {
     const NttContext& c = *m.ctx;
     const GadgetParams g = gadget_params(c.modulus, b, digits);
     if (!stream_is_capturing(s)) m.ready.wait(s);
-    if (c.gold) gadget_tile_lt<ArithGold>(m, d_y, d_x, batch, g, s);
-    else if (c.use_f64) gadget_tile_lt<ArithF64>(m, d_y, d_x, batch, g, s);
-    else gadget_tile_lt<ArithU64>(m, d_y, d_x, batch, g, s);
+    for_flavour(c, [&](auto a) { gadget_tile_lt<decltype(a)>(m, d_y, d_x, batch, g, s); });
     LSR_HIP(hipGetLastError());
 }
 
-// Host buffers through bounded device chunks on the context's work stream: `in_words` words go up and `out_words` words come back
-// per item, `run(d_out, d_in, now, s)` enqueues the work of `now` items.
-template <class Run>
-static void host_staged(const NttContext& c, uint64_t* out, const uint64_t* in, size_t count, size_t out_words, size_t in_words, Run&& run) {
-    DeviceGuard guard(c.device);
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(count, ((256ull << 20) / 8) / (in_words + out_words)));
-    DeviceBuffer<uint64_t> din(chunk * in_words), dout(chunk * out_words);
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    for (size_t j0 = 0; j0 < count; j0 += chunk) {
-        const size_t now = std::min(chunk, count - j0);
-        LSR_HIP(hipMemcpyAsync(din.ptr, in + j0 * in_words, now * in_words * 8, hipMemcpyHostToDevice, s));
-        run(dout.ptr, din.ptr, now, s);
-        LSR_HIP(hipMemcpyAsync(out + j0 * out_words, dout.ptr, now * out_words * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
-}
+// (host buffers: host_staged, lsr_ring_call.hpp)
 
 }  // namespace lsr
 
@@ -139,14 +116,9 @@ static int admissible_check(const char* where, const NttContext& ctx, unsigned b
                                             : ": no digit count is admissible at this base (lsr_ring_gadget_min_digits gives 0)"));
 }
 
+// every call here has one operand: `what` names the pair
 static void require_apart(const void* out, size_t out_bytes, const void* in, size_t in_bytes, const char* what) {
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + out_bytes;
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + in_bytes;
-    if (o0 < i1 && i0 < o1) throw std::runtime_error(std::string(what) + ": the output must not share memory with the operand");
-}
-
-static void require_device() {
-    if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
+    lsr::require_apart(out, out_bytes, in, in_bytes, (std::string(what) + ": the output must not share memory with the operand").c_str());
 }
 
 static int decompose_call(const char* where, const NttContext* ctx, uint64_t* out, const uint64_t* x, size_t count, unsigned b, size_t digits, bool device,
@@ -157,7 +129,7 @@ static int decompose_call(const char* where, const NttContext* ctx, uint64_t* ou
     return lsr::abi_guarded(where, [&] {
         const size_t n = ctx->degree;
         require_apart(out, count * digits * n * 8, x, count * n * 8, "out overlaps x");
-        require_device();
+        lsr::require_device();
         if (device) {
             lsr::DeviceGuard guard(ctx->device);
             lsr::decompose_device(*ctx, out, x, count, b, digits, static_cast<hipStream_t>(stream));
@@ -177,7 +149,7 @@ static int recompose_call(const char* where, const NttContext* ctx, uint64_t* ou
     return lsr::abi_guarded(where, [&] {
         const size_t n = ctx->degree;
         require_apart(out, count * n * 8, z, count * digits * n * 8, "out overlaps z");
-        require_device();
+        lsr::require_device();
         if (device) {
             lsr::DeviceGuard guard(ctx->device);
             lsr::recompose_device(*ctx, out, z, count, b, digits, static_cast<hipStream_t>(stream));
@@ -195,7 +167,7 @@ static int linf_call(const char* where, const NttContext* ctx, const uint64_t* x
     return lsr::abi_guarded(where, [&] {
         const size_t n = ctx->degree;
         require_apart(linf, count * 8, x, count * n * 8, "linf overlaps x");
-        require_device();
+        lsr::require_device();
         if (device) {
             lsr::DeviceGuard guard(ctx->device);
             lsr::linf_device(*ctx, x, count, linf, static_cast<hipStream_t>(stream));
@@ -221,7 +193,7 @@ static int matvec_gadget_call(const char* where, const LsrRingMatrix* mat, uint6
         if (ctx.logn > lsr::kTileLog)
             throw std::runtime_error("n = " + std::to_string(n) + " is above 4096, where the product has no fused form: decompose x with "
                                      "lsr_ntt_ring_decompose_batch_device and pass the digits to lsr_ntt_ring_matvec_batch_device");
-        require_device();
+        lsr::require_device();
         if (device) {
             lsr::DeviceGuard guard(ctx.device);
             lsr::matvec_gadget_device(*mat, y, x, batch, b, digits, static_cast<hipStream_t>(stream));

@@ -10,6 +10,7 @@
 
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
+#include "lsr_ring_call.hpp"
 #include "lsr_ring_matrix.hpp"
 #include "lsr_ring_matvec_kernels.hpp"
 #include "lsr_runtime.hpp"
@@ -23,7 +24,7 @@ static_assert(LSR_RING_MATVEC_MAX_ROWS <= 65535 && LSR_RING_MATVEC_MAX_MATRIX_BY
 
 static int row_block_of(const NttContext& c) {
     if (c.logn > kTileLog) return 1;   // the composed route goes row by row
-    return c.gold ? MatvecRowBlock<ArithGold>::value : c.use_f64 ? MatvecRowBlock<ArithF64>::value : MatvecRowBlock<ArithU64>::value;
+    return for_flavour(c, [](auto a) -> int { return MatvecRowBlock<decltype(a)>::value; });
 }
 
 template <class A, int LT>
@@ -36,16 +37,10 @@ static void matvec_tile(const LsrRingMatrix& m, uint64_t* d_y, const uint64_t* d
                        c.mod, Flavour<A>::fwd(c), Flavour<A>::inv(c), Flavour<A>::consts(c));
 }
 
-#define LSR_MATVEC_CASE(LT) case LT: matvec_tile<A, LT>(m, d_y, d_x, batch, s); break;
 template <class A>
 static void matvec_tile_lt(const LsrRingMatrix& m, uint64_t* d_y, const uint64_t* d_x, size_t batch, hipStream_t s) {
-    switch (m.ctx->logn) {
-        LSR_MATVEC_CASE(1) LSR_MATVEC_CASE(2) LSR_MATVEC_CASE(3) LSR_MATVEC_CASE(4) LSR_MATVEC_CASE(5) LSR_MATVEC_CASE(6)
-        LSR_MATVEC_CASE(7) LSR_MATVEC_CASE(8) LSR_MATVEC_CASE(9) LSR_MATVEC_CASE(10) LSR_MATVEC_CASE(11)
-        default: matvec_tile<A, 12>(m, d_y, d_x, batch, s); break;
-    }
+    for_tile_log<1, 12>(m.ctx->logn, [&](auto t) { matvec_tile<A, decltype(t)::value>(m, d_y, d_x, batch, s); });
 }
-#undef LSR_MATVEC_CASE
 
 // Polynomials of the composed route's dense chunk: a third of the Infinity Cache budget of a two-pass transform, as each of
 // ring_dot's workspace arrays (lsr_ring_dot.hip).  A function of n (and of the process-wide chunk size) only.
@@ -67,13 +62,9 @@ static void matvec_composed(const LsrRingMatrix& m, uint64_t* d_y, const uint64_
         }
     }
     // The next ring call on the context (which may be a mat-vec on another stream) starts behind the last copy out of `dense`.
-    // Wait, then record, as every ring call does: another thread's ring call may have recorded the event since this call's last
-    // inner product released ring_mutex, and the chain of the workspaces' users must stay transitive.
-    std::lock_guard<std::mutex> ring_lock(c.ring_mutex);
-    if (!stream_is_capturing(s)) {
-        c.ring_event.wait(s);
-        c.ring_event.record(s);
-    }
+    // An empty ring call (wait, then record, under ring_mutex): another thread's ring call may have recorded the event since this
+    // call's last inner product released ring_mutex, and the chain of the workspaces' users must stay transitive.
+    ring_call(c, c.ring_dot_scratch, 0, false, s, [] {});
 }
 
 // One call on the device (caller validated the arguments).
@@ -84,28 +75,15 @@ static void matvec_device(const LsrRingMatrix& m, uint64_t* d_y, const uint64_t*
         matvec_composed(m, d_y, d_x, batch, s);
         return;
     }
-    if (c.gold) matvec_tile_lt<ArithGold>(m, d_y, d_x, batch, s);
-    else if (c.use_f64) matvec_tile_lt<ArithF64>(m, d_y, d_x, batch, s);
-    else matvec_tile_lt<ArithU64>(m, d_y, d_x, batch, s);
+    for_flavour(c, [&](auto a) { matvec_tile_lt<decltype(a)>(m, d_y, d_x, batch, s); });
     LSR_HIP(hipGetLastError());
 }
 
 // host buffers through bounded device chunks of whole vectors on the context's work stream
 static void host_matvec(const LsrRingMatrix& m, uint64_t* y, const uint64_t* x, size_t batch) {
-    const NttContext& c = *m.ctx;
-    DeviceGuard guard(c.device);
-    const size_t n = c.degree, vec_words = (m.rows + m.cols) * n;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, ((256ull << 20) / 8) / vec_words));
-    DeviceBuffer<uint64_t> dx(chunk * m.cols * n), dy(chunk * m.rows * n);
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    for (size_t j0 = 0; j0 < batch; j0 += chunk) {
-        const size_t now = std::min(chunk, batch - j0);
-        LSR_HIP(hipMemcpyAsync(dx.ptr, x + j0 * m.cols * n, now * m.cols * n * 8, hipMemcpyHostToDevice, s));
-        matvec_device(m, dy.ptr, dx.ptr, now, s);
-        LSR_HIP(hipMemcpyAsync(y + j0 * m.rows * n, dy.ptr, now * m.rows * n * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
+    const size_t n = m.ctx->degree;
+    host_staged(*m.ctx, y, x, batch, m.rows * n, m.cols * n,
+                [&](uint64_t* d_y, const uint64_t* d_x, size_t now, hipStream_t s) { matvec_device(m, d_y, d_x, now, s); });
 }
 
 // device: m is a device pointer, the work is enqueued on `s`; else m is a host pointer and the matrix is complete on return (with
@@ -166,13 +144,12 @@ static LsrRingMatrix* matrix_create_guarded(const char* where, const NttContext*
     if (matrix_check(where, ctx, m, rows, cols) != 0) return nullptr;
     LsrRingMatrix* mat = nullptr;
     lsr::abi_guarded(where, [&] {
-        if (ctx->logn > lsr::kTwoPassMaxLog2)
-            throw std::runtime_error("ring matrix on a context above n = 131072 is not supported (lsr_cyclic_ntt_context_create_large)");
+        lsr::refuse_above_two_pass(*ctx, "ring matrix on a context above n = 131072 is not supported (lsr_cyclic_ntt_context_create_large)");
         if (rows * cols * ctx->degree * 8 > LSR_RING_MATVEC_MAX_MATRIX_BYTES)
             throw std::runtime_error("rows * cols * n * 8 = " + std::to_string(rows * cols * ctx->degree * 8) + " bytes are above LSR_RING_MATVEC_MAX_MATRIX_BYTES (" +
                                      std::to_string(LSR_RING_MATVEC_MAX_MATRIX_BYTES) + ")");
         if (precheck) (*precheck)();
-        if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
+        lsr::require_device();
         mat = lsr::matrix_create(*ctx, m, rows, cols, device, static_cast<hipStream_t>(stream), fill);
     });
     return mat;
@@ -191,10 +168,8 @@ static int matvec_check(const char* where, const LsrRingMatrix* mat, const void*
 
 static void matvec_validate(const LsrRingMatrix& mat, const uint64_t* y, const uint64_t* x, size_t batch) {
     const size_t n = mat.ctx->degree;
-    const uintptr_t y0 = reinterpret_cast<uintptr_t>(y), y1 = y0 + batch * mat.rows * n * 8;
-    const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), x1 = x0 + batch * mat.cols * n * 8;
-    if (y0 < x1 && x0 < y1) throw std::runtime_error("y overlaps x: the output must not share memory with the operand");
-    if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
+    lsr::require_apart(y, batch * mat.rows * n * 8, x, batch * mat.cols * n * 8, "y overlaps x: the output must not share memory with the operand");
+    lsr::require_device();
 }
 
 extern "C" {

@@ -13,6 +13,7 @@
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
 #include "lsr_ntt_kernels.hpp"
+#include "lsr_ring_call.hpp"
 #include "lsr_runtime.hpp"
 
 namespace lsr {
@@ -24,23 +25,10 @@ static void ring_tile(const NttContext& c, uint64_t* d_c, const uint64_t* d_a, c
                        Flavour<A>::inv(c), Flavour<A>::consts(c));
 }
 
-#define LSR_RING_CASE(LT) case LT: ring_tile<A, LT, MID, BHAT>(c, d_c, d_a, d_b, total, s); break;
 template <class A, bool MID, bool BHAT>
 static void ring_tile_lt(const NttContext& c, int lt, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t total, hipStream_t s) {
-    if constexpr (MID) {   // the low lt = log n - 4 (n = 2^17: - 5) bits of a two-pass transform
-        switch (lt) {
-            LSR_RING_CASE(9) LSR_RING_CASE(10) LSR_RING_CASE(11)
-            default: ring_tile<A, 12, MID, BHAT>(c, d_c, d_a, d_b, total, s); break;
-        }
-    } else {
-        switch (lt) {
-            LSR_RING_CASE(1) LSR_RING_CASE(2) LSR_RING_CASE(3) LSR_RING_CASE(4) LSR_RING_CASE(5) LSR_RING_CASE(6)
-            LSR_RING_CASE(7) LSR_RING_CASE(8) LSR_RING_CASE(9) LSR_RING_CASE(10) LSR_RING_CASE(11)
-            default: ring_tile<A, 12, MID, BHAT>(c, d_c, d_a, d_b, total, s); break;
-        }
-    }
+    for_tile_log<MID ? 9 : 1, 12>(lt, [&](auto t) { ring_tile<A, decltype(t)::value, MID, BHAT>(c, d_c, d_a, d_b, total, s); });
 }
-#undef LSR_RING_CASE
 
 // Polynomials per chunk of an n > 4096 product: two arrays are live between passes (the c chunk and the workspace chunk), so each
 // gets half of the Infinity Cache budget of a two-pass transform (ntt_chunk_bytes(): 256 MiB -> 128 MiB each, 256 polynomials at
@@ -66,7 +54,7 @@ static void ring_mul_enqueue(const NttContext& c, uint64_t* d_c, const uint64_t*
         }
         return;
     }
-    const int lt = c.logn - std::max(c.logn - kTileLog, 4);
+    const int lt = mid_tile_log(c);
     const size_t chunk = ring_chunk_polys(c);
     uint64_t* const b_hat = ws + chunk * n;
     if (shared_b) launch_ntt(c, b_hat, 1, false, s, nullptr, nullptr, d_b);
@@ -82,31 +70,17 @@ static void ring_mul_enqueue(const NttContext& c, uint64_t* d_c, const uint64_t*
     }
 }
 
-// One call on the device (caller validated the arguments): workspace, ordering brackets, launches.
-static void refuse_large(const NttContext& c) {   // the middle pass below assumes ONE strided round on either side
-    if (c.logn > kTwoPassMaxLog2) throw std::runtime_error("ring multiply on a context above n = 131072 is not supported (lsr_cyclic_ntt_context_create_large)");
+static void refuse_large(const NttContext& c) {
+    refuse_above_two_pass(c, "ring multiply on a context above n = 131072 is not supported (lsr_cyclic_ntt_context_create_large)");
 }
 
+// One call on the device (caller validated the arguments): workspace, ordering brackets, launches.
 static void ring_mul_device(const NttContext& c, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t b_rows, hipStream_t s) {
     refuse_large(c);
     const bool shared_b = b_rows == 1 && batch > 1;
-    std::lock_guard<std::mutex> lock(c.ring_mutex);
-    const bool capturing = stream_is_capturing(s);
-    if ((c.logn > kTileLog || shared_b) && !c.ring_scratch.ptr) {
-        // the workspace is allocated once and never resized, so a graph captured after one eager call keeps valid pointers; an
-        // allocation inside the capture would not be part of the graph
-        if (capturing)
-            throw std::runtime_error("this call needs the context's workspace, which the first such call allocates: make one eager (uncaptured) "
-                                     "call on this context before capturing");
-        c.ring_scratch.allocate(ring_scratch_words(c));
-    }
-    // (a capturing stream: no brackets — lsr_runtime.hpp, stream_is_capturing)
-    if (!capturing) c.ring_event.wait(s);
-    if (c.gold) ring_mul_enqueue<ArithGold>(c, d_c, d_a, d_b, batch, shared_b, s);
-    else if (c.use_f64) ring_mul_enqueue<ArithF64>(c, d_c, d_a, d_b, batch, shared_b, s);
-    else ring_mul_enqueue<ArithU64>(c, d_c, d_a, d_b, batch, shared_b, s);
-    LSR_HIP(hipGetLastError());
-    if (!capturing) c.ring_event.record(s);
+    ring_call(c, c.ring_scratch, ring_scratch_words(c), c.logn > kTileLog || shared_b, s, [&] {
+        for_flavour(c, [&](auto a) { ring_mul_enqueue<decltype(a)>(c, d_c, d_a, d_b, batch, shared_b, s); });
+    });
 }
 
 // host buffers through bounded device chunks on the context's work stream
@@ -115,7 +89,7 @@ static void host_ring_mul(const NttContext& c, uint64_t* out, const uint64_t* a,
     DeviceGuard guard(c.device);
     const size_t n = c.degree;
     const bool shared_b = b_rows == 1 && batch > 1;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, (256ull << 20) / (n * 8)));
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, kStagingBytes / (n * 8)));
     DeviceBuffer<uint64_t> da(chunk * n), db(shared_b ? n : chunk * n);
     std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
     hipStream_t s = work_stream(c);
@@ -143,17 +117,13 @@ static int ring_mul_check(const char* where, const NttContext* ctx, const void* 
     return 0;
 }
 
-static void require_device() {
-    if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
-}
-
 extern "C" {
 
 int lsr_ntt_ring_mul_batch(const NttContext* ctx, uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t b_rows) noexcept {
     if (ring_mul_check("lsr_ntt_ring_mul_batch", ctx, c, a, b, batch, b_rows) != 0) return -1;
     if (batch == 0) return 0;
     return lsr::abi_guarded("lsr_ntt_ring_mul_batch", [&] {
-        require_device();
+        lsr::require_device();
         lsr::host_ring_mul(*ctx, c, a, b, batch, b_rows);
     });
 }
@@ -163,7 +133,7 @@ int lsr_ntt_ring_mul_batch_device(const NttContext* ctx, uint64_t* d_c, const ui
     if (ring_mul_check("lsr_ntt_ring_mul_batch_device", ctx, d_c, d_a, d_b, batch, b_rows) != 0) return -1;
     if (batch == 0) return 0;
     return lsr::abi_guarded("lsr_ntt_ring_mul_batch_device", [&] {
-        require_device();
+        lsr::require_device();
         lsr::DeviceGuard guard(ctx->device);
         lsr::ring_mul_device(*ctx, d_c, d_a, d_b, batch, b_rows, static_cast<hipStream_t>(stream));
     });

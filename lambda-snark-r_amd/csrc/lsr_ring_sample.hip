@@ -6,6 +6,7 @@
 
 #include "lambda_snark/batch.h"
 #include "lsr_keys.hpp"
+#include "lsr_ring_call.hpp"
 #include "lsr_ring_matrix.hpp"
 #include "lsr_ring_sample_kernels.hpp"
 #include "lsr_runtime.hpp"
@@ -75,7 +76,7 @@ static void sample_device(const NttContext& c, uint64_t* d_out, uint64_t first, 
 static void host_sample(const NttContext& c, uint64_t* out, uint64_t count, const SampleCall& call, const uint64_t* keys) {
     DeviceGuard guard(c.device);
     const size_t n = c.degree;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, ((256ull << 20) / 8) / n));
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, (kStagingBytes / 8) / n));
     const uint64_t chunk_groups = chunk / call.components + 2;
     DeviceBuffer<uint64_t> d_out(chunk * n), d_keys(chunk_groups * 4);
     std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
@@ -110,7 +111,7 @@ static int sample_call(const char* where, const NttContext* ctx, uint64_t* out, 
     if (count == 0) return 0;
     return lsr::abi_guarded(where, [&] {
         if (index_base + components < index_base) throw std::runtime_error("index_base + components overflows 64 bits");
-        if (lsr::visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
+        lsr::require_device();
         const lsr::SampleCall call{kind, param, std::min<uint64_t>(components, count), domain, index_base};
         if (device) {
             lsr::DeviceGuard guard(ctx->device);

@@ -1,4 +1,5 @@
-// The sizing of the context's ring inner-product workspace (NttContext::ring_dot_scratch), shared by the calls that use it:
+// The sizing of the context's ring inner-product workspace (NttContext::ring_dot_scratch) and the flags of a sum taken in groups of
+// terms through it, shared by the calls that use it:
 // lsr_ring_dot.hip and lsr_ring_fold.hip (§5g).  Sizes are functions of n and of the process-wide chunk size alone.
 #pragma once
 #include <algorithm>
@@ -20,5 +21,7 @@ inline size_t ring_dot_chunk_polys(const NttContext& c) {
 inline size_t ring_dot_scratch_words(const NttContext& c) {
     return (c.logn > kTileLog ? 2 : 1) * ring_dot_chunk_polys(c) * c.degree;
 }
+// the flags of one launch of a sum taken in groups of terms: it starts the sums (first group) and / or finishes them (last group)
+inline uint32_t ring_dot_flags(bool first, bool last) { return (first ? kRingDotFirst : 0u) | (last ? kRingDotLast : 0u); }
 
 }  // namespace lsr

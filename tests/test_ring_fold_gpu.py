@@ -2,7 +2,7 @@
 (lsr_ntt_ring_fold_batch / _device).  Pinned against the schoolbook definition, word for word against the ring inner
 product on the gathered operands in every arithmetic flavour, against the oracle's composition INTT(sum NTT . NTT) at every degree
 2^1 .. 2^17, at the accumulator's worst case, under a shrunken workspace (term groups, component chunks), in the commitment chain it
-exists for, and in its device form across streams."""
+exists for, and in its device form across streams and under graph capture."""
 import os
 import subprocess
 import sys
@@ -262,6 +262,60 @@ def test_device_form_is_ordered_across_streams(pkg, q, n):
     v = ctx.ring_dot(a, b).reshape(vectors, width, n)
     assert np.array_equal(_host(d_v), v)
     assert np.array_equal(_host(d_out), ctx.ring_fold(v, p, terms))
+    ctx.close()
+
+
+def test_graph_capture_after_eager_warm_up(pkg):
+    """The fold needs the context's workspace at every n, so n = 64 reaches the path."""
+    import torch
+    q, n, outputs, terms, width = Q_NORTH, 64, 2, 2, 2
+    rng = np.random.default_rng(73)
+    ctx = pkg.NttContext(q, n, device=0)
+    d_v = torch.zeros((outputs * terms, width, n), dtype=torch.int64, device="cuda")
+    d_p = torch.zeros((outputs, terms, n), dtype=torch.int64, device="cuda")
+    d_out = torch.empty((outputs, width, n), dtype=torch.int64, device="cuda")
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):      # eager warm-up: allocates the workspace
+        ctx.ring_fold_device(d_out.data_ptr(), d_v.data_ptr(), d_p.data_ptr(), outputs, terms, terms, width, side.cuda_stream)
+    side.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        ctx.ring_fold_device(d_out.data_ptr(), d_v.data_ptr(), d_p.data_ptr(), outputs, terms, terms, width, torch.cuda.current_stream().cuda_stream)
+    for _ in range(2):                 # two replays, each on fresh inputs
+        v, p = _operands(rng, q, n, outputs, terms, terms, width)
+        d_v.copy_(_dev(torch, v))
+        d_p.copy_(_dev(torch, p))
+        graph.replay()
+        torch.cuda.synchronize()
+        assert _host(d_out).tolist() == schoolbook_fold(v, p, terms, q, -1)
+    ctx.close()
+
+
+def test_first_call_under_capture_is_refused(pkg):
+    import torch
+    q, n, outputs, terms, width = Q_NORTH, 64, 2, 2, 2
+    rng = np.random.default_rng(74)
+    ctx = pkg.NttContext(q, n, device=0)
+    v, p = _operands(rng, q, n, outputs, terms, terms, width)
+    d_v, d_p = _dev(torch, v), _dev(torch, p)
+    d_out = torch.zeros((outputs, width, n), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    graph = torch.cuda.CUDAGraph()
+    rc = None
+    with torch.cuda.graph(graph, stream=side):
+        d_out.add_(0)                  # (keeps the captured graph non-empty)
+        rc = ctx._lib.lsr_ntt_ring_fold_batch_device(ctx.handle, d_out.data_ptr(), d_v.data_ptr(), d_p.data_ptr(), outputs, terms, terms, width,
+                                                     torch.cuda.current_stream().cuda_stream)
+    assert rc == -1
+    assert "eager" in pkg._abi.last_error()
+    graph.replay()                     # the capture stayed usable
+    torch.cuda.synchronize()
+    assert not bool(d_out.any())       # and holds no launch of the refused call
+    ctx.ring_fold_device(d_out.data_ptr(), d_v.data_ptr(), d_p.data_ptr(), outputs, terms, terms, width, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert _host(d_out).tolist() == schoolbook_fold(v, p, terms, q, -1)      # the context still works
     ctx.close()
 
 
