@@ -305,6 +305,43 @@ int lsr_ntt_ring_fold_batch(const NttContext* ctx, uint64_t* out, const uint64_t
 int lsr_ntt_ring_fold_batch_device(const NttContext* ctx, uint64_t* d_out, const uint64_t* d_v, const uint64_t* d_p,
                                    size_t outputs, size_t terms, size_t term_stride, size_t width, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: Galois automorphisms of ring elements and the twisted ring inner product ---------------- */
+/* sigma_g: X -> X^g in the ring of the context.  With n the context's degree, N = 2 n on negacyclic contexts
+ * (X^n + 1) and N = n on cyclic ones (X^n - 1); a Galois element is an odd g with 1 <= g < N.  sigma_g(sum_i x_i X^i) =
+ * sum_i x_i X^(i g) reduced in the ring; with h = g^-1 mod N, on canonical words in natural coefficient order:
+ *   negacyclic: s = (j h) mod 2 n;  out[j] = x[s] if s < n, else q - x[s - n] (0 where x[s - n] is 0);
+ *   cyclic:     out[j] = x[(j h) mod n].
+ * g = N - 1 is the conjugation: the constant coefficient of sigma_{N-1}(a) b is the inner product of the coefficient vectors of a and
+ * b mod q.  sigma_g sigma_h = sigma_{g h mod N}.  The output for a word >= q is unspecified (arithmetic on the word: it never faults).
+ *
+ * lsr_ntt_ring_automorphism_batch(_device): out[e] = sigma_g(x[e]), e < count, buffers [count][n].  Served on every context the
+ * library creates and at every n (large cyclic contexts up to 2^22 included): it runs no transform, needs no workspace and takes
+ * no part in the context's ring ordering — the device form is asynchronous in plain stream order (as
+ * lsr_ntt_ring_decompose_batch_device) and capturable with no warm-up call.
+ * lsr_ntt_ring_dot_galois_batch(_device): c_j = sum_{i < terms} sigma_g(a_{j,i}) b_{j,i}, shapes and b_rows of lsr_ntt_ring_dot_batch.
+ * c equals lsr_ntt_ring_dot_batch applied to the materialised sigma_g(a) word for word, in every arithmetic flavour; g = 1 equals
+ * lsr_ntt_ring_dot_batch.  The permutation and the sign are applied where the fused kernel reads a: sigma_g(a) never exists in
+ * memory.  Served at n <= 4096 only (as lsr_ntt_ring_matvec_gadget_batch); above, compose the two calls.  Workspace, ordering event
+ * and graph capture: the contract of lsr_ntt_ring_dot_batch, and its workspace (a shared b needs it: one eager ring inner product
+ * on the context before a capture).
+ * g is passed by value and validated on the host: the device forms enqueue only.
+ *
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL context or buffer;
+ * (2) inner product only: b_rows not 1 or batch, then terms == 0; (3) g even (both rings: read without the context).  (4) Then
+ * count == 0 or batch == 0 is a no-op that returns 0.  (5) A size that overflows size_t: batch * terms, b_rows * terms, or a
+ * polynomial count times 16 bytes (a polynomial of the smallest ring) — all of these without reading the context.  Then (6) g >= N;
+ * the byte size of a buffer overflowing size_t at the context's n; inner product only: n above 4096, terms above
+ * LSR_RING_DOT_MAX_TERMS; the output overlapping an input in address range (there is no in-place form); no visible device.
+ *
+ * The host forms stage through bounded device chunks and return when the output is complete. */
+int lsr_ntt_ring_automorphism_batch(const NttContext* ctx, uint64_t* out, const uint64_t* x, size_t count, uint64_t g) LSR_NOEXCEPT;
+int lsr_ntt_ring_automorphism_batch_device(const NttContext* ctx, uint64_t* d_out, const uint64_t* d_x, size_t count, uint64_t g,
+                                           void* stream) LSR_NOEXCEPT;
+int lsr_ntt_ring_dot_galois_batch(const NttContext* ctx, uint64_t* c, const uint64_t* a, const uint64_t* b,
+                                  size_t batch, size_t terms, size_t b_rows, uint64_t g) LSR_NOEXCEPT;
+int lsr_ntt_ring_dot_galois_batch_device(const NttContext* ctx, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b,
+                                         size_t batch, size_t terms, size_t b_rows, uint64_t g, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

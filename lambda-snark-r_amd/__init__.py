@@ -348,7 +348,58 @@ class _RingFold:
                "lsr_ntt_ring_fold_batch_device")
 
 
-class NttContext(_RingGadget, _RingSample, _RingFold):
+class _RingGalois:
+    """Galois automorphisms sigma_g: X -> X^g on a context (``NttContext``: N = 2 n, ``CyclicNtt``: N = n; g odd, 1 <= g < N; batch.h
+    "Galois automorphisms")."""
+
+    _GALOIS_ORDER_PER_N = 2   # N / n: X has order 2 n modulo X^n + 1
+
+    @property
+    def galois_conjugation(self):
+        """N - 1, the element of the conjugation X -> X^-1: coefficient 0 of ring_dot_galois(a, b, N - 1) is <a, b> mod q."""
+        return self._GALOIS_ORDER_PER_N * self.n - 1
+
+    def ring_automorphism(self, x, g):
+        """sigma_g of every element of x [n] or [..., n] (canonical words in, canonical words out; same shape)."""
+        x_in = _u64_array(x)
+        if x_in.shape[-1] != self.n:
+            raise ValueError("x must be [n] or [..., n]")
+        x2 = np.ascontiguousarray(x_in.reshape(-1, self.n))
+        out = np.empty_like(x2)
+        _check(self._lib.lsr_ntt_ring_automorphism_batch(self._h, out.ctypes.data, x2.ctypes.data, x2.shape[0], int(g)),
+               "lsr_ntt_ring_automorphism_batch")
+        return out.reshape(x_in.shape)
+
+    def ring_automorphism_device(self, d_out, d_x, count, g, stream=0):
+        """Device buffers: out and x [count][n], out apart from x.  Asynchronous on `stream` in plain stream order; enqueues only."""
+        _check(self._lib.lsr_ntt_ring_automorphism_batch_device(self._h, d_out, d_x, count, int(g), stream),
+               "lsr_ntt_ring_automorphism_batch_device")
+
+    def ring_dot_galois(self, a, b, g):
+        """c = sum_i sigma_g(a_i) * b_i in the context's ring, equal to ring_dot(ring_automorphism(a, g), b) word for word (n <= 4096);
+        shapes as ring_dot."""
+        n = self.n
+        a_in = _u64_array(a)
+        if a_in.ndim < 2 or a_in.shape[-1] != n:
+            raise ValueError("a must be [terms, n] or [batch, terms, n]")
+        terms = a_in.shape[-2]
+        if terms == 0:
+            raise ValueError("terms must be at least 1")
+        a3 = np.ascontiguousarray(a_in.reshape(-1, terms, n))
+        b3 = np.ascontiguousarray(_u64_array(b).reshape(-1, terms, n))
+        batch, b_rows = a3.shape[0], b3.shape[0]
+        out = np.empty((batch, n), dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_dot_galois_batch(self._h, out.ctypes.data, a3.ctypes.data, b3.ctypes.data, batch, terms, b_rows, int(g)),
+               "lsr_ntt_ring_dot_galois_batch")
+        return out[0] if a_in.ndim == 2 else out
+
+    def ring_dot_galois_device(self, d_c, d_a, d_b, batch, terms, b_rows, g, stream=0):
+        """Device buffers, shapes as ring_dot_device.  Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ntt_ring_dot_galois_batch_device(self._h, d_c, d_a, d_b, batch, terms, b_rows, int(g), stream),
+               "lsr_ntt_ring_dot_galois_batch_device")
+
+
+class NttContext(_RingGadget, _RingSample, _RingFold, _RingGalois):
     """RAII handle over ``NttContext*`` (cpp-core/include/lambda_snark/ntt.h:25-41)."""
 
     def __init__(self, q, n, device=-1):
@@ -954,10 +1005,12 @@ def prover_max_log2_size():
     return int(_abi.lib().lsr_prover_max_log2_size())
 
 
-class CyclicNtt(_RingGadget, _RingSample, _RingFold):
+class CyclicNtt(_RingGadget, _RingSample, _RingFold, _RingGalois):
     """The transform pair of rust-api/lambda-snark/src/ntt.rs: ``forward(coeffs)`` = ``ntt_forward(coeffs, modulus, omega)``
     (natural order in and out), ``inverse(evals)`` = ``ntt_inverse``.  One handle per (modulus, n, omega).  n above 2^17 (up to 2^22,
     NTT_MODULUS only) goes through ``lsr_cyclic_ntt_context_create_large``."""
+
+    _GALOIS_ORDER_PER_N = 1   # X has order n modulo X^n - 1
 
     def __init__(self, n, modulus=NTT_MODULUS, omega=0, device=-1):
         self._lib = _abi.lib()

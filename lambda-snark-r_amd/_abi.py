@@ -106,6 +106,10 @@ SIGNATURES = {
     "lsr_ntt_ring_dot_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, vp]),
     "lsr_ntt_ring_fold_batch": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, c_size]),
     "lsr_ntt_ring_fold_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, c_size, vp]),
+    "lsr_ntt_ring_automorphism_batch": (c_int, [vp, vp, vp, c_size, u64]),
+    "lsr_ntt_ring_automorphism_batch_device": (c_int, [vp, vp, vp, c_size, u64, vp]),
+    "lsr_ntt_ring_dot_galois_batch": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, u64]),
+    "lsr_ntt_ring_dot_galois_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, u64, vp]),
     "lsr_ntt_ring_matrix_create": (vp, [vp, vp, c_size, c_size]),
     "lsr_ntt_ring_matrix_create_device": (vp, [vp, vp, c_size, c_size, vp]),
     "lsr_ntt_ring_matrix_free": (None, [vp]),

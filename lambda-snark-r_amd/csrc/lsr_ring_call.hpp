@@ -1,5 +1,5 @@
 // The host call path shared by the fused ring operations (lsr_ring_mul.hip, lsr_ring_dot.hip, lsr_ring_fold.hip, lsr_ring_matvec.hip,
-// lsr_ring_gadget.hip, lsr_ring_sample.hip and the ring combination of lsr_commit.hip): the dispatch from a context to a kernel
+// lsr_ring_gadget.hip, lsr_ring_galois.hip, lsr_ring_sample.hip and the ring combination of lsr_commit.hip): the dispatch from a context to a kernel
 // instantiation, the bracket that keeps the context's workspaces safe across streams and threads, the argument checks
 // the entry points have in common and the staging of host buffers.  Host code only.
 #pragma once
@@ -89,6 +89,35 @@ void host_staged(const NttContext& c, uint64_t* out, const uint64_t* in, size_t 
         LSR_HIP(hipMemcpyAsync(din.ptr, in + j0 * in_words, now * in_words * 8, hipMemcpyHostToDevice, s));
         run(dout.ptr, din.ptr, now, s);
         LSR_HIP(hipMemcpyAsync(out + j0 * out_words, dout.ptr, now * out_words * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+// The host buffers of a ring inner product c_j = sum_i f(a_{j,i}) b_{j,i} ([batch][terms][n] against [b_rows][terms][n]) through
+// bounded device chunks on the context's work stream: whole outputs while one output's terms fit the staging bound, else one output
+// at a time with its terms in groups (the accumulator stays on the device between groups).
+// `run(d_c, d_a, d_b, now, group, b_rows, s, first, last)` enqueues the device call of `now` outputs over `group` terms; first / last:
+// the group starts / finishes the sums.
+template <class Run>
+void host_staged_dot(const NttContext& c, uint64_t* out, const uint64_t* a, const uint64_t* b, size_t batch, size_t terms, size_t b_rows, Run&& run) {
+    DeviceGuard guard(c.device);
+    const size_t n = c.degree;
+    const bool shared_b = b_rows == 1 && batch > 1;
+    const size_t bound = std::max<size_t>(1, kStagingBytes / (n * 8));          // polynomials per staged operand
+    const size_t group_max = std::min(terms, bound), chunk = group_max == terms ? std::max<size_t>(1, std::min(batch, bound / terms)) : 1;
+    DeviceBuffer<uint64_t> da(chunk * group_max * n), db((shared_b ? 1 : chunk) * group_max * n), dc(chunk * n);
+    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
+    hipStream_t s = work_stream(c);
+    for (size_t j0 = 0; j0 < batch; j0 += chunk) {
+        const size_t now = std::min(chunk, batch - j0);
+        for (size_t i0 = 0; i0 < terms; i0 += group_max) {
+            const size_t group = std::min(group_max, terms - i0), off = (j0 * terms + i0) * n;
+            LSR_HIP(hipMemcpyAsync(da.ptr, a + off, now * group * n * 8, hipMemcpyHostToDevice, s));
+            if (!shared_b) LSR_HIP(hipMemcpyAsync(db.ptr, b + off, now * group * n * 8, hipMemcpyHostToDevice, s));
+            else if (j0 == 0 || group != terms) LSR_HIP(hipMemcpyAsync(db.ptr, b + i0 * n, group * n * 8, hipMemcpyHostToDevice, s));
+            run(dc.ptr, da.ptr, db.ptr, now, group, shared_b ? 1 : now, s, i0 == 0, i0 + group == terms);
+        }
+        LSR_HIP(hipMemcpyAsync(out + j0 * n, dc.ptr, now * n * 8, hipMemcpyDeviceToHost, s));
         LSR_HIP(hipStreamSynchronize(s));
     }
 }

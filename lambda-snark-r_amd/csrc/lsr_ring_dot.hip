@@ -100,29 +100,12 @@ static void ring_dot_device(const NttContext& c, uint64_t* d_c, const uint64_t* 
     });
 }
 
-// host buffers through bounded device chunks on the context's work stream: whole outputs while one output's terms fit the staging
-// bound, else one output at a time with its terms in groups (the accumulator stays on the device between groups)
+// (host buffers: host_staged_dot, lsr_ring_call.hpp)
 static void host_ring_dot(const NttContext& c, uint64_t* out, const uint64_t* a, const uint64_t* b, size_t batch, size_t terms, size_t b_rows) {
-    DeviceGuard guard(c.device);
-    const size_t n = c.degree;
-    const bool shared_b = b_rows == 1 && batch > 1;
-    const size_t bound = std::max<size_t>(1, kStagingBytes / (n * 8));          // polynomials per staged operand
-    const size_t group_max = std::min(terms, bound), chunk = group_max == terms ? std::max<size_t>(1, std::min(batch, bound / terms)) : 1;
-    DeviceBuffer<uint64_t> da(chunk * group_max * n), db((shared_b ? 1 : chunk) * group_max * n), dc(chunk * n);
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    for (size_t j0 = 0; j0 < batch; j0 += chunk) {
-        const size_t now = std::min(chunk, batch - j0);
-        for (size_t i0 = 0; i0 < terms; i0 += group_max) {
-            const size_t group = std::min(group_max, terms - i0), off = (j0 * terms + i0) * n;
-            LSR_HIP(hipMemcpyAsync(da.ptr, a + off, now * group * n * 8, hipMemcpyHostToDevice, s));
-            if (!shared_b) LSR_HIP(hipMemcpyAsync(db.ptr, b + off, now * group * n * 8, hipMemcpyHostToDevice, s));
-            else if (j0 == 0 || group != terms) LSR_HIP(hipMemcpyAsync(db.ptr, b + i0 * n, group * n * 8, hipMemcpyHostToDevice, s));
-            ring_dot_device(c, dc.ptr, da.ptr, db.ptr, now, group, shared_b ? 1 : now, s, i0 == 0, i0 + group == terms);
-        }
-        LSR_HIP(hipMemcpyAsync(out + j0 * n, dc.ptr, now * n * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
+    host_staged_dot(c, out, a, b, batch, terms, b_rows,
+                    [&](uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t now, size_t group, size_t rows, hipStream_t s, bool first, bool last) {
+                        ring_dot_device(c, d_c, d_a, d_b, now, group, rows, s, first, last);
+                    });
 }
 
 }  // namespace lsr

@@ -1,6 +1,6 @@
 // The sizing of the context's ring inner-product workspace (NttContext::ring_dot_scratch) and the flags of a sum taken in groups of
 // terms through it, shared by the calls that use it:
-// lsr_ring_dot.hip and lsr_ring_fold.hip (§5g).  Sizes are functions of n and of the process-wide chunk size alone.
+// lsr_ring_dot.hip, lsr_ring_fold.hip (§5g) and lsr_ring_galois.hip (§5h).  Sizes are functions of n and of the process-wide chunk size alone.
 #pragma once
 #include <algorithm>
 
