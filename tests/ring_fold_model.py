@@ -2,11 +2,13 @@
 out[j][c] = sum_{i < terms} p[j][i] * v[j term_stride + i][c].
 
   * gather:          the ring-dot operands the fold is defined by — a[(j, c)][i] = v[j term_stride + i][c], b[(j, c)][i] = p[j][i];
-  * schoolbook_fold: the definition on Python integers, through ring_tile_model.schoolbook_dot on the gathered operands.
-The tests at the bottom (no GPU) pin the gather by hand."""
+  * schoolbook_fold: the definition on Python integers, through ring_tile_model.schoolbook_dot on the gathered operands;
+  * fold_ref:        the oracle's composition INTT(sum NTT . NTT) on the gathered operands, for the sizes the schoolbook is too slow at.
+The tests at the bottom (no GPU) pin the gather by hand; ring_galois_model.test_references_equal_the_schoolbook holds fold_ref against
+schoolbook_fold."""
 import numpy as np
 
-from ring_tile_model import schoolbook_dot
+from ring_tile_model import oracle_dot, schoolbook_dot
 
 
 def vectors_needed(outputs, terms, term_stride):
@@ -31,6 +33,13 @@ def schoolbook_fold(v, p, term_stride, q, sign):
     a, b = gather(v, p, term_stride)
     flat = schoolbook_dot(a, b, q, sign)
     return [flat[j * width:(j + 1) * width] for j in range(outputs)]
+
+
+def fold_ref(oracle, q, n, v, p, term_stride, cyclic, omega):
+    """[outputs, width, n] uint64: ring_tile_model.oracle_dot (the oracle's transforms around pointwise sums) on the gathered
+    operands."""
+    a, b = gather(v, p, term_stride)
+    return oracle_dot(oracle, q, n, a, b, cyclic, omega).reshape(p.shape[0], v.shape[1], n)
 
 
 # ---- the gather by hand (CPU only) ---------------------------------------------------------------------------------------------------

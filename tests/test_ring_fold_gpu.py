@@ -2,7 +2,9 @@
 (lsr_ntt_ring_fold_batch / _device).  Pinned against the schoolbook definition, word for word against the ring inner
 product on the gathered operands in every arithmetic flavour, against the oracle's composition INTT(sum NTT . NTT) at every degree
 2^1 .. 2^17, at the accumulator's worst case, under a shrunken workspace (term groups, component chunks), in the commitment chain it
-exists for, and in its device form across streams and under graph capture."""
+exists for, and in its device form across streams and under graph capture.
+Every flavour and tile size against CPU references: tests/test_ring_galois_fold_sweep_gpu.py (LT = 1 .. 12) and
+tests/test_ring_cyclic_two_pass_gpu.py (the cyclic MID instantiations)."""
 import os
 import subprocess
 import sys

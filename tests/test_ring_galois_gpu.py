@@ -3,7 +3,8 @@
 definition, by the group law and the ring homomorphism in every arithmetic flavour at every kernel form, the fused call word for word
 against the composition of the two plain calls, its constant term against the integer inner product, at the accumulator's worst case,
 under a shrunken workspace (term groups), in its refusals that read the context, and in its device form across streams and under
-graph capture."""
+graph capture.
+Every flavour and tile size LT = 1 .. 12 of both kernels against CPU references: tests/test_ring_galois_fold_sweep_gpu.py."""
 import os
 import subprocess
 import sys
