@@ -21,9 +21,25 @@ def centred_poly(words, t):
     return np.array([combine_model.centred(int(c), t) for c in np.ravel(words)], dtype=np.int64)
 
 
+def centred_words(words, t):
+    """centred_poly in the shape of `words` and without the Python loop (t < 2^63), for the calls of many thousand terms"""
+    c = np.asarray(words, dtype=np.uint64) % np.uint64(t)
+    return np.where(c > np.uint64(t // 2), c.astype(np.int64) - np.int64(t), c.astype(np.int64))
+
+
 def weight(polys, t):
     """sum over every coefficient of every polynomial of |c'|: what the budget is compared with"""
     return combine_model.weight(np.ravel(polys), t)
+
+
+def fold_shared_rows(polys, row_of_term, distinct, t):
+    """Terms that share a row: sum_i p'_i * row[r(i)] = sum_r (sum_{i : r(i) = r} p'_i) * row[r].  polys: uint64 [terms][n] words,
+    row_of_term: [terms] indices below `distinct` -> uint64 [distinct][n] words whose centred representatives are the inner sums
+    (asserted to lie within (-t/2, t/2], so that centring returns them)."""
+    sums = np.zeros((distinct, polys.shape[1]), dtype=np.int64)
+    np.add.at(sums, np.asarray(row_of_term), centred_words(polys, t))
+    assert int(np.abs(sums).max()) < t // 2, "the folded coefficients leave the centred range"
+    return np.where(sums < 0, sums + np.int64(t), sums).astype(np.uint64)
 
 
 def layout(n, k, moduli):
@@ -55,6 +71,23 @@ def dot_sparse(residues, polys, q):
     return np.array([int(v) % q for v in total], dtype=np.uint64)
 
 
+def dot_schoolbook(residues, polys, q):
+    """the same by the definition, on Python integers: coefficient x + y of the product receives p[x] a[y], negated past X^n"""
+    n = residues.shape[1]
+    acc = [0] * n
+    for a, p in zip(residues, polys):
+        a = [int(v) for v in a]
+        for x, c in enumerate(int(c) for c in p):
+            if c == 0:
+                continue
+            for y, v in enumerate(a):
+                if x + y < n:
+                    acc[x + y] += c * v
+                else:
+                    acc[x + y - n] -= c * v
+    return np.array([v % q for v in acc], dtype=np.uint64)
+
+
 def dot_dense(oracle, residues, polys, q):
     """the same through the oracle's negacyclic transforms"""
     n = residues.shape[1]
@@ -66,9 +99,9 @@ def dot_dense(oracle, residues, polys, q):
     return np.asarray(oracle.ntt_inverse(q, n, summed)).reshape(n)
 
 
-def combine_row(rows, polys, t, n, k, moduli, oracle=None):
+def combine_row(rows, polys, t, n, k, moduli, oracle=None, schoolbook=False):
     """wire rows (uint64 [terms][words]) and coefficient words (uint64 [terms][n]) -> the combined row (uint64 [words]); the dense form
-    when an oracle is given, the sparse one otherwise"""
+    when an oracle is given, the schoolbook when asked for, the sparse form otherwise"""
     head, blocks = layout(n, k, moduli)
     centred = np.array([centred_poly(p, t) for p in polys])
     out = np.zeros(rows.shape[1], dtype=np.uint64)
@@ -77,14 +110,18 @@ def combine_row(rows, polys, t, n, k, moduli, oracle=None):
         for c in range(k + 1):
             lo = first + c * n
             comp = np.ascontiguousarray(rows[:, lo:lo + n])
-            out[lo:lo + n] = dot_dense(oracle, comp, centred, q) if oracle is not None else dot_sparse(comp, centred, q)
+            if schoolbook:
+                out[lo:lo + n] = dot_schoolbook(comp, centred, q)
+            else:
+                out[lo:lo + n] = dot_dense(oracle, comp, centred, q) if oracle is not None else dot_sparse(comp, centred, q)
     return out
 
 
-def combine_rows(rows, polys, term_stride, t, n, k, moduli, oracle=None):
+def combine_rows(rows, polys, term_stride, t, n, k, moduli, oracle=None, schoolbook=False):
     """the whole call: polys uint64 [outputs][terms][n] -> uint64 [outputs][words]"""
     outputs, terms = polys.shape[:2]
-    return np.array([combine_row(rows[j * term_stride:j * term_stride + terms], polys[j], t, n, k, moduli, oracle) for j in range(outputs)])
+    return np.array([combine_row(rows[j * term_stride:j * term_stride + terms], polys[j], t, n, k, moduli, oracle, schoolbook)
+                     for j in range(outputs)])
 
 
 def message(msgs, polys, t):

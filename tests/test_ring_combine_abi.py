@@ -127,3 +127,50 @@ def test_sparse_and_dense_forms_agree(oracle):
         # a dense polynomial through both forms as well
         full = rng.integers(0, 2**63, size=(3, n), dtype=np.uint64)
         assert np.array_equal(model.combine_row(rows, full, t, n, k, moduli), model.combine_row(rows, full, t, n, k, moduli, oracle=oracle))
+
+
+def test_schoolbook_by_hand_and_against_the_sparse_form():
+    q, t = 17592169062401, rns_model.plain_modulus(4096)
+    a, p = np.array([[3, q - 5]], dtype=np.uint64), np.array([[2, -7]], dtype=np.int64)
+    # (2 - 7X)(3 + (q - 5)X) mod X^2 + 1 = 6 + 7(q - 5) + (2(q - 5) - 21) X
+    assert model.dot_schoolbook(a, p, q).tolist() == [(6 + 7 * (q - 5)) % q, (2 * (q - 5) - 21) % q]
+    rng = np.random.default_rng(6)
+    for n in (2, 4, 16, 64):
+        for modulus in (q, rns_model.rns_moduli(n)[1], (1 << 60) - 93):
+            residues = rng.integers(0, modulus, size=(3, n), dtype=np.uint64)
+            residues[0, 0], residues[2, n - 1] = modulus - 1, 0
+            polys = rng.integers(-(t // 2), t // 2 + 1, size=(3, n), dtype=np.int64)           # the full centred range (-t/2, t/2]
+            polys[1, 0], polys[1, n - 1] = t // 2, -(t // 2)
+            assert np.array_equal(model.dot_schoolbook(residues, polys, modulus), model.dot_sparse(residues, polys, modulus)), (n, modulus)
+    # through combine_row: the header and every component of both blocks
+    n, k, moduli = 16, 2, rns_model.rns_moduli(16)
+    rows = _rows(rng, 3, n, k, moduli, model.rns_header(n, k, t, moduli))
+    words = rng.integers(0, 2**64, size=(3, n), dtype=np.uint64)
+    assert np.array_equal(model.combine_row(rows, words, t, n, k, moduli, schoolbook=True), model.combine_row(rows, words, t, n, k, moduli))
+
+
+def test_centred_words_equals_centred_poly():
+    rng = np.random.default_rng(7)
+    for t in (rns_model.plain_modulus(2), rns_model.plain_modulus(4096), rns_model.plain_modulus(131072)):
+        words = rng.integers(0, 2**64, size=(3, 50), dtype=np.uint64)
+        words[0, :8] = [0, 1, t // 2, t // 2 + 1, t - 1, t, t + 5, 2**64 - 1]
+        got = model.centred_words(words, t)
+        assert got.shape == words.shape and got.dtype == np.int64
+        assert np.array_equal(got.ravel(), model.centred_poly(words, t))
+        assert int(np.abs(got).sum()) == model.weight(words, t)
+
+
+def test_folding_the_polynomials_of_shared_rows_keeps_the_combination():
+    rng = np.random.default_rng(8)
+    n, k, q, t = 32, 1, 17592169062401, rns_model.plain_modulus(4096)
+    distinct, terms = 3, 11
+    pool = _rows(rng, distinct, n, k, (q,), [8 * (4 + (k + 1) * n), 1, n | (k << 32), q, t])
+    polys = np.zeros((terms, n), dtype=np.uint64)
+    for i in range(terms):
+        polys[i, rng.choice(n, size=3, replace=False)] = rng.choice(np.array([1, t - 1, t + 1, 2, t - 2], dtype=np.uint64), size=3)
+    row_of_term = (2 + np.arange(terms)) % distinct
+    folded = model.fold_shared_rows(polys, row_of_term, distinct, t)
+    assert folded.shape == (distinct, n)
+    for r in range(distinct):
+        assert model.centred_poly(folded[r], t).tolist() == sum(model.centred_poly(p, t) for p in polys[row_of_term == r]).tolist()
+    assert np.array_equal(model.combine_row(pool, folded, t, n, k, (q,)), model.combine_row(pool[row_of_term], polys, t, n, k, (q,)))
