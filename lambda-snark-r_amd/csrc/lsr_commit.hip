@@ -119,48 +119,42 @@ struct LweContext {
 
 namespace lsr {
 
+static RoundConsts<ArithF64> round_consts(const LweContext& c) { return {c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64}; }
+
 static void matvec(const LweContext& c, uint64_t* out, const uint64_t* mat, const uint64_t* vec, const uint64_t* add, uint32_t rows, uint32_t cols,
                    uint32_t row_stride, uint32_t col_stride, uint64_t batch, hipStream_t s) {
     const uint64_t work = batch * rows * (uint64_t)c.n;
     if (!work) return;
     const unsigned grid = static_cast<unsigned>((work + 255) / 256);
-    if (c.ntt->use_f64)
-        hipLaunchKernelGGL(matvec_kernel<true>, dim3(grid), dim3(256), 0, s, out, mat, vec, add, rows, cols, row_stride, col_stride, (uint32_t)c.logn, batch, c.ntt->mod);
-    else
-        hipLaunchKernelGGL(matvec_kernel<false>, dim3(grid), dim3(256), 0, s, out, mat, vec, add, rows, cols, row_stride, col_stride, (uint32_t)c.logn, batch, c.ntt->mod);
+    for_bool(c.ntt->use_f64, [&](auto f64) {
+        hipLaunchKernelGGL(matvec_kernel<decltype(f64)::value>, dim3(grid), dim3(256), 0, s, out, mat, vec, add, rows, cols, row_stride, col_stride,
+                           (uint32_t)c.logn, batch, c.ntt->mod);
+    });
     LSR_HIP(hipGetLastError());
 }
 
 // out[j] = M^(T) vec[j] (+ add) for the k x k matrix; rank-specialised kernels for k <= 4, generic otherwise
-template <int K>
-static void launch_square(const LweContext& c, uint64_t* out, const uint64_t* mat, const uint64_t* vec, const uint64_t* add, bool transposed,
+static void matvec_square(const LweContext& c, uint64_t* out, const uint64_t* mat, const uint64_t* vec, const uint64_t* add, bool transposed,
                           uint64_t batch, hipStream_t s) {
+    if (!batch) return;
+    if (c.k > 4) {
+        if (transposed) matvec(c, out, mat, vec, add, c.k, c.k, 1, c.k, batch, s);
+        else matvec(c, out, mat, vec, add, c.k, c.k, c.k, 1, batch, s);
+        return;
+    }
     constexpr int JB = 4;   // witness vectors per lane
     const uint64_t lanes = ((batch + JB - 1) / JB) * c.n;
     const unsigned grid = static_cast<unsigned>((lanes + 255) / 256);
     const uint32_t logn = static_cast<uint32_t>(c.logn);
-    if (c.ntt->use_f64) {
-        if (transposed) hipLaunchKernelGGL((matvec_square_kernel<K, true, true, JB>), dim3(grid), dim3(256), 0, s, out, mat, vec, add, logn, batch, c.ntt->mod);
-        else hipLaunchKernelGGL((matvec_square_kernel<K, true, false, JB>), dim3(grid), dim3(256), 0, s, out, mat, vec, add, logn, batch, c.ntt->mod);
-    } else {
-        if (transposed) hipLaunchKernelGGL((matvec_square_kernel<K, false, true, JB>), dim3(grid), dim3(256), 0, s, out, mat, vec, add, logn, batch, c.ntt->mod);
-        else hipLaunchKernelGGL((matvec_square_kernel<K, false, false, JB>), dim3(grid), dim3(256), 0, s, out, mat, vec, add, logn, batch, c.ntt->mod);
-    }
+    for_rank(c.k, [&](auto rank) {
+        for_bool(c.ntt->use_f64, [&](auto f64) {
+            for_bool(transposed, [&](auto tr) {
+                hipLaunchKernelGGL((matvec_square_kernel<decltype(rank)::value, decltype(f64)::value, decltype(tr)::value, JB>), dim3(grid), dim3(256), 0, s, out,
+                                   mat, vec, add, logn, batch, c.ntt->mod);
+            });
+        });
+    });
     LSR_HIP(hipGetLastError());
-}
-
-static void matvec_square(const LweContext& c, uint64_t* out, const uint64_t* mat, const uint64_t* vec, const uint64_t* add, bool transposed,
-                          uint64_t batch, hipStream_t s) {
-    if (!batch) return;
-    switch (c.k) {
-        case 1: launch_square<1>(c, out, mat, vec, add, transposed, batch, s); break;
-        case 2: launch_square<2>(c, out, mat, vec, add, transposed, batch, s); break;
-        case 3: launch_square<3>(c, out, mat, vec, add, transposed, batch, s); break;
-        case 4: launch_square<4>(c, out, mat, vec, add, transposed, batch, s); break;
-        default:
-            if (transposed) matvec(c, out, mat, vec, add, c.k, c.k, 1, c.k, batch, s);
-            else matvec(c, out, mat, vec, add, c.k, c.k, c.k, 1, batch, s);
-    }
 }
 
 // staging of a batch's stream keys and messages (every commit path), grown on demand
@@ -410,14 +404,6 @@ constexpr int kFusedStreams = LSR_FUSED_STREAMS;                          // chu
 constexpr size_t kVerifyChunkBytes = size_t(LSR_VERIFY_CHUNK_MIB) << 20;  // openings at n >= 2^16: workspace of the u vectors per chunk
 constexpr int kVerifyStreams = LSR_VERIFY_STREAMS;                        // chunk lanes of the openings (lane 0 = the caller's stream)
 
-template <int K>
-static void launch_mid(const LweContext& c, const uint64_t* ws, uint64_t* d_u, size_t vectors, hipStream_t s) {
-    const unsigned grid = static_cast<unsigned>(vectors << (c.logn - 12));
-    hipLaunchKernelGGL((mlwe_mid_fused8<K>), dim3(grid), dim3(kF8Threads), 0, s, ws, d_u, c.a_perm.ptr, (uint32_t)vectors, c.ntt->mod, c.ntt->fwd_f64.ptr,
-                       c.ntt->inv_f64.ptr);
-    LSR_HIP(hipGetLastError());
-}
-
 // lanes 1.. of a chunk schedule (lane 0 is the caller's stream: every stream a process opens competes for the runtime's few
 // hardware queues, and two lanes that land on one queue overlap nothing — profiles/r02_commit_hw_queues.txt)
 static void ensure_side_streams(const LweContext& c, int lanes) {
@@ -434,6 +420,23 @@ static void join_lanes(const LweContext& c, hipStream_t s, int lanes) {
         c.ev_join[i - 1].record(c.side[i - 1]);
         c.ev_join[i - 1].wait(s);
     }
+}
+// The chunk-lane schedule (caller holds c.mutex): `count` items, `chunk` at a time, dealt round-robin to at most `max_lanes` lanes, each
+// with a slot of `slot_words` words of ws_mid (and, for the blinding residues sampled across two rounds, of `side_words` words of
+// ws_e1_slots; 0: none).  body(first, now, stream, slot_index) enqueues the launches of one chunk on its lane's stream.
+template <class Body>
+static void chunk_lanes(const LweContext& c, hipStream_t s, size_t count, size_t chunk, int max_lanes, size_t slot_words, size_t side_words, Body&& body) {
+    const int lanes = static_cast<int>(std::min<size_t>((size_t)max_lanes, (count + chunk - 1) / chunk));
+    ensure_side_streams(c, lanes);
+    c.ws_mid.reserve(slot_words * lanes);
+    if (side_words) c.ws_e1_slots.reserve(side_words * lanes);
+    fork_lanes(c, s, lanes);
+    size_t index = 0;
+    for (size_t first = 0; first < count; first += chunk, ++index) {
+        const size_t slot = index % lanes;
+        body(first, std::min(chunk, count - first), slot == 0 ? s : c.side[slot - 1], slot);
+    }
+    join_lanes(c, s, lanes);
 }
 
 // bracket of an asynchronous entry point (caller holds c.mutex): order this call behind the previous one on the same context
@@ -454,15 +457,6 @@ static void wait_for_async(const LweContext& c) {
 // middle stage of chunk t, the forward strided round of chunk t + 1 and the inverse strided round of chunk t - 1 as roles of one
 // kernel (lsr_commit_fused.hpp, mlwe_mixed), t = -1 .. chunks; two workspace slots alternate.  No events inside a lane: the launch
 // boundaries are the dependencies.
-template <int K>
-static void launch_mixed(const LweContext& c, const MixedJob& job, hipStream_t s) {
-    const unsigned grid = (job.units_m + job.units_f + job.units_i) * 8u;
-    if (!grid) return;
-    hipLaunchKernelGGL((mlwe_mixed<K>), dim3(grid), dim3(kF8Threads), 0, s, job, c.a_perm.ptr, c.ntt->mod, c.ntt->fwd_f64.ptr, c.ntt->inv_f64.ptr,
-                       RoundConsts<ArithF64>{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64});
-    LSR_HIP(hipGetLastError());
-}
-
 static void mlwe_matvec_mixed(const LweContext& c, const uint64_t* d_r, const uint64_t* d_e1, uint64_t* d_u, size_t batch, hipStream_t s) {
     const uint32_t k = c.k;
     const size_t vec_words = (size_t)k << c.logn;
@@ -520,12 +514,12 @@ static void mlwe_matvec_mixed(const LweContext& c, const uint64_t* d_r, const ui
                 job.periods = std::min(job.units_m, units_s / job.s_per_m);
             }
             hipStream_t st = lane == 0 ? s : c.side[lane - 1];
-            switch (k) {
-                case 1: launch_mixed<1>(c, job, st); break;
-                case 2: launch_mixed<2>(c, job, st); break;
-                case 3: launch_mixed<3>(c, job, st); break;
-                default: launch_mixed<4>(c, job, st); break;
-            }
+            const unsigned grid = (job.units_m + units_s) * 8u;      // not empty: see above
+            for_rank(k, [&](auto rank) {
+                hipLaunchKernelGGL((mlwe_mixed<decltype(rank)::value>), dim3(grid), dim3(kF8Threads), 0, st, job, c.a_perm.ptr, c.ntt->mod, c.ntt->fwd_f64.ptr,
+                                   c.ntt->inv_f64.ptr, round_consts(c));
+            });
+            LSR_HIP(hipGetLastError());
         }
         if (!any && t >= 0) break;
     }
@@ -550,35 +544,24 @@ static void mlwe_matvec_fused(const LweContext& c, const uint64_t* d_r, const ui
     const size_t vec_words = (size_t)k << c.logn;
     const bool sample = !d_e1 && d_keys;
     const size_t chunk = std::max<size_t>(1, (sample ? kSampledChunkBytes : kFusedChunkBytes) / (vec_words * 8));
-    const int streams = static_cast<int>(std::min<size_t>((size_t)kFusedStreams, (batch + chunk - 1) / chunk));
-    ensure_side_streams(c, streams);
-    auto lane = [&](size_t i) { return i == 0 ? s : c.side[i - 1]; };
     const size_t slot_words = std::min(chunk, batch) * vec_words;
-    c.ws_mid.reserve(slot_words * streams);
-    const bool split_sampling = sample && c.cdf_entries <= 127;
-    const size_t side_words = slot_words / 16;                    // int8 samples of half the rows: 1/16 of the chunk's words
-    if (split_sampling) c.ws_e1_slots.reserve(side_words * streams);
-    fork_lanes(c, s, streams);
-    size_t index = 0;
-    for (size_t first = 0; first < batch; first += chunk, ++index) {
-        const size_t now = std::min(chunk, batch - first);
-        hipStream_t st = lane(index % streams);
-        uint64_t* const ws = c.ws_mid.ptr + (index % streams) * slot_words;
+    // split sampling: the int8 samples of half the rows, 1/16 of the chunk's words
+    const size_t side_words = sample && c.cdf_entries <= 127 ? slot_words / 16 : 0;
+    chunk_lanes(c, s, batch, chunk, kFusedStreams, slot_words, side_words, [&](size_t first, size_t now, hipStream_t st, size_t slot) {
+        uint64_t* const ws = c.ws_mid.ptr + slot * slot_words;
         uint64_t* const out = d_u + first * vec_words;
         BlindSampler bs{sample ? d_keys + 4 * first : nullptr, c.cdf.ptr, c.cdf_entries, k, kDomE1, nullptr};
-        if (split_sampling) bs.side = c.ws_e1_slots.ptr + (index % streams) * side_words;
+        if (side_words) bs.side = c.ws_e1_slots.ptr + slot * side_words;
         if (bs.side) launch_top_round_forward_sampling(*c.ntt, ws, d_r + first * vec_words, now * k, st, bs);
         else launch_top_round_forward(*c.ntt, ws, d_r + first * vec_words, now * k, st);
-        switch (k) {
-            case 1: launch_mid<1>(c, ws, out, now, st); break;
-            case 2: launch_mid<2>(c, ws, out, now, st); break;
-            case 3: launch_mid<3>(c, ws, out, now, st); break;
-            default: launch_mid<4>(c, ws, out, now, st); break;
-        }
+        for_rank(k, [&](auto rank) {
+            hipLaunchKernelGGL((mlwe_mid_fused8<decltype(rank)::value>), dim3(static_cast<unsigned>(now << (c.logn - 12))), dim3(kF8Threads), 0, st, ws, out,
+                               c.a_perm.ptr, (uint32_t)now, c.ntt->mod, c.ntt->fwd_f64.ptr, c.ntt->inv_f64.ptr);
+        });
+        LSR_HIP(hipGetLastError());
         if (sample) launch_top_round_inverse_sampled(*c.ntt, out, now * k, st, bs);
         else launch_top_round_inverse(*c.ntt, out, now * k, st, d_e1 + first * vec_words);
-    }
-    join_lanes(c, s, streams);
+    });
 }
 
 // u = INTT(A_hat^T NTT(r)) + e1 on device-resident [batch][k][n] arrays.  Unfused form: r is overwritten by NTT(r), which
@@ -721,24 +704,17 @@ static void commit_rows_general(const LweContext& c, const uint64_t* d_msgs, siz
 }
 
 // n = 4096: one launch, one workgroup per commitment (lsr_commit_tile.hpp)
-template <int K>
-static void launch_commit_tile(const LweContext& c, const CommitTileJob& job, hipStream_t s) {
-    hipLaunchKernelGGL((commit_tile_kernel<K>), dim3(job.batch), dim3(kF8Threads), 0, s, job, c.ab_perm.ptr, c.ntt->mod, c.ntt->fwd_f64.ptr, c.ntt->inv_f64.ptr,
-                       RoundConsts<ArithF64>{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64});
-    LSR_HIP(hipGetLastError());
-}
 static void commit_rows_tile(const LweContext& c, const uint64_t* d_msgs, size_t msg_len, size_t batch, const uint64_t* d_keys, uint64_t* d_rows, hipStream_t s) {
     const size_t row_words = kHeaderWords + ((size_t)c.k + 1) * c.n;
     for (size_t first = 0; first < batch; first += 0x40000000u) {            // grid limit: 2^30 workgroups per launch
         const size_t now = std::min<size_t>(batch - first, 0x40000000u);
         const CommitTileJob job{d_rows + first * row_words, d_keys + 4 * first, d_msgs + first * msg_len, (uint64_t)msg_len, (uint64_t)std::min<size_t>(msg_len, c.n),
                                 c.cdf.ptr, c.cdf_entries, (uint32_t)now, c.q, c.t};
-        switch (c.k) {
-            case 1: launch_commit_tile<1>(c, job, s); break;
-            case 2: launch_commit_tile<2>(c, job, s); break;
-            case 3: launch_commit_tile<3>(c, job, s); break;
-            default: launch_commit_tile<4>(c, job, s); break;
-        }
+        for_rank(c.k, [&](auto rank) {
+            hipLaunchKernelGGL((commit_tile_kernel<decltype(rank)::value>), dim3(job.batch), dim3(kF8Threads), 0, s, job, c.ab_perm.ptr, c.ntt->mod,
+                               c.ntt->fwd_f64.ptr, c.ntt->inv_f64.ptr, round_consts(c));
+        });
+        LSR_HIP(hipGetLastError());
     }
 }
 
@@ -757,56 +733,42 @@ static void commit_rows_fused(const LweContext& c, const uint64_t* d_msgs, size_
     const uint32_t k = c.k, n = c.n;
     const size_t vec_words = (size_t)k << c.logn, row_words = kHeaderWords + ((size_t)k + 1) * n;
     const size_t chunk = std::max<size_t>(1, kFullCommitChunkBytes / (vec_words * 8));
-    const int streams = static_cast<int>(std::min<size_t>((size_t)kFusedStreams, (batch + chunk - 1) / chunk));
-    ensure_side_streams(c, streams);
     const size_t slot_words = std::min(chunk, batch) * vec_words;
-    c.ws_mid.reserve(slot_words * streams);
-    const RoundConsts<ArithF64> cs{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64};
     const int r = c.logn - 12, lo = 12;                                  // top R = 4 (n = 2^16) or 5 (2^17) index bits in the outer rounds
-    fork_lanes(c, s, streams);
-    size_t index = 0;
-    for (size_t first = 0; first < batch; first += chunk, ++index) {
-        const size_t now = std::min(chunk, batch - first);
-        hipStream_t st = index % streams == 0 ? s : c.side[index % streams - 1];
-        uint64_t* const ws = c.ws_mid.ptr + (index % streams) * slot_words;
+    chunk_lanes(c, s, batch, chunk, kFusedStreams, slot_words, 0, [&](size_t first, size_t now, hipStream_t st, size_t slot) {
+        uint64_t* const ws = c.ws_mid.ptr + slot * slot_words;
         uint64_t* const rows = d_rows + first * row_words;
         const CommitTopJob job{rows, ws, d_keys + 4 * first, d_msgs + first * msg_len, (uint64_t)msg_len, (uint64_t)std::min<size_t>(msg_len, n), c.cdf.ptr,
                                c.cdf_entries, (uint32_t)now, k, (uint64_t)row_words, c.q, c.t};
         const unsigned grid_f = static_cast<unsigned>((now * k << c.logn) >> (r + 8)), grid_i = static_cast<unsigned>((now * (k + 1) << c.logn) >> (r + 8));
-        if (r == 4) hipLaunchKernelGGL((commit_top_forward_kernel<4>), dim3(grid_f), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->fwd_f64.ptr);
-        else hipLaunchKernelGGL((commit_top_forward_kernel<5>), dim3(grid_f), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->fwd_f64.ptr);
+        for_top_bits(r, [&](auto bits) {
+            hipLaunchKernelGGL((commit_top_forward_kernel<decltype(bits)::value>), dim3(grid_f), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->fwd_f64.ptr);
+        });
         uint64_t* const body = rows + kHeaderWords;
-        switch (k) {
-            case 1: launch_mid_general<1, 2>(c, ws, vec_words, body, row_words, c.ab_perm.ptr, now, st); break;
-            case 2: launch_mid_general<2, 3>(c, ws, vec_words, body, row_words, c.ab_perm.ptr, now, st); break;
-            case 3: launch_mid_general<3, 4>(c, ws, vec_words, body, row_words, c.ab_perm.ptr, now, st); break;
-            default:
-#if LSR_K4_SINGLE_PASS     // five accumulators: 128 VGPRs with a few spilled registers, against a second one-column pass over the workspace
-                launch_mid_general<4, 5>(c, ws, vec_words, body, row_words, c.ab_perm.ptr, now, st);
-#else
+        for_rank(k, [&](auto rank) {
+            constexpr int K = decltype(rank)::value;
+            // rank 4 in one pass: five accumulators, 128 VGPRs with a few spilled registers, against a second one-column pass over the workspace
+            if constexpr (K == 4 && !LSR_K4_SINGLE_PASS) {
                 launch_mid_general<4, 4>(c, ws, vec_words, body, row_words, c.a_perm.ptr, now, st);
                 launch_mid_general<4, 1>(c, ws, vec_words, body + vec_words, row_words, c.b_perm.ptr, now, st);
-#endif
-        }
-        if (r == 4) hipLaunchKernelGGL((commit_top_inverse_kernel<4>), dim3(grid_i), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->inv_f64.ptr, cs);
-        else hipLaunchKernelGGL((commit_top_inverse_kernel<5>), dim3(grid_i), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->inv_f64.ptr, cs);
+            } else {
+                launch_mid_general<K, K + 1>(c, ws, vec_words, body, row_words, c.ab_perm.ptr, now, st);
+            }
+        });
+        for_top_bits(r, [&](auto bits) {
+            hipLaunchKernelGGL((commit_top_inverse_kernel<decltype(bits)::value>), dim3(grid_i), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->inv_f64.ptr,
+                               round_consts(c));
+        });
         LSR_HIP(hipGetLastError());
-    }
-    join_lanes(c, s, streams);
+    });
 }
 
 // ---- two-prime RNS rows (lsr_commit_rns.hpp) ----
 static RnsTilePrime rns_tile_prime(const LweContext& c, const double* mat) {
-    return RnsTilePrime{mat, c.ntt->mod, c.ntt->fwd_f64.ptr, c.ntt->inv_f64.ptr, RoundConsts<ArithF64>{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64}};
+    return RnsTilePrime{mat, c.ntt->mod, c.ntt->fwd_f64.ptr, c.ntt->inv_f64.ptr, round_consts(c)};
 }
 static bool rns_tile(const LweContext& c) { return c.rns && c.logn == 12 && c.ab_perm.ptr && c.sib->ab_perm.ptr && c.s_perm.ptr && c.sib->s_perm.ptr; }
 
-template <int K>
-static void launch_commit_rns_tile(const LweContext& c, const CommitRnsTileJob& job, hipStream_t s) {
-    hipLaunchKernelGGL((commit_rns_tile_kernel<K>), dim3(job.batch), dim3(kF8Threads), 0, s, job, rns_tile_prime(c, c.ab_perm.ptr),
-                       rns_tile_prime(*c.sib, c.sib->ab_perm.ptr));
-    LSR_HIP(hipGetLastError());
-}
 // "rns-tile": one launch, one workgroup per commitment, both primes
 static void commit_rows_rns_tile(const LweContext& c, const uint64_t* d_msgs, size_t msg_len, size_t batch, const uint64_t* d_keys, uint64_t* d_rows,
                                  hipStream_t s) {
@@ -815,12 +777,11 @@ static void commit_rows_rns_tile(const LweContext& c, const uint64_t* d_msgs, si
         const size_t now = std::min<size_t>(batch - first, 0x40000000u);
         const CommitRnsTileJob job{d_rows + first * words, d_keys + 4 * first, d_msgs + first * msg_len, (uint64_t)msg_len,
                                    (uint64_t)std::min<size_t>(msg_len, c.n), c.cdf.ptr, c.cdf_entries, (uint32_t)now, c.rc};
-        switch (c.k) {
-            case 1: launch_commit_rns_tile<1>(c, job, s); break;
-            case 2: launch_commit_rns_tile<2>(c, job, s); break;
-            case 3: launch_commit_rns_tile<3>(c, job, s); break;
-            default: launch_commit_rns_tile<4>(c, job, s); break;
-        }
+        for_rank(c.k, [&](auto rank) {
+            hipLaunchKernelGGL((commit_rns_tile_kernel<decltype(rank)::value>), dim3(job.batch), dim3(kF8Threads), 0, s, job, rns_tile_prime(c, c.ab_perm.ptr),
+                               rns_tile_prime(*c.sib, c.sib->ab_perm.ptr));
+        });
+        LSR_HIP(hipGetLastError());
     }
 }
 // "rns-general": the general kernels once per prime from the same stream keys (so r, e1, e2 are the same integers under both), the
@@ -992,126 +953,160 @@ static bool parse_commitment(const LweContext& c, const LweCommitment* cm, const
     return true;
 }
 
-template <int K>
-static void launch_verify_tile(const LweContext& c, const VerifyTileJob& job, hipStream_t s) {
-    hipLaunchKernelGGL((verify_tile_kernel<K>), dim3(job.count), dim3(kF8Threads), 0, s, job, c.s_perm.ptr, c.ntt->mod, c.ntt->fwd_f64.ptr, c.ntt->inv_f64.ptr,
-                       RoundConsts<ArithF64>{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64});
-    LSR_HIP(hipGetLastError());
-}
+// ---- openings and decoding: one pipeline with two ends ----------------------------------------------------------
+// the end of an opening: the decoded slots are compared with the claimed messages (lwe_verify_opening, commitment.cpp:200-232) ...
+struct CompareEnd {
+    const uint64_t* d_msgs;      // [count][msg_len] claimed messages (raw words), device
+    size_t msg_len;              // 1 .. n
+};
+// ... or stored
+struct StoreEnd {
+    uint64_t* d_out;             // [count][slots] decoded plaintext slots, device
+    size_t slots;                // 1 .. n
+    bool noise;                  // also the per-row maximum of bitlen(rho), in c.ws_vflags
+};
 
-template <int K>
-static void launch_verify_rns_tile(const LweContext& c, const VerifyRnsTileJob& job, hipStream_t s) {
-    hipLaunchKernelGGL((verify_rns_tile_kernel<K>), dim3(job.count), dim3(kF8Threads), 0, s, job, rns_tile_prime(c, c.s_perm.ptr),
-                       rns_tile_prime(*c.sib, c.sib->s_perm.ptr));
-    LSR_HIP(hipGetLastError());
-}
-// openings of RNS rows (the verdict state c.ws_vflags / c.ws_vbad is cleared by the caller): w_p = v_p - <s, u_p> under each prime,
-// the CRT lift and the rounded decode in the sink (tile) or in an elementwise kernel (general)
-static void verify_rows_rns(const LweContext& c, const uint64_t* d_rows, const uint64_t* d_msgs, size_t msg_len, size_t count, hipStream_t s) {
+// general form under one prime: w = v - INTT(<s_hat, NTT(u)>) of `count` rows into ci.ws_e2, the header and canonicity marks of the
+// rows into c.ws_vbad on the way.  ci: the context itself, or (prime = 0 / 1) either half of the RNS pair c
+static void open_rows_general(const LweContext& c, const LweContext& ci, int prime, const uint64_t* d_rows, size_t count, hipStream_t s) {
     const uint32_t n = c.n, k = c.k;
-    if (rns_tile(c)) {
-        const VerifyRnsTileJob job{d_rows, d_msgs, (uint64_t)msg_len, c.ws_vflags.ptr, c.ws_vbad, (uint32_t)count, c.rc};
-        switch (k) {
-            case 1: launch_verify_rns_tile<1>(c, job, s); break;
-            case 2: launch_verify_rns_tile<2>(c, job, s); break;
-            case 3: launch_verify_rns_tile<3>(c, job, s); break;
-            default: launch_verify_rns_tile<4>(c, job, s); break;
-        }
-        return;
-    }
-    const uint64_t kn = (uint64_t)k * n;
-    for (int prime = 0; prime < 2; ++prime) {
-        const LweContext& ci = prime ? *c.sib : c;
-        ensure_workspace(ci, count);
+    const uint64_t kn = (uint64_t)k * n, nk = (uint64_t)n | ((uint64_t)k << 32);
+    ensure_workspace(ci, count);
+    if (c.rns)
         hipLaunchKernelGGL(rns_unpack_kernel, dim3(grid_for(count * (kRnsHeaderWords + kn + n))), dim3(256), 0, s, d_rows, ci.ws_u.ptr, ci.ws_v.ptr, c.ws_vbad, kn,
-                           (uint64_t)n, (uint64_t)count, prime, c.rc, (uint64_t)n | ((uint64_t)k << 32));
-        launch_ntt(*ci.ntt, ci.ws_u.ptr, count * k, false, s);
-        launch_ntt(*ci.ntt, ci.ws_v.ptr, count, false, s);
-        matvec(ci, ci.ws_e2.ptr, ci.s_hat.ptr, ci.ws_u.ptr, nullptr, 1, k, 0, 1, count, s);            // <s_hat, u_hat>
-        hipLaunchKernelGGL(rsub_mod_kernel, dim3(grid_for(count * n)), dim3(256), 0, s, ci.ws_e2.ptr, ci.ws_v.ptr, (uint64_t)count * n, ci.q);
-        launch_ntt(*ci.ntt, ci.ws_e2.ptr, count, true, s);
-    }
-    const uint64_t lanes = (uint64_t)count * msg_len;
-    hipLaunchKernelGGL(rns_decode_compare_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, c.ws_e2.ptr, c.sib->ws_e2.ptr, d_msgs,
-                       (uint64_t)msg_len, (uint32_t)c.logn, (uint64_t)count, c.rc, c.sib->ntt->mod, c.ws_vflags.ptr);
-    LSR_HIP(hipGetLastError());
+                           (uint64_t)n, (uint64_t)count, prime, c.rc, nk);
+    else
+        hipLaunchKernelGGL(unpack_commitments_kernel, dim3(grid_for(count * (kHeaderWords + kn + n))), dim3(256), 0, s, d_rows, ci.ws_u.ptr, ci.ws_v.ptr, c.ws_vbad,
+                           kn, (uint64_t)n, (uint64_t)count, c.q, c.t, nk);
+    launch_ntt(*ci.ntt, ci.ws_u.ptr, count * k, false, s);
+    launch_ntt(*ci.ntt, ci.ws_v.ptr, count, false, s);
+    matvec(ci, ci.ws_e2.ptr, ci.s_hat.ptr, ci.ws_u.ptr, nullptr, 1, k, 0, 1, count, s);            // <s_hat, u_hat>
+    hipLaunchKernelGGL(rsub_mod_kernel, dim3(grid_for(count * n)), dim3(256), 0, s, ci.ws_e2.ptr, ci.ws_v.ptr, (uint64_t)count * n, ci.q);
+    launch_ntt(*ci.ntt, ci.ws_e2.ptr, count, true, s);
 }
 
-// `count` openings from device-resident wire rows and claimed messages (1 <= msg_len <= n), enqueued on `s`; caller holds c.mutex.
-// Leaves the per-row OR of (decoded ^ claimed) in c.ws_vflags and the per-row "not a canonical commitment of this context" mark in
-// c.ws_vbad — lwe_verify_opening (commitment.cpp:200-232) for a whole batch:
-//   v - INTT(<s_hat, NTT(u)>) decoded slot-wise and compared with the message words as given.
-static void verify_rows_device(const LweContext& c, const uint64_t* d_rows, const uint64_t* d_msgs, size_t msg_len, size_t count, hipStream_t s) {
+// lanes of the elementwise decoding kernels: every coefficient with the noise, the first `slots` of each row without
+static unsigned decode_store_grid(const LweContext& c, size_t count, size_t slots, bool noise) {
+    return (unsigned)(((uint64_t)count * (noise ? (size_t)c.n : slots) + 255) / 256);
+}
+
+// `count` device-resident wire rows opened as v - INTT(<s_hat, NTT(u)>), decoded slot-wise and handed to `end`; enqueued on `s`, caller
+// holds c.mutex.  Leaves the per-row "not a canonical commitment of this context" mark in c.ws_vbad and, in c.ws_vflags, the per-row OR
+// of (decoded ^ claimed) (CompareEnd) or the per-row maximum of bitlen(rho) (StoreEnd with noise).  Five forms: rns-tile, rns-general,
+// tile (n = 4096), top (n = 2^16 / 2^17 on chunk lanes) and general; only the last launch of each depends on the end.
+template <class End>
+static void open_rows_device(const LweContext& c, const uint64_t* d_rows, size_t count, const End& end, hipStream_t s) {
+    constexpr bool compare = std::is_same<End, CompareEnd>::value;
     const uint32_t n = c.n, k = c.k;
-    const size_t kn = (size_t)k * n, row = kHeaderWords + kn + n;
     // one allocation, one clear, one copy back: [flags: count x u64 | bad: count x u32]
     const size_t state_words = count + (count + 1) / 2;
     c.ws_vflags.reserve(state_words);
     c.ws_vbad = reinterpret_cast<uint32_t*>(c.ws_vflags.ptr + count);
     zero_words_async(reinterpret_cast<uint64_t*>(c.ws_vflags.ptr), state_words, s);
-    if (c.rns) {
-        verify_rows_rns(c, d_rows, d_msgs, msg_len, count, s);
+    unsigned long long* const flags = c.ws_vflags.ptr;
+    uint32_t* const bad = c.ws_vbad;
+    if (rns_tile(c)) {                      // one launch, one workgroup per row, both primes: the CRT lift and the end in the sink
+        const RnsTilePrime a = rns_tile_prime(c, c.s_perm.ptr), b = rns_tile_prime(*c.sib, c.sib->s_perm.ptr);
+        for_rank(k, [&](auto rank) {
+            constexpr int K = decltype(rank)::value;
+            if constexpr (compare) {
+                const VerifyRnsTileJob job{d_rows, end.d_msgs, (uint64_t)end.msg_len, flags, bad, (uint32_t)count, c.rc};
+                hipLaunchKernelGGL((verify_rns_tile_kernel<K>), dim3(job.count), dim3(kF8Threads), 0, s, job, a, b);
+            } else {
+                const DecodeRnsTileJob job{d_rows, end.d_out, (uint64_t)end.slots, flags, bad, (uint32_t)count, c.rc};
+                for_bool(end.noise, [&](auto noise) {
+                    hipLaunchKernelGGL((decode_rns_tile_kernel<K, decltype(noise)::value>), dim3(job.count), dim3(kF8Threads), 0, s, job, a, b);
+                });
+            }
+        });
+        LSR_HIP(hipGetLastError());
         return;
     }
-    if (c.s_perm.ptr && c.logn == 12) {     // one launch, one workgroup per opening: the row is read once (lsr_commit_tile.hpp)
-        const VerifyTileJob job{d_rows, d_msgs, (uint64_t)msg_len, c.ws_vflags.ptr, c.ws_vbad, (uint32_t)count, c.q, c.t};
-        switch (k) {
-            case 1: launch_verify_tile<1>(c, job, s); break;
-            case 2: launch_verify_tile<2>(c, job, s); break;
-            case 3: launch_verify_tile<3>(c, job, s); break;
-            default: launch_verify_tile<4>(c, job, s); break;
+    if (c.rns) {                            // w_p under each prime, the CRT lift and the end in an elementwise kernel
+        open_rows_general(c, c, 0, d_rows, count, s);
+        open_rows_general(c, *c.sib, 1, d_rows, count, s);
+        if constexpr (compare) {
+            const uint64_t lanes = (uint64_t)count * end.msg_len;
+            hipLaunchKernelGGL(rns_decode_compare_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, c.ws_e2.ptr, c.sib->ws_e2.ptr, end.d_msgs,
+                               (uint64_t)end.msg_len, (uint32_t)c.logn, (uint64_t)count, c.rc, c.sib->ntt->mod, flags);
+        } else {
+            for_bool(end.noise, [&](auto noise) {
+                hipLaunchKernelGGL(rns_decode_store_kernel<decltype(noise)::value>, dim3(decode_store_grid(c, count, end.slots, end.noise)), dim3(256), 0, s,
+                                   c.ws_e2.ptr, c.sib->ws_e2.ptr, end.d_out, (uint64_t)end.slots, (uint32_t)c.logn, (uint64_t)count, c.rc, c.sib->ntt->mod, flags);
+            });
         }
+        LSR_HIP(hipGetLastError());
+        return;
+    }
+    if (c.s_perm.ptr && c.logn == 12) {     // one launch, one workgroup per row: the row is read once (lsr_commit_tile.hpp)
+        for_rank(k, [&](auto rank) {
+            constexpr int K = decltype(rank)::value;
+            if constexpr (compare) {
+                const VerifyTileJob job{d_rows, end.d_msgs, (uint64_t)end.msg_len, flags, bad, (uint32_t)count, c.q, c.t};
+                hipLaunchKernelGGL((verify_tile_kernel<K>), dim3(job.count), dim3(kF8Threads), 0, s, job, c.s_perm.ptr, c.ntt->mod, c.ntt->fwd_f64.ptr,
+                                   c.ntt->inv_f64.ptr, round_consts(c));
+            } else {
+                const DecodeTileJob job{d_rows, end.d_out, (uint64_t)end.slots, flags, bad, (uint32_t)count, c.q, c.t};
+                for_bool(end.noise, [&](auto noise) {
+                    hipLaunchKernelGGL((decode_tile_kernel<K, decltype(noise)::value>), dim3(job.count), dim3(kF8Threads), 0, s, job, c.s_perm.ptr, c.ntt->mod,
+                                       c.ntt->fwd_f64.ptr, c.ntt->inv_f64.ptr, round_consts(c));
+                });
+            }
+        });
+        LSR_HIP(hipGetLastError());
         return;
     }
     if (c.s_perm.ptr && c.a_perm.ptr) {     // n = 2^16 / 2^17: three launches per chunk, u read once, v read once (lsr_commit_tile.hpp)
-        const size_t vec_words = (size_t)k << c.logn;
+        const size_t vec_words = (size_t)k << c.logn, row = kHeaderWords + vec_words + n;
         const size_t chunk = std::max<size_t>(1, kVerifyChunkBytes / (vec_words * 8));
         const size_t slot = std::min(chunk, count);
-        // chunk lanes like the commitments' (commit_rows_fused): a chunk's three launches are a dependent chain whose fills and drains
-        // the other lane's kernels cover (one lane: 1.84 ms per 1024 openings at rank 4, neither memory nor FP64 half busy)
-        const int streams = static_cast<int>(std::min<size_t>((size_t)kVerifyStreams, (count + chunk - 1) / chunk));
-        ensure_side_streams(c, streams);
         const size_t slot_words = slot * (vec_words + n);
-        c.ws_mid.reserve(slot_words * streams);
-        const RoundConsts<ArithF64> cs{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64};
         const int r = c.logn - 12, lo = 12;
-        fork_lanes(c, s, streams);                    // behind the clear of the verdict state above
-        size_t index = 0;
-        for (size_t first = 0; first < count; first += chunk, ++index) {
-            const size_t now = std::min(chunk, count - first);
-            hipStream_t st = index % streams == 0 ? s : c.side[index % streams - 1];
-            uint64_t* const ws = c.ws_mid.ptr + (index % streams) * slot_words;
+        // chunk lanes like the commitments' (commit_rows_fused), forked behind the clear of the verdict state above: a chunk's three
+        // launches are a dependent chain whose fills and drains the other lane's kernels cover (one lane: 1.84 ms per 1024 openings at
+        // rank 4, neither memory nor FP64 half busy)
+        chunk_lanes(c, s, count, chunk, kVerifyStreams, slot_words, 0, [&](size_t first, size_t now, hipStream_t st, size_t slot_index) {
+            uint64_t* const ws = c.ws_mid.ptr + slot_index * slot_words;
             uint64_t* const ws_out = ws + slot * vec_words;
-            const VerifyTopJob job{d_rows + first * row, ws, ws_out, d_msgs + first * msg_len, (uint64_t)msg_len, (uint64_t)row, c.ws_vflags.ptr + first,
-                                   c.ws_vbad + first, (uint32_t)now, k, c.q, c.t};
-            const unsigned grid_f = static_cast<unsigned>((now * k << c.logn) >> (r + 8)), grid_i = static_cast<unsigned>((now << c.logn) >> (r + 8));
-            if (r == 4) hipLaunchKernelGGL((verify_top_forward_kernel<4>), dim3(grid_f), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->fwd_f64.ptr);
-            else hipLaunchKernelGGL((verify_top_forward_kernel<5>), dim3(grid_f), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->fwd_f64.ptr);
-            switch (k) {
-                case 1: launch_mid_general<1, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
-                case 2: launch_mid_general<2, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
-                case 3: launch_mid_general<3, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
-                default: launch_mid_general<4, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
+            VerifyTopJob job{d_rows + first * row, ws, ws_out, nullptr, 0, (uint64_t)row, flags + first, bad + first, (uint32_t)now, k, c.q, c.t};
+            if constexpr (compare) {
+                job.msgs = end.d_msgs + first * end.msg_len;
+                job.msg_len = end.msg_len;
             }
-            if (r == 4) hipLaunchKernelGGL((verify_top_inverse_kernel<4>), dim3(grid_i), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->inv_f64.ptr, cs);
-            else hipLaunchKernelGGL((verify_top_inverse_kernel<5>), dim3(grid_i), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->inv_f64.ptr, cs);
+            const unsigned grid_f = static_cast<unsigned>((now * k << c.logn) >> (r + 8)), grid_i = static_cast<unsigned>((now << c.logn) >> (r + 8));
+            for_top_bits(r, [&](auto bits) {
+                hipLaunchKernelGGL((verify_top_forward_kernel<decltype(bits)::value>), dim3(grid_f), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->fwd_f64.ptr);
+            });
+            for_rank(k, [&](auto rank) { launch_mid_general<decltype(rank)::value, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); });
+            for_top_bits(r, [&](auto bits) {
+                constexpr int R = decltype(bits)::value;
+                if constexpr (compare) {
+                    hipLaunchKernelGGL((verify_top_inverse_kernel<R>), dim3(grid_i), dim3(256), 0, st, job, lo, c.ntt->mod, c.ntt->inv_f64.ptr, round_consts(c));
+                } else {
+                    const DecodeTopJob inv{job.rows, ws_out, end.d_out + first * end.slots, (uint64_t)end.slots, (uint64_t)row, job.flags, job.bad, (uint32_t)now, k,
+                                           c.q, c.t};
+                    for_bool(end.noise, [&](auto noise) {
+                        hipLaunchKernelGGL((decode_top_inverse_kernel<R, decltype(noise)::value>), dim3(grid_i), dim3(256), 0, st, inv, lo, c.ntt->mod,
+                                           c.ntt->inv_f64.ptr, round_consts(c));
+                    });
+                }
+            });
             LSR_HIP(hipGetLastError());
-        }
-        join_lanes(c, s, streams);
+        });
         return;
     }
     // general form: split the rows (header and canonicity checks on the way), transform, product, subtract, inverse, decode
-    ensure_workspace(c, count);
-    hipLaunchKernelGGL(unpack_commitments_kernel, dim3(grid_for(count * row)), dim3(256), 0, s, d_rows, c.ws_u.ptr, c.ws_v.ptr, c.ws_vbad, (uint64_t)kn,
-                       (uint64_t)n, (uint64_t)count, c.q, c.t, (uint64_t)n | ((uint64_t)k << 32));
-    launch_ntt(*c.ntt, c.ws_u.ptr, count * k, false, s);
-    launch_ntt(*c.ntt, c.ws_v.ptr, count, false, s);
-    matvec(c, c.ws_e2.ptr, c.s_hat.ptr, c.ws_u.ptr, nullptr, 1, k, 0, 1, count, s);            // <s_hat, u_hat>
-    hipLaunchKernelGGL(rsub_mod_kernel, dim3(grid_for(count * n)), dim3(256), 0, s, c.ws_e2.ptr, c.ws_v.ptr, (uint64_t)count * n, c.q);
-    launch_ntt(*c.ntt, c.ws_e2.ptr, count, true, s);
-    const uint64_t lanes = (uint64_t)count * msg_len;
-    hipLaunchKernelGGL(decode_compare_batch_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, c.ws_e2.ptr, d_msgs, (uint64_t)msg_len,
-                       (uint32_t)c.logn, (uint64_t)count, c.t, c.ntt->mod, c.ws_vflags.ptr);
+    open_rows_general(c, c, 0, d_rows, count, s);
+    if constexpr (compare) {
+        const uint64_t lanes = (uint64_t)count * end.msg_len;
+        hipLaunchKernelGGL(decode_compare_batch_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, c.ws_e2.ptr, end.d_msgs, (uint64_t)end.msg_len,
+                           (uint32_t)c.logn, (uint64_t)count, c.t, c.ntt->mod, flags);
+    } else {
+        for_bool(end.noise, [&](auto noise) {
+            hipLaunchKernelGGL(decode_store_batch_kernel<decltype(noise)::value>, dim3(decode_store_grid(c, count, end.slots, end.noise)), dim3(256), 0, s,
+                               c.ws_e2.ptr, end.d_out, (uint64_t)end.slots, (uint32_t)c.logn, (uint64_t)count, c.t, c.ntt->mod, flags);
+        });
+    }
     LSR_HIP(hipGetLastError());
 }
 
@@ -1121,24 +1116,51 @@ static size_t verify_chunk(const LweContext& c, size_t count) {
     return std::max<size_t>(1, std::min<size_t>(count, (1ull << 30) / per_opening));
 }
 
-// rows (host, back to back) and messages -> results, `chunk` openings per pass; rows may live in pageable or pinned memory
-static void verify_host_rows(const LweContext& c, const uint64_t* rows, const uint64_t* messages, size_t msg_len, size_t count, int* results, hipStream_t s) {
+// Rows on the host (back to back; pageable or pinned memory) through the opening pipeline, verify_chunk() rows per pass: the rows go up
+// to c.ws_rows, `enqueue(first, now)` stages what else the pass needs in c.ws_dm (chunk x n words, no allocation per call) and
+// enqueues the pipeline on `s`, the verdict state comes back in one copy and `finish(row, bad, flags)` takes each row's share of it
+template <class Enqueue, class Finish>
+static void open_host_rows(const LweContext& c, const uint64_t* rows, size_t count, hipStream_t s, Enqueue&& enqueue, Finish&& finish) {
     const size_t row = row_words(c);
     const size_t chunk = verify_chunk(c, count);
     c.ws_rows.reserve(chunk * row);
-    ensure_input_space(c, chunk);                            // ws_dm: chunk x n message slots (msg_len <= n here), no allocation per call
-    uint64_t* const d_msgs = c.ws_dm.ptr;
+    ensure_input_space(c, chunk);
     std::vector<unsigned long long> state(chunk + (chunk + 1) / 2);
     for (size_t first = 0; first < count; first += chunk) {
         const size_t now = std::min(chunk, count - first);
         LSR_HIP(hipMemcpyAsync(c.ws_rows.ptr, rows + first * row, now * row * 8, hipMemcpyHostToDevice, s));
-        LSR_HIP(hipMemcpyAsync(d_msgs, messages + first * msg_len, now * msg_len * 8, hipMemcpyHostToDevice, s));
-        verify_rows_device(c, c.ws_rows.ptr, d_msgs, msg_len, now, s);
+        enqueue(first, now);
         LSR_HIP(hipMemcpyAsync(state.data(), c.ws_vflags.ptr, (now + (now + 1) / 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
         LSR_HIP(hipStreamSynchronize(s));
         const uint32_t* const host_bad = reinterpret_cast<const uint32_t*>(state.data() + now);
-        for (size_t j = 0; j < now; ++j) results[first + j] = host_bad[j] ? -1 : (state[j] == 0 ? 1 : 0);
+        for (size_t j = 0; j < now; ++j) finish(first + j, host_bad[j] != 0, state[j]);
     }
+}
+
+// rows and claimed messages (1 <= msg_len <= n) -> results: 1 / 0 / -1 as lwe_verify_opening
+static void verify_host_rows(const LweContext& c, const uint64_t* rows, const uint64_t* messages, size_t msg_len, size_t count, int* results, hipStream_t s) {
+    open_host_rows(
+        c, rows, count, s,
+        [&](size_t first, size_t now) {
+            LSR_HIP(hipMemcpyAsync(c.ws_dm.ptr, messages + first * msg_len, now * msg_len * 8, hipMemcpyHostToDevice, s));
+            open_rows_device(c, c.ws_rows.ptr, now, CompareEnd{c.ws_dm.ptr, msg_len}, s);
+        },
+        [&](size_t j, bool bad, unsigned long long flags) { results[j] = bad ? -1 : (flags == 0 ? 1 : 0); });
+}
+
+// rows -> messages[count][slots] (1 <= slots <= n), status[count], noise_bits[count] (optional)
+static void decode_host_rows(const LweContext& c, const uint64_t* rows, size_t count, size_t slots, uint64_t* messages, int* status, uint32_t* noise_bits,
+                             hipStream_t s) {
+    open_host_rows(
+        c, rows, count, s,
+        [&](size_t first, size_t now) {
+            open_rows_device(c, c.ws_rows.ptr, now, StoreEnd{c.ws_dm.ptr, slots, noise_bits != nullptr}, s);
+            LSR_HIP(hipMemcpyAsync(messages + first * slots, c.ws_dm.ptr, now * slots * 8, hipMemcpyDeviceToHost, s));
+        },
+        [&](size_t j, bool bad, unsigned long long flags) {
+            status[j] = bad ? -1 : 1;
+            if (noise_bits) noise_bits[j] = (uint32_t)flags;
+        });
 }
 
 static int screen_opening(const LweContext& c, const uint64_t* body, size_t msg_len);
@@ -1228,168 +1250,6 @@ static void verify_opening_batch_flat(const LweContext& c, const uint64_t* words
     std::lock_guard<std::mutex> lock(c.mutex);
     wait_for_async(c);
     verify_host_rows(c, words, messages, msg_len, count, results, work_stream(*c.ntt));
-}
-
-// ---- decoding rows: the opening's pipelines with a storing sink ------------------------------------------------------
-template <int K>
-static void launch_decode_tile(const LweContext& c, const DecodeTileJob& job, bool noise, hipStream_t s) {
-    const RoundConsts<ArithF64> cs{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64};
-    if (noise)
-        hipLaunchKernelGGL((decode_tile_kernel<K, true>), dim3(job.count), dim3(kF8Threads), 0, s, job, c.s_perm.ptr, c.ntt->mod, c.ntt->fwd_f64.ptr,
-                           c.ntt->inv_f64.ptr, cs);
-    else
-        hipLaunchKernelGGL((decode_tile_kernel<K, false>), dim3(job.count), dim3(kF8Threads), 0, s, job, c.s_perm.ptr, c.ntt->mod, c.ntt->fwd_f64.ptr,
-                           c.ntt->inv_f64.ptr, cs);
-    LSR_HIP(hipGetLastError());
-}
-template <int K>
-static void launch_decode_rns_tile(const LweContext& c, const DecodeRnsTileJob& job, bool noise, hipStream_t s) {
-    const RnsTilePrime a = rns_tile_prime(c, c.s_perm.ptr), b = rns_tile_prime(*c.sib, c.sib->s_perm.ptr);
-    if (noise) hipLaunchKernelGGL((decode_rns_tile_kernel<K, true>), dim3(job.count), dim3(kF8Threads), 0, s, job, a, b);
-    else hipLaunchKernelGGL((decode_rns_tile_kernel<K, false>), dim3(job.count), dim3(kF8Threads), 0, s, job, a, b);
-    LSR_HIP(hipGetLastError());
-}
-template <int R>
-static void launch_decode_top_inverse(const LweContext& c, const DecodeTopJob& job, unsigned grid, bool noise, hipStream_t s) {
-    const RoundConsts<ArithF64> cs{c.ntt->n_inv_f64, c.ntt->w_last_scaled_f64};
-    if (noise) hipLaunchKernelGGL((decode_top_inverse_kernel<R, true>), dim3(grid), dim3(256), 0, s, job, 12, c.ntt->mod, c.ntt->inv_f64.ptr, cs);
-    else hipLaunchKernelGGL((decode_top_inverse_kernel<R, false>), dim3(grid), dim3(256), 0, s, job, 12, c.ntt->mod, c.ntt->inv_f64.ptr, cs);
-}
-// lanes of the elementwise decoding kernels: every coefficient with the noise, the first `slots` of each row without
-static unsigned decode_store_grid(const LweContext& c, size_t count, size_t slots, bool noise) {
-    return (unsigned)(((uint64_t)count * (noise ? (size_t)c.n : slots) + 255) / 256);
-}
-
-// `count` device-resident wire rows -> d_out[count][slots] (1 <= slots <= n), enqueued on `s`; caller holds c.mutex.  The same state as
-// verify_rows_device leaves: the per-row "not a canonical commitment of this context" mark in c.ws_vbad, and in c.ws_vflags, instead
-// of the compare flags, the per-row maximum of bitlen(rho) (noise only).  Pipeline selection, screening, chunking, chunk lanes and
-// workspaces are those of verify_rows_device; only the last stage differs.
-static void decode_rows_device(const LweContext& c, const uint64_t* d_rows, size_t count, size_t slots, uint64_t* d_out, bool noise, hipStream_t s) {
-    const uint32_t n = c.n, k = c.k;
-    const size_t state_words = count + (count + 1) / 2;
-    c.ws_vflags.reserve(state_words);
-    c.ws_vbad = reinterpret_cast<uint32_t*>(c.ws_vflags.ptr + count);
-    zero_words_async(reinterpret_cast<uint64_t*>(c.ws_vflags.ptr), state_words, s);
-    if (c.rns) {
-        if (rns_tile(c)) {
-            const DecodeRnsTileJob job{d_rows, d_out, (uint64_t)slots, c.ws_vflags.ptr, c.ws_vbad, (uint32_t)count, c.rc};
-            switch (k) {
-                case 1: launch_decode_rns_tile<1>(c, job, noise, s); break;
-                case 2: launch_decode_rns_tile<2>(c, job, noise, s); break;
-                case 3: launch_decode_rns_tile<3>(c, job, noise, s); break;
-                default: launch_decode_rns_tile<4>(c, job, noise, s); break;
-            }
-            return;
-        }
-        const uint64_t kn = (uint64_t)k * n;
-        for (int prime = 0; prime < 2; ++prime) {
-            const LweContext& ci = prime ? *c.sib : c;
-            ensure_workspace(ci, count);
-            hipLaunchKernelGGL(rns_unpack_kernel, dim3(grid_for(count * (kRnsHeaderWords + kn + n))), dim3(256), 0, s, d_rows, ci.ws_u.ptr, ci.ws_v.ptr, c.ws_vbad, kn,
-                               (uint64_t)n, (uint64_t)count, prime, c.rc, (uint64_t)n | ((uint64_t)k << 32));
-            launch_ntt(*ci.ntt, ci.ws_u.ptr, count * k, false, s);
-            launch_ntt(*ci.ntt, ci.ws_v.ptr, count, false, s);
-            matvec(ci, ci.ws_e2.ptr, ci.s_hat.ptr, ci.ws_u.ptr, nullptr, 1, k, 0, 1, count, s);            // <s_hat, u_hat>
-            hipLaunchKernelGGL(rsub_mod_kernel, dim3(grid_for(count * n)), dim3(256), 0, s, ci.ws_e2.ptr, ci.ws_v.ptr, (uint64_t)count * n, ci.q);
-            launch_ntt(*ci.ntt, ci.ws_e2.ptr, count, true, s);
-        }
-        const unsigned grid = decode_store_grid(c, count, slots, noise);
-        if (noise)
-            hipLaunchKernelGGL(rns_decode_store_kernel<true>, dim3(grid), dim3(256), 0, s, c.ws_e2.ptr, c.sib->ws_e2.ptr, d_out, (uint64_t)slots, (uint32_t)c.logn,
-                               (uint64_t)count, c.rc, c.sib->ntt->mod, c.ws_vflags.ptr);
-        else
-            hipLaunchKernelGGL(rns_decode_store_kernel<false>, dim3(grid), dim3(256), 0, s, c.ws_e2.ptr, c.sib->ws_e2.ptr, d_out, (uint64_t)slots, (uint32_t)c.logn,
-                               (uint64_t)count, c.rc, c.sib->ntt->mod, c.ws_vflags.ptr);
-        LSR_HIP(hipGetLastError());
-        return;
-    }
-    const size_t kn = (size_t)k * n, row = kHeaderWords + kn + n;
-    if (c.s_perm.ptr && c.logn == 12) {
-        const DecodeTileJob job{d_rows, d_out, (uint64_t)slots, c.ws_vflags.ptr, c.ws_vbad, (uint32_t)count, c.q, c.t};
-        switch (k) {
-            case 1: launch_decode_tile<1>(c, job, noise, s); break;
-            case 2: launch_decode_tile<2>(c, job, noise, s); break;
-            case 3: launch_decode_tile<3>(c, job, noise, s); break;
-            default: launch_decode_tile<4>(c, job, noise, s); break;
-        }
-        return;
-    }
-    if (c.s_perm.ptr && c.a_perm.ptr) {     // n = 2^16 / 2^17: the chunks, chunk lanes and workspace of verify_rows_device
-        const size_t vec_words = (size_t)k << c.logn;
-        const size_t chunk = std::max<size_t>(1, kVerifyChunkBytes / (vec_words * 8));
-        const size_t slot = std::min(chunk, count);
-        const int streams = static_cast<int>(std::min<size_t>((size_t)kVerifyStreams, (count + chunk - 1) / chunk));
-        ensure_side_streams(c, streams);
-        const size_t slot_words = slot * (vec_words + n);
-        c.ws_mid.reserve(slot_words * streams);
-        const int r = c.logn - 12, lo = 12;
-        fork_lanes(c, s, streams);
-        size_t index = 0;
-        for (size_t first = 0; first < count; first += chunk, ++index) {
-            const size_t now = std::min(chunk, count - first);
-            hipStream_t st = index % streams == 0 ? s : c.side[index % streams - 1];
-            uint64_t* const ws = c.ws_mid.ptr + (index % streams) * slot_words;
-            uint64_t* const ws_out = ws + slot * vec_words;
-            const VerifyTopJob fwd{d_rows + first * row, ws, ws_out, nullptr, 0, (uint64_t)row, c.ws_vflags.ptr + first, c.ws_vbad + first, (uint32_t)now, k, c.q,
-                                   c.t};
-            const DecodeTopJob inv{d_rows + first * row, ws_out, d_out + first * slots, (uint64_t)slots, (uint64_t)row, c.ws_vflags.ptr + first,
-                                   c.ws_vbad + first, (uint32_t)now, k, c.q, c.t};
-            const unsigned grid_f = static_cast<unsigned>((now * k << c.logn) >> (r + 8)), grid_i = static_cast<unsigned>((now << c.logn) >> (r + 8));
-            if (r == 4) hipLaunchKernelGGL((verify_top_forward_kernel<4>), dim3(grid_f), dim3(256), 0, st, fwd, lo, c.ntt->mod, c.ntt->fwd_f64.ptr);
-            else hipLaunchKernelGGL((verify_top_forward_kernel<5>), dim3(grid_f), dim3(256), 0, st, fwd, lo, c.ntt->mod, c.ntt->fwd_f64.ptr);
-            switch (k) {
-                case 1: launch_mid_general<1, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
-                case 2: launch_mid_general<2, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
-                case 3: launch_mid_general<3, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
-                default: launch_mid_general<4, 1>(c, ws, vec_words, ws_out, n, c.s_perm.ptr, now, st); break;
-            }
-            if (r == 4) launch_decode_top_inverse<4>(c, inv, grid_i, noise, st);
-            else launch_decode_top_inverse<5>(c, inv, grid_i, noise, st);
-            LSR_HIP(hipGetLastError());
-        }
-        join_lanes(c, s, streams);
-        return;
-    }
-    ensure_workspace(c, count);
-    hipLaunchKernelGGL(unpack_commitments_kernel, dim3(grid_for(count * row)), dim3(256), 0, s, d_rows, c.ws_u.ptr, c.ws_v.ptr, c.ws_vbad, (uint64_t)kn,
-                       (uint64_t)n, (uint64_t)count, c.q, c.t, (uint64_t)n | ((uint64_t)k << 32));
-    launch_ntt(*c.ntt, c.ws_u.ptr, count * k, false, s);
-    launch_ntt(*c.ntt, c.ws_v.ptr, count, false, s);
-    matvec(c, c.ws_e2.ptr, c.s_hat.ptr, c.ws_u.ptr, nullptr, 1, k, 0, 1, count, s);            // <s_hat, u_hat>
-    hipLaunchKernelGGL(rsub_mod_kernel, dim3(grid_for(count * n)), dim3(256), 0, s, c.ws_e2.ptr, c.ws_v.ptr, (uint64_t)count * n, c.q);
-    launch_ntt(*c.ntt, c.ws_e2.ptr, count, true, s);
-    const unsigned grid = decode_store_grid(c, count, slots, noise);
-    if (noise)
-        hipLaunchKernelGGL(decode_store_batch_kernel<true>, dim3(grid), dim3(256), 0, s, c.ws_e2.ptr, d_out, (uint64_t)slots, (uint32_t)c.logn, (uint64_t)count, c.t,
-                           c.ntt->mod, c.ws_vflags.ptr);
-    else
-        hipLaunchKernelGGL(decode_store_batch_kernel<false>, dim3(grid), dim3(256), 0, s, c.ws_e2.ptr, d_out, (uint64_t)slots, (uint32_t)c.logn, (uint64_t)count, c.t,
-                           c.ntt->mod, c.ws_vflags.ptr);
-    LSR_HIP(hipGetLastError());
-}
-
-// rows (host, back to back) -> messages[count][slots], status[count], noise_bits[count] (optional), verify_chunk() rows per pass
-static void decode_host_rows(const LweContext& c, const uint64_t* rows, size_t count, size_t slots, uint64_t* messages, int* status, uint32_t* noise_bits,
-                             hipStream_t s) {
-    const size_t row = row_words(c);
-    const size_t chunk = verify_chunk(c, count);
-    c.ws_rows.reserve(chunk * row);
-    ensure_input_space(c, chunk);                            // ws_dm: chunk x n slots (slots <= n)
-    uint64_t* const d_out = c.ws_dm.ptr;
-    std::vector<unsigned long long> state(chunk + (chunk + 1) / 2);
-    for (size_t first = 0; first < count; first += chunk) {
-        const size_t now = std::min(chunk, count - first);
-        LSR_HIP(hipMemcpyAsync(c.ws_rows.ptr, rows + first * row, now * row * 8, hipMemcpyHostToDevice, s));
-        decode_rows_device(c, c.ws_rows.ptr, now, slots, d_out, noise_bits != nullptr, s);
-        LSR_HIP(hipMemcpyAsync(messages + first * slots, d_out, now * slots * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipMemcpyAsync(state.data(), c.ws_vflags.ptr, (now + (now + 1) / 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-        const uint32_t* const host_bad = reinterpret_cast<const uint32_t*>(state.data() + now);
-        for (size_t j = 0; j < now; ++j) {
-            status[first + j] = host_bad[j] ? -1 : 1;
-            if (noise_bits) noise_bits[first + j] = (uint32_t)state[j];
-        }
-    }
 }
 
 // RNS rows: the same sum under each prime (combine_kernel per residue block).  The budget is Q / 2t ~ 2^67: any coefficient below t
@@ -2097,7 +1957,7 @@ int lsr_lwe_verify_rows_device(const LweContext* ctx, const uint64_t* d_rows, co
         std::lock_guard<std::mutex> lock(ctx->mutex);
         hipStream_t s = static_cast<hipStream_t>(stream);
         lsr::begin_async(*ctx, s);
-        lsr::verify_rows_device(*ctx, d_rows, d_messages, msg_len, count, s);
+        lsr::open_rows_device(*ctx, d_rows, count, lsr::CompareEnd{d_messages, msg_len}, s);
         hipLaunchKernelGGL(lsr::opening_verdict_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, ctx->ws_vflags.ptr, ctx->ws_vbad, d_results,
                            (uint64_t)count);
         LSR_HIP(hipGetLastError());
@@ -2136,7 +1996,7 @@ int lsr_lwe_decode_rows_device(const LweContext* ctx, const uint64_t* d_rows, si
         std::lock_guard<std::mutex> lock(ctx->mutex);
         hipStream_t s = static_cast<hipStream_t>(stream);
         lsr::begin_async(*ctx, s);
-        lsr::decode_rows_device(*ctx, d_rows, count, slots, d_messages, d_noise_bits != nullptr, s);
+        lsr::open_rows_device(*ctx, d_rows, count, lsr::StoreEnd{d_messages, slots, d_noise_bits != nullptr}, s);
         hipLaunchKernelGGL(lsr::decode_status_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, ctx->ws_vflags.ptr, ctx->ws_vbad, d_status, d_noise_bits,
                            (uint64_t)count);
         LSR_HIP(hipGetLastError());

@@ -1,7 +1,8 @@
 // The host call path shared by the fused ring operations (lsr_ring_mul.hip, lsr_ring_dot.hip, lsr_ring_fold.hip, lsr_ring_matvec.hip,
 // lsr_ring_gadget.hip, lsr_ring_galois.hip, lsr_ring_sample.hip and the ring combination of lsr_commit.hip): the dispatch from a context to a kernel
 // instantiation, the bracket that keeps the context's workspaces safe across streams and threads, the argument checks
-// the entry points have in common and the staging of host buffers.  Host code only.
+// the entry points have in common and the staging of host buffers.  The dispatch helpers (for_tile_log, for_rank, for_top_bits,
+// for_bool, for_flavour) also serve the commitment pipelines of lsr_commit.hip.  Host code only.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -21,6 +22,27 @@ void for_tile_log(int lt, F&& f) {
     } else {
         f(std::integral_constant<int, HI>{});
     }
+}
+
+// f(std::integral_constant<int, K>{}) for the module rank K = k in 1 .. 4; any other k goes to 4 (a caller with a generic form for
+// larger ranks takes it first)
+template <class F>
+void for_rank(uint32_t k, F&& f) {
+    for_tile_log<1, 4>(static_cast<int>(k), f);
+}
+
+// f(std::integral_constant<int, R>{}) for the R = 4 (n = 2^16) or 5 (n = 2^17) index bits of a top round
+template <class F>
+void for_top_bits(int r, F&& f) {
+    if (r == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 5>{});
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time switch as a template argument
+template <class F>
+void for_bool(bool on, F&& f) {
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 // f(A{}) for the arithmetic flavour A of the context's kernels

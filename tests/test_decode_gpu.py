@@ -409,6 +409,26 @@ def test_fused_chunks_and_chunk_lanes(pkg):
     assert np.array_equal(got[good], msgs[pick][good]) and np.array_equal(bits[good], base_bits[pick][good])
 
 
+def test_fused_chunks_failing_verdicts_past_the_first_chunk(pkg):
+    """The openings of the same 260 rows (three chunks on two chunk lanes, the third reusing slot 0): a malformed row and a wrongly
+    claimed row in every chunk.  Each verdict, its bad mark and its claimed message sit at the chunk's offset into the batch."""
+    ctx = _ctx(pkg, "default", 65536, 2)
+    t = ctx.plain_modulus
+    rng = np.random.default_rng(260)
+    msgs = rng.integers(0, t, size=(3, 4), dtype=np.uint64)
+    base = _commit(ctx, msgs, 4, [7, 8, 9])
+    pick = np.arange(260) % 3
+    rows, claimed = base[pick], msgs[pick]
+    bad, wrong = [5, 130, 259], [7, 131, 258]
+    for j in bad:
+        rows[j, ctx.commitment_words - 1 - j] = 2**63
+    for j in wrong:
+        claimed[j, j % 4] = (claimed[j, j % 4] + 1) % t
+    want = [-1 if j in bad else 0 if j in wrong else 1 for j in range(260)]
+    assert _verify_device(ctx, rows, claimed) == want
+    assert pkg.verify_openings_words(ctx, rows, claimed) == want
+
+
 @pytest.mark.parametrize("n,k", [(4096, 2), (8192, 2)])
 def test_decode_is_ordered_behind_a_commit_on_another_stream(pkg, n, k):
     """lsr_lwe_commit_rows_device on stream A, then lsr_lwe_decode_rows_device of those rows on stream B with no synchronisation by
