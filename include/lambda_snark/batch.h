@@ -182,8 +182,8 @@ int lsr_ntt_ring_matvec_batch_device(const LsrRingMatrix* mat, uint64_t* d_y, co
  * lsr_ntt_ring_recompose_batch(_device): out[j] = sum_d B^d z[j][d] mod q for ANY canonical z [count][digits][n], short or not — the
  *   gadget product G z.  Needs only 2 <= b <= 32, D >= 1, b (D - 1) <= 64, not admissibility.  out must not overlap z.
  * lsr_ntt_ring_linf_batch(_device): linf[j] = max over the n coefficients of |centred x[j]|, x [count][n]; UINT64_MAX when some word of
- *   element j is >= q (a verifier passes untrusted data: the case is defined, and the other elements are unaffected).  The l2 norm is
- *   not offered: n (q/2)^2 does not fit 64 bits.
+ *   element j is >= q (a verifier passes untrusted data: the case is defined, and the other elements are unaffected).  The exact l2
+ *   norm, which does not fit 64 bits, is lsr_ntt_ring_l2sq_batch below ("norms and projections of ring vectors").
  * lsr_ntt_ring_matvec_gadget_batch(_device): x [batch][xcols][n] with xcols * digits == lsr_ntt_ring_matrix_cols(mat) ->
  *   y [batch][rows][n] = lsr_ntt_ring_matvec_batch(mat, G^-1(x)) word for word.  n <= 4096: one launch, no workspace (the digits are
  *   extracted as the tile kernel loads x).  n > 4096 is refused: there lsr_ntt_ring_matvec_batch is itself a composed route, so
@@ -341,6 +341,61 @@ int lsr_ntt_ring_dot_galois_batch(const NttContext* ctx, uint64_t* c, const uint
                                   size_t batch, size_t terms, size_t b_rows, uint64_t g) LSR_NOEXCEPT;
 int lsr_ntt_ring_dot_galois_batch_device(const NttContext* ctx, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b,
                                          size_t batch, size_t terms, size_t b_rows, uint64_t g, void* stream) LSR_NOEXCEPT;
+
+/* ---------------- NTT: norms and projections of ring vectors ---------------- */
+/* The relation a LaBRADOR / Greyhound-style argument proves is |s|_2 <= B, and it proves it through the Johnson-Lindenstrauss
+ * projection p = Pi s in Z^256 of the witness.  Integer code that reads only q and n of the context, as the
+ * sampling calls: every context and arithmetic flavour is served by one path.
+ * A vector is `width` ring elements, [width][n] canonical words; its flattened position is pos = c n + k and len = width n.
+ * centred(v) = v if v <= floor(q/2), else v - q, as lsr_ntt_ring_linf_batch.
+ *
+ * lsr_ntt_ring_l2sq_batch(_device): x [count][width][n] -> out [count][2], the low word then the high word of sum_pos centred(x)^2
+ *   as an unsigned 128-bit integer.  Both words are UINT64_MAX when a word of the vector is >= q or the sum is 2^128 - 1 or more
+ *   (whatever the order of summation: the terms are non-negative and a partial sum that overflows is remembered); the other vectors
+ *   of the batch are unaffected.  No workspace, plain stream order, capturable from the first call.
+ *
+ * lsr_ntt_ring_project_batch(_device): x [count][width][n] -> out [count][LSR_RING_PROJECT_ROWS] int64 and status [count] int32.
+ *   Vector j uses key keys[4 (j / components) ..]; row r of its matrix is the stream (key, domain, index_base + 256 (j % components)
+ *   + r) of "seeded ring sampling" above, ceil(count / components) keys are read.  Entry pi[r][pos] = (f & 1) - (f >> 1) with
+ *   f = (word[pos / 32] >> 2 (pos % 32)) & 3 of that stream: 0, +1, -1, 0 for f = 0 .. 3, so +-1 with probability 1/4 each.
+ *   out[j][r] = sum_pos pi[r][pos] centred(x[j][pos]), an exact int64 stored as its two's-complement word.
+ *   status[j]: 1 — done; -1 — a word of the vector is >= q; 0 — some |centred| is above `bound` (and no word is >= q).  For a status
+ *   other than 1 all 256 outputs of that vector are 0; the other vectors are unaffected.
+ *   bound is the caller's l-infinity bound: len bound <= 2^63 - 1 is what makes the 64-bit sum exact.
+ *   The matrix is generated from the streams inside the kernel that applies it and never exists in memory.  The device form
+ *   enqueues three launches (the outputs zeroed and the status set to 1; the slices of the vectors added into the outputs by 64-bit
+ *   integer atomics — wrapping adds, the same word in any order; the outputs of a refused vector cleared) and allocates nothing:
+ *   capturable from the first call.  out and status are written by all three, so nothing else may touch them in between.
+ * lsr_ntt_ring_project_matrix_batch(_device): rows rows_first .. rows_first + rows - 1 of the matrix of ONE (key, index_base) — the
+ *   matrix of a vector with j % components = 0 — as ring elements: out [rows][width][n] with words 0, 1, q - 1.  Coefficient 0 of
+ *   lsr_ntt_ring_dot_galois_batch(row r, s, conjugation) is then p_r mod q, which is how a verifier proves p_r.  (A separate entry,
+ *   not a kind of lsr_ntt_ring_sample_batch: a row spans `width` elements.)  key: four words, host memory for the plain form and
+ *   device memory for the _device form.
+ * The plain forms take host buffers, staged through bounded device chunks of whole vectors (rows), and return when the output is
+ * complete; the _device forms take device buffers on the context's device and are asynchronous on `stream`.
+ *
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL context, buffer, keys or
+ * status; (2) components == 0, then bound == 0; rows_first + rows above 256.  (3) Then count == 0, width == 0 or rows == 0 is a no-op
+ * that returns 0.  (4) A size that overflows size_t without reading the context: count * width (rows * width), that times 16 bytes,
+ * count * 256 * 8.  Then (5) the rules that read the context: bound above floor(q/2), len above 2^32 (the positions a stream's block
+ * counter reaches), len * bound above 2^63 - 1; index_base + 256 components (matrix: index_base + 256) overflowing 64 bits; the
+ * byte size of a buffer overflowing size_t at the context's n; out (then status) overlapping x in address range; no visible
+ * device. */
+#define LSR_RING_PROJECT_ROWS 256
+int lsr_ntt_ring_l2sq_batch(const NttContext* ctx, const uint64_t* x, size_t count, size_t width, uint64_t* out) LSR_NOEXCEPT;
+int lsr_ntt_ring_l2sq_batch_device(const NttContext* ctx, const uint64_t* d_x, size_t count, size_t width, uint64_t* d_out,
+                                   void* stream) LSR_NOEXCEPT;
+int lsr_ntt_ring_project_batch(const NttContext* ctx, int64_t* out, int32_t* status, const uint64_t* x, size_t count, size_t width,
+                               uint64_t bound, const uint64_t* keys, size_t components, uint32_t domain,
+                               uint64_t index_base) LSR_NOEXCEPT;
+int lsr_ntt_ring_project_batch_device(const NttContext* ctx, int64_t* d_out, int32_t* d_status, const uint64_t* d_x, size_t count,
+                                      size_t width, uint64_t bound, const uint64_t* d_keys, size_t components, uint32_t domain,
+                                      uint64_t index_base, void* stream) LSR_NOEXCEPT;
+int lsr_ntt_ring_project_matrix_batch(const NttContext* ctx, uint64_t* out, size_t rows_first, size_t rows, size_t width,
+                                      const uint64_t* key, uint32_t domain, uint64_t index_base) LSR_NOEXCEPT;
+int lsr_ntt_ring_project_matrix_batch_device(const NttContext* ctx, uint64_t* d_out, size_t rows_first, size_t rows, size_t width,
+                                             const uint64_t* d_key, uint32_t domain, uint64_t index_base,
+                                             void* stream) LSR_NOEXCEPT;
 
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform

@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_PROJECT_ROWS", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -399,7 +399,81 @@ class _RingGalois:
                "lsr_ntt_ring_dot_galois_batch_device")
 
 
-class NttContext(_RingGadget, _RingSample, _RingFold, _RingGalois):
+# batch.h LSR_RING_PROJECT_ROWS: the rows of the Johnson-Lindenstrauss projection
+RING_PROJECT_ROWS = 256
+
+
+class _RingNorm:
+    """Exact l2 norms and seeded Johnson-Lindenstrauss projections of ring vectors on a context (``NttContext`` and ``CyclicNtt``;
+    batch.h "norms and projections of ring vectors").  A vector is [width, n] canonical words."""
+
+    def _ring_vectors(self, x):
+        x_in = _u64_array(x, "x")
+        if x_in.ndim < 2 or x_in.shape[-1] != self.n:
+            raise ValueError("x must be [width, n] or [..., width, n]")
+        width = x_in.shape[-2]
+        return x_in, np.ascontiguousarray(x_in.reshape(-1, width, self.n)), width
+
+    def ring_l2sq(self, x):
+        """sum of the squared centred coefficients of every vector of x [..., width, n], exact, as Python ints (an object array of
+        shape x.shape[:-2]; an int for one vector); 2^128 - 1 for a vector with a word >= q or a sum that does not fit below it."""
+        x_in, x3, width = self._ring_vectors(x)
+        out = np.empty((x3.shape[0], 2), dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_l2sq_batch(self._h, x3.ctypes.data, x3.shape[0], width, out.ctypes.data), "lsr_ntt_ring_l2sq_batch")
+        values = [int(lo) | (int(hi) << 64) for lo, hi in out.tolist()]
+        if x_in.ndim == 2:
+            return values[0]
+        res = np.empty(len(values), dtype=object)
+        res[:] = values
+        return res.reshape(x_in.shape[:-2])
+
+    def ring_l2sq_device(self, d_x, count, width, d_out, stream=0):
+        """Device buffers: x [count][width][n], out [count][2] (low word, high word).  Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ntt_ring_l2sq_batch_device(self._h, d_x, count, width, d_out, stream), "lsr_ntt_ring_l2sq_batch_device")
+
+    def ring_project(self, x, bound, keys, components=None, domain=17, index_base=0):
+        """(p, status) for x [count, width, n] (or [width, n]: one vector): p int64 [count, 256] with p[j][r] = <pi_r, centred x[j]>
+        over the integers, status int32 [count] (1 done; 0 some |coefficient| above bound; -1 a word >= q; p[j] is 0 unless 1).
+        Vector j uses key j // components and the streams index_base + 256 (j % components) + r; keys as ring_sample;
+        components=None spreads the vectors evenly over the keys given."""
+        x_in, x3, width = self._ring_vectors(x)
+        k2 = _ring_keys(keys)
+        count = x3.shape[0]
+        if components is None:
+            components = max(1, -(-count // k2.shape[0]))
+        components = int(components)
+        if components > 0 and k2.shape[0] < -(-count // components):
+            raise ValueError("keys must hold ceil(count / components) keys")
+        out = np.empty((count, RING_PROJECT_ROWS), dtype=np.int64)
+        status = np.empty(count, dtype=np.int32)
+        _check(self._lib.lsr_ntt_ring_project_batch(self._h, out.ctypes.data, status.ctypes.data, x3.ctypes.data, count, width, int(bound),
+                                                    k2.ctypes.data, components, domain, index_base), "lsr_ntt_ring_project_batch")
+        return (out[0], status[0]) if x_in.ndim == 2 else (out, status)
+
+    def ring_project_device(self, d_out, d_status, d_x, count, width, bound, d_keys, components, domain=17, index_base=0, stream=0):
+        """Device buffers: out [count][256] int64, status [count] int32, x [count][width][n], d_keys [ceil(count / components)][4]
+        words.  Asynchronous on `stream`; enqueues only and allocates nothing."""
+        _check(self._lib.lsr_ntt_ring_project_batch_device(self._h, d_out, d_status, d_x, count, width, int(bound), d_keys, components, domain,
+                                                           index_base, stream), "lsr_ntt_ring_project_batch_device")
+
+    def ring_project_matrix(self, key, width, rows_first=0, rows=RING_PROJECT_ROWS, domain=17, index_base=0):
+        """Rows rows_first .. rows_first + rows - 1 of the projection matrix of (key, index_base) as ring elements [rows, width, n]
+        with words 0, 1, q - 1: coefficient 0 of ring_dot_galois(row r, s, galois_conjugation) is p_r mod q."""
+        k2 = _ring_keys(key)
+        if k2.shape[0] != 1:
+            raise ValueError("key must be one 256-bit key")
+        out = np.empty((int(rows), int(width), self.n), dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_project_matrix_batch(self._h, out.ctypes.data, rows_first, rows, width, k2.ctypes.data, domain, index_base),
+               "lsr_ntt_ring_project_matrix_batch")
+        return out
+
+    def ring_project_matrix_device(self, d_out, rows_first, rows, width, d_key, domain=17, index_base=0, stream=0):
+        """Device buffers: out [rows][width][n], d_key four words.  Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ntt_ring_project_matrix_batch_device(self._h, d_out, rows_first, rows, width, d_key, domain, index_base, stream),
+               "lsr_ntt_ring_project_matrix_batch_device")
+
+
+class NttContext(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm):
     """RAII handle over ``NttContext*`` (cpp-core/include/lambda_snark/ntt.h:25-41)."""
 
     def __init__(self, q, n, device=-1):
@@ -1005,7 +1079,7 @@ def prover_max_log2_size():
     return int(_abi.lib().lsr_prover_max_log2_size())
 
 
-class CyclicNtt(_RingGadget, _RingSample, _RingFold, _RingGalois):
+class CyclicNtt(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm):
     """The transform pair of rust-api/lambda-snark/src/ntt.rs: ``forward(coeffs)`` = ``ntt_forward(coeffs, modulus, omega)``
     (natural order in and out), ``inverse(evals)`` = ``ntt_inverse``.  One handle per (modulus, n, omega).  n above 2^17 (up to 2^22,
     NTT_MODULUS only) goes through ``lsr_cyclic_ntt_context_create_large``."""

@@ -1,0 +1,254 @@
+// Norms and projections of ring vectors (batch.h "norms and projections of ring vectors"): the exact l2 norm squared of
+// a vector of ring elements, the Johnson-Lindenstrauss projection p = Pi s whose matrix is expanded from ChaCha20 streams inside the
+// kernel that applies it, and the rows of Pi as ring elements.  Integer code that reads only q and n of the context: one path for every
+// flavour, every ring degree and both rings.  No workspace and no part in the context's ring ordering: the device forms enqueue
+// kernels in plain stream order and nothing else.
+#include <algorithm>
+
+#include "lambda_snark/batch.h"
+#include "lsr_ring_call.hpp"
+#include "lsr_ring_norm_kernels.hpp"
+#include "lsr_runtime.hpp"
+
+namespace lsr {
+
+static_assert(kProjectRows == LSR_RING_PROJECT_ROWS, "batch.h and the kernels agree on the rows of the projection");
+static_assert(kProjectRows == kNormThreads, "one lane per row");
+static_assert(kProjectSlice % 256 == 0, "a slice is whole stream blocks");
+
+struct ProjectCall {
+    uint64_t len;             // width n
+    uint64_t bound;
+    uint64_t components;
+    uint32_t domain;
+    uint64_t index_base;
+};
+
+static void l2sq_device(const NttContext& c, const uint64_t* d_x, size_t count, size_t width, uint64_t* d_out, hipStream_t s) {
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(count, 1u << 20));
+    hipLaunchKernelGGL(ring_l2sq_kernel, dim3(grid), dim3(kNormThreads), 0, s, d_out, d_x, count, (uint64_t)width << c.logn, c.modulus);
+    LSR_HIP(hipGetLastError());
+}
+
+// vectors [first, first + count) of a call (vector `first` at d_out, d_status and d_x); d_keys holds the key groups from group_base on
+static void project_device(const NttContext& c, int64_t* d_out, int32_t* d_status, const uint64_t* d_x, uint64_t first, uint64_t count,
+                           const ProjectCall& call, const uint64_t* d_keys, uint64_t group_base, hipStream_t s) {
+    const unsigned sweep = static_cast<unsigned>(std::min<uint64_t>((count * kProjectRows + kNormThreads - 1) / kNormThreads, 256 * 32));
+    hipLaunchKernelGGL(ring_project_init_kernel, dim3(sweep), dim3(kNormThreads), 0, s, d_out, d_status, (size_t)count);
+    LSR_HIP(hipGetLastError());
+    ProjectJob job{};
+    job.keys = d_keys;
+    job.index_base = call.index_base;
+    job.components = call.components;
+    job.group_base = group_base;
+    job.len = call.len;
+    job.q = c.modulus;
+    job.bound = call.bound;
+    job.slices = static_cast<uint32_t>((call.len + kProjectSlice - 1) / kProjectSlice);      // len <= 2^32: at most 2^21
+    job.domain = call.domain;
+    // one launch covers at most 2^30 workgroups
+    const uint64_t step = std::max<uint64_t>(1, (1ull << 30) / job.slices);
+    for (uint64_t j0 = 0; j0 < count; j0 += step) {
+        const uint64_t now = std::min(step, count - j0);
+        job.out = d_out + j0 * kProjectRows;
+        job.status = d_status + j0;
+        job.x = d_x + j0 * call.len;
+        job.first = first + j0;
+        hipLaunchKernelGGL(ring_project_kernel,dim3(static_cast<unsigned>(now * job.slices)), dim3(kNormThreads), 0, s, job);
+        LSR_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(ring_project_finish_kernel, dim3(static_cast<unsigned>(std::min<uint64_t>(count, 1u << 20))), dim3(kNormThreads), 0, s, d_out,
+                       d_status, (size_t)count);
+    LSR_HIP(hipGetLastError());
+}
+
+// host buffers through bounded device chunks of whole vectors on the context's work stream; each chunk brings its own key groups
+static void host_project(const NttContext& c, int64_t* out, int32_t* status, const uint64_t* x, uint64_t count, const ProjectCall& call,
+                         const uint64_t* keys) {
+    DeviceGuard guard(c.device);
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, (kStagingBytes / 8) / (call.len + kProjectRows)));
+    const uint64_t chunk_groups = chunk / call.components + 2;
+    DeviceBuffer<uint64_t> d_x(chunk * call.len), d_out(chunk * kProjectRows), d_keys(chunk_groups * 4);
+    DeviceBuffer<int32_t> d_status(chunk);
+    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
+    hipStream_t s = work_stream(c);
+    for (uint64_t j0 = 0; j0 < count; j0 += chunk) {
+        const uint64_t now = std::min(chunk, count - j0);
+        const uint64_t g0 = j0 / call.components, g1 = (j0 + now - 1) / call.components;
+        LSR_HIP(hipMemcpyAsync(d_keys.ptr, keys + 4 * g0, (g1 - g0 + 1) * 32, hipMemcpyHostToDevice, s));
+        LSR_HIP(hipMemcpyAsync(d_x.ptr, x + j0 * call.len, now * call.len * 8, hipMemcpyHostToDevice, s));
+        project_device(c, reinterpret_cast<int64_t*>(d_out.ptr), d_status.ptr, d_x.ptr, j0, now, call, d_keys.ptr, g0, s);
+        LSR_HIP(hipMemcpyAsync(out + j0 * kProjectRows, d_out.ptr, now * kProjectRows * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(status + j0, d_status.ptr, now * 4, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+// rows [rows_first, rows_first + rows) of the matrix of (d_key, index_base) into d_out [rows][len]
+static void project_matrix_device(const NttContext& c, uint64_t* d_out, uint64_t rows_first, uint64_t rows, uint64_t len, const uint64_t* d_key,
+                                  uint32_t domain, uint64_t index_base, hipStream_t s) {
+    ProjectMatrixJob job{};
+    job.key = d_key;
+    job.len = len;
+    job.q = c.modulus;
+    job.chunks = static_cast<uint32_t>((len + 65535) >> 16);      // len <= 2^32: at most 2^16, times 256 rows
+    job.domain = domain;
+    job.out = d_out;
+    job.index = index_base + rows_first;
+    hipLaunchKernelGGL(ring_project_matrix_kernel, dim3(static_cast<unsigned>(rows * job.chunks)), dim3(kNormThreads), 0, s, job);
+    LSR_HIP(hipGetLastError());
+}
+
+static void host_project_matrix(const NttContext& c, uint64_t* out, uint64_t rows_first, uint64_t rows, uint64_t len, const uint64_t* key, uint32_t domain,
+                                uint64_t index_base) {
+    DeviceGuard guard(c.device);
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(rows, (kStagingBytes / 8) / len));
+    DeviceBuffer<uint64_t> d_out(chunk * len), d_key(4);
+    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
+    hipStream_t s = work_stream(c);
+    LSR_HIP(hipMemcpyAsync(d_key.ptr, key, 32, hipMemcpyHostToDevice, s));
+    for (uint64_t r0 = 0; r0 < rows; r0 += chunk) {
+        const uint64_t now = std::min(chunk, rows - r0);
+        project_matrix_device(c, d_out.ptr, rows_first + r0, now, len, d_key.ptr, domain, index_base, s);
+        LSR_HIP(hipMemcpyAsync(out + r0 * len, d_out.ptr, now * len * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+}  // namespace lsr
+
+// ------------------------------------------------------------------------------------------------
+// C-ABI
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+const char* const kOverflow = "the sizes of the buffers overflow size_t";
+
+// step 4 of batch.h's order, without the context: elements = the ring elements of the largest buffer (16 bytes each in the smallest
+// ring), projections = vectors with 256 eight-byte outputs each
+bool sizes_overflow(size_t a, size_t b, size_t projections) {
+    size_t elements = 0, bytes = 0;
+    return __builtin_mul_overflow(a, b, &elements) || __builtin_mul_overflow(elements, (size_t)16, &bytes) ||
+           __builtin_mul_overflow(projections, (size_t)LSR_RING_PROJECT_ROWS * 8, &bytes);
+}
+
+// width n, the length of a vector; throws when it or its `vectors`-fold byte size does not fit
+uint64_t vector_length(const NttContext& ctx, size_t vectors, size_t width) {
+    size_t len = 0, bytes = 0;
+    if (__builtin_mul_overflow(width, (size_t)ctx.degree, &len) || __builtin_mul_overflow(len, (size_t)8, &bytes) || __builtin_mul_overflow(bytes, vectors, &bytes))
+        throw std::runtime_error("the sizes of the buffers overflow size_t at this ring degree");
+    return len;
+}
+
+void require_projectable(uint64_t len) {
+    if (len > (1ull << 32))
+        throw std::runtime_error("width * n = " + std::to_string(len) + " is above 2^32, the positions one stream's block counter reaches");
+}
+
+int l2sq_call(const char* where, const NttContext* ctx, const uint64_t* x, size_t count, size_t width, uint64_t* out, bool device, void* stream) noexcept {
+    if (!ctx || !x || !out) return lsr::abi_refuse(where, "NULL context or buffer");
+    if (count == 0 || width == 0) return 0;
+    if (sizes_overflow(count, width, 0)) return lsr::abi_refuse(where, kOverflow);
+    return lsr::abi_guarded(where, [&] {
+        const uint64_t len = vector_length(*ctx, count, width);
+        lsr::require_apart(out, count * 16, x, count * len * 8, "out overlaps x: the output must not share memory with the operand");
+        lsr::require_device();
+        if (device) {
+            lsr::DeviceGuard guard(ctx->device);
+            lsr::l2sq_device(*ctx, x, count, width, out, static_cast<hipStream_t>(stream));
+        } else {
+            lsr::host_staged(*ctx, out, x, count, 2, len, [&](uint64_t* d_out, const uint64_t* d_in, size_t now, hipStream_t s) {
+                lsr::l2sq_device(*ctx, d_in, now, width, d_out, s);
+            });
+        }
+    });
+}
+
+int project_call(const char* where, const NttContext* ctx, int64_t* out, int32_t* status, const uint64_t* x, size_t count, size_t width, uint64_t bound,
+                 const uint64_t* keys, size_t components, uint32_t domain, uint64_t index_base, bool device, void* stream) noexcept {
+    if (!ctx || !out || !status || !x || !keys) return lsr::abi_refuse(where, "NULL context, buffer, keys or status");
+    if (components == 0) return lsr::abi_refuse(where, "components must be at least 1");
+    if (bound == 0) return lsr::abi_refuse(where, "bound must be at least 1");
+    if (count == 0 || width == 0) return 0;
+    if (sizes_overflow(count, width, count)) return lsr::abi_refuse(where, kOverflow);
+    return lsr::abi_guarded(where, [&] {
+        if (bound > ctx->modulus / 2)
+            throw std::runtime_error("bound = " + std::to_string(bound) + " is above floor(q / 2) = " + std::to_string(ctx->modulus / 2));
+        size_t len = 0;
+        if (__builtin_mul_overflow(width, (size_t)ctx->degree, &len)) throw std::runtime_error("width * n overflows size_t");
+        require_projectable(len);
+        if (bound > (uint64_t)INT64_MAX / len)
+            throw std::runtime_error("width * n * bound = " + std::to_string(len) + " * " + std::to_string(bound) + " is above 2^63 - 1: a 64-bit sum would not be exact");
+        uint64_t span = 0;
+        if (__builtin_mul_overflow((uint64_t)components, (uint64_t)LSR_RING_PROJECT_ROWS, &span) || index_base + span < index_base)
+            throw std::runtime_error("index_base + 256 * components overflows 64 bits");
+        vector_length(*ctx, count, width);
+        const char* const apart = "the outputs must not share memory with the operand";
+        lsr::require_apart(out, count * LSR_RING_PROJECT_ROWS * 8, x, count * len * 8, (std::string("out overlaps x: ") + apart).c_str());
+        lsr::require_apart(status, count * 4, x, count * len * 8, (std::string("status overlaps x: ") + apart).c_str());
+        lsr::require_device();
+        // min(components, count): the same streams, and the kernel's 32-bit division applies more often
+        const lsr::ProjectCall call{len, bound, std::min<uint64_t>(components, count), domain, index_base};
+        if (device) {
+            lsr::DeviceGuard guard(ctx->device);
+            lsr::project_device(*ctx, out, status, x, 0, count, call, keys, 0, static_cast<hipStream_t>(stream));
+        } else {
+            lsr::host_project(*ctx, out, status, x, count, call, keys);
+        }
+    });
+}
+
+int project_matrix_call(const char* where, const NttContext* ctx, uint64_t* out, size_t rows_first, size_t rows, size_t width, const uint64_t* key,
+                        uint32_t domain, uint64_t index_base, bool device, void* stream) noexcept {
+    if (!ctx || !out || !key) return lsr::abi_refuse(where, "NULL context, buffer or key");
+    if (rows_first > LSR_RING_PROJECT_ROWS || rows > LSR_RING_PROJECT_ROWS - rows_first)
+        return lsr::abi_refuse(where, "rows_first + rows = " + std::to_string(rows_first) + " + " + std::to_string(rows) + " is above " +
+                                          std::to_string(LSR_RING_PROJECT_ROWS) + ", the rows of a projection");
+    if (rows == 0 || width == 0) return 0;
+    if (sizes_overflow(rows, width, 0)) return lsr::abi_refuse(where, kOverflow);
+    return lsr::abi_guarded(where, [&] {
+        const uint64_t len = vector_length(*ctx, rows, width);
+        require_projectable(len);
+        if (index_base + LSR_RING_PROJECT_ROWS < index_base) throw std::runtime_error("index_base + 256 overflows 64 bits");
+        lsr::require_device();
+        if (device) {
+            lsr::DeviceGuard guard(ctx->device);
+            lsr::project_matrix_device(*ctx, out, rows_first, rows, len, key, domain, index_base, static_cast<hipStream_t>(stream));
+        } else {
+            lsr::host_project_matrix(*ctx, out, rows_first, rows, len, key, domain, index_base);
+        }
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsr_ntt_ring_l2sq_batch(const NttContext* ctx, const uint64_t* x, size_t count, size_t width, uint64_t* out) noexcept {
+    return l2sq_call("lsr_ntt_ring_l2sq_batch", ctx, x, count, width, out, false, nullptr);
+}
+int lsr_ntt_ring_l2sq_batch_device(const NttContext* ctx, const uint64_t* d_x, size_t count, size_t width, uint64_t* d_out, void* stream) noexcept {
+    return l2sq_call("lsr_ntt_ring_l2sq_batch_device", ctx, d_x, count, width, d_out, true, stream);
+}
+
+int lsr_ntt_ring_project_batch(const NttContext* ctx, int64_t* out, int32_t* status, const uint64_t* x, size_t count, size_t width, uint64_t bound,
+                               const uint64_t* keys, size_t components, uint32_t domain, uint64_t index_base) noexcept {
+    return project_call("lsr_ntt_ring_project_batch", ctx, out, status, x, count, width, bound, keys, components, domain, index_base, false, nullptr);
+}
+int lsr_ntt_ring_project_batch_device(const NttContext* ctx, int64_t* d_out, int32_t* d_status, const uint64_t* d_x, size_t count, size_t width,
+                                      uint64_t bound, const uint64_t* d_keys, size_t components, uint32_t domain, uint64_t index_base,
+                                      void* stream) noexcept {
+    return project_call("lsr_ntt_ring_project_batch_device", ctx, d_out, d_status, d_x, count, width, bound, d_keys, components, domain, index_base, true,
+                        stream);
+}
+
+int lsr_ntt_ring_project_matrix_batch(const NttContext* ctx, uint64_t* out, size_t rows_first, size_t rows, size_t width, const uint64_t* key,
+                                      uint32_t domain, uint64_t index_base) noexcept {
+    return project_matrix_call("lsr_ntt_ring_project_matrix_batch", ctx, out, rows_first, rows, width, key, domain, index_base, false, nullptr);
+}
+int lsr_ntt_ring_project_matrix_batch_device(const NttContext* ctx, uint64_t* d_out, size_t rows_first, size_t rows, size_t width, const uint64_t* d_key,
+                                             uint32_t domain, uint64_t index_base, void* stream) noexcept {
+    return project_matrix_call("lsr_ntt_ring_project_matrix_batch_device", ctx, d_out, rows_first, rows, width, d_key, domain, index_base, true, stream);
+}
+
+}  // extern "C"

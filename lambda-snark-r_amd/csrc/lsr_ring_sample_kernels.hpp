@@ -42,26 +42,7 @@ struct RingSampleJob {
     uint32_t logn;
 };
 
-struct RingStream {
-    const uint64_t* key;
-    uint64_t index;
-};
-
-__device__ __forceinline__ RingStream ring_stream_of(const uint64_t* keys, uint64_t e, uint64_t components, uint64_t group_base, uint64_t index_base) {
-    uint64_t group, member;
-    if (components == 1) {
-        group = e;
-        member = 0;
-    } else if (((e | components) >> 32) == 0) {      // the usual case: a 32-bit division
-        const uint32_t g = (uint32_t)e / (uint32_t)components;
-        group = g;
-        member = (uint32_t)e - g * (uint32_t)components;
-    } else {
-        group = e / components;
-        member = e - group * components;
-    }
-    return RingStream{keys + 4 * (group - group_base), index_base + member};
-}
+// (RingStream and ring_stream_of, the key and stream index of element e: lsr_sampler.hpp)
 
 // r in [0, m) -> the stored word: r - beta as a canonical residue (beta = 0: r itself)
 __device__ __forceinline__ uint64_t ring_sample_value(uint64_t r, uint64_t beta, uint64_t q) { return r >= beta ? r - beta : q - (beta - r); }

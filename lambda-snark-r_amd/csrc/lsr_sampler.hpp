@@ -54,6 +54,29 @@ __device__ __forceinline__ void stream_block(const uint64_t* __restrict__ key4, 
     for (int j = 0; j < 8; ++j) w[j] = (uint64_t)(x[2 * j] + init[2 * j]) | ((uint64_t)(x[2 * j + 1] + init[2 * j + 1]) << 32);
 }
 
+// The stream of element e of a ring call (lsr_ring_sample_kernels.hpp, lsr_ring_norm_kernels.hpp): key keys[4 (e / components -
+// group_base) ..], stream index index_base + e % components.
+struct RingStream {
+    const uint64_t* key;
+    uint64_t index;
+};
+
+__device__ __forceinline__ RingStream ring_stream_of(const uint64_t* keys, uint64_t e, uint64_t components, uint64_t group_base, uint64_t index_base) {
+    uint64_t group, member;
+    if (components == 1) {
+        group = e;
+        member = 0;
+    } else if (((e | components) >> 32) == 0) {      // the usual case: a 32-bit division
+        const uint32_t g = (uint32_t)e / (uint32_t)components;
+        group = g;
+        member = (uint32_t)e - g * (uint32_t)components;
+    } else {
+        group = e / components;
+        member = e - group * components;
+    }
+    return RingStream{keys + 4 * (group - group_base), index_base + member};
+}
+
 // Magnitudes of COUNT samples at once: first k with cdf63[k] >= u[s] (cdf63 = table >> 1, non-decreasing, last entry 2^63 - 1;
 // u = stream word >> 1) — the value the reference's scan selects (utils.cpp:101-108) — computed the way the reference computes
 // it: a branch-free pass over the WHOLE table, count += (cdf63[k] < u).  Every lane reads the same LDS word per step (a
