@@ -397,6 +397,47 @@ int lsr_ntt_ring_project_matrix_batch_device(const NttContext* ctx, uint64_t* d_
                                              const uint64_t* d_key, uint32_t domain, uint64_t index_base,
                                              void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: batched ring Gram matrices G = A B^T ---------------- */
+/* Every pairwise ring inner product of the vectors of one family with the vectors of another, or of one family with itself — the
+ * "garbage" polynomials g_il = <s_i, s_l> and h_il = <phi_i, s_l> + <phi_l, s_i> of a LaBRADOR / Greyhound style argument (DESIGN.md
+ * section 5j).  The ring is the context's (X^n + 1 on negacyclic contexts, X^n - 1 on cyclic ones); words are canonical ([0,q) in,
+ * canonical out) in natural coefficient order.  a: [batch][ra][width][n], b: [batch][rb][width][n]; a family is one index j < batch.
+ *   Cross form (b != NULL): g is [batch][ra][rb][n], g[j][i][l] = sum_{c < width} a[j][i][c] * b[j][l][c].  b may be the pointer a
+ *     (the full square matrix of one family; with rb == ra it is transformed once).
+ *   Symmetric form (b == NULL): rb must equal ra =: r; only i <= l is computed and stored, g is [batch][r (r + 1) / 2][n] and the
+ *     pair (i, l) is polynomial i r - i (i - 1) / 2 + (l - i) of its family.
+ * Every output equals lsr_ntt_ring_dot_batch(ctx, ., a[j][i], b[j][l], 1, width, 1) word for word, in every arithmetic flavour and
+ * at every n from 2 to 131072 (all arithmetic is exact).  Each of the (ra + rb) width operand polynomials of a family is transformed
+ * once and each output inverse-transformed once; between them runs a register-blocked pointwise product over E x E outputs per
+ * workgroup.  lsr_ntt_ring_gram_block: that edge E for the context's flavour (0 on NULL), as lsr_ntt_ring_matrix_row_block.
+ *
+ * Limits: ra, rb <= LSR_RING_GRAM_MAX_VECTORS, width <= LSR_RING_DOT_MAX_TERMS, one family's operands ((ra + rb) width n 8 bytes;
+ * symmetric form: ra for ra + rb) and one family's outputs each <= LSR_RING_GRAM_MAX_FAMILY_BYTES.
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL ctx, g or a; (2) ra == 0,
+ * width == 0, or b != NULL and rb == 0; (3) b == NULL and rb != ra; (4) ra or rb above LSR_RING_GRAM_MAX_VECTORS, width above
+ * LSR_RING_DOT_MAX_TERMS; (5) a size that overflows size_t: batch ra width, batch rb width, the output count, or one of them times
+ * 16 bytes (a polynomial of the smallest ring) — all of these without reading the context.  Then batch == 0 is a no-op that returns
+ * 0.  Then (6) a context above n = 131072; (7) a family above LSR_RING_GRAM_MAX_FAMILY_BYTES; (8) more vectors in a family (ra + rb;
+ * symmetric: ra) than the workspace holds polynomials — the message names LAMBDA_SNARK_NTT_CHUNK_MIB, which sizes it; (9) g
+ * overlapping a, then b, in address range; (10) no visible device.
+ *
+ * lsr_ntt_ring_gram_batch: host buffers, whole families staged through bounded device chunks; returns when g is complete.
+ * lsr_ntt_ring_gram_batch_device: device buffers on the context's device, asynchronous on `stream` (enqueues only).  a and b are
+ * never written.
+ *
+ * Workspace, ordering and graph capture: the contract of lsr_ntt_ring_dot_batch above, and its workspace — no other.  Every call
+ * uses it (its size depends on n alone): families that fit are taken in chunks of whole families, a family that does not fit in
+ * groups of columns, the running sums waiting in g as canonical evaluation-domain words between groups.  The first eager ring inner
+ * product, fold or Gram call on the context allocates it; a capturing call that would have to allocate it returns -1: make one eager
+ * call first.  FP64-flavour contexts re-centre the running sums every LSR_RING_DOT_F64_RECENTRE_PERIOD columns. */
+#define LSR_RING_GRAM_MAX_VECTORS 64
+#define LSR_RING_GRAM_MAX_FAMILY_BYTES 1073741824
+int lsr_ntt_ring_gram_batch(const NttContext* ctx, uint64_t* g, const uint64_t* a, const uint64_t* b, size_t batch, size_t ra, size_t rb,
+                            size_t width) LSR_NOEXCEPT;
+int lsr_ntt_ring_gram_batch_device(const NttContext* ctx, uint64_t* d_g, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t ra,
+                                   size_t rb, size_t width, void* stream) LSR_NOEXCEPT;
+size_t lsr_ntt_ring_gram_block(const NttContext* ctx) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_PROJECT_ROWS", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_PROJECT_ROWS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -473,7 +473,60 @@ class _RingNorm:
                "lsr_ntt_ring_project_matrix_batch_device")
 
 
-class NttContext(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm):
+# the most vectors of one family of a ring Gram matrix (batch.h LSR_RING_GRAM_MAX_VECTORS)
+RING_GRAM_MAX_VECTORS = 64
+
+
+def ring_gram_index(r, i, l):
+    """The polynomial of the pair (i, l), i <= l < r, in the packed upper triangle a symmetric ring_gram returns."""
+    r, i, l = int(r), int(i), int(l)
+    if not 0 <= i <= l < r:
+        raise ValueError("ring_gram_index takes 0 <= i <= l < r")
+    return i * r - i * (i - 1) // 2 + (l - i)
+
+
+class _RingGram:
+    """Ring Gram matrices G = A B^T of families of ring vectors on a context (``NttContext`` and ``CyclicNtt``; batch.h "batched ring
+    Gram matrices")."""
+
+    @property
+    def ring_gram_block(self):
+        """The edge E of the register block of the Gram kernel in this context's arithmetic flavour."""
+        return int(self._lib.lsr_ntt_ring_gram_block(self._h))
+
+    def ring_gram(self, a, b=None):
+        """g[j][i][l] = sum_c a[j][i][c] * b[j][l][c] in the context's ring (host arrays): a is [batch, ra, width, n], b is
+        [batch, rb, width, n]; returns [batch, ra, rb, n].  b=None: the family with itself, only i <= l, returned packed as
+        [batch, ra (ra + 1) / 2, n] (ring_gram_index).  3-d operands ([ra, width, n]) are a batch of one, and so is the result."""
+        n = self.n
+        a_in = _u64_array(a, "a")
+        if a_in.ndim not in (3, 4) or a_in.shape[-1] != n:
+            raise ValueError("a must be [ra, width, n] or [batch, ra, width, n]")
+        ra, width = a_in.shape[-3], a_in.shape[-2]
+        a4 = np.ascontiguousarray(a_in.reshape(-1, ra, width, n))
+        batch = a4.shape[0]
+        if b is None:
+            out = np.empty((batch, ra * (ra + 1) // 2, n), dtype=np.uint64)
+            _check(self._lib.lsr_ntt_ring_gram_batch(self._h, out.ctypes.data, a4.ctypes.data, None, batch, ra, ra, width), "lsr_ntt_ring_gram_batch")
+            return out[0] if a_in.ndim == 3 else out
+        b_in = a_in if b is a else _u64_array(b, "b")
+        if b_in.ndim != a_in.ndim or b_in.shape[-1] != n or b_in.shape[-2] != width:
+            raise ValueError("b must be [rb, width, n] or [batch, rb, width, n], with the width and the rank of a")
+        rb = b_in.shape[-3]
+        b4 = a4 if b_in is a_in else np.ascontiguousarray(b_in.reshape(-1, rb, width, n))
+        if b4.shape[0] != batch:
+            raise ValueError("a and b must hold the same number of families")
+        out = np.empty((batch, ra, rb, n), dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_gram_batch(self._h, out.ctypes.data, a4.ctypes.data, b4.ctypes.data, batch, ra, rb, width), "lsr_ntt_ring_gram_batch")
+        return out[0] if a_in.ndim == 3 else out
+
+    def ring_gram_device(self, d_g, d_a, d_b, batch, ra, rb, width, stream=0):
+        """Device buffers: a [batch][ra][width][n], b [batch][rb][width][n], g [batch][ra][rb][n]; d_b of 0 or None: the symmetric
+        form, g [batch][ra (ra + 1) / 2][n].  Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ntt_ring_gram_batch_device(self._h, d_g, d_a, d_b or None, batch, ra, rb, width, stream), "lsr_ntt_ring_gram_batch_device")
+
+
+class NttContext(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm, _RingGram):
     """RAII handle over ``NttContext*`` (cpp-core/include/lambda_snark/ntt.h:25-41)."""
 
     def __init__(self, q, n, device=-1):
@@ -1079,7 +1132,7 @@ def prover_max_log2_size():
     return int(_abi.lib().lsr_prover_max_log2_size())
 
 
-class CyclicNtt(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm):
+class CyclicNtt(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm, _RingGram):
     """The transform pair of rust-api/lambda-snark/src/ntt.rs: ``forward(coeffs)`` = ``ntt_forward(coeffs, modulus, omega)``
     (natural order in and out), ``inverse(evals)`` = ``ntt_inverse``.  One handle per (modulus, n, omega).  n above 2^17 (up to 2^22,
     NTT_MODULUS only) goes through ``lsr_cyclic_ntt_context_create_large``."""
