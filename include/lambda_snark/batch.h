@@ -380,8 +380,31 @@ int lsr_ntt_ring_dot_galois_batch_device(const NttContext* ctx, uint64_t* d_c, c
  * count * 256 * 8.  Then (5) the rules that read the context: bound above floor(q/2), len above 2^32 (the positions a stream's block
  * counter reaches), len * bound above 2^63 - 1; index_base + 256 components (matrix: index_base + 256) overflowing 64 bits; the
  * byte size of a buffer overflowing size_t at the context's n; out (then status) overlapping x in address range; no visible
- * device. */
+ * device.
+ *
+ * lsr_ntt_ring_project_adjoint_batch(_device): the adjoint Pi^T w of the projection, as ring vectors — the
+ *   step that turns the 256 constraints on p into ring constraints: with weights w in Z_q^256, the constant coefficient of
+ *   <sigma_{-1}(Pi^T w), s> is <w, p> mod q.  weights [groups][sets][256] canonical words, groups = ceil(count / components): all
+ *   vectors of one key group (the witness vectors of one proof) share their weights.  Vector j < count has the matrix of
+ *   lsr_ntt_ring_project_batch exactly: key keys[4 (j / components) ..], row r the stream (key, domain, index_base +
+ *   256 (j % components) + r), entry pi[r][pos] from the 2-bit field as above; ceil(count / components) key groups are read.
+ *   out [count][sets][width][n] canonical words.  conjugate == 0: out[j][k][pos] = sum_r weights[j / components][k][r] pi_j[r][pos]
+ *   mod q.  conjugate == 1: every ring element of that result is replaced by its image under sigma_g, g = N - 1 (N = 2n on
+ *   negacyclic contexts, N = n on cyclic ones) — word for word what lsr_ntt_ring_automorphism_batch returns for that g.
+ *   status[j]: 1 — done; -1 — a weight word of the vector's group (any set) is >= q: then all sets * width * n outputs of that vector
+ *   are 0; the other vectors are unaffected.  Exact integer arithmetic for every modulus a context admits (plain 64-bit sums below
+ *   q = 2^55, a reduction per step above).  1 <= sets <= LSR_RING_PROJECT_ADJOINT_MAX_SETS.
+ *   The device form is one kernel that writes every output word and the status itself (more than 2^30 workgroups: several
+ *   launches): no init pass, no atomics, nothing allocated, no workspace, no part in the context's ring ordering; plain stream order,
+ *   capturable from the first call.  The plain form stages whole vectors through bounded device chunks, each with its own key and
+ *   weight groups.
+ *   Refusals, in this order: (1) NULL context, out, status, weights or keys; (2) components == 0, then sets == 0 or sets above
+ *   LSR_RING_PROJECT_ADJOINT_MAX_SETS, then conjugate other than 0 or 1.  (3) Then count == 0 or width == 0 is a no-op that returns 0.
+ *   (4) A size that overflows size_t without reading the context: count * sets, that times width, that times 16 bytes.  Then (5) the
+ *   rules that read the context: len above 2^32; index_base + 256 components overflowing 64 bits; the byte size of a buffer
+ *   overflowing size_t at the context's n; out (then status) overlapping weights in address range; no visible device. */
 #define LSR_RING_PROJECT_ROWS 256
+#define LSR_RING_PROJECT_ADJOINT_MAX_SETS 16
 int lsr_ntt_ring_l2sq_batch(const NttContext* ctx, const uint64_t* x, size_t count, size_t width, uint64_t* out) LSR_NOEXCEPT;
 int lsr_ntt_ring_l2sq_batch_device(const NttContext* ctx, const uint64_t* d_x, size_t count, size_t width, uint64_t* d_out,
                                    void* stream) LSR_NOEXCEPT;
@@ -396,6 +419,13 @@ int lsr_ntt_ring_project_matrix_batch(const NttContext* ctx, uint64_t* out, size
 int lsr_ntt_ring_project_matrix_batch_device(const NttContext* ctx, uint64_t* d_out, size_t rows_first, size_t rows, size_t width,
                                              const uint64_t* d_key, uint32_t domain, uint64_t index_base,
                                              void* stream) LSR_NOEXCEPT;
+int lsr_ntt_ring_project_adjoint_batch(const NttContext* ctx, uint64_t* out, int32_t* status, const uint64_t* weights, size_t count,
+                                       size_t sets, size_t width, int conjugate, const uint64_t* keys, size_t components,
+                                       uint32_t domain, uint64_t index_base) LSR_NOEXCEPT;
+int lsr_ntt_ring_project_adjoint_batch_device(const NttContext* ctx, uint64_t* d_out, int32_t* d_status, const uint64_t* d_weights,
+                                              size_t count, size_t sets, size_t width, int conjugate, const uint64_t* d_keys,
+                                              size_t components, uint32_t domain, uint64_t index_base,
+                                              void* stream) LSR_NOEXCEPT;
 
 /* ---------------- NTT: batched ring Gram matrices G = A B^T ---------------- */
 /* Every pairwise ring inner product of the vectors of one family with the vectors of another, or of one family with itself — the

@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_PROJECT_ROWS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -401,6 +401,8 @@ class _RingGalois:
 
 # batch.h LSR_RING_PROJECT_ROWS: the rows of the Johnson-Lindenstrauss projection
 RING_PROJECT_ROWS = 256
+# batch.h LSR_RING_PROJECT_ADJOINT_MAX_SETS: the most weight sets of one ring_project_adjoint call
+RING_PROJECT_ADJOINT_MAX_SETS = 16
 
 
 class _RingNorm:
@@ -471,6 +473,41 @@ class _RingNorm:
         """Device buffers: out [rows][width][n], d_key four words.  Asynchronous on `stream`; enqueues only."""
         _check(self._lib.lsr_ntt_ring_project_matrix_batch_device(self._h, d_out, rows_first, rows, width, d_key, domain, index_base, stream),
                "lsr_ntt_ring_project_matrix_batch_device")
+
+    def ring_project_adjoint(self, weights, width, count, keys, components=None, conjugate=False, domain=17, index_base=0):
+        """(out, status) = the adjoint Pi^T w of ring_project: weights [groups, sets, 256] canonical words (or
+        [sets, 256]: one group), groups = ceil(count / components) -> out uint64 [count, sets, width, n] with out[j][k][pos] =
+        sum_r weights[j // components][k][r] pi_j[r][pos] mod q, pi_j the matrix ring_project uses for vector j; conjugate: every
+        element under sigma_{N-1} (ring_automorphism with g = galois_conjugation).  status int32 [count]: 1, or -1 (out[j] all 0)
+        when a weight of the vector's group is >= q.  components=None spreads the vectors evenly over the keys given."""
+        w = _u64_array(weights, "weights")
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[2] != RING_PROJECT_ROWS:
+            raise ValueError("weights must be [groups, sets, 256] or [sets, 256]")
+        k2 = _ring_keys(keys)
+        count, width = int(count), int(width)
+        if components is None:
+            components = max(1, -(-count // k2.shape[0]))
+        components = int(components)
+        groups = -(-count // components) if components > 0 else 0
+        if k2.shape[0] < groups or w.shape[0] < groups:
+            raise ValueError("keys and weights must hold ceil(count / components) groups")
+        sets = w.shape[1]
+        out = np.empty((count, sets, width, self.n), dtype=np.uint64)
+        status = np.empty(count, dtype=np.int32)
+        _check(self._lib.lsr_ntt_ring_project_adjoint_batch(self._h, out.ctypes.data, status.ctypes.data, w.ctypes.data, count, sets, width,
+                                                            int(bool(conjugate)), k2.ctypes.data, components, domain, index_base),
+               "lsr_ntt_ring_project_adjoint_batch")
+        return out, status
+
+    def ring_project_adjoint_device(self, d_out, d_status, d_weights, count, sets, width, conjugate, d_keys, components, domain=17, index_base=0,
+                                    stream=0):
+        """Device buffers: out [count][sets][width][n], status [count] int32, weights [ceil(count / components)][sets][256], d_keys
+        [ceil(count / components)][4] words.  Asynchronous on `stream`; one kernel, allocates nothing."""
+        _check(self._lib.lsr_ntt_ring_project_adjoint_batch_device(self._h, d_out, d_status, d_weights, count, sets, width, int(conjugate), d_keys,
+                                                                   components, domain, index_base, stream),
+               "lsr_ntt_ring_project_adjoint_batch_device")
 
 
 # the most vectors of one family of a ring Gram matrix (batch.h LSR_RING_GRAM_MAX_VECTORS, DESIGN.md §5j)

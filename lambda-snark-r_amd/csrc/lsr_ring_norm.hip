@@ -1,6 +1,6 @@
 // Norms and projections of ring vectors (batch.h "norms and projections of ring vectors"): the exact l2 norm squared of
 // a vector of ring elements, the Johnson-Lindenstrauss projection p = Pi s whose matrix is expanded from ChaCha20 streams inside the
-// kernel that applies it, and the rows of Pi as ring elements.  Integer code that reads only q and n of the context: one path for every
+// kernel that applies it, the rows of Pi as ring elements, and the adjoint Pi^T w of weight vectors (§5k).  Integer code that reads only q and n of the context: one path for every
 // flavour, every ring degree and both rings.  No workspace and no part in the context's ring ordering: the device forms enqueue
 // kernels in plain stream order and nothing else.
 #include <algorithm>
@@ -15,6 +15,7 @@ namespace lsr {
 static_assert(kProjectRows == LSR_RING_PROJECT_ROWS, "batch.h and the kernels agree on the rows of the projection");
 static_assert(kProjectRows == kNormThreads, "one lane per row");
 static_assert(kProjectSlice % 256 == 0, "a slice is whole stream blocks");
+static_assert(kAdjointMaxSets == LSR_RING_PROJECT_ADJOINT_MAX_SETS, "batch.h and the kernels agree on the weight sets of one call");
 
 struct ProjectCall {
     uint64_t len;             // width n
@@ -111,6 +112,71 @@ static void host_project_matrix(const NttContext& c, uint64_t* out, uint64_t row
         const uint64_t now = std::min(chunk, rows - r0);
         project_matrix_device(c, d_out.ptr, rows_first + r0, now, len, d_key.ptr, domain, index_base, s);
         LSR_HIP(hipMemcpyAsync(out + r0 * len, d_out.ptr, now * len * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+struct ProjectAdjointCall {
+    uint64_t len;             // width n
+    uint64_t sets;
+    uint64_t components;
+    uint32_t conjugate;       // 0 or 1, as the entry point takes it
+    uint32_t domain;
+    uint64_t index_base;
+};
+
+// vectors [first, first + count) of a call (vector `first` at d_out and d_status); d_keys and d_weights hold the groups from
+// group_base on.  One kernel, in plain stream order.
+static void project_adjoint_device(const NttContext& c, uint64_t* d_out, int32_t* d_status, const uint64_t* d_weights, uint64_t first, uint64_t count,
+                                   const ProjectAdjointCall& call, const uint64_t* d_keys, uint64_t group_base, hipStream_t s) {
+    ProjectAdjointJob job{};
+    job.weights = d_weights;
+    job.keys = d_keys;
+    job.index_base = call.index_base;
+    job.components = call.components;
+    job.group_base = group_base;
+    job.len = call.len;
+    job.n = c.degree;
+    job.q = c.modulus;
+    job.blocks = static_cast<uint32_t>((call.len + 255) >> 8);      // len <= 2^32: at most 2^24
+    job.sets = static_cast<uint32_t>(call.sets);
+    job.domain = call.domain;
+    job.conjugate = call.conjugate ? (c.cyclic ? 1u : 2u) : 0u;
+    const bool wide = c.modulus >> 55 != 0;                          // 256 words below 2^55 sum to less than 2^63
+    // one launch covers at most 2^30 workgroups
+    const uint64_t step = std::max<uint64_t>(1, (1ull << 30) / job.blocks);
+    for (uint64_t j0 = 0; j0 < count; j0 += step) {
+        const uint64_t now = std::min(step, count - j0);
+        job.out = d_out + j0 * call.sets * call.len;
+        job.status = d_status + j0;
+        job.first = first + j0;
+        const dim3 grid(static_cast<unsigned>(now * job.blocks));
+        if (wide) hipLaunchKernelGGL(ring_project_adjoint_kernel<true>, grid, dim3(kNormThreads), 0, s, job);
+        else hipLaunchKernelGGL(ring_project_adjoint_kernel<false>, grid, dim3(kNormThreads), 0, s, job);
+        LSR_HIP(hipGetLastError());
+    }
+}
+
+// host buffers through bounded device chunks of whole vectors on the context's work stream; each chunk brings its own key groups and
+// weight groups
+static void host_project_adjoint(const NttContext& c, uint64_t* out, int32_t* status, const uint64_t* weights, uint64_t count,
+                                 const ProjectAdjointCall& call, const uint64_t* keys) {
+    DeviceGuard guard(c.device);
+    const uint64_t per_vector = call.sets * call.len, per_group = call.sets * kProjectRows;
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, (kStagingBytes / 8) / per_vector));
+    const uint64_t chunk_groups = chunk / call.components + 2;
+    DeviceBuffer<uint64_t> d_out(chunk * per_vector), d_weights(chunk_groups * per_group), d_keys(chunk_groups * 4);
+    DeviceBuffer<int32_t> d_status(chunk);
+    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
+    hipStream_t s = work_stream(c);
+    for (uint64_t j0 = 0; j0 < count; j0 += chunk) {
+        const uint64_t now = std::min(chunk, count - j0);
+        const uint64_t g0 = j0 / call.components, g1 = (j0 + now - 1) / call.components;
+        LSR_HIP(hipMemcpyAsync(d_keys.ptr, keys + 4 * g0, (g1 - g0 + 1) * 32, hipMemcpyHostToDevice, s));
+        LSR_HIP(hipMemcpyAsync(d_weights.ptr, weights + g0 * per_group, (g1 - g0 + 1) * per_group * 8, hipMemcpyHostToDevice, s));
+        project_adjoint_device(c, d_out.ptr, d_status.ptr, d_weights.ptr, j0, now, call, d_keys.ptr, g0, s);
+        LSR_HIP(hipMemcpyAsync(out + j0 * per_vector, d_out.ptr, now * per_vector * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(status + j0, d_status.ptr, now * 4, hipMemcpyDeviceToHost, s));
         LSR_HIP(hipStreamSynchronize(s));
     }
 }
@@ -220,9 +286,61 @@ int project_matrix_call(const char* where, const NttContext* ctx, uint64_t* out,
     });
 }
 
+int project_adjoint_call(const char* where, const NttContext* ctx, uint64_t* out, int32_t* status, const uint64_t* weights, size_t count, size_t sets,
+                         size_t width, int conjugate, const uint64_t* keys, size_t components, uint32_t domain, uint64_t index_base, bool device,
+                         void* stream) noexcept {
+    if (!ctx || !out || !status || !weights || !keys) return lsr::abi_refuse(where, "NULL context, buffer, weights, keys or status");
+    if (components == 0) return lsr::abi_refuse(where, "components must be at least 1");
+    if (sets == 0 || sets > LSR_RING_PROJECT_ADJOINT_MAX_SETS)
+        return lsr::abi_refuse(where, "sets = " + std::to_string(sets) + " is not in 1 .. " + std::to_string(LSR_RING_PROJECT_ADJOINT_MAX_SETS));
+    if (conjugate != 0 && conjugate != 1) return lsr::abi_refuse(where, "conjugate = " + std::to_string(conjugate) + " is neither 0 nor 1");
+    if (count == 0 || width == 0) return 0;
+    size_t outputs = 0;       // count * sets vectors of `width` elements
+    if (__builtin_mul_overflow(count, sets, &outputs) || sizes_overflow(outputs, width, 0)) return lsr::abi_refuse(where, kOverflow);
+    return lsr::abi_guarded(where, [&] {
+        size_t len = 0;
+        if (__builtin_mul_overflow(width, (size_t)ctx->degree, &len)) throw std::runtime_error("width * n overflows size_t");
+        require_projectable(len);
+        uint64_t span = 0;
+        if (__builtin_mul_overflow((uint64_t)components, (uint64_t)LSR_RING_PROJECT_ROWS, &span) || index_base + span < index_base)
+            throw std::runtime_error("index_base + 256 * components overflows 64 bits");
+        vector_length(*ctx, outputs, width);
+        const size_t groups = (count - 1) / components + 1;
+        size_t weight_bytes = 0;
+        if (__builtin_mul_overflow(groups, sets * LSR_RING_PROJECT_ROWS * 8, &weight_bytes))
+            throw std::runtime_error("the size of the weights overflows size_t");
+        const char* const apart = "the outputs must not share memory with the weights";
+        lsr::require_apart(out, outputs * len * 8, weights, weight_bytes, (std::string("out overlaps weights: ") + apart).c_str());
+        lsr::require_apart(status, count * 4, weights, weight_bytes, (std::string("status overlaps weights: ") + apart).c_str());
+        lsr::require_device();
+        // min(components, count): the same streams and groups, and the kernel's 32-bit division applies more often
+        const lsr::ProjectAdjointCall call{len, sets, std::min<uint64_t>(components, count), (uint32_t)conjugate, domain, index_base};
+        if (device) {
+            lsr::DeviceGuard guard(ctx->device);
+            lsr::project_adjoint_device(*ctx, out, status, weights, 0, count, call, keys, 0, static_cast<hipStream_t>(stream));
+        } else {
+            lsr::host_project_adjoint(*ctx, out, status, weights, count, call, keys);
+        }
+    });
+}
+
 }  // namespace
 
 extern "C" {
+
+int lsr_ntt_ring_project_adjoint_batch(const NttContext* ctx, uint64_t* out, int32_t* status, const uint64_t* weights, size_t count, size_t sets,
+                                       size_t width, int conjugate, const uint64_t* keys, size_t components, uint32_t domain,
+                                       uint64_t index_base) noexcept {
+    return project_adjoint_call("lsr_ntt_ring_project_adjoint_batch", ctx, out, status, weights, count, sets, width, conjugate, keys, components, domain,
+                                index_base, false, nullptr);
+}
+int lsr_ntt_ring_project_adjoint_batch_device(const NttContext* ctx, uint64_t* d_out, int32_t* d_status, const uint64_t* d_weights, size_t count,
+                                              size_t sets, size_t width, int conjugate, const uint64_t* d_keys, size_t components, uint32_t domain,
+                                              uint64_t index_base, void* stream) noexcept {
+    return project_adjoint_call("lsr_ntt_ring_project_adjoint_batch_device", ctx, d_out, d_status, d_weights, count, sets, width, conjugate, d_keys,
+                                components, domain, index_base, true, stream);
+}
+
 
 int lsr_ntt_ring_l2sq_batch(const NttContext* ctx, const uint64_t* x, size_t count, size_t width, uint64_t* out) noexcept {
     return l2sq_call("lsr_ntt_ring_l2sq_batch", ctx, x, count, width, out, false, nullptr);

@@ -13,6 +13,8 @@
 //   L2SQ: one workgroup per vector, a 128-bit sum per lane with a sticky overflow bit (the terms are non-negative, so a partial sum
 //     that overflows means the total does: the saturation does not depend on the order), wave reduction, the waves through LDS.
 //   MATRIX: a workgroup generates 256 blocks of one row into LDS (one block per lane) and writes the 65536 entries coalesced.
+//   ADJOINT (§5k): out = Pi^T w.  A workgroup generates one block of all 256 rows into LDS (one row per lane); then a lane owns one
+//     position and walks the rows with the weights broadcast from LDS.  One launch that writes every output word and the status.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -195,6 +197,146 @@ __global__ void __launch_bounds__(kNormThreads) ring_project_matrix_kernel(Proje
     for (uint32_t i = l; i < now; i += kNormThreads) {
         const uint32_t f = (uint32_t)(words[i >> 5] >> (2 * (i & 31u))) & 3u;
         dst[i] = f == 1 ? 1 : (f == 2 ? job.q - 1 : 0);
+    }
+}
+
+// ---- the adjoint Pi^T w --------------------------------------------------------------------------------------------------
+// The dual of PROJECT: there a lane owns a row and the coefficient is broadcast, here a lane owns a position and the weight is.
+
+#ifndef LSR_ADJOINT_SET_BLOCK
+#define LSR_ADJOINT_SET_BLOCK 4                   // weight sets accumulated per pass over the rows (1, 2 or 4; timed in §5k)
+#endif
+constexpr int kAdjointSetBlock = LSR_ADJOINT_SET_BLOCK;
+constexpr int kAdjointMaxSets = 16;               // LSR_RING_PROJECT_ADJOINT_MAX_SETS
+constexpr int kAdjointRowPitch = kProjectRows + 8;      // dwords between half-word h and h + 1 of the rows: four consecutive h, four banks
+static_assert(kAdjointSetBlock == 1 || kAdjointSetBlock == 2 || kAdjointSetBlock == 4, "the set block is 1, 2 or 4");
+
+struct ProjectAdjointJob {
+    uint64_t* out;            // [count][sets][len], vector `first` of the call at out
+    int32_t* status;          // [count]
+    const uint64_t* weights;  // [groups][sets][256], the group of vector j at weights + (j / components - group_base) sets 256
+    const uint64_t* keys;     // [groups][4], as ProjectJob
+    uint64_t index_base;
+    uint64_t components;
+    uint64_t group_base;
+    uint64_t first;           // vectors [first, first + gridDim.x / blocks) of the call
+    uint64_t len;             // width n, at most 2^32
+    uint64_t n;               // a power of two
+    uint64_t q;
+    uint32_t blocks;          // ceil(len / 256): workgroups per vector
+    uint32_t sets;
+    uint32_t domain;
+    uint32_t conjugate;       // 0: as computed; 1: X -> X^(n-1) of X^n - 1; 2: X -> X^(2n-1) of X^n + 1
+};
+
+// LIVE sets over the 256 rows for the position whose 2-bit field sits at bit `shift` of the half-words halves[r] (consecutive rows,
+// consecutive dwords: a wavefront reads four addresses in four banks).  wt: [kAdjointSetBlock][256] weights (the same address in every
+// lane: a broadcast), WIDE: followed by their negatives mod q.  Not WIDE (q < 2^55): two plain sums of at most 256 words below 2^55
+// and one reduction of their difference.  WIDE: one sum mod q, a conditional subtraction per step that also covers the carry out of
+// bit 63 (q up to 2^64).
+template <int LIVE, bool WIDE>
+__device__ __forceinline__ void adjoint_rows(const uint32_t* halves, uint32_t shift, const uint64_t* wt, uint64_t q, uint64_t (&res)[kAdjointSetBlock]) {
+    if constexpr (WIDE) {
+        uint64_t acc[LIVE];
+#pragma unroll
+        for (int k = 0; k < LIVE; ++k) acc[k] = 0;
+#pragma unroll 4
+        for (int r = 0; r < kProjectRows; ++r) {
+            const uint32_t f =(halves[r] >> shift) & 3u;
+            const uint64_t take = 0ull - (uint64_t)(f == 1u), drop = 0ull - (uint64_t)(f == 2u);
+#pragma unroll
+            for (int k = 0; k < LIVE; ++k) {
+                const uint64_t v = (wt[k * kProjectRows + r] & take) | (wt[(kAdjointSetBlock + k) * kProjectRows + r] & drop);
+                const uint64_t t = acc[k] + v;                       // acc, v < q: the true sum is below 2 q
+                acc[k] = (t < v || t >= q) ? t - q : t;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < LIVE; ++k) res[k] = acc[k];
+    } else {
+        uint64_t plus[LIVE], minus[LIVE];
+#pragma unroll
+        for (int k = 0; k < LIVE; ++k) plus[k] = minus[k] = 0;
+#pragma unroll 8
+        for (int r = 0; r < kProjectRows; ++r) {
+            // the field's two bits moved to bit 31 and spread by an arithmetic shift: one 32-bit mask serves both halves of a word
+            const uint32_t h = halves[r];
+            const uint64_t take = (uint64_t)(int64_t)((int32_t)(h << (31u - shift)) >> 31);                 // f & 1: +w
+            const uint64_t drop = (uint64_t)(int64_t)((int32_t)(h << (30u - shift)) >> 31);                 // f >> 1: -w; f = 3: both, 0
+#pragma unroll
+            for (int k = 0; k < LIVE; ++k) {
+                const uint64_t w = wt[k * kProjectRows + r];
+                plus[k] += w & take;
+                minus[k] += w & drop;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < LIVE; ++k) {
+            const int64_t d = (int64_t)(plus[k] - minus[k]);         // both below 2^63: the difference is exact
+            const uint64_t m = (uint64_t)(d < 0 ? -d : d) % q;
+            res[k] = (d < 0 && m != 0) ? q - m : m;
+        }
+    }
+}
+
+// workgroup (vector, block): positions [256 block, 256 block + 256) of one vector for every set.  Lane r generates block `block` of
+// row r once; then lane p owns position 256 block + p.  The kernel writes every output word and the status itself.
+template <bool WIDE>
+__global__ void __launch_bounds__(kNormThreads) ring_project_adjoint_kernel(ProjectAdjointJob job) {
+    __shared__ uint32_t halves[16 * kAdjointRowPitch];                                 // half-word h of row r at h pitch + r
+    __shared__ uint64_t wt[(WIDE ? 2 : 1) * kAdjointSetBlock * kProjectRows];
+    const uint32_t t = threadIdx.x;
+    const uint32_t local = blockIdx.x / job.blocks, block = blockIdx.x - local * job.blocks;
+    const uint64_t q = job.q;
+    const RingStream st = ring_stream_of(job.keys, job.first + local, job.components, job.group_base, 0);      // index: j % components
+    const uint64_t* __restrict__ wg = job.weights + (uint64_t)((st.key - job.keys) >> 2) * job.sets * kProjectRows;
+    {
+        uint64_t w[8];
+        stream_block(st.key, job.domain, job.index_base + (uint64_t)kProjectRows * st.index + t, block, w);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            halves[(2 * i) * kAdjointRowPitch + t] = (uint32_t)w[i];
+            halves[(2 * i + 1) * kAdjointRowPitch + t] = (uint32_t)(w[i] >> 32);
+        }
+    }
+    bool not_below_q = false;
+    for (uint32_t k = 0; k < job.sets; ++k) not_below_q |= wg[k * kProjectRows + t] >= q;
+    not_below_q = __syncthreads_or(not_below_q);      // (the barrier also publishes `halves`)
+    if (block == 0 && t == 0) job.status[local] = not_below_q ? -1 : 1;
+
+    // position and destination of this lane: element base + i -> base + (n - i) mod n under the conjugation, negated in X^n + 1
+    const uint64_t pos = (uint64_t)block * 256 + t;
+    const bool live = pos < job.len;
+    const uint64_t i = pos & (job.n - 1);
+    const uint64_t dest = job.conjugate ? pos - i + ((job.n - i) & (job.n - 1)) : pos;
+    const bool negate = job.conjugate == 2 && i != 0;
+    uint64_t* __restrict__ o = job.out + (uint64_t)local * job.sets * job.len + dest;
+    if (not_below_q) {                                // the same in every lane of the workgroup
+        if (live)
+            for (uint32_t k = 0; k < job.sets; ++k) o[k * job.len] = 0;
+        return;
+    }
+    const uint32_t* mine = halves + (t >> 4) * kAdjointRowPitch;
+    const uint32_t shift = 2 * (t & 15u);
+    for (uint32_t k0 = 0; k0 < job.sets; k0 += kAdjointSetBlock) {
+        const uint32_t now = min((uint32_t)kAdjointSetBlock, job.sets - k0);
+        if (k0) __syncthreads();                      // the previous block of sets has been read
+        for (uint32_t k = 0; k < now; ++k) {
+            const uint64_t w = wg[(k0 + k) * kProjectRows + t];
+            wt[k * kProjectRows + t] = w;
+            if constexpr (WIDE) wt[(kAdjointSetBlock + k) * kProjectRows + t] = w ? q - w : 0;
+        }
+        __syncthreads();
+        uint64_t res[kAdjointSetBlock];
+        switch (now) {                                // the same in every lane
+            case 1: adjoint_rows<1, WIDE>(mine, shift, wt, q, res); break;
+            case 2: if constexpr (kAdjointSetBlock >= 2) adjoint_rows<2, WIDE>(mine, shift, wt, q, res); break;
+            case 3: if constexpr (kAdjointSetBlock >= 4) adjoint_rows<3, WIDE>(mine, shift, wt, q, res); break;
+            default: if constexpr (kAdjointSetBlock >= 4) adjoint_rows<4, WIDE>(mine, shift, wt, q, res); break;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < (uint32_t)kAdjointSetBlock; ++k)      // (unrolled: res stays in registers)
+            if (live && k < now) o[(uint64_t)(k0 + k) * job.len] = (negate && res[k] != 0) ? q - res[k] : res[k];
     }
 }
 
