@@ -427,6 +427,55 @@ int lsr_ntt_ring_project_adjoint_batch_device(const NttContext* ctx, uint64_t* d
                                               size_t components, uint32_t domain, uint64_t index_base,
                                               void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: scalar-weighted aggregation of ring vectors ---------------- */
+/* lsr_ntt_ring_scalar_combine_batch(_device): sums of ring vectors weighted by SCALARS of Z_q, plus an addend —
+ * the step of a LaBRADOR / Greyhound-style argument that collapses the L constraint families with constant-term conditions by
+ * scalars psi^(k) in Z_q^L and adds the back-projection: phi''^(k)_i = sum_l psi^(k)_l phi'^(l)_i + (Pi^T w^(k))_i.  A scalar acts
+ * coefficient-wise, so no transform runs: out[sets x len] = weights[sets x terms] v[terms x len] mod q per vector, v read once for
+ * all sets.  A vector is `width` ring elements, [width][n] canonical words, pos = c n + k and len = width n, as above.
+ *   v: [vectors][width][n] with vectors = (count - 1) term_stride + terms.  term_stride as lsr_ntt_ring_fold_batch: 0 — every output
+ *     sums the same `terms` vectors; terms — disjoint groups; any other value is allowed.
+ *   weights: [groups][sets][terms] canonical words, groups = ceil(count / components): the vectors of one group (one proof) share
+ *     their weights, the convention of lsr_ntt_ring_project_adjoint_batch.
+ *   addend: NULL, or [count][sets][width][n].
+ *   out: [count][sets][width][n] canonical words,
+ *     out[j][k][pos] = (addend ? addend[j][k][pos] : 0) + sum_{i < terms} weights[j / components][k][i] v[j term_stride + i][pos] mod q.
+ *   addend may be EXACTLY out (the in-place form: what follows lsr_ntt_ring_project_adjoint_batch with conjugate = 1, whose output
+ *     layout this is); any other overlap is refused.
+ *   status[j]: 1 — done; -1 — a weight word of the vector's group (any set) is >= q: then all sets * len outputs of that vector are
+ *     0, in place included, and the other vectors are unaffected (the adjoint's rule).
+ *   Words of v and addend are canonical by contract, as in lsr_ntt_ring_fold_batch: a word >= q gives an unspecified result and never
+ *   faults.  The result is the exact integer residue, so it does not depend on the arithmetic flavour.  Served on every context the
+ *   library creates — negacyclic FP64 and 64-bit flavours, the 60-bit prime, Goldilocks cyclic contexts, those above n = 131072
+ *   included: the call reads only q, the flavour's reduction constants and n, and no twiddle table.
+ * Limits: 1 <= sets <= LSR_RING_SCALAR_COMBINE_MAX_SETS, 1 <= terms <= LSR_RING_DOT_MAX_TERMS, len <= 2^32.
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL ctx, out, status, v or
+ * weights; (2) components == 0, then sets == 0 or above LSR_RING_SCALAR_COMBINE_MAX_SETS, then terms == 0 or above
+ * LSR_RING_DOT_MAX_TERMS.  (3) Then count == 0 or width == 0 is a no-op that returns 0.  (4) A size that overflows size_t without
+ * reading the context: vectors, vectors * width, count * sets, count * sets * width, groups * sets * terms, or one of these times 16
+ * bytes.  Then (5) the rules that read the context: len above 2^32; the byte size of a buffer overflowing size_t at the context's n;
+ * out overlapping v, then weights, then status, then an addend that is neither NULL nor equal to out; no visible device.
+ *
+ * The device form is one kernel that writes every output word and the status itself (more than 2^30 workgroups: several launches):
+ * no init pass, no atomics, no workspace, nothing allocated, no part in the context's ring ordering; plain stream order, capturable
+ * from the first call.  A workgroup owns LSR_RING_SCALAR_COMBINE_TILE positions of one vector, two per lane with 16-byte accesses,
+ * when v, out and addend are 16-byte aligned (half as many, one per lane, when one of them is not) and stages the weights
+ * LSR_RING_SCALAR_COMBINE_STAGE terms at a time; FP64-flavour contexts re-centre the running sums every
+ * LSR_RING_DOT_F64_RECENTRE_PERIOD products.
+ * The plain form takes host buffers and returns when out and status are complete: whole outputs go through bounded device chunks,
+ * each with its weight groups (term_stride == 0: v goes up once); an output whose terms exceed the bound takes them in groups, the
+ * in-place addend carrying the running sum from one group to the next. */
+#define LSR_RING_SCALAR_COMBINE_MAX_SETS 16
+#define LSR_RING_SCALAR_COMBINE_TILE 512
+#define LSR_RING_SCALAR_COMBINE_STAGE 128
+int lsr_ntt_ring_scalar_combine_batch(const NttContext* ctx, uint64_t* out, int32_t* status, const uint64_t* v, const uint64_t* weights,
+                                      const uint64_t* addend, size_t count, size_t sets, size_t terms, size_t term_stride, size_t width,
+                                      size_t components) LSR_NOEXCEPT;
+int lsr_ntt_ring_scalar_combine_batch_device(const NttContext* ctx, uint64_t* d_out, int32_t* d_status, const uint64_t* d_v,
+                                             const uint64_t* d_weights, const uint64_t* d_addend, size_t count, size_t sets,
+                                             size_t terms, size_t term_stride, size_t width, size_t components,
+                                             void* stream) LSR_NOEXCEPT;
+
 /* ---------------- NTT: batched ring Gram matrices G = A B^T ---------------- */
 /* Every pairwise ring inner product of the vectors of one family with the vectors of another, or of one family with itself — the
  * "garbage" polynomials g_il = <s_i, s_l> and h_il = <phi_i, s_l> + <phi_l, s_i> of a LaBRADOR / Greyhound style argument (DESIGN.md

@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -510,6 +510,59 @@ class _RingNorm:
                "lsr_ntt_ring_project_adjoint_batch_device")
 
 
+# batch.h LSR_RING_SCALAR_COMBINE_MAX_SETS: the most weight sets of one ring_scalar_combine call
+RING_SCALAR_COMBINE_MAX_SETS = 16
+
+
+class _RingScalar:
+    """Scalar-weighted aggregation of ring vectors with an addend on a context (``NttContext`` and ``CyclicNtt``; batch.h
+    "scalar-weighted aggregation of ring vectors").  A vector is [width, n] canonical words."""
+
+    def ring_scalar_combine(self, v, weights, count, term_stride=0, components=None, addend=None):
+        """(out, status): out uint64 [count, sets, width, n] with out[j][k] = addend[j][k] + sum_i weights[j // components][k][i] *
+        v[j term_stride + i] mod q, the weights SCALARS of Z_q.  v is [vectors, width, n] with vectors >= (count - 1) term_stride +
+        terms; weights [groups, sets, terms] canonical words (or [sets, terms]: one group), groups = ceil(count / components);
+        addend None or [count, sets, width, n].  status int32 [count]: 1, or -1 (out[j] all 0) when a weight of the vector's group
+        is >= q.  components=None spreads the vectors evenly over the weight groups given."""
+        n = self.n
+        v_in, w = _u64_array(v, "v"), _u64_array(weights, "weights")
+        if v_in.ndim != 3 or v_in.shape[-1] != n:
+            raise ValueError("v must be [vectors, width, n]")
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3:
+            raise ValueError("weights must be [groups, sets, terms] or [sets, terms]")
+        v3, w3 = np.ascontiguousarray(v_in), np.ascontiguousarray(w)
+        count, term_stride, width = int(count), int(term_stride), v3.shape[1]
+        sets, terms = w3.shape[1], w3.shape[2]
+        if components is None:
+            components = max(1, -(-count // max(1, w3.shape[0])))
+        components = int(components)
+        if components > 0 and w3.shape[0] < -(-count // components):
+            raise ValueError("weights must hold ceil(count / components) groups")
+        if count < 0 or term_stride < 0 or (count and v3.shape[0] < (count - 1) * term_stride + terms):
+            raise ValueError("v must hold (count - 1) * term_stride + terms vectors")
+        a4 = None
+        if addend is not None:
+            a4 = np.ascontiguousarray(_u64_array(addend, "addend"))
+            if a4.shape != (count, sets, width, n):
+                raise ValueError("addend must be [count, sets, width, n]")
+        out = np.empty((count, sets, width, n), dtype=np.uint64)
+        status = np.empty(count, dtype=np.int32)
+        _check(self._lib.lsr_ntt_ring_scalar_combine_batch(self._h, out.ctypes.data, status.ctypes.data, v3.ctypes.data, w3.ctypes.data,
+                                                           None if a4 is None else a4.ctypes.data, count, sets, terms, term_stride, width, components),
+               "lsr_ntt_ring_scalar_combine_batch")
+        return out, status
+
+    def ring_scalar_combine_device(self, d_out, d_status, d_v, d_weights, d_addend, count, sets, terms, term_stride, width, components, stream=0):
+        """Device buffers: out [count][sets][width][n], status [count] int32, v [(count - 1) term_stride + terms][width][n], weights
+        [ceil(count / components)][sets][terms]; d_addend 0 or None, a buffer laid out as out, or d_out itself (in place).
+        Asynchronous on `stream`; one kernel, allocates nothing."""
+        _check(self._lib.lsr_ntt_ring_scalar_combine_batch_device(self._h, d_out, d_status, d_v, d_weights, d_addend or None, count, sets, terms,
+                                                                  term_stride, width, components, stream),
+               "lsr_ntt_ring_scalar_combine_batch_device")
+
+
 # the most vectors of one family of a ring Gram matrix (batch.h LSR_RING_GRAM_MAX_VECTORS, DESIGN.md §5j)
 RING_GRAM_MAX_VECTORS = 64
 
@@ -563,7 +616,7 @@ class _RingGram:
         _check(self._lib.lsr_ntt_ring_gram_batch_device(self._h, d_g, d_a, d_b or None, batch, ra, rb, width, stream), "lsr_ntt_ring_gram_batch_device")
 
 
-class NttContext(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm, _RingGram):
+class NttContext(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm, _RingScalar, _RingGram):
     """RAII handle over ``NttContext*`` (cpp-core/include/lambda_snark/ntt.h:25-41)."""
 
     def __init__(self, q, n, device=-1):
@@ -1169,7 +1222,7 @@ def prover_max_log2_size():
     return int(_abi.lib().lsr_prover_max_log2_size())
 
 
-class CyclicNtt(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm, _RingGram):
+class CyclicNtt(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm, _RingScalar, _RingGram):
     """The transform pair of rust-api/lambda-snark/src/ntt.rs: ``forward(coeffs)`` = ``ntt_forward(coeffs, modulus, omega)``
     (natural order in and out), ``inverse(evals)`` = ``ntt_inverse``.  One handle per (modulus, n, omega).  n above 2^17 (up to 2^22,
     NTT_MODULUS only) goes through ``lsr_cyclic_ntt_context_create_large``."""

@@ -139,6 +139,8 @@ SIGNATURES = {
     "lsr_ntt_ring_project_matrix_batch_device": (c_int, [vp, vp, c_size, c_size, c_size, vp, u32, u64, vp]),
     "lsr_ntt_ring_project_adjoint_batch": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, c_int, vp, c_size, u32, u64]),
     "lsr_ntt_ring_project_adjoint_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, c_int, vp, c_size, u32, u64, vp]),
+    "lsr_ntt_ring_scalar_combine_batch": (c_int, [vp, vp, vp, vp, vp, vp, c_size, c_size, c_size, c_size, c_size, c_size]),
+    "lsr_ntt_ring_scalar_combine_batch_device": (c_int, [vp, vp, vp, vp, vp, vp, c_size, c_size, c_size, c_size, c_size, c_size, vp]),
     "lsr_ntt_ring_gram_batch": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, c_size]),
     "lsr_ntt_ring_gram_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, c_size, vp]),
     "lsr_ntt_ring_gram_block": (c_size, [vp]),
