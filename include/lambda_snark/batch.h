@@ -517,6 +517,47 @@ int lsr_ntt_ring_gram_batch_device(const NttContext* ctx, uint64_t* d_g, const u
                                    size_t rb, size_t width, void* stream) LSR_NOEXCEPT;
 size_t lsr_ntt_ring_gram_block(const NttContext* ctx) LSR_NOEXCEPT;
 
+/* ---------------- NTT: the symmetrised packed Gram matrix and ring quadratic forms ---------------- */
+/* The two pieces that close a LaBRADOR / Greyhound style verifier's equations <z, z> = sum g_il c_i c_l and sum_i <phi_i, z> c_i =
+ * sum h_il c_i c_l on the device.  Ring, word and order conventions: the Gram call's above.
+ *
+ * lsr_ntt_ring_gram_sym2_batch(_device): a and b are [batch][r][width][n], both non-NULL (b may be the pointer a); h is
+ * [batch][r (r + 1) / 2][n] in the packed order of the symmetric Gram form, with
+ *   h[j][(i, l)] = <a_i, b_l> + <a_l, b_i> for i < l,   h[j][(i, i)] = <a_i, b_i> (once).
+ * Every off-diagonal word equals (lsr_ntt_ring_dot_batch(a_i, b_l) + lsr_ntt_ring_dot_batch(a_l, b_i)) mod q and every diagonal word
+ * lsr_ntt_ring_dot_batch(a_i, b_i), in every flavour.  Plan, limits, workspace, ordering and capture contract: lsr_ntt_ring_gram_batch's
+ * cross form with ra = rb = r (one third mode of its kernel: a block pair adds both products into one accumulator).  Refusals: those of
+ * lsr_ntt_ring_gram_batch in its order with ra = rb = r, (1) including a NULL b.
+ *
+ * lsr_ntt_ring_quadform_batch(_device): g is [batch][r (r + 1) / 2][n] in the same packed order, c is [c_rows][r][n] with c_rows ==
+ * batch (challenges per family) or c_rows == 1 (one set for every family), out is [batch][n]:
+ *   out[j] = sum_i g[j][(i, i)] c_i c_i + offdiag * sum_{i < l} g[j][(i, l)] c_i c_l.
+ * offdiag is a scalar word below q: 2 for a g that stores each off-diagonal entry once (the symmetric Gram form), 1 for an h that
+ * already holds both cross terms (the sym2 form); any other canonical word is allowed.  Every output word equals the composed route
+ * (lsr_ntt_ring_mul_batch per pair, a scaling by offdiag mod q, lsr_ntt_ring_dot_batch with terms = r (r + 1) / 2) in every flavour
+ * and at every n from 2 to 131072: all arithmetic is exact.  r + r (r + 1) / 2 forward transforms (a shared c: once per call) and one
+ * inverse per family; between them a pointwise kernel evaluates the form row by row of the triangle, the rows split into slices
+ * balanced by pairs whose partial sums are added in a fixed order (no atomics).
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL ctx, out, g or c; (2) r
+ * == 0; (3) c_rows neither 1 nor batch; (4) r above LSR_RING_GRAM_MAX_VECTORS; (5) a size that overflows size_t: batch r (r + 1) / 2,
+ * c_rows r, or one of them times 16 bytes — all of these without reading the context.  Then batch == 0 is a no-op that returns 0.
+ * Then (6) a context above n = 131072; (7) offdiag >= q; (8) one family's g above LSR_RING_GRAM_MAX_FAMILY_BYTES; (9) r + 2
+ * polynomials (the transformed c of one family, one of g, one partial sum) not fitting the workspace — the message names
+ * LAMBDA_SNARK_NTT_CHUNK_MIB, which sizes it; (10) out overlapping g, then c, in address range; (11) no visible device.
+ * The host form stages whole families through bounded device chunks (a shared c goes up once) and returns when out is complete; the
+ * _device form takes device buffers on the context's device and only enqueues on `stream`.  g and c are never written.
+ * Workspace, ordering and graph capture: the contract of lsr_ntt_ring_dot_batch above, and its workspace — no other.  A family
+ * whose transforms do not fit it is taken in groups of consecutive packed pairs with the transformed c resident, the running sum
+ * waiting in out as canonical evaluation-domain words between groups. */
+int lsr_ntt_ring_gram_sym2_batch(const NttContext* ctx, uint64_t* h, const uint64_t* a, const uint64_t* b, size_t batch, size_t r,
+                                 size_t width) LSR_NOEXCEPT;
+int lsr_ntt_ring_gram_sym2_batch_device(const NttContext* ctx, uint64_t* d_h, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t r,
+                                        size_t width, void* stream) LSR_NOEXCEPT;
+int lsr_ntt_ring_quadform_batch(const NttContext* ctx, uint64_t* out, const uint64_t* g, const uint64_t* c, size_t batch, size_t r,
+                                size_t c_rows, uint64_t offdiag) LSR_NOEXCEPT;
+int lsr_ntt_ring_quadform_batch_device(const NttContext* ctx, uint64_t* d_out, const uint64_t* d_g, const uint64_t* d_c, size_t batch,
+                                       size_t r, size_t c_rows, uint64_t offdiag, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

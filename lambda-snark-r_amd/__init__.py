@@ -615,6 +615,60 @@ class _RingGram:
         form, g [batch][ra (ra + 1) / 2][n].  Asynchronous on `stream`; enqueues only."""
         _check(self._lib.lsr_ntt_ring_gram_batch_device(self._h, d_g, d_a, d_b or None, batch, ra, rb, width, stream), "lsr_ntt_ring_gram_batch_device")
 
+    def ring_gram_sym2(self, a, b):
+        """The symmetrised packed Gram matrix of two families (host arrays): a and b are [batch, r, width, n] (b may be
+        a itself); returns h [batch, r (r + 1) / 2, n] (ring_gram_index) with h[j][(i, l)] = <a_i, b_l> + <a_l, b_i> for i < l and
+        h[j][(i, i)] = <a_i, b_i>.  3-d operands ([r, width, n]) are a batch of one, and so is the result."""
+        n = self.n
+        a_in = _u64_array(a, "a")
+        b_in = a_in if b is a else _u64_array(b, "b")
+        if a_in.ndim not in (3, 4) or a_in.shape[-1] != n:
+            raise ValueError("a must be [r, width, n] or [batch, r, width, n]")
+        if b_in.shape != a_in.shape:
+            raise ValueError("b must have the shape of a")
+        r, width = a_in.shape[-3], a_in.shape[-2]
+        a4 = np.ascontiguousarray(a_in.reshape(-1, r, width, n))
+        b4 = a4 if b_in is a_in else np.ascontiguousarray(b_in.reshape(-1, r, width, n))
+        batch = a4.shape[0]
+        out = np.empty((batch, r * (r + 1) // 2, n), dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_gram_sym2_batch(self._h, out.ctypes.data, a4.ctypes.data, b4.ctypes.data, batch, r, width), "lsr_ntt_ring_gram_sym2_batch")
+        return out[0] if a_in.ndim == 3 else out
+
+    def ring_gram_sym2_device(self, d_h, d_a, d_b, batch, r, width, stream=0):
+        """Device buffers: a and b [batch][r][width][n] (d_b may be d_a), h [batch][r (r + 1) / 2][n].  Asynchronous on `stream`; enqueues
+        only."""
+        _check(self._lib.lsr_ntt_ring_gram_sym2_batch_device(self._h, d_h, d_a, d_b or None, batch, r, width, stream), "lsr_ntt_ring_gram_sym2_batch_device")
+
+    def ring_quadform(self, g, c, offdiag=2):
+        """out[j] = sum_i g[j][(i, i)] c_i c_i + offdiag * sum_{i < l} g[j][(i, l)] c_i c_l in the context's ring (host arrays, DESIGN.md
+        §5m): g is [batch, r (r + 1) / 2, n] in the packed order of a symmetric ring_gram (ring_gram_index), c is [batch, r, n], or
+        [r, n]: one set of challenges shared by every family; returns [batch, n].  offdiag: a word below q — 2 for a ring_gram(s), 1
+        for a ring_gram_sym2(phi, s).  A 2-d g is a batch of one, and so is the result."""
+        n = self.n
+        g_in, c_in = _u64_array(g, "g"), _u64_array(c, "c")
+        if g_in.ndim not in (2, 3) or g_in.shape[-1] != n:
+            raise ValueError("g must be [pairs, n] or [batch, pairs, n]")
+        if c_in.ndim not in (2, 3) or c_in.shape[-1] != n:
+            raise ValueError("c must be [r, n] or [batch, r, n]")
+        r, pairs = c_in.shape[-2], g_in.shape[-2]
+        if pairs != r * (r + 1) // 2:
+            raise ValueError("g must hold r (r + 1) / 2 polynomials per family for the r polynomials of c")
+        g3 = np.ascontiguousarray(g_in.reshape(-1, pairs, n))
+        c3 = np.ascontiguousarray(c_in.reshape(-1, r, n))
+        batch, c_rows = g3.shape[0], (1 if c_in.ndim == 2 else c3.shape[0])
+        if c_rows not in (1, batch):
+            raise ValueError("c must hold one set of challenges ([r, n]) or one per family of g")
+        out = np.empty((batch, n), dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_quadform_batch(self._h, out.ctypes.data, g3.ctypes.data, c3.ctypes.data, batch, r, c_rows, int(offdiag)),
+               "lsr_ntt_ring_quadform_batch")
+        return out[0] if g_in.ndim == 2 else out
+
+    def ring_quadform_device(self, d_out, d_g, d_c, batch, r, c_rows, offdiag=2, stream=0):
+        """Device buffers: g [batch][r (r + 1) / 2][n], c [c_rows][r][n] with c_rows 1 or batch, out [batch][n].  Asynchronous on
+        `stream`; enqueues only."""
+        _check(self._lib.lsr_ntt_ring_quadform_batch_device(self._h, d_out, d_g, d_c, batch, r, c_rows, int(offdiag), stream),
+               "lsr_ntt_ring_quadform_batch_device")
+
 
 class NttContext(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm, _RingScalar, _RingGram):
     """RAII handle over ``NttContext*`` (cpp-core/include/lambda_snark/ntt.h:25-41)."""

@@ -8,6 +8,8 @@
 //   2. ring_gram_kernel: the register-blocked pointwise product, canonical evaluation-domain words into g (a later column group
 //      loads them and adds: kRingDotFirst / kRingDotLast);
 //   3. after the last group launch_ntt (inverse) in place on the outputs in g.
+// The symmetrised form (lsr_ntt_ring_gram_sym2_batch): h[j][(i, l)] = <a_i, b_l> + <a_l, b_i> for i < l and <a_i, b_i> on
+// the diagonal, packed as the symmetric form's g — the same plan with ra = rb = r and the SYM2 mode of the kernel.
 // One path for every n <= 131072, every flavour, cyclic and negacyclic contexts.  The workspace is ring_dot_scratch
 // (lsr_ring_workspace.hpp), under the same mutex and event as the ring inner product.
 #include <algorithm>
@@ -30,25 +32,31 @@ static size_t gram_workspace_polys(const NttContext& c) { return ring_dot_scratc
 
 static size_t gram_outputs(size_t ra, size_t rb, bool sym) { return sym ? ra * (ra + 1) / 2 : ra * rb; }
 
+// sym: the packed upper triangle (b-hat == a-hat); sym2: the packed symmetrised form of two families
 template <class A>
-static void gram_launch(const NttContext& c, uint64_t* g, const uint64_t* ahat, const uint64_t* bhat, const GramShape& shape, bool sym,
+static void gram_launch(const NttContext& c, uint64_t* g, const uint64_t* ahat, const uint64_t* bhat, const GramShape& shape, bool sym, bool sym2,
                         size_t families, hipStream_t s) {
     constexpr int E = kGramEdge<A>;
     const unsigned bi = (shape.ra + E - 1) / E, bl = (shape.rb + E - 1) / E;
-    const dim3 grid(static_cast<unsigned>((c.degree + kGramThreads - 1) / kGramThreads), sym ? bi * (bi + 1) / 2 : bi * bl,
+    const dim3 grid(static_cast<unsigned>((c.degree + kGramThreads - 1) / kGramThreads), sym || sym2 ? bi * (bi + 1) / 2 : bi * bl,
                     static_cast<unsigned>(families));
+    if (sym2) {
+        hipLaunchKernelGGL((ring_gram_kernel<A, E, true, true>), grid, dim3(kGramThreads), 0, s, g, ahat, bhat, shape, c.mod);
+        return;
+    }
     for_bool(sym, [&](auto y) {
         hipLaunchKernelGGL((ring_gram_kernel<A, E, decltype(y)::value>), grid, dim3(kGramThreads), 0, s, g, ahat, bhat, shape, c.mod);
     });
 }
 
-// b == nullptr: the symmetric form.  b == a with rb == ra: the cross form on ONE set of transforms.
+// b == nullptr: the symmetric form.  b == a with rb == ra: the cross form on ONE set of transforms.  sym2 (b != nullptr, rb == ra):
+// the symmetrised packed form.
 template <class A>
 static void ring_gram_enqueue(const NttContext& c, uint64_t* d_g, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t ra, size_t rb,
-                              size_t width, hipStream_t s) {
+                              size_t width, bool sym2, hipStream_t s) {
     const size_t n = c.degree, polys = gram_workspace_polys(c);
     const bool sym = d_b == nullptr, one_set = sym || (d_b == d_a && rb == ra);
-    const size_t vectors = sym ? ra : ra + rb, outs = gram_outputs(ra, rb, sym);
+    const size_t vectors = sym ? ra : ra + rb, outs = gram_outputs(ra, rb, sym || sym2);
     const size_t a_fam = ra * width * n, b_fam = rb * width * n, g_fam = outs * n;
     uint64_t* const ws = c.ring_dot_scratch.ptr;
     if (one_set) d_b = d_a;
@@ -61,7 +69,7 @@ static void ring_gram_enqueue(const NttContext& c, uint64_t* d_g, const uint64_t
             if (!one_set) launch_ntt(c, bhat, now * rb * width, false, s, nullptr, nullptr, d_b + j0 * b_fam);
             const GramShape shape{(uint32_t)c.logn, (uint32_t)ra, (uint32_t)rb, (uint32_t)width, ring_dot_flags(true, true),
                                   width * n, a_fam, width * n, b_fam, g_fam};
-            gram_launch<A>(c, d_g + j0 * g_fam, ws, bhat, shape, sym, now, s);
+            gram_launch<A>(c, d_g + j0 * g_fam, ws, bhat, shape, sym, sym2, now, s);
             launch_ntt(c, d_g + j0 * g_fam, now * outs, true, s);
         }
         return;
@@ -79,7 +87,7 @@ static void ring_gram_enqueue(const NttContext& c, uint64_t* d_g, const uint64_t
                     launch_ntt(c, bhat + l * wnow * n, wnow, false, s, nullptr, nullptr, d_b + j * b_fam + (l * width + c0) * n);
             const GramShape shape{(uint32_t)c.logn, (uint32_t)ra, (uint32_t)rb, (uint32_t)wnow, ring_dot_flags(c0 == 0, c0 + wnow == width),
                                   wnow * n, 0, wnow * n, 0, g_fam};
-            gram_launch<A>(c, d_g + j * g_fam, ws, bhat, shape, sym, 1, s);
+            gram_launch<A>(c, d_g + j * g_fam, ws, bhat, shape, sym, sym2, 1, s);
         }
         launch_ntt(c, d_g + j * g_fam, outs, true, s);
     }
@@ -87,21 +95,22 @@ static void ring_gram_enqueue(const NttContext& c, uint64_t* d_g, const uint64_t
 
 // One call on the device (caller validated the arguments): workspace, ordering brackets, launches.
 static void ring_gram_device(const NttContext& c, uint64_t* d_g, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t ra, size_t rb,
-                             size_t width, hipStream_t s) {
+                             size_t width, bool sym2, hipStream_t s) {
     ring_call(c, c.ring_dot_scratch, ring_dot_scratch_words(c), true, s, [&] {
-        for_flavour(c, [&](auto a) { ring_gram_enqueue<decltype(a)>(c, d_g, d_a, d_b, batch, ra, rb, width, s); });
+        for_flavour(c, [&](auto a) { ring_gram_enqueue<decltype(a)>(c, d_g, d_a, d_b, batch, ra, rb, width, sym2, s); });
     });
 }
 
 // host buffers through bounded device chunks of whole families on the context's work stream (host_staged with two operands; b == a
 // with rb == ra goes up once)
-static void host_ring_gram(const NttContext& c, uint64_t* g, const uint64_t* a, const uint64_t* b, size_t batch, size_t ra, size_t rb, size_t width) {
+static void host_ring_gram(const NttContext& c, uint64_t* g, const uint64_t* a, const uint64_t* b, size_t batch, size_t ra, size_t rb, size_t width,
+                           bool sym2) {
     const size_t n = c.degree;
     const bool sym = b == nullptr, one_set = sym || (b == a && rb == ra);
-    const size_t a_words = ra * width * n, b_words = one_set ? 0 : rb * width * n, g_words = gram_outputs(ra, rb, sym) * n;
+    const size_t a_words = ra * width * n, b_words = one_set ? 0 : rb * width * n, g_words = gram_outputs(ra, rb, sym || sym2) * n;
     if (sym) {
         host_staged(c, g, a, batch, g_words, a_words,
-                    [&](uint64_t* d_g, const uint64_t* d_a, size_t now, hipStream_t s) { ring_gram_device(c, d_g, d_a, nullptr, now, ra, rb, width, s); });
+                    [&](uint64_t* d_g, const uint64_t* d_a, size_t now, hipStream_t s) { ring_gram_device(c, d_g, d_a, nullptr, now, ra, rb, width, false, s); });
         return;
     }
     DeviceGuard guard(c.device);
@@ -113,7 +122,7 @@ static void host_ring_gram(const NttContext& c, uint64_t* g, const uint64_t* a, 
         const size_t now = std::min(chunk, batch - j0);
         LSR_HIP(hipMemcpyAsync(da.ptr, a + j0 * a_words, now * a_words * 8, hipMemcpyHostToDevice, s));
         if (!one_set) LSR_HIP(hipMemcpyAsync(db.ptr, b + j0 * b_words, now * b_words * 8, hipMemcpyHostToDevice, s));
-        ring_gram_device(c, dg.ptr, da.ptr, one_set ? da.ptr : db.ptr, now, ra, rb, width, s);
+        ring_gram_device(c, dg.ptr, da.ptr, one_set ? da.ptr : db.ptr, now, ra, rb, width, sym2, s);
         LSR_HIP(hipMemcpyAsync(g + j0 * g_words, dg.ptr, now * g_words * 8, hipMemcpyDeviceToHost, s));
         LSR_HIP(hipStreamSynchronize(s));
     }
@@ -127,10 +136,10 @@ static void host_ring_gram(const NttContext& c, uint64_t* g, const uint64_t* a, 
 namespace {
 
 // Argument checks that read no context (and never dereference ctx), in the documented order: -1 and a message, 1 for the empty call
-// (a no-op), 0 to go on.
+// (a no-op), 0 to go on.  sym2: the symmetrised form, whose b must not be NULL.
 int ring_gram_check(const char* where, const NttContext* ctx, const void* g, const void* a, const void* b, size_t batch, size_t ra, size_t rb,
-                    size_t width) {
-    if (!ctx || !g || !a) return lsr::abi_refuse(where, "NULL context or buffer");
+                    size_t width, bool sym2 = false) {
+    if (!ctx || !g || !a || (sym2 && !b)) return lsr::abi_refuse(where, "NULL context or buffer");
     if (ra == 0 || width == 0 || (b && rb == 0)) return lsr::abi_refuse(where, "ra, rb and width must be at least 1");
     if (!b && rb != ra)
         return lsr::abi_refuse(where, "the symmetric form (b == NULL) takes rb == ra, got ra = " + std::to_string(ra) + ", rb = " + std::to_string(rb));
@@ -141,7 +150,7 @@ int ring_gram_check(const char* where, const NttContext* ctx, const void* g, con
         return lsr::abi_refuse(where, "width = " + std::to_string(width) + " is above LSR_RING_DOT_MAX_TERMS (" + std::to_string(LSR_RING_DOT_MAX_TERMS) + ")");
     // every product a shape takes, in polynomials and then in bytes at the smallest ring (n = 2, 16 bytes a polynomial)
     size_t vecs = 0, a_polys = 0, b_polys = 0, g_polys = 0, bytes = 0;
-    const size_t outs = lsr::gram_outputs(ra, rb, b == nullptr);
+    const size_t outs = lsr::gram_outputs(ra, rb, b == nullptr || sym2);
     const bool overflow = __builtin_mul_overflow(batch, ra, &vecs) || __builtin_mul_overflow(vecs, width, &a_polys) ||
                           __builtin_mul_overflow(batch, rb, &vecs) || __builtin_mul_overflow(vecs, width, &b_polys) ||
                           __builtin_mul_overflow(batch, outs, &g_polys) || __builtin_mul_overflow(a_polys, (size_t)16, &bytes) ||
@@ -152,10 +161,10 @@ int ring_gram_check(const char* where, const NttContext* ctx, const void* g, con
 
 // The checks of a non-empty call that read the context, still before any device work.
 void ring_gram_validate(const NttContext& ctx, const uint64_t* g, const uint64_t* a, const uint64_t* b, size_t batch, size_t ra, size_t rb,
-                        size_t width) {
+                        size_t width, bool sym2 = false) {
     lsr::refuse_above_two_pass(ctx, "ring Gram matrix on a context above n = 131072 is not supported (lsr_cyclic_ntt_context_create_large)");
     const bool sym = b == nullptr;
-    const size_t poly_bytes = (size_t)ctx.degree * 8, vectors = sym ? ra : ra + rb, outs = lsr::gram_outputs(ra, rb, sym);
+    const size_t poly_bytes = (size_t)ctx.degree * 8, vectors = sym ? ra : ra + rb, outs = lsr::gram_outputs(ra, rb, sym || sym2);
     // (at most 128 * 65536 and 4096 polynomials of at most 2^20 bytes: no overflow)
     if (vectors * width * poly_bytes > LSR_RING_GRAM_MAX_FAMILY_BYTES || outs * poly_bytes > LSR_RING_GRAM_MAX_FAMILY_BYTES)
         throw std::runtime_error("one family takes " + std::to_string(vectors * width * poly_bytes) + " bytes of operands and " +
@@ -184,7 +193,7 @@ int lsr_ntt_ring_gram_batch(const NttContext* ctx, uint64_t* g, const uint64_t* 
     if (rc != 0) return rc < 0 ? -1 : 0;
     return lsr::abi_guarded("lsr_ntt_ring_gram_batch", [&] {
         ring_gram_validate(*ctx, g, a, b, batch, ra, rb, width);
-        lsr::host_ring_gram(*ctx, g, a, b, batch, ra, rb, width);
+        lsr::host_ring_gram(*ctx, g, a, b, batch, ra, rb, width, false);
     });
 }
 
@@ -195,7 +204,28 @@ int lsr_ntt_ring_gram_batch_device(const NttContext* ctx, uint64_t* d_g, const u
     return lsr::abi_guarded("lsr_ntt_ring_gram_batch_device", [&] {
         ring_gram_validate(*ctx, d_g, d_a, d_b, batch, ra, rb, width);
         lsr::DeviceGuard guard(ctx->device);
-        lsr::ring_gram_device(*ctx, d_g, d_a, d_b, batch, ra, rb, width, static_cast<hipStream_t>(stream));
+        lsr::ring_gram_device(*ctx, d_g, d_a, d_b, batch, ra, rb, width, false, static_cast<hipStream_t>(stream));
+    });
+}
+
+int lsr_ntt_ring_gram_sym2_batch(const NttContext* ctx, uint64_t* h, const uint64_t* a, const uint64_t* b, size_t batch, size_t r,
+                                 size_t width) noexcept {
+    const int rc = ring_gram_check("lsr_ntt_ring_gram_sym2_batch", ctx, h, a, b, batch, r, r, width, true);
+    if (rc != 0) return rc < 0 ? -1 : 0;
+    return lsr::abi_guarded("lsr_ntt_ring_gram_sym2_batch", [&] {
+        ring_gram_validate(*ctx, h, a, b, batch, r, r, width, true);
+        lsr::host_ring_gram(*ctx, h, a, b, batch, r, r, width, true);
+    });
+}
+
+int lsr_ntt_ring_gram_sym2_batch_device(const NttContext* ctx, uint64_t* d_h, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t r,
+                                        size_t width, void* stream) noexcept {
+    const int rc = ring_gram_check("lsr_ntt_ring_gram_sym2_batch_device", ctx, d_h, d_a, d_b, batch, r, r, width, true);
+    if (rc != 0) return rc < 0 ? -1 : 0;
+    return lsr::abi_guarded("lsr_ntt_ring_gram_sym2_batch_device", [&] {
+        ring_gram_validate(*ctx, d_h, d_a, d_b, batch, r, r, width, true);
+        lsr::DeviceGuard guard(ctx->device);
+        lsr::ring_gram_device(*ctx, d_h, d_a, d_b, batch, r, r, width, true, static_cast<hipStream_t>(stream));
     });
 }
 

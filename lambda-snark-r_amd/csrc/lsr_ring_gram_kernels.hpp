@@ -8,16 +8,21 @@
 // Grid: x = runs of positions, y = block pairs, z = families of the chunk.  Cross form: y = i-block * ceil(rb / E) + l-block.
 // Symmetric form (SYM, b-hat == a-hat): only the pairs i-block <= l-block are launched, rows of the upper triangle one after the
 // other, and a diagonal block stores only i <= l; output (i, l) is polynomial i r - i (i - 1) / 2 + (l - i) of the family.
+// Symmetrised form (SYM2, with SYM; lsr_ntt_ring_gram_sym2_batch): ra == rb, the same block pairs and the same packed
+// outputs, but output (i, l), i < l, is <a_i, b_l> + <a_l, b_i> and output (i, i) is <a_i, b_i> once.  A block pair I < L loads a_I,
+// b_L, a_L and b_I per column and adds both products into the same accumulators; a diagonal block has a_L = a_I and b_I = b_L in
+// registers already and skips the second product where i == l.
 // Partial blocks (ra or rb no multiple of E): the counts ni, nl of live vectors are workgroup-uniform; a dead row reads the block's
 // last live vector again (a uniform offset, never out of range: the same cache lines) and is not stored.  (Guarding the loads and
 // products of dead rows by uniform branches instead was measured: DESIGN.md §5j.)
 // Addressing: 64-bit.  The workgroup-uniform part of every address (family, vector, column) is a 64-bit scalar offset, the lane adds
 // its position; a family's operands may exceed 2^31 bytes.
 // Accumulator contract: ntt_tile_ring_dot's (lsr_ntt_kernels.hpp).  F64 — both operands are canonical, a product is |r| <= 0.875 q,
-// the accumulator starts at 0 or at a carried-in canonical word (< q) and is re-centred every kRingDotF64Period columns and after the
-// last one: |acc| <= q + 0.875 * 32 q < 2^50, exact; after the last re-centring |acc| <= q/2 + 1, store_reduced's domain.  U64 —
-// canonical products and canonical sums.  Goldilocks — gold_add.  g always receives canonical words: the next column group loads
-// them and adds (kRingDotFirst clear), launch_ntt's inverse takes them after the last group.
+// the accumulator starts at 0 or at a carried-in canonical word (< q) and is re-centred every kRingDotF64Period columns (SYM2, two
+// products per column: every kRingDotF64Period / 2 columns) and after the last one: |acc| <= q + 0.875 * 32 q < 2^50, exact; after
+// the last re-centring |acc| <= q/2 + 1, store_reduced's domain.  U64 — canonical products and canonical sums.  Goldilocks —
+// gold_add.  g always receives canonical words: the next column group loads them and adds (kRingDotFirst clear), launch_ntt's
+// inverse takes them after the last group.
 #pragma once
 #include <type_traits>
 
@@ -42,7 +47,7 @@ struct GramShape {
     size_t g_fam;                          // words of one family's outputs
 };
 
-template <class A, int E, bool SYM>
+template <class A, int E, bool SYM, bool SYM2 = false>
 __global__ void __launch_bounds__(kGramThreads) ring_gram_kernel(uint64_t* __restrict__ g, const uint64_t* __restrict__ ahat,
                                                                    const uint64_t* __restrict__ bhat, GramShape s, ModParams p) {
     using elem = typename A::elem;
@@ -65,6 +70,12 @@ __global__ void __launch_bounds__(kGramThreads) ring_gram_kernel(uint64_t* __res
     const uint64_t* const ap = ahat + blockIdx.z * s.a_fam + i0 * s.a_vec;
     const uint64_t* const bp = bhat + blockIdx.z * s.b_fam + l0 * s.b_vec;
     uint64_t* const gp = g + blockIdx.z * s.g_fam;
+    // SYM2: the transposed operands a_L and b_I of the second product (a diagonal block has them in x and y)
+    static_assert(SYM || !SYM2, "the symmetrised form is a mode of the packed form");
+    const bool diag = SYM2 && ib == lb;
+    const uint64_t* const ap2 = ahat + blockIdx.z * s.a_fam + l0 * s.a_vec;
+    const uint64_t* const bp2 = bhat + blockIdx.z * s.b_fam + i0 * s.b_vec;
+    constexpr uint32_t kPeriod = SYM2 ? kRingDotF64Period / 2 : kRingDotF64Period;
     // (ii, ll) of the block is an output of this workgroup; its polynomial within the family
     auto live = [&](int ii, int ll) { return (uint32_t)ii < ni && (uint32_t)ll < nl && (!SYM || i0 + ii <= l0 + ll); };
     auto slot = [&](int ii, int ll) -> size_t {
@@ -92,8 +103,25 @@ __global__ void __launch_bounds__(kGramThreads) ring_gram_kernel(uint64_t* __res
         for (int ii = 0; ii < E; ++ii)
 #pragma unroll
             for (int ll = 0; ll < E; ++ll) acc[ii][ll] = ring_accumulate<A>(acc[ii][ll], ring_product<A>(x[ii], y[ll], p), p);
+        if constexpr (SYM2) {
+            elem xt[E], yt[E];
+            if (diag) {
+#pragma unroll
+                for (int k = 0; k < E; ++k) xt[k] = x[k], yt[k] = y[k];
+            } else {
+#pragma unroll
+                for (int ll = 0; ll < E; ++ll) xt[ll] = A::load(ap2[min((uint32_t)ll, nl - 1u) * s.a_vec + col + pos], p);
+#pragma unroll
+                for (int ii = 0; ii < E; ++ii) yt[ii] = A::load(bp2[min((uint32_t)ii, ni - 1u) * s.b_vec + col + pos], p);
+            }
+#pragma unroll
+            for (int ii = 0; ii < E; ++ii)
+#pragma unroll
+                for (int ll = 0; ll < E; ++ll)
+                    if (!(diag && ii == ll)) acc[ii][ll] = ring_accumulate<A>(acc[ii][ll], ring_product<A>(xt[ll], yt[ii], p), p);
+        }
         if constexpr (std::is_same_v<A, ArithF64>) {
-            if ((c & (kRingDotF64Period - 1u)) == kRingDotF64Period - 1u || c + 1 == s.ncols) {
+            if ((c & (kPeriod - 1u)) == kPeriod - 1u || c + 1 == s.ncols) {
 #pragma unroll
                 for (int ii = 0; ii < E; ++ii)
 #pragma unroll
