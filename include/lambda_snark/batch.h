@@ -558,6 +558,69 @@ int lsr_ntt_ring_quadform_batch(const NttContext* ctx, uint64_t* out, const uint
 int lsr_ntt_ring_quadform_batch_device(const NttContext* ctx, uint64_t* d_out, const uint64_t* d_g, const uint64_t* d_c, size_t batch,
                                        size_t r, size_t c_rows, uint64_t offdiag, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: operator-norm-bounded ring challenges ---------------- */
+/* The challenges of a LaBRADOR/Greyhound-style argument, drawn on the device: elements with kappa1
+ * coefficients +-1 and kappa2 coefficients +-2 whose operator norm — the largest |c(zeta)| over the complex roots zeta of the ring's
+ * modulus polynomial — is at most T, which is what makes ||c s|| <= T ||s|| hold.  Integer code that reads q, n and the ring of the
+ * context: every arithmetic flavour, negacyclic and cyclic contexts, n <= LSR_RING_OPNORM_MAX_DEGREE.
+ *
+ * The fixed-point operator norm.  A float comparison against T is not reproducible between a device, a model and a verifier on
+ * another machine, so the norm is an integer function.  Table: C[j] = round(2^30 cos(pi j / n)), 0 <= j < 2n, int32 (no entry is
+ * within 2.6e-4 of a rounding tie for any power of two n <= 4096: double-precision cos of any honest libm reproduces it).  For an
+ * element with centred coefficients c_i and an exponent e: Re_e = sum_i c_i C[(i e) mod 2n], Im_e = sum_i c_i C[(i e - n/2) mod 2n];
+ *   N(c) = max over e in E of Re_e^2 + Im_e^2, an unsigned 128-bit integer in units of 2^-60;
+ *   E = {2k + 1 : 0 <= k < n/2} on a negacyclic context, {2k : 0 <= k <= n/2} on a cyclic one: one representative per conjugate
+ *   pair of the ring's complex embeddings.
+ * "||c||_op <= T" MEANS N(c) <= T^2 2^60.  sqrt(N(c)) / 2^30 differs from the true operator norm by at most sqrt(2) ||c||_1 2^-31
+ * (every table entry is off by at most 1/2, in Re and in Im), which is below n max|c_i| 2^-30.5.
+ *
+ * lsr_ring_opnorm_table: the table of degree n into out[2n].  Host only, no device needed.  -1 for a NULL out or an n that is not a
+ *   power of two in [2, LSR_RING_OPNORM_MAX_DEGREE].
+ * lsr_ntt_ring_opnorm_batch(_device): x [count][n] canonical residues, out [count][2]: N(c) as low word, high word (the layout of
+ *   lsr_ntt_ring_l2sq_batch).  An element's output is all ones (both words) if it holds a word >= q or a centred coefficient above
+ *   2^15 in magnitude: that bound keeps every Re and Im inside int64 (2^12 2^15 2^30 = 2^57), the products are 32 x 32 + 64
+ *   multiply-adds.  Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL
+ *   context or buffer; (2) a context with n above LSR_RING_OPNORM_MAX_DEGREE.  (3) Then count == 0 is a no-op that returns 0.  Then
+ *   (4) a size that overflows size_t; out overlapping x; no visible device.
+ * lsr_ntt_ring_opnorm_prepare: builds the table on the host, uploads it once and caches it in the context (2n words, freed with
+ *   it).  lsr_ntt_ring_opnorm_batch(_device), and lsr_ntt_ring_challenge_batch(_device) with opnorm_bound != 0, do this themselves
+ *   on first use, SYNCHRONOUSLY (an allocation and a blocking copy, refused on a capturing stream).  After it the _device forms
+ *   enqueue one kernel and allocate nothing: they can be captured into a HIP graph.  Refuses NULL, n above the limit, no device.
+ *
+ * lsr_ntt_ring_challenge_batch(_device): out [count][n] canonical residues (1, 2, q - 1, q - 2 and 0), tries int32 [count].
+ * Keys, components, domain, index_base and streams exactly as "seeded ring sampling" above: element e uses key
+ * keys[4 (e / components) ..] and stream index index_base + (e % components); device-resident SHA3 digests are valid keys.
+ *   Candidate of attempt t = 0, 1, ...: LSR_RING_SAMPLE_BALL's inside-out shuffle with kappa = kappa1 + kappa2 steps, read from
+ *     the element's stream at word offset t LSR_RING_CHALLENGE_ATTEMPT_WORDS.  c = 0; for s = 0 .. kappa-1: i = n - kappa + s,
+ *     j = draw(i + 1; word t 2^18 + a kappa + s for a = 0, 1, ...; U = 63); c[i] = c[j]; then c[j] = +-(s < kappa2 ? 2 : 1), minus
+ *     when bit 63 of word t 2^18 + s is set.  Uniform over the elements with exactly kappa1 coefficients +-1 and kappa2
+ *     coefficients +-2.  With kappa <= n <= 4096 an attempt's word indices stay below 2^18 past its offset, and with max_tries <=
+ *     LSR_RING_CHALLENGE_MAX_TRIES all word indices stay below 2^28.
+ *   Acceptance.  opnorm_bound == 0: attempt 0 is taken, tries[e] = 1; with kappa2 == 0 the output is word for word
+ *     LSR_RING_SAMPLE_BALL with kappa = kappa1.  Otherwise (T = opnorm_bound): the first attempt t < max_tries with N(c) <=
+ *     T^2 2^60 is written and tries[e] = t + 1.
+ *   No attempt passes: the element is written as zeros and tries[e] = 0 — the caller re-keys.  At LaBRADOR's parameters (n = 64,
+ *     kappa1 = 31, kappa2 = 10, T = 15) a candidate passes with probability about 0.177 (20 000 samples of the model), so
+ *     max_tries = 256 fails with probability about 0.823^256, about 2^-72.
+ * Like the sampling above this is NOT constant-time, and need not be: challenges are public.
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL context, buffer, tries
+ * or keys; (2) components == 0; (3) kappa1 + kappa2 == 0 or above n; (4) kappa2 > 0 with q < 5; (5) max_tries == 0 or above
+ * LSR_RING_CHALLENGE_MAX_TRIES; (6) opnorm_bound >= 2^32; (7) a context with n above LSR_RING_OPNORM_MAX_DEGREE.  (8) Then
+ * count == 0 is a no-op that returns 0.  Then (9) index_base + components overflowing 64 bits; no visible device. */
+#define LSR_RING_OPNORM_MAX_DEGREE 4096
+#define LSR_RING_CHALLENGE_ATTEMPT_WORDS 262144
+#define LSR_RING_CHALLENGE_MAX_TRIES 1024
+int lsr_ring_opnorm_table(uint32_t n, int32_t* out) LSR_NOEXCEPT;
+int lsr_ntt_ring_opnorm_prepare(const NttContext* ctx) LSR_NOEXCEPT;
+int lsr_ntt_ring_opnorm_batch(const NttContext* ctx, const uint64_t* x, size_t count, uint64_t* out) LSR_NOEXCEPT;
+int lsr_ntt_ring_opnorm_batch_device(const NttContext* ctx, const uint64_t* d_x, size_t count, uint64_t* d_out, void* stream) LSR_NOEXCEPT;
+int lsr_ntt_ring_challenge_batch(const NttContext* ctx, uint64_t* out, int32_t* tries, size_t count, uint32_t kappa1, uint32_t kappa2,
+                                 uint64_t opnorm_bound, uint32_t max_tries, const uint64_t* keys, size_t components, uint32_t domain,
+                                 uint64_t index_base) LSR_NOEXCEPT;
+int lsr_ntt_ring_challenge_batch_device(const NttContext* ctx, uint64_t* d_out, int32_t* d_tries, size_t count, uint32_t kappa1,
+                                        uint32_t kappa2, uint64_t opnorm_bound, uint32_t max_tries, const uint64_t* d_keys,
+                                        size_t components, uint32_t domain, uint64_t index_base, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -314,6 +314,81 @@ class _RingSample:
         if not handle:
             raise CoreError("lsr_ntt_ring_matrix_create_seeded failed: " + _abi.last_error())
         return RingMatrix(self, handle)
+
+
+# batch.h LSR_RING_OPNORM_MAX_DEGREE, LSR_RING_CHALLENGE_*: the largest ring degree of the operator norm, the stream words set aside for
+# one attempt of a challenge and the cap on max_tries
+RING_OPNORM_MAX_DEGREE = 4096
+RING_CHALLENGE_ATTEMPT_WORDS = 1 << 18
+RING_CHALLENGE_MAX_TRIES = 1024
+
+
+def ring_opnorm_table(n):
+    """C[j] = round(2^30 cos(pi j / n)), 0 <= j < 2n, as int32 (batch.h lsr_ring_opnorm_table): the table of the fixed-point operator
+    norm of a ring of degree n, a power of two in [2, RING_OPNORM_MAX_DEGREE].  Host only."""
+    n = int(n)
+    if not 0 <= n < 1 << 32:
+        raise ValueError("n must fit 32 bits")
+    out = np.zeros(2 * n if n <= RING_OPNORM_MAX_DEGREE else 1, dtype=np.int32)
+    _check(_abi.lib().lsr_ring_opnorm_table(n, out.ctypes.data), "lsr_ring_opnorm_table")
+    return out
+
+
+class _RingChallenge:
+    """The fixed-point operator norm and operator-norm-bounded challenges on a context (``NttContext`` and ``CyclicNtt``; batch.h
+    "operator-norm-bounded ring challenges").  N(c) is an integer in units of 2^-60; "norm <= T" means N(c) <= T^2 2^60."""
+
+    def ring_opnorm_prepare(self):
+        """Builds the context's cosine table and makes it resident on the device (once): behind it ring_opnorm_device and
+        ring_challenge_device enqueue only and can be captured into a graph."""
+        _check(self._lib.lsr_ntt_ring_opnorm_prepare(self._h), "lsr_ntt_ring_opnorm_prepare")
+
+    def ring_opnorm(self, x):
+        """N(c) of every element of x [..., n] as Python ints (an object array of shape x.shape[:-1]; an int for one element);
+        2^128 - 1 for an element with a word >= q or a centred coefficient above 2^15 in magnitude."""
+        x_in = _u64_array(x, "x")
+        if x_in.shape[-1] != self.n:
+            raise ValueError("x must be [n] or [..., n]")
+        x2 = np.ascontiguousarray(x_in.reshape(-1, self.n))
+        out = np.empty((x2.shape[0], 2), dtype=np.uint64)
+        _check(self._lib.lsr_ntt_ring_opnorm_batch(self._h, x2.ctypes.data, x2.shape[0], out.ctypes.data), "lsr_ntt_ring_opnorm_batch")
+        values = [int(lo) | (int(hi) << 64) for lo, hi in out.tolist()]
+        if x_in.ndim == 1:
+            return values[0]
+        res = np.empty(len(values), dtype=object)
+        res[:] = values
+        return res.reshape(x_in.shape[:-1])
+
+    def ring_opnorm_device(self, d_x, count, d_out, stream=0):
+        """Device buffers: x [count][n], out [count][2] (low word, high word).  Asynchronous on `stream`; the first call on a context
+        without ring_opnorm_prepare uploads the table synchronously."""
+        _check(self._lib.lsr_ntt_ring_opnorm_batch_device(self._h, d_x, count, d_out, stream), "lsr_ntt_ring_opnorm_batch_device")
+
+    def ring_challenge(self, count, kappa1, kappa2, opnorm_bound, keys, components=None, max_tries=256, domain=16, index_base=0):
+        """(out, tries): out [count, n] challenges with kappa1 coefficients +-1 and kappa2 coefficients +-2, tries int32 [count].
+        opnorm_bound T > 0: element e is its first candidate with N(c) <= T^2 2^60 and tries[e] the attempts that took (zeros and 0
+        when max_tries candidates failed: re-key); T = 0: the first candidate, tries 1 (kappa2 = 0: RING_SAMPLE_BALL).  Keys,
+        components, domain and index_base as ring_sample."""
+        k2 = _ring_keys(keys)
+        count = int(count)
+        if components is None:
+            components = max(1, -(-count // k2.shape[0]))
+        components = int(components)
+        if components > 0 and k2.shape[0] < -(-count // components):
+            raise ValueError("keys must hold ceil(count / components) keys")
+        out = np.empty((count, self.n), dtype=np.uint64)
+        tries = np.empty(count, dtype=np.int32)
+        _check(self._lib.lsr_ntt_ring_challenge_batch(self._h, out.ctypes.data, tries.ctypes.data, count, kappa1, kappa2, int(opnorm_bound), max_tries,
+                                                      k2.ctypes.data, components, domain, index_base), "lsr_ntt_ring_challenge_batch")
+        return out, tries
+
+    def ring_challenge_device(self, d_out, d_tries, count, kappa1, kappa2, opnorm_bound, d_keys, components, max_tries=256, domain=16,
+                              index_base=0, stream=0):
+        """Device buffers: out [count][n], tries int32 [count]; d_keys [ceil(count / components)][4] words (8-byte aligned; transcript
+        digests are valid keys).  Asynchronous on `stream`; with opnorm_bound != 0 the first call on a context without
+        ring_opnorm_prepare uploads the table synchronously."""
+        _check(self._lib.lsr_ntt_ring_challenge_batch_device(self._h, d_out, d_tries, count, kappa1, kappa2, int(opnorm_bound), max_tries, d_keys,
+                                                             components, domain, index_base, stream), "lsr_ntt_ring_challenge_batch_device")
 
 
 class _RingFold:
@@ -670,7 +745,7 @@ class _RingGram:
                "lsr_ntt_ring_quadform_batch_device")
 
 
-class NttContext(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm, _RingScalar, _RingGram):
+class NttContext(_RingGadget, _RingSample, _RingChallenge, _RingFold, _RingGalois, _RingNorm, _RingScalar, _RingGram):
     """RAII handle over ``NttContext*`` (cpp-core/include/lambda_snark/ntt.h:25-41)."""
 
     def __init__(self, q, n, device=-1):
@@ -1276,7 +1351,7 @@ def prover_max_log2_size():
     return int(_abi.lib().lsr_prover_max_log2_size())
 
 
-class CyclicNtt(_RingGadget, _RingSample, _RingFold, _RingGalois, _RingNorm, _RingScalar, _RingGram):
+class CyclicNtt(_RingGadget, _RingSample, _RingChallenge, _RingFold, _RingGalois, _RingNorm, _RingScalar, _RingGram):
     """The transform pair of rust-api/lambda-snark/src/ntt.rs: ``forward(coeffs)`` = ``ntt_forward(coeffs, modulus, omega)``
     (natural order in and out), ``inverse(evals)`` = ``ntt_inverse``.  One handle per (modulus, n, omega).  n above 2^17 (up to 2^22,
     NTT_MODULUS only) goes through ``lsr_cyclic_ntt_context_create_large``."""

@@ -148,6 +148,12 @@ SIGNATURES = {
     "lsr_ntt_ring_gram_sym2_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, vp]),
     "lsr_ntt_ring_quadform_batch": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, u64]),
     "lsr_ntt_ring_quadform_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, u64, vp]),
+    "lsr_ring_opnorm_table": (c_int, [u32, vp]),
+    "lsr_ntt_ring_opnorm_prepare": (c_int, [vp]),
+    "lsr_ntt_ring_opnorm_batch": (c_int, [vp, vp, c_size, vp]),
+    "lsr_ntt_ring_opnorm_batch_device": (c_int, [vp, vp, c_size, vp, vp]),
+    "lsr_ntt_ring_challenge_batch": (c_int, [vp, vp, vp, c_size, u32, u32, u64, u32, vp, c_size, u32, u64]),
+    "lsr_ntt_ring_challenge_batch_device": (c_int, [vp, vp, vp, c_size, u32, u32, u64, u32, vp, c_size, u32, u64, vp]),
     "lsr_sample_gaussian_seeded": (c_int, [vp, c_size, c_double, u64, u32, u64]),
     "lsr_gaussian_cdf": (c_size, [c_double, vp, c_size]),
     "lsr_lwe_context_create_seeded": (vp, [ctypes.POINTER(PublicParams), u64, c_int]),

@@ -1,5 +1,5 @@
 // The host call path shared by the fused ring operations (lsr_ring_mul.hip, lsr_ring_dot.hip, lsr_ring_fold.hip, lsr_ring_matvec.hip,
-// lsr_ring_gadget.hip, lsr_ring_galois.hip, lsr_ring_sample.hip and the ring combination of lsr_commit.hip): the dispatch from a context to a kernel
+// lsr_ring_gadget.hip, lsr_ring_galois.hip, lsr_ring_sample.hip, lsr_ring_challenge.hip and the ring combination of lsr_commit.hip): the dispatch from a context to a kernel
 // instantiation, the bracket that keeps the context's workspaces safe across streams and threads, the argument checks
 // the entry points have in common and the staging of host buffers.  The dispatch helpers (for_tile_log, for_rank, for_top_bits,
 // for_bool, for_flavour) also serve the commitment pipelines of lsr_commit.hip.  Host code only.

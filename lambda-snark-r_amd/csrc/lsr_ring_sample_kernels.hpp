@@ -21,7 +21,6 @@
 namespace lsr {
 
 constexpr int kRingSampleThreads = 256;
-constexpr uint32_t kRingSampleMaxWords = 64;        // LSR_RING_SAMPLE_MAX_WORDS
 constexpr uint32_t kBallChunkWords = 2048;          // first-attempt words resident in LDS at a time: one block per lane
 constexpr int kBallLdsMaxLog = 17;                  // the polynomial as 2-bit codes: 32 KiB at n = 131072
 
@@ -47,23 +46,7 @@ struct RingSampleJob {
 // r in [0, m) -> the stored word: r - beta as a canonical residue (beta = 0: r itself)
 __device__ __forceinline__ uint64_t ring_sample_value(uint64_t r, uint64_t beta, uint64_t q) { return r >= beta ? r - beta : q - (beta - r); }
 
-// field 0 of a word reduced mod m: 2^L <= 2 (m - 1), so one subtraction
-__device__ __forceinline__ uint64_t ring_sample_last_resort(uint64_t word, uint64_t mask, uint64_t m) {
-    const uint64_t c = word & mask;
-    return c >= m ? c - m : c;
-}
-
-// fields `from` .. F-1 of one word: true and r when one is below m
-__device__ __forceinline__ bool ring_sample_scan(uint64_t word, uint32_t from, uint32_t fields, uint32_t width, uint64_t mask, uint64_t m, uint64_t& r) {
-    for (uint32_t f = from; f < fields; ++f) {
-        const uint64_t c = (word >> (f * width)) & mask;      // f >= 1 only when width <= 32
-        if (c < m) {
-            r = c;
-            return true;
-        }
-    }
-    return false;
-}
+// (ring_sample_last_resort, ring_sample_scan and ball_draw, shared with lsr_ring_challenge_kernels.hpp: lsr_sampler.hpp)
 
 // The slow path of a lane: `pending` (bit s: coefficient s of the block has no value yet) after field 0 of the first-attempt words
 // w; fills only what is missing.
@@ -165,26 +148,6 @@ __device__ __forceinline__ void ball_set(uint32_t* codes, uint64_t* dst, uint32_
     } else {
         dst[i] = code == 0 ? 0 : (code == 1 ? 1 : q - 1);
     }
-}
-
-// j = draw(i + 1; word a kappa + s, a = 0, 1, ...; U = 63) with the first-attempt word given (lane 0 only; i >= 1)
-__device__ __forceinline__ uint32_t ball_draw(const RingStream st, uint32_t domain, uint32_t kappa, uint32_t s, uint32_t i, uint64_t word) {
-    const uint32_t width = 32 - __clz(i);                   // bitlen((i + 1) - 1)
-    const uint32_t fields = 63 / width;
-    const uint64_t mask = (1ull << width) - 1, m = (uint64_t)i + 1;
-    uint64_t r;
-    if (ring_sample_scan(word, 0, fields, width, mask, m, r)) return (uint32_t)r;
-    uint64_t w[8];
-    for (uint32_t a = 1; a < kRingSampleMaxWords; ++a) {
-        const uint32_t x = a * kappa + s;                    // below 64 n <= 2^28
-        stream_block(st.key, domain, st.index, x >> 3, w);
-        uint64_t pick = w[0];
-#pragma unroll
-        for (int t = 1; t < 8; ++t) pick = (x & 7u) == (uint32_t)t ? w[t] : pick;
-        word = pick;
-        if (ring_sample_scan(word, 0, fields, width, mask, m, r)) return (uint32_t)r;
-    }
-    return (uint32_t)ring_sample_last_resort(word, mask, m);
 }
 
 // dynamic LDS: min(kappa rounded up to 8, kBallChunkWords) words, then (LDS) n / 16 code words (at least one)

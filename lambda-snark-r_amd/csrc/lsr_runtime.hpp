@@ -188,6 +188,8 @@ struct HandleDeleter {
 
 // The opaque C-ABI handle (reference: struct NttContext, cpp-core/src/ntt.cpp:21-26).
 struct NttContext {
+    // modulus and degree stay the first two fields: the refusals of lsr_ntt_ring_challenge_batch read nothing else of a context, and
+    // tests/test_ring_challenge_abi.py checks their order on a handle that holds only these
     uint64_t modulus = 0;
     uint32_t degree = 0;
     int logn = 0;
@@ -229,6 +231,10 @@ struct NttContext {
     // records ring_event after its last copy out of the buffer, so the next ring call starts behind it.
     mutable std::mutex ring_matvec_mutex;
     mutable lsr::DeviceBuffer<uint64_t> ring_matvec_scratch;
+    // the cosine table of the fixed-point operator norm (lsr_ring_challenge.hip, n <= 4096): 2 n words, built on the host and uploaded
+    // by lsr_ntt_ring_opnorm_prepare or by the first call that needs it, never resized, freed with the context
+    mutable std::mutex opnorm_mutex;
+    mutable lsr::DeviceBuffer<int32_t> opnorm_table;
 };
 
 namespace lsr {

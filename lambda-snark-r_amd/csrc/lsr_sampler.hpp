@@ -77,6 +77,50 @@ __device__ __forceinline__ RingStream ring_stream_of(const uint64_t* keys, uint6
     return RingStream{keys + 4 * (group - group_base), index_base + member};
 }
 
+// The rejection primitive draw(m; w_0, w_1, ...; U) of the ring samplers (batch.h "seeded ring sampling"; lsr_ring_sample_kernels.hpp,
+// lsr_ring_challenge_kernels.hpp): the first L-bit field below m, fields in order within a word, words in order.
+constexpr uint32_t kRingSampleMaxWords = 64;        // LSR_RING_SAMPLE_MAX_WORDS
+
+// field 0 of a word reduced mod m: 2^L <= 2 (m - 1), so one subtraction
+__device__ __forceinline__ uint64_t ring_sample_last_resort(uint64_t word, uint64_t mask, uint64_t m) {
+    const uint64_t c = word & mask;
+    return c >= m ? c - m : c;
+}
+
+// fields `from` .. F-1 of one word: true and r when one is below m
+__device__ __forceinline__ bool ring_sample_scan(uint64_t word, uint32_t from, uint32_t fields, uint32_t width, uint64_t mask, uint64_t m, uint64_t& r) {
+    for (uint32_t f = from; f < fields; ++f) {
+        const uint64_t c = (word >> (f * width)) & mask;      // f >= 1 only when width <= 32
+        if (c < m) {
+            r = c;
+            return true;
+        }
+    }
+    return false;
+}
+
+// j = draw(i + 1; word base + a kappa + s, a = 0, 1, ...; U = 63) with the first-attempt word given (lane 0 only; i >= 1).  base: the
+// word offset of the shuffle in its stream, a multiple of 8 (0: BALL; attempt t of a challenge: lsr_ring_challenge_kernels.hpp)
+__device__ __forceinline__ uint32_t ball_draw(const RingStream st, uint32_t domain, uint32_t kappa, uint32_t s, uint32_t i, uint64_t word,
+                                              uint32_t base = 0) {
+    const uint32_t width = 32 - __clz(i);                   // bitlen((i + 1) - 1)
+    const uint32_t fields = 63 / width;
+    const uint64_t mask = (1ull << width) - 1, m = (uint64_t)i + 1;
+    uint64_t r;
+    if (ring_sample_scan(word, 0, fields, width, mask, m, r)) return (uint32_t)r;
+    uint64_t w[8];
+    for (uint32_t a = 1; a < kRingSampleMaxWords; ++a) {
+        const uint32_t x = base + a * kappa + s;             // below 64 n <= 2^28 (a challenge: below 2^18 past its base)
+        stream_block(st.key, domain, st.index, x >> 3, w);
+        uint64_t pick = w[0];
+#pragma unroll
+        for (int t = 1; t < 8; ++t) pick = (x & 7u) == (uint32_t)t ? w[t] : pick;
+        word = pick;
+        if (ring_sample_scan(word, 0, fields, width, mask, m, r)) return (uint32_t)r;
+    }
+    return (uint32_t)ring_sample_last_resort(word, mask, m);
+}
+
 // Magnitudes of COUNT samples at once: first k with cdf63[k] >= u[s] (cdf63 = table >> 1, non-decreasing, last entry 2^63 - 1;
 // u = stream word >> 1) — the value the reference's scan selects (utils.cpp:101-108) — computed the way the reference computes
 // it: a branch-free pass over the WHOLE table, count += (cdf63[k] < u).  Every lane reads the same LDS word per step (a
