@@ -621,6 +621,82 @@ int lsr_ntt_ring_challenge_batch_device(const NttContext* ctx, uint64_t* d_out, 
                                         uint32_t kappa2, uint64_t opnorm_bound, uint32_t max_tries, const uint64_t* d_keys,
                                         size_t components, uint32_t domain, uint64_t index_base, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: bit-packed ring elements ---------------- */
+/* lsr_ntt_ring_pack_batch(_device), lsr_ntt_ring_unpack_batch(_device): the bytes of a proof message from short ring elements and
+ * back — base-2^b digits of lsr_ntt_ring_decompose_batch (whose range [-B/2, B/2 - 1] is exactly that of a
+ * b-bit two's-complement field), folded witnesses with a known l-infinity bound, ternary and BALL elements (2 bits), uniform
+ * elements (bitlen(q - 1) bits) — instead of one 64-bit word per coefficient.
+ *
+ * An element is n coefficients x[0..n) of a context (canonical residues, natural order).
+ * `bits` lies in [1, 63]; `mode` is one of two new macros.
+ *
+ * - `LSR_RING_PACK_CENTRED` (0):
+ *   - v = x if x <= (q-1)/2, else x - q, which is `ring_linf`'s centring.
+ *   - v is *in range* iff -2^(bits-1) <= v <= 2^(bits-1) - 1.
+ *   - The field is v mod 2^bits, in two's complement.
+ * - `LSR_RING_PACK_RESIDUE` (1):
+ *   - x is in range iff x < 2^bits.
+ *   - The field is the low `bits` bits of x.
+ * - Stream:
+ *   - Bit b of field i is bit i*bits + b of the element's bit stream.
+ *   - Stream bit t is bit t mod 64 of word floor(t/64).
+ *   - An element occupies W = ceil(n*bits/64) words; `size_t lsr_ring_pack_words(uint32_t n, unsigned bits)` returns W on the host,
+ *     and 0 for bits outside [1, 63].
+ *   - Bits from n*bits upward in the last word are zero. That can only happen at n < 64; for n >= 64 the packed elements are
+ *     contiguous with no padding.
+ * - **pack**: x [count][n] -> out [count][W], status [count] (int32).
+ *   - status = -1 if some word of the element is >= q. This outranks everything, as in `ring_project`.
+ *   - status = 0 if none is >= q but some coefficient is out of range.
+ *   - status = 1 otherwise.
+ *   - Whatever the status, every field is the low `bits` bits of v (CENTRED) or of x (RESIDUE); for a word >= q it is the low bits
+ *     of the word itself.
+ *   - The output is therefore defined for every input, an element spread over many workgroups needs no second pass, and other
+ *     elements are unaffected.
+ * - **unpack**: in [count][W] -> out [count][n], status [count].
+ *   - CENTRED: sign-extend the field to v. It is valid iff |v| <= (q-1)/2, and the word is v or q + v.
+ *   - RESIDUE: the field f is valid iff f < q, and the word is f.
+ *   - An invalid field writes the word 0 and makes the status 0.
+ *   - A non-zero padding bit makes the status 0. Otherwise the status is 1.
+ *   - A status-1 decode is the unique preimage: pack(unpack(w)) = w and unpack(pack(x)) = x with both statuses 1. This uniqueness
+ *     is what a Fiat-Shamir verifier needs.
+ *   - Every word of `out` is below q, whatever came in.
+ * - `unsigned lsr_ring_pack_min_bits(uint64_t q, int mode, uint64_t bound)`, host only.
+ *   - CENTRED: it returns the smallest number of bits whose range holds every |v| <= bound, which is bitlen(bound) + 1 for
+ *     bound >= 1.
+ *   - RESIDUE: it returns bitlen(bound).
+ *   - It returns 0 if that exceeds 63, or if bound is 0 or above (q-1)/2 (CENTRED) or q-1 (RESIDUE).
+ *
+ * The calls read only q and n of a context, like lsr_ntt_ring_sample_batch and lsr_ntt_ring_l2sq_batch: one integer code path
+ * serves negacyclic and cyclic contexts, every arithmetic flavour and every ring degree (2 .. 2^22), 64-bit moduli included (the
+ * centring compares are unsigned).
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL context, buffer or
+ * status; (2) unknown mode, or bits outside [1, 63].  (3) Then count == 0 is a no-op that returns 0.  Then (4) count * n or
+ * count * W (or their bytes) overflowing size_t; the output overlapping the input, the output overlapping status, status overlapping
+ * the input; a word buffer that is not 8-byte aligned or a status that is not 4-byte aligned; (5) no visible device.  (1), (2) and
+ * the overflow check read nothing of the context but its degree.
+ *
+ * The _device forms only enqueue kernels, in plain stream order: no workspace, nothing allocated, no event, no part in the
+ * context's ring ordering; they can be captured into a HIP graph from the first call.  Pack at n >= 64: a workgroup owns a tile of
+ * LSR_RING_PACK_TILE coefficients (two per lane with 16-byte loads) when x is 16-byte aligned, half as many (one per lane) when it
+ * is not; the tile's fields are staged in LDS and leave as coalesced 8-byte stores of whole output words.  Unpack at n >= 64 stages
+ * the tile's stream words in LDS and stores two words per lane (16 bytes) when out is 16-byte aligned.  Where an element spans several workgroups (n above the tile) a kernel first sets
+ * the statuses to 1 and the workgroups lower them with atomicMin; smaller elements get their status written directly.
+ * The plain forms take host buffers and return when out and status are complete: whole elements go through bounded device chunks
+ * on the context's work stream; pack uploads words and downloads only packed words and statuses, unpack is the reverse. */
+#define LSR_RING_PACK_CENTRED 0
+#define LSR_RING_PACK_RESIDUE 1
+#define LSR_RING_PACK_TILE 512
+size_t lsr_ring_pack_words(uint32_t n, unsigned bits) LSR_NOEXCEPT;
+unsigned lsr_ring_pack_min_bits(uint64_t q, int mode, uint64_t bound) LSR_NOEXCEPT;
+int lsr_ntt_ring_pack_batch(const NttContext* ctx, uint64_t* out, int32_t* status, const uint64_t* x, size_t count, int mode,
+                            unsigned bits) LSR_NOEXCEPT;
+int lsr_ntt_ring_pack_batch_device(const NttContext* ctx, uint64_t* d_out, int32_t* d_status, const uint64_t* d_x, size_t count, int mode,
+                                   unsigned bits, void* stream) LSR_NOEXCEPT;
+int lsr_ntt_ring_unpack_batch(const NttContext* ctx, uint64_t* out, int32_t* status, const uint64_t* in, size_t count, int mode,
+                              unsigned bits) LSR_NOEXCEPT;
+int lsr_ntt_ring_unpack_batch_device(const NttContext* ctx, uint64_t* d_out, int32_t* d_status, const uint64_t* d_in, size_t count,
+                                     int mode, unsigned bits, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

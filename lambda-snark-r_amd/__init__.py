@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PACK_CENTRED", "RING_PACK_RESIDUE", "ring_pack_words", "ring_pack_min_bits", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -391,6 +391,67 @@ class _RingChallenge:
                                                              components, domain, index_base, stream), "lsr_ntt_ring_challenge_batch_device")
 
 
+# batch.h LSR_RING_PACK_*: the field of a coefficient is its centred value in two's complement, or the residue itself
+RING_PACK_CENTRED, RING_PACK_RESIDUE = 0, 1
+
+
+def ring_pack_words(n, bits):
+    """W = ceil(n bits / 64), the words of one packed element (batch.h lsr_ring_pack_words); 0 for bits outside [1, 63].  Host only."""
+    if not 0 <= int(bits) < 2**32:
+        return 0
+    return _abi.lib().lsr_ring_pack_words(int(n), int(bits))
+
+
+def ring_pack_min_bits(q, mode, bound):
+    """The fewest bits whose range holds every |v| <= bound (RING_PACK_CENTRED) or every x <= bound (RING_PACK_RESIDUE) under q
+    (batch.h lsr_ring_pack_min_bits); 0 when there are none.  Host only."""
+    return _abi.lib().lsr_ring_pack_min_bits(int(q), int(mode), int(bound))
+
+
+class _RingPack:
+    """Bit-packed encoding and decoding of short ring elements on a context (``NttContext`` and ``CyclicNtt``; batch.h "bit-packed
+    ring elements")."""
+
+    def ring_pack(self, x, bits, mode=RING_PACK_CENTRED):
+        """x [n] or [count, n] canonical words -> (words uint64 [W] or [count, W], status int32 [] or [count]) with W =
+        ring_pack_words(n, bits).  status 1: every coefficient in range; 0: one is not (its field is truncated); -1: a word >= q."""
+        x_in = _u64_array(x, "x")
+        if x_in.ndim not in (1, 2) or x_in.shape[-1] != self.n:
+            raise ValueError("x must be [n] or [count, n]")
+        x2 = np.ascontiguousarray(x_in.reshape(-1, self.n))
+        out = np.zeros((x2.shape[0], ring_pack_words(self.n, bits)), dtype=np.uint64)
+        status = np.zeros(x2.shape[0], dtype=np.int32)
+        _check(self._lib.lsr_ntt_ring_pack_batch(self._h, out.ctypes.data, status.ctypes.data, x2.ctypes.data, x2.shape[0], int(mode), int(bits)),
+               "lsr_ntt_ring_pack_batch")
+        return (out[0], status[0]) if x_in.ndim == 1 else (out, status)
+
+    def ring_pack_device(self, d_out, d_status, d_x, count, bits, mode=RING_PACK_CENTRED, stream=0):
+        """Device buffers: out [count][W], status int32 [count], x [count][n]; 8-byte aligned.  Asynchronous on `stream`; enqueues
+        only, allocates nothing."""
+        _check(self._lib.lsr_ntt_ring_pack_batch_device(self._h, d_out, d_status, d_x, count, int(mode), int(bits), stream),
+               "lsr_ntt_ring_pack_batch_device")
+
+    def ring_unpack(self, words, bits, mode=RING_PACK_CENTRED):
+        """words [W] or [count, W] -> (x uint64 [n] or [count, n], status int32 [] or [count]).  status 1: the canonical encoding of x;
+        0: an invalid field (its word is 0) or a non-zero padding bit — CHECK IT before the data is used."""
+        w_in = _u64_array(words, "words")
+        wpe = ring_pack_words(self.n, bits)
+        if w_in.ndim not in (1, 2) or (wpe and w_in.shape[-1] != wpe):
+            raise ValueError("words must be [W] or [count, W] with W = ring_pack_words(n, bits)")
+        w2 = np.ascontiguousarray(w_in.reshape(w_in.shape[0] if w_in.ndim == 2 else 1, -1))
+        out = np.zeros((w2.shape[0], self.n), dtype=np.uint64)
+        status = np.zeros(w2.shape[0], dtype=np.int32)
+        _check(self._lib.lsr_ntt_ring_unpack_batch(self._h, out.ctypes.data, status.ctypes.data, w2.ctypes.data, w2.shape[0], int(mode), int(bits)),
+               "lsr_ntt_ring_unpack_batch")
+        return (out[0], status[0]) if w_in.ndim == 1 else (out, status)
+
+    def ring_unpack_device(self, d_out, d_status, d_in, count, bits, mode=RING_PACK_CENTRED, stream=0):
+        """Device buffers: out [count][n], status int32 [count], in [count][W]; 8-byte aligned.  Asynchronous on `stream`; enqueues
+        only, allocates nothing."""
+        _check(self._lib.lsr_ntt_ring_unpack_batch_device(self._h, d_out, d_status, d_in, count, int(mode), int(bits), stream),
+               "lsr_ntt_ring_unpack_batch_device")
+
+
 class _RingFold:
     """Fold of ring vectors by ring-valued challenges on a context (``NttContext`` and ``CyclicNtt``; batch.h)."""
 
@@ -745,7 +806,7 @@ class _RingGram:
                "lsr_ntt_ring_quadform_batch_device")
 
 
-class NttContext(_RingGadget, _RingSample, _RingChallenge, _RingFold, _RingGalois, _RingNorm, _RingScalar, _RingGram):
+class NttContext(_RingGadget, _RingSample, _RingChallenge, _RingPack, _RingFold, _RingGalois, _RingNorm, _RingScalar, _RingGram):
     """RAII handle over ``NttContext*`` (cpp-core/include/lambda_snark/ntt.h:25-41)."""
 
     def __init__(self, q, n, device=-1):
@@ -1351,7 +1412,7 @@ def prover_max_log2_size():
     return int(_abi.lib().lsr_prover_max_log2_size())
 
 
-class CyclicNtt(_RingGadget, _RingSample, _RingChallenge, _RingFold, _RingGalois, _RingNorm, _RingScalar, _RingGram):
+class CyclicNtt(_RingGadget, _RingSample, _RingChallenge, _RingPack, _RingFold, _RingGalois, _RingNorm, _RingScalar, _RingGram):
     """The transform pair of rust-api/lambda-snark/src/ntt.rs: ``forward(coeffs)`` = ``ntt_forward(coeffs, modulus, omega)``
     (natural order in and out), ``inverse(evals)`` = ``ntt_inverse``.  One handle per (modulus, n, omega).  n above 2^17 (up to 2^22,
     NTT_MODULUS only) goes through ``lsr_cyclic_ntt_context_create_large``."""

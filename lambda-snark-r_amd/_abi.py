@@ -154,6 +154,12 @@ SIGNATURES = {
     "lsr_ntt_ring_opnorm_batch_device": (c_int, [vp, vp, c_size, vp, vp]),
     "lsr_ntt_ring_challenge_batch": (c_int, [vp, vp, vp, c_size, u32, u32, u64, u32, vp, c_size, u32, u64]),
     "lsr_ntt_ring_challenge_batch_device": (c_int, [vp, vp, vp, c_size, u32, u32, u64, u32, vp, c_size, u32, u64, vp]),
+    "lsr_ring_pack_words": (c_size, [u32, ctypes.c_uint]),
+    "lsr_ring_pack_min_bits": (ctypes.c_uint, [u64, c_int, u64]),
+    "lsr_ntt_ring_pack_batch": (c_int, [vp, vp, vp, vp, c_size, c_int, ctypes.c_uint]),
+    "lsr_ntt_ring_pack_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_int, ctypes.c_uint, vp]),
+    "lsr_ntt_ring_unpack_batch": (c_int, [vp, vp, vp, vp, c_size, c_int, ctypes.c_uint]),
+    "lsr_ntt_ring_unpack_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_int, ctypes.c_uint, vp]),
     "lsr_sample_gaussian_seeded": (c_int, [vp, c_size, c_double, u64, u32, u64]),
     "lsr_gaussian_cdf": (c_size, [c_double, vp, c_size]),
     "lsr_lwe_context_create_seeded": (vp, [ctypes.POINTER(PublicParams), u64, c_int]),
