@@ -697,6 +697,73 @@ int lsr_ntt_ring_unpack_batch(const NttContext* ctx, uint64_t* out, int32_t* sta
 int lsr_ntt_ring_unpack_batch_device(const NttContext* ctx, uint64_t* d_out, int32_t* d_status, const uint64_t* d_in, size_t count,
                                      int mode, unsigned bits, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: ring products under any modulus (two NTT primes and CRT) ---------------- */
+/* An NttContext exists only for a prime q = 1 (mod 2n).  An LsrRingMod is "the ring Z_q[X]/(X^n + 1)" for ANY q >= 2 — a prime
+ * = 5 (mod 8), Kyber's 3329 at n = 256, a power of two — as long as the products fit the two primes below.
+ *
+ * - Primes: p1, p2 are the two 44-bit NTT primes of an RNS commitment context of the same n (lsr_rns_commit_moduli): p1 the default
+ *   commitment modulus for n, p2 the largest 44-bit prime = 1 (mod 2n) other than p1; both in (2^43, 2^44), P = p1 p2.
+ *   lsr_ring_mod_primes(n, primes) reports them on the host (0, or -1 when n is no power of two in [2, 131072]).  The handle owns
+ *   one ordinary negacyclic context per prime; lsr_ring_mod_prime_context(h, i), i in {0, 1}, lends it (NULL otherwise; never free it).
+ * - Centred representative (the toolkit's convention): for x in [0, q), v = x if x <= floor(q/2), else x - q.  With h = floor(q/2),
+ *   |v| <= h.
+ * - Capacity: max_terms = floor(((P - 1)/2) / (n h^2)) (128-bit host arithmetic, saturated at SIZE_MAX).  A sum of `terms`
+ *   products of ring elements has coefficients of magnitude at most terms n h^2, so up to max_terms it is recovered exactly from its
+ *   residues mod P.  lsr_ring_mod_capacity(q, n) computes it without a device; lsr_ring_mod_max_terms(h) reads it (0 on NULL).
+ * - Admissible (q, n): q >= 2, n a power of two in [2, 131072], the two primes exist, max_terms >= 1 (capacity returns 0 otherwise).
+ *   Then h < 2^43 < p_i: the residue of v mod p_i is v, or v + p_i for a negative v.  lsr_ring_mod_create refuses everything else
+ *   (NULL and lsr_last_error naming the rule).  lsr_ring_mod_free is NULL-safe and waits for the handle's pending work.
+ *
+ * The two streaming kernels, at every n the handle admits, device buffers, asynchronous on `stream`:
+ * - lsr_ring_mod_lift_batch_device(h, i, d_out, d_x, count): words mod q (count words: any number of polynomials) -> canonical
+ *   residues mod p_i of their centred representatives.  d_out may be d_x itself.
+ * - lsr_ring_mod_reduce_batch_device(h, d_out, d_r0, d_r1, count, accumulate): for residues r0 < p1, r1 < p2, X is the unique
+ *   integer in [-(P-1)/2, (P-1)/2] with those residues; the output is X mod q in [0, q), or with accumulate != 0 that value added
+ *   mod q to the word d_out holds (which is below q).  d_out may be d_r0 or d_r1 itself.
+ * Both are one pass with 16-byte accesses per lane where every buffer is 16-byte aligned (8-byte ones otherwise), use no workspace,
+ * take no part in any ordering and can be captured into a HIP graph from the first call.  Refusals, in this order: NULL handle or
+ * buffer; (lift) i outside {0, 1}; then count == 0 is a no-op that returns 0; then count * 8 overflowing size_t, a buffer that is
+ * not 8-byte aligned, an output that overlaps an operand without being it; no visible device.
+ *
+ * Composition.  Together with lsr_ring_mod_prime_context these two calls put every bilinear call of the toolkit under q: lift the
+ * operands for prime 0 and for prime 1, run the call on each prime's context, reduce the two results.  That covers
+ * lsr_ntt_ring_mul_batch, lsr_ntt_ring_dot_batch, lsr_ntt_ring_fold_batch, lsr_ntt_ring_matvec_batch, lsr_ntt_ring_gram_batch,
+ * lsr_ntt_ring_gram_sym2_batch and lsr_ntt_ring_dot_galois_batch, at every n.  The caller keeps ONE bound: the number of products
+ * summed per output must not exceed max_terms (a gram_sym2 entry sums two).  Longer sums are split by the caller and the parts
+ * reduced with `accumulate`.
+ *
+ * The fused calls, n <= 4096:
+ *   c_j = a_j b_j (mul) and c_j = sum_{i < terms} a_{j,i} b_{j,i} (dot) in Z_q[X]/(X^n + 1), canonical; inputs in [0, q).
+ * Shapes, b_rows in {1, batch} and the host-staged plain forms are those of lsr_ntt_ring_mul_batch and lsr_ntt_ring_dot_batch; mul's c
+ * may alias a or b exactly, dot's c may not overlap an operand.  One launch per prime of a tile kernel that centres and re-bases
+ * the operands as it loads them — the lifted operands never exist in memory — then one reduce launch.  A shared b (b_rows == 1,
+ * batch > 1) is lifted and transformed once per prime.  terms above max_terms are taken in groups of at most max_terms, each reduced
+ * with accumulate: exactness never depends on the caller knowing the capacity.
+ * Refusals (-1 and lsr_last_error, before any device work), in this order: NULL handle or buffer; b_rows not in {1, batch}; (dot)
+ * terms == 0.  Then batch == 0 is a no-op that returns 0.  Then: n above 4096 (the message names the composed route above); terms
+ * above LSR_RING_DOT_MAX_TERMS; sizes overflowing size_t; c overlapping an operand; no visible device.
+ * Workspace, ordering and graph capture: the workspace belongs to the handle, its size depends on n alone and lsr_ring_mod_create
+ * allocates it, so the _device forms capture into a HIP graph from the first call.  The batch is taken in chunks.  Calls on one
+ * handle are ordered by an event of the handle's own (as a context's ring calls are); a captured call is not bracketed. */
+typedef struct LsrRingMod LsrRingMod;
+LsrRingMod* lsr_ring_mod_create(uint64_t q, uint32_t n, int device) LSR_NOEXCEPT;
+void lsr_ring_mod_free(LsrRingMod* h) LSR_NOEXCEPT;
+uint64_t lsr_ring_mod_modulus(const LsrRingMod* h) LSR_NOEXCEPT;
+const NttContext* lsr_ring_mod_prime_context(const LsrRingMod* h, int i) LSR_NOEXCEPT;
+size_t lsr_ring_mod_max_terms(const LsrRingMod* h) LSR_NOEXCEPT;
+int lsr_ring_mod_primes(uint32_t n, uint64_t primes[2]) LSR_NOEXCEPT;
+size_t lsr_ring_mod_capacity(uint64_t q, uint32_t n) LSR_NOEXCEPT;
+int lsr_ring_mod_lift_batch_device(const LsrRingMod* h, int i, uint64_t* d_out, const uint64_t* d_x, size_t count, void* stream) LSR_NOEXCEPT;
+int lsr_ring_mod_reduce_batch_device(const LsrRingMod* h, uint64_t* d_out, const uint64_t* d_r0, const uint64_t* d_r1, size_t count,
+                                     int accumulate, void* stream) LSR_NOEXCEPT;
+int lsr_ring_mod_mul_batch(const LsrRingMod* h, uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t b_rows) LSR_NOEXCEPT;
+int lsr_ring_mod_mul_batch_device(const LsrRingMod* h, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t b_rows,
+                                  void* stream) LSR_NOEXCEPT;
+int lsr_ring_mod_dot_batch(const LsrRingMod* h, uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t terms,
+                           size_t b_rows) LSR_NOEXCEPT;
+int lsr_ring_mod_dot_batch_device(const LsrRingMod* h, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms,
+                                  size_t b_rows, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

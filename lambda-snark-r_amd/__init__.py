@@ -26,7 +26,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PACK_CENTRED", "RING_PACK_RESIDUE", "ring_pack_words", "ring_pack_min_bits", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PACK_CENTRED", "RING_PACK_RESIDUE", "ring_pack_words", "ring_pack_min_bits", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "RingMod", "ring_mod_primes", "ring_mod_capacity", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -918,6 +918,128 @@ class NttContext(_RingGadget, _RingSample, _RingChallenge, _RingPack, _RingFold,
     def ring_matrix_device(self, d_m, rows, cols, stream=0):
         """A RingMatrix of the device buffer d_m [rows][cols][n], asynchronous on `stream`."""
         return _ring_matrix_device(self, d_m, rows, cols, stream)
+
+
+def ring_mod_primes(n):
+    """``lsr_ring_mod_primes``: the two 44-bit NTT primes (p1, p2) a RingMod of ring degree n computes under (host only)."""
+    out = (ctypes.c_uint64 * 2)()
+    if _abi.lib().lsr_ring_mod_primes(int(n), out) != 0:
+        raise ValueError("unsupported ring degree")
+    return int(out[0]), int(out[1])
+
+
+def ring_mod_capacity(q, n):
+    """``lsr_ring_mod_capacity``: how many products mod q, degree n, one sum may hold (max_terms); 0 when (q, n) is not admissible
+    (host only)."""
+    if not (0 <= int(q) < 2**64 and 0 <= int(n) < 2**32):
+        return 0
+    return int(_abi.lib().lsr_ring_mod_capacity(int(q), int(n)))
+
+
+class _BorrowedNttContext(NttContext):
+    """One of the two prime contexts of a RingMod: every member of NttContext, owned by the RingMod (close() only lets go)."""
+
+    def __init__(self, owner, handle, q, n):   # pylint: disable=super-init-not-called
+        self._lib, self._h, self._owner = owner._lib, handle, owner
+        self.q, self.n = int(q), int(n)
+
+    def close(self):
+        self._h = self._owner = None
+
+    __del__ = close
+
+
+class RingMod:
+    """RAII handle over ``LsrRingMod*``: the ring Z_q[X]/(X^n + 1) for any modulus q >= 2 through two NTT primes and CRT (batch.h
+    "ring products under any modulus")."""
+
+    def __init__(self, q, n, device=-1):
+        self._lib = _abi.lib()
+        self.q, self.n = int(q), int(n)
+        if not (0 <= self.q < 2**64 and 0 <= self.n < 2**32):
+            raise CoreError(f"lsr_ring_mod_create({q}, {n}): out of range")
+        self._h = self._lib.lsr_ring_mod_create(self.q, self.n, device)
+        if not self._h:
+            raise CoreError(f"lsr_ring_mod_create({q}, {n}) returned NULL: {_abi.last_error()}")
+        self._primes = ring_mod_primes(self.n)
+        self._contexts = [None, None]
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def primes(self):
+        return self._primes
+
+    @property
+    def max_terms(self):
+        return int(self._lib.lsr_ring_mod_max_terms(self._h))
+
+    def prime_context(self, i):
+        """The handle's negacyclic NttContext of prime i (0 or 1), borrowed: valid until this RingMod is closed."""
+        if i not in (0, 1):
+            raise ValueError("the prime index must be 0 or 1")
+        if self._contexts[i] is None:
+            self._contexts[i] = _BorrowedNttContext(self, self._lib.lsr_ring_mod_prime_context(self._h, i), self._primes[i], self.n)
+        return self._contexts[i]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for ctx in self._contexts:
+                if ctx is not None:
+                    ctx.close()
+            self._lib.lsr_ring_mod_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def lift_device(self, i, d_out, d_x, count, stream=0):
+        """d_out[e] = the residue mod prime i of the centred representative of d_x[e], e < count words; d_out may be d_x."""
+        _check(self._lib.lsr_ring_mod_lift_batch_device(self._h, i, d_out, d_x, count, stream), "lsr_ring_mod_lift_batch_device")
+
+    def reduce_device(self, d_out, d_r0, d_r1, count, accumulate=False, stream=0):
+        """d_out[e] = (or, accumulate: += mod q) the word mod q of the centred integer with residues d_r0[e] mod p1, d_r1[e] mod p2."""
+        _check(self._lib.lsr_ring_mod_reduce_batch_device(self._h, d_out, d_r0, d_r1, count, int(bool(accumulate)), stream),
+               "lsr_ring_mod_reduce_batch_device")
+
+    def mul(self, a, b):
+        """a * b mod (X^n + 1, q): a is [n] or [batch, n], b is [n] (shared by every product) or [batch, n]; numpy in and out."""
+        a2 = np.ascontiguousarray(_u64_array(a).reshape(-1, self.n))
+        b2 = np.ascontiguousarray(_u64_array(b).reshape(-1, self.n))
+        out = np.empty_like(a2)
+        _check(self._lib.lsr_ring_mod_mul_batch(self._h, out.ctypes.data, a2.ctypes.data, b2.ctypes.data, a2.shape[0], b2.shape[0]), "lsr_ring_mod_mul_batch")
+        return out.reshape(np.shape(a)) if np.ndim(a) == 1 else out
+
+    def mul_device(self, d_c, d_a, d_b, batch, b_rows, stream=0):
+        """Device buffers [batch][n] (b: [b_rows][n], b_rows 1 or batch), asynchronous on `stream`."""
+        _check(self._lib.lsr_ring_mod_mul_batch_device(self._h, d_c, d_a, d_b, batch, b_rows, stream), "lsr_ring_mod_mul_batch_device")
+
+    def dot(self, a, b):
+        """sum_i a_i * b_i mod (X^n + 1, q): a is [terms, n] or [batch, terms, n], b is [terms, n] (shared by every output) or
+        [batch, terms, n]; numpy in and out ([n] or [batch, n])."""
+        a_in = _u64_array(a)
+        if a_in.ndim < 2 or a_in.shape[-1] != self.n:
+            raise ValueError("a must be [terms, n] or [batch, terms, n]")
+        terms = a_in.shape[-2]
+        if terms == 0:
+            raise ValueError("terms must be at least 1")
+        a3 = np.ascontiguousarray(a_in.reshape(-1, terms, self.n))
+        b3 = np.ascontiguousarray(_u64_array(b).reshape(-1, terms, self.n))
+        out = np.empty((a3.shape[0], self.n), dtype=np.uint64)
+        _check(self._lib.lsr_ring_mod_dot_batch(self._h, out.ctypes.data, a3.ctypes.data, b3.ctypes.data, a3.shape[0], terms, b3.shape[0]),
+               "lsr_ring_mod_dot_batch")
+        return out[0] if a_in.ndim == 2 else out
+
+    def dot_device(self, d_c, d_a, d_b, batch, terms, b_rows, stream=0):
+        """Device buffers: c [batch][n], a [batch][terms][n], b [b_rows][terms][n] (b_rows 1 or batch), asynchronous on `stream`."""
+        _check(self._lib.lsr_ring_mod_dot_batch_device(self._h, d_c, d_a, d_b, batch, terms, b_rows, stream), "lsr_ring_mod_dot_batch_device")
 
 
 class Params:

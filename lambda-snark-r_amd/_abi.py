@@ -160,6 +160,19 @@ SIGNATURES = {
     "lsr_ntt_ring_pack_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_int, ctypes.c_uint, vp]),
     "lsr_ntt_ring_unpack_batch": (c_int, [vp, vp, vp, vp, c_size, c_int, ctypes.c_uint]),
     "lsr_ntt_ring_unpack_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_int, ctypes.c_uint, vp]),
+    "lsr_ring_mod_create": (vp, [u64, u32, c_int]),
+    "lsr_ring_mod_free": (None, [vp]),
+    "lsr_ring_mod_modulus": (u64, [vp]),
+    "lsr_ring_mod_prime_context": (vp, [vp, c_int]),
+    "lsr_ring_mod_max_terms": (c_size, [vp]),
+    "lsr_ring_mod_primes": (c_int, [u32, vp]),
+    "lsr_ring_mod_capacity": (c_size, [u64, u32]),
+    "lsr_ring_mod_lift_batch_device": (c_int, [vp, c_int, vp, vp, c_size, vp]),
+    "lsr_ring_mod_reduce_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_int, vp]),
+    "lsr_ring_mod_mul_batch": (c_int, [vp, vp, vp, vp, c_size, c_size]),
+    "lsr_ring_mod_mul_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, vp]),
+    "lsr_ring_mod_dot_batch": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size]),
+    "lsr_ring_mod_dot_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, vp]),
     "lsr_sample_gaussian_seeded": (c_int, [vp, c_size, c_double, u64, u32, u64]),
     "lsr_gaussian_cdf": (c_size, [c_double, vp, c_size]),
     "lsr_lwe_context_create_seeded": (vp, [ctypes.POINTER(PublicParams), u64, c_int]),

@@ -284,19 +284,7 @@ static LweContext* create_lwe_context(const PublicParams* params, uint64_t key_s
 }
 
 static void destroy_lwe_context(LweContext* c);
-// (q1, q2) of an RNS context for ring degree n: q1 = what a default context picks, q2 = the largest 44-bit prime = 1 (mod 2n) other than q1
-static bool rns_moduli_for(uint32_t n, uint64_t out[2]) {
-    const uint64_t q1 = select_commit_modulus(0, n);
-    if (!q1) return false;
-    uint64_t q2 = largest_prime_congruent_one(2ull * n, 44);
-    if (q2 == q1) {
-        for (q2 = q1 - 2ull * n; q2 > (1ull << 43) && !is_prime_u64(q2); q2 -= 2ull * n) {}
-        if (q2 <= (1ull << 43)) return false;
-    }
-    out[0] = q1;
-    out[1] = q2;
-    return q2 != 0;
-}
+// ((q1, q2) of an RNS context for ring degree n: rns_moduli_for, lsr_host_math.hpp)
 // Two sibling single-prime contexts with the same keys.  params->modulus is ignored.
 static LweContext* create_rns_context(const PublicParams* params, uint64_t key_seed, int device) {
     if (!params) {

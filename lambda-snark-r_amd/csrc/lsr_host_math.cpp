@@ -201,6 +201,29 @@ uint64_t plain_modulus_for(uint32_t n) {
     return largest_prime_congruent_one(2ull * n, 20);   // SEAL PlainModulus::Batching(n, 20)
 }
 
+bool rns_moduli_for(uint32_t n, uint64_t out[2]) {
+    const uint64_t q1 = select_commit_modulus(0, n);
+    if (!q1) return false;
+    uint64_t q2 = largest_prime_congruent_one(2ull * n, 44);
+    if (q2 == q1) {
+        for (q2 = q1 - 2ull * n; q2 > (1ull << 43) && !is_prime_u64(q2); q2 -= 2ull * n) {}
+        if (q2 <= (1ull << 43)) return false;
+    }
+    out[0] = q1;
+    out[1] = q2;
+    return q2 != 0;
+}
+
+size_t ring_mod_capacity(uint64_t q, uint32_t n) {
+    uint64_t p[2];
+    if (q < 2 || !rns_moduli_for(n, p)) return 0;
+    const uint64_t h = q >> 1;
+    if (h >> 43) return 0;                                  // n h^2 >= 2^87 > (P - 1) / 2; below, n h^2 < 2^17 2^86 fits 128 bits
+    const u128 bound = ((u128)p[0] * p[1] - 1) / 2, term = (u128)n * h * h;
+    const u128 terms = bound / term;
+    return terms > (u128)SIZE_MAX ? SIZE_MAX : (size_t)terms;
+}
+
 uint64_t os_entropy64() {
     uint64_t v = 0;
     os_entropy_fill(&v, sizeof v);

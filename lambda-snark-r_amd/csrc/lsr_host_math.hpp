@@ -71,6 +71,14 @@ uint32_t gaussian_scan_entries(const std::vector<uint64_t>& cdf);
 // Commitment parameter selection (DESIGN.md "Commitment definition").
 uint64_t select_commit_modulus(uint64_t requested, uint32_t n);
 uint64_t plain_modulus_for(uint32_t n);
+// The two 44-bit NTT primes of ring degree n, shared by the RNS commitment contexts (lsr_commit.hip) and the ring
+// handles of an arbitrary modulus (lsr_ring_mod.hip, §5p): out[0] = what a default commitment context picks, out[1] = the largest
+// 44-bit prime = 1 (mod 2n) other than out[0]; both in (2^43, 2^44).  false: n is no power of two in [2, 131072] or there is no second prime.
+bool rns_moduli_for(uint32_t n, uint64_t out[2]);
+// How many products of ring elements mod q, degree n, may be summed and still be recovered from residues mod the two primes above
+// (P = p1 p2): floor(((P - 1) / 2) / (n h^2)) with h = floor(q / 2), saturated at SIZE_MAX.  0: (q, n) is not admissible — q < 2, n
+// not a power of two in [2, 131072], no prime pair, or not even one product fits.
+size_t ring_mod_capacity(uint64_t q, uint32_t n);
 
 uint64_t os_entropy64();
 

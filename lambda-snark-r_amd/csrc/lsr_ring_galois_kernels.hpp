@@ -88,11 +88,30 @@ __global__ void __launch_bounds__(kThreads) ring_automorphism_kernel(uint64_t* _
 // workgroup-uniform, so a word costs one add and one mask over the plain kernel's addressing — but lane and register parts no longer
 // split in the SOURCE offset, which is one per-lane byte offset.  The ragged-tile clips survive: the resource spans the outputs the
 // tile has, and a word of an absent output gets the out-of-range lane offset (reads 0; -0 = 0).
-template <class A, int LT, bool BHAT>
-__global__ void __launch_bounds__(kThreads) ntt_tile_ring_dot_galois(uint64_t* c, const uint64_t* __restrict__ a, const uint64_t* __restrict__ b,
-                                                                       size_t total, uint32_t nterms, size_t a_os, size_t b_os, uint32_t flags,
-                                                                       GaloisParams g, ModParams p, const typename A::twid* __restrict__ fwd,
-                                                                       const typename A::twid* __restrict__ inv, RoundConsts<A> cs) {
+//
+// The body is shared with the lift-on-load family below through a word source `Src`:
+//   Src::kPermuted   the words of a are fetched through src.g (GaloisSource) or at the plain kernel's addresses (LiftSource);
+//   src.word(x)      (not kPermuted) what becomes of a raw operand word of a or b before A::load.
+struct GaloisSource {
+    static constexpr bool kPermuted = true;
+    GaloisParams g;
+    __device__ __forceinline__ uint32_t lane_product(uint32_t j) const { return j * g.h; }   // the lane part of j h
+};
+// A word x in [0, q) of a ring element mod q as the canonical residue mod a prime p of its centred representative (lsr_ring_mod.hip,
+// DESIGN.md §5p): x itself up to half = floor(q / 2), else x - q + p.  rebase = p - q mod 2^64; the sum wraps to the true value,
+// which lies in (p - half, p) because half < 2^43 < p.
+struct LiftSource {
+    static constexpr bool kPermuted = false;
+    uint64_t half, rebase;
+    __device__ __forceinline__ uint32_t lane_product(uint32_t) const { return 0u; }
+    __device__ __forceinline__ uint64_t word(uint64_t x) const { return x <= half ? x : x + rebase; }
+};
+
+template <class A, int LT, bool BHAT, class Src>
+__device__ __forceinline__ void tile_ring_dot_from_source(uint64_t* c, const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, size_t total,
+                                                          uint32_t nterms, size_t a_os, size_t b_os, uint32_t flags, Src src, ModParams p,
+                                                          const typename A::twid* __restrict__ fwd, const typename A::twid* __restrict__ inv,
+                                                          RoundConsts<A> cs) {
     __shared__ uint64_t lds[kLdsWords];
     using elem = typename A::elem;
     using twid = typename A::twid;
@@ -124,18 +143,25 @@ __global__ void __launch_bounds__(kThreads) ntt_tile_ring_dot_galois(uint64_t* c
     auto operand_word = [&](rsrc_t r, uint32_t os, int k) -> uint64_t {
         const uint32_t reg = reg_offset<LO0, R0>(k);
         const bool present = !kStrided || (base0 >> LT) + (reg >> LT) < outputs;
-        return buf_load64<kAuxStream>(r, present ? operand_bytes(base0, os) : kRingDotOutOfRange, operand_bytes(reg, os));
+        const uint64_t raw = buf_load64<kAuxStream>(r, present ? operand_bytes(base0, os) : kRingDotOutOfRange, operand_bytes(reg, os));
+        if constexpr (Src::kPermuted) return raw;
+        else return src.word(raw);
     };
-    // Word k of round 0 of sigma_g(a): the same clips, the source word s & (n - 1) of the word's own output, negated where s & n
-    const uint32_t lane_jh = (base0 & nmask) * g.h;
-    auto galois_word = [&](rsrc_t r, uint32_t os, int k) -> uint64_t {
-        const uint32_t reg = reg_offset<LO0, R0>(k);
-        const uint32_t output = kStrided ? (base0 >> LT) + (reg >> LT) : 0u;
-        const uint32_t s = (lane_jh + (reg & nmask) * g.h) & g.mask;
-        const uint32_t src = kStrided ? ((s & nmask) + output * os) * 8u : (s & nmask) * 8u;
-        // (not a streaming load: the eight words of a cache line go to eight different lanes)
-        const uint64_t word = buf_load64(r, output < outputs ? src : kRingDotOutOfRange, 0);
-        return (s & n) ? galois_negate(word, p.q) : word;
+    // Word k of round 0 of a.  kPermuted, sigma_g(a): the same clips, the source word s & (n - 1) of the word's own output, negated
+    // where s & n
+    const uint32_t lane_jh = src.lane_product(base0 & nmask);
+    auto a_word = [&](rsrc_t r, uint32_t os, int k) -> uint64_t {
+        if constexpr (Src::kPermuted) {
+            const uint32_t reg = reg_offset<LO0, R0>(k);
+            const uint32_t output = kStrided ? (base0 >> LT) + (reg >> LT) : 0u;
+            const uint32_t s = (lane_jh + (reg & nmask) * src.g.h) & src.g.mask;
+            const uint32_t from = kStrided ? ((s & nmask) + output * os) * 8u : (s & nmask) * 8u;
+            // (not a streaming load: the eight words of a cache line go to eight different lanes)
+            const uint64_t word = buf_load64(r, output < outputs ? from : kRingDotOutOfRange, 0);
+            return (s & n) ? galois_negate(word, p.q) : word;
+        } else {
+            return operand_word(r, os, k);
+        }
     };
     const uint32_t a_step = (uint32_t)a_os, b_step = (uint32_t)b_os;                  // used when kStrided only: terms n <= 2^27 there
     // first inverse round's twiddles; SKIP_TOP when that round is also the transform's last stage
@@ -163,7 +189,7 @@ __global__ void __launch_bounds__(kThreads) ntt_tile_ring_dot_galois(uint64_t* c
         }
         const rsrc_t ra = make_rsrc(a_tile, operand_words(a_step) * 8u);
         if constexpr (BHAT) {
-            ring_forward_tile_from<A, LT, false, 0, false>(v, w, lds, [&](int k) { return galois_word(ra, a_step, k); }, ftab, block_pos, nmask, p,
+            ring_forward_tile_from<A, LT, false, 0, false>(v, w, lds, [&](int k) { return a_word(ra, a_step, k); }, ftab, block_pos, nmask, p,
                                                            [&](twid (&slot)[kRoundTwiddles]) {
                                                                if (last_term) inverse_first(slot);
                                                            });
@@ -178,7 +204,7 @@ __global__ void __launch_bounds__(kThreads) ntt_tile_ring_dot_galois(uint64_t* c
         } else {
             elem ah[kRegs];
             // a's last round prefetches b's first-round twiddles (round 0 of the same table) into the free slot
-            ring_forward_tile_from<A, LT, false, 0, false>(v, w, lds, [&](int k) { return galois_word(ra, a_step, k); }, ftab, block_pos, nmask, p,
+            ring_forward_tile_from<A, LT, false, 0, false>(v, w, lds, [&](int k) { return a_word(ra, a_step, k); }, ftab, block_pos, nmask, p,
                                                            [&](twid (&slot)[kRoundTwiddles]) {
                                                                load_round_twiddles<A, LO0, R0, false, false>(slot, base0, block_pos, nmask, p.logn, ftab);
                                                            });
@@ -240,6 +266,26 @@ __global__ void __launch_bounds__(kThreads) ntt_tile_ring_dot_galois(uint64_t* c
             __syncthreads();
         }
     });
+}
+
+template <class A, int LT, bool BHAT>
+__global__ void __launch_bounds__(kThreads) ntt_tile_ring_dot_galois(uint64_t* c, const uint64_t* __restrict__ a, const uint64_t* __restrict__ b,
+                                                                       size_t total, uint32_t nterms, size_t a_os, size_t b_os, uint32_t flags,
+                                                                       GaloisParams g, ModParams p, const typename A::twid* __restrict__ fwd,
+                                                                       const typename A::twid* __restrict__ inv, RoundConsts<A> cs) {
+    tile_ring_dot_from_source<A, LT, BHAT>(c, a, b, total, nterms, a_os, b_os, flags, GaloisSource{g}, p, fwd, inv, cs);
+}
+
+// c_j = sum_{i < nterms} a_{j,i} b_{j,i} mod the prime of `p`, where a and b hold words mod ANOTHER modulus q that are centred against q
+// and re-based to the prime as they are read (LiftSource): one of the two launches of lsr_ring_mod_dot_batch (lsr_ring_mod.hip).
+// Behind the load this is ntt_tile_ring_dot<A, LT, false, BHAT> on the operands lift(a), lift(b), which never exist in memory.  BHAT:
+// b holds transforms mod the prime and is read as it is.  An absent output's words read 0, and lift(0) = 0.
+template <class A, int LT, bool BHAT>
+__global__ void __launch_bounds__(kThreads) ntt_tile_ring_dot_lift(uint64_t* c, const uint64_t* __restrict__ a, const uint64_t* __restrict__ b,
+                                                                     size_t total, uint32_t nterms, size_t a_os, size_t b_os, uint32_t flags,
+                                                                     LiftSource lift, ModParams p, const typename A::twid* __restrict__ fwd,
+                                                                     const typename A::twid* __restrict__ inv, RoundConsts<A> cs) {
+    tile_ring_dot_from_source<A, LT, BHAT>(c, a, b, total, nterms, a_os, b_os, flags, lift, p, fwd, inv, cs);
 }
 
 }  // namespace lsr
