@@ -764,6 +764,70 @@ int lsr_ring_mod_dot_batch(const LsrRingMod* h, uint64_t* c, const uint64_t* a, 
 int lsr_ring_mod_dot_batch_device(const LsrRingMod* h, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms,
                                   size_t b_rows, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: resident matrices under any modulus (y = M x and y = M G^-1(x) on a ring handle) ---------------- */
+/* The module product with a public matrix — an Ajtai commitment t = A s, Kyber's A s, a commitment to the digits of a long witness —
+ * in Z_q[X]/(X^n + 1) for the q of an LsrRingMod, n <= 4096.  Every output is exact and canonical in [0, q).
+ *
+ * Capacity with a short operand (host only):
+ *   lsr_ring_mod_capacity_bounded(q, n, bound) = floor(((P - 1)/2) / (n floor(q/2) bound))
+ * counts the negacyclic products of one operand of centred magnitude <= floor(q/2) and one of magnitude <= bound that one sum may
+ * hold.  128-bit host arithmetic, saturated at SIZE_MAX as lsr_ring_mod_capacity; 0 for bound == 0, for bound > floor(q/2) and
+ * wherever lsr_ring_mod_capacity(q, n) is 0; lsr_ring_mod_capacity_bounded(q, n, floor(q/2)) == lsr_ring_mod_capacity(q, n).
+ *
+ * The matrix.  m is [rows][cols][n], words in [0, q).  The handle keeps two device copies: for each prime the forward transform (the
+ * order the context's transform writes) of the lifted entries.  Lifetime and ownership are lsr_ntt_ring_matrix_create's: create
+ * copies (the host form is complete on return, the device form enqueues on `stream` and later calls on other streams start behind
+ * it), the matrix is immutable, the handle h must outlive it, lsr_ring_mod_matrix_free is NULL-safe and waits for the matrix's ready
+ * event and for the handle's pending work; _rows, _cols and _row_block return 0 on NULL (_row_block: the rows of M one workgroup
+ * keeps in registers, that of the prime contexts' kernels).
+ * lsr_ring_mod_matrix_create_seeded: entry M[r][c] is the UNIFORM element of lsr_ntt_ring_sample_batch's definition with modulus q,
+ * one key and stream index index_base + r cols + c, sampled on the device; the handle is indistinguishable from _create_device of
+ * those words.  Complete on return.
+ * Limits: rows in [1, LSR_RING_MATVEC_MAX_ROWS], cols in [1, LSR_RING_DOT_MAX_TERMS], rows cols n 8 <= LSR_RING_MATVEC_MAX_MATRIX_BYTES
+ * per prime.
+ * Refusals of create (NULL and lsr_last_error naming the entry point, before any device work), in this order: NULL h or m / key;
+ * rows == 0; cols == 0; rows above its cap; cols above its cap; rows cols 16 above the byte cap; n above 4096 (the message names
+ * the composed route: lift M per prime, lsr_ntt_ring_matrix_create_device on lsr_ring_mod_prime_context, lift x, two
+ * lsr_ntt_ring_matvec_batch_device, reduce, with the columns in groups of max_terms); rows cols n 8 above the byte cap; (seeded)
+ * index_base + rows cols overflowing 64 bits; no visible device.
+ *
+ * The products.
+ *   lsr_ring_mod_matvec_batch:        x [batch][cols][n], y [batch][rows][n]:  y[j][r] = sum_c M[r][c] x[j][c] in R_q — word for word
+ *                                     lsr_ring_mod_dot_batch(h, ., x, M[r], batch, cols, 1) row by row.
+ *   lsr_ring_mod_matvec_gadget_batch: x [batch][xcols][n] with xcols digits == cols:  y = M G^-1(x), G^-1 as defined under "gadget
+ *                                     decomposition" above, taken against q: the centred word against floor(q/2), the offset off, digit
+ *                                     z_d in [-B/2, B/2 - 1], matrix column xc digits + d <- digit d of x[.][xc].  Word for word the
+ *                                     plain product on the decomposed vector, which never exists in memory.  (b, D) must be admissible
+ *                                     for q by the rule stated there; lsr_ring_gadget_min_digits(q, b) answers it for any q.
+ * Grouping rule: matrix columns are taken in groups, each reduced into y with accumulate from the second on — at most max_terms
+ * columns per group for the plain product, at most lsr_ring_mod_capacity_bounded(q, n, B/2) for the gadget product (a digit's
+ * magnitude is at most B/2); a gadget group may end between two digits of one column of x.  Exactness never depends on the caller
+ * knowing either capacity.
+ * Refusals of the products (-1 and lsr_last_error, before any device work), in this order: NULL mat or buffer; (gadget) base_log2
+ * outside [2, 32], digits == 0 or base_log2 digits > 64; (gadget) (b, D) not admissible for q; (gadget) cols % digits != 0.  Then
+ * batch == 0 is a no-op that returns 0.  Then: y overlapping x in address range; no visible device.
+ * The plain forms take host buffers through bounded device chunks on the first prime context's work stream and return when y is
+ * complete; the _device forms enqueue only.  Workspace, ordering and graph capture are the fused products': no allocation after
+ * create (the per-prime sums go to the handle's workspace in chunks of whole vectors or, where rows n exceeds 2^22 words, of one
+ * vector and a range of rows), calls on one handle are ordered by the handle's event, a captured call is not bracketed and the
+ * _device forms capture into a HIP graph from the first call. */
+typedef struct LsrRingModMatrix LsrRingModMatrix;
+size_t lsr_ring_mod_capacity_bounded(uint64_t q, uint32_t n, uint64_t bound) LSR_NOEXCEPT;
+LsrRingModMatrix* lsr_ring_mod_matrix_create(const LsrRingMod* h, const uint64_t* m, size_t rows, size_t cols) LSR_NOEXCEPT;
+LsrRingModMatrix* lsr_ring_mod_matrix_create_device(const LsrRingMod* h, const uint64_t* d_m, size_t rows, size_t cols, void* stream) LSR_NOEXCEPT;
+LsrRingModMatrix* lsr_ring_mod_matrix_create_seeded(const LsrRingMod* h, const uint64_t key[4], uint32_t domain, uint64_t index_base, size_t rows,
+                                                    size_t cols) LSR_NOEXCEPT;
+void lsr_ring_mod_matrix_free(LsrRingModMatrix* mat) LSR_NOEXCEPT;
+size_t lsr_ring_mod_matrix_rows(const LsrRingModMatrix* mat) LSR_NOEXCEPT;
+size_t lsr_ring_mod_matrix_cols(const LsrRingModMatrix* mat) LSR_NOEXCEPT;
+size_t lsr_ring_mod_matrix_row_block(const LsrRingModMatrix* mat) LSR_NOEXCEPT;
+int lsr_ring_mod_matvec_batch(const LsrRingModMatrix* mat, uint64_t* y, const uint64_t* x, size_t batch) LSR_NOEXCEPT;
+int lsr_ring_mod_matvec_batch_device(const LsrRingModMatrix* mat, uint64_t* d_y, const uint64_t* d_x, size_t batch, void* stream) LSR_NOEXCEPT;
+int lsr_ring_mod_matvec_gadget_batch(const LsrRingModMatrix* mat, uint64_t* y, const uint64_t* x, size_t batch, unsigned base_log2,
+                                     size_t digits) LSR_NOEXCEPT;
+int lsr_ring_mod_matvec_gadget_batch_device(const LsrRingModMatrix* mat, uint64_t* d_y, const uint64_t* d_x, size_t batch, unsigned base_log2,
+                                            size_t digits, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

@@ -16,6 +16,7 @@ All arithmetic happens in liblambda_snark_core.so (HIP, gfx950).  Nothing here c
 CPU fallback.  (The directory name has a hyphen; load it through ``__graft_entry__.load_package()``.)
 """
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -26,7 +27,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PACK_CENTRED", "RING_PACK_RESIDUE", "ring_pack_words", "ring_pack_min_bits", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "RingMod", "ring_mod_primes", "ring_mod_capacity", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PACK_CENTRED", "RING_PACK_RESIDUE", "ring_pack_words", "ring_pack_min_bits", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "RingMod", "ring_mod_primes", "ring_mod_capacity", "ring_mod_capacity_bounded", "RingModMatrix", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -936,6 +937,89 @@ def ring_mod_capacity(q, n):
     return int(_abi.lib().lsr_ring_mod_capacity(int(q), int(n)))
 
 
+def ring_mod_capacity_bounded(q, n, bound):
+    """``lsr_ring_mod_capacity_bounded``: how many products of an element mod q with an element of centred magnitude <= bound, degree n,
+    one sum may hold; 0 for bound == 0, bound > q // 2 or an inadmissible (q, n) (host only)."""
+    if not (0 <= int(q) < 2**64 and 0 <= int(n) < 2**32 and 0 <= int(bound) < 2**64):
+        return 0
+    return int(_abi.lib().lsr_ring_mod_capacity_bounded(int(q), int(n), int(bound)))
+
+
+class RingModMatrix:
+    """A rows x cols matrix over Z_q[X]/(X^n + 1) resident on a RingMod's device (``LsrRingModMatrix*``, batch.h "resident matrices
+    under any modulus").  Made by ``RingMod.matrix`` (host array), ``matrix_device`` (device pointer) or
+    ``matrix_seeded``.  Its RingMod must stay open for every call; closing the RingMod closes its matrices first."""
+
+    def __init__(self, ring, handle):
+        self._ring, self._lib, self._h, self.n = ring, ring._lib, handle, ring.n
+        ring._matrices.add(self)
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def rows(self):
+        return self._lib.lsr_ring_mod_matrix_rows(self._h)
+
+    @property
+    def cols(self):
+        return self._lib.lsr_ring_mod_matrix_cols(self._h)
+
+    @property
+    def row_block(self):
+        """Rows of M one workgroup of the kernel keeps in registers."""
+        return self._lib.lsr_ring_mod_matrix_row_block(self._h)
+
+    def matvec(self, x):
+        """y = M x mod (X^n + 1, q): x is [cols, n] (returns [rows, n]) or [batch, cols, n] (returns [batch, rows, n]); numpy in and out."""
+        x_in = _u64_array(x)
+        if x_in.ndim not in (2, 3) or x_in.shape[-2:] != (self.cols, self.n):
+            raise ValueError("x must be [cols, n] or [batch, cols, n]")
+        x3 = np.ascontiguousarray(x_in.reshape(-1, self.cols, self.n))
+        out = np.empty((x3.shape[0], self.rows, self.n), dtype=np.uint64)
+        _check(self._lib.lsr_ring_mod_matvec_batch(self._h, out.ctypes.data, x3.ctypes.data, x3.shape[0]), "lsr_ring_mod_matvec_batch")
+        return out[0] if x_in.ndim == 2 else out
+
+    def matvec_device(self, d_y, d_x, batch, stream=0):
+        """Device buffers: y [batch][rows][n], x [batch][cols][n], asynchronous on `stream`."""
+        _check(self._lib.lsr_ring_mod_matvec_batch_device(self._h, d_y, d_x, batch, stream), "lsr_ring_mod_matvec_batch_device")
+
+    def matvec_gadget(self, x, base_log2, digits):
+        """y = M G^-1(x) with the digits taken against q and never stored: x is [xcols, n] or [batch, xcols, n], xcols * digits == cols."""
+        x_in = _u64_array(x)
+        if x_in.ndim not in (2, 3) or x_in.shape[-1] != self.n or x_in.shape[-2] * int(digits) != self.cols:
+            raise ValueError("x must be [xcols, n] or [batch, xcols, n] with xcols * digits == cols")
+        x3 = np.ascontiguousarray(x_in.reshape(-1, x_in.shape[-2], self.n))
+        out = np.empty((x3.shape[0], self.rows, self.n), dtype=np.uint64)
+        _check(self._lib.lsr_ring_mod_matvec_gadget_batch(self._h, out.ctypes.data, x3.ctypes.data, x3.shape[0], base_log2, digits),
+               "lsr_ring_mod_matvec_gadget_batch")
+        return out[0] if x_in.ndim == 2 else out
+
+    def matvec_gadget_device(self, d_y, d_x, batch, base_log2, digits, stream=0):
+        """Device buffers: y [batch][rows][n], x [batch][cols / digits][n], asynchronous on `stream`."""
+        _check(self._lib.lsr_ring_mod_matvec_gadget_batch_device(self._h, d_y, d_x, batch, base_log2, digits, stream),
+               "lsr_ring_mod_matvec_gadget_batch_device")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.lsr_ring_mod_matrix_free(self._h)      # (reads the RingMod's handle: still open, see RingMod.close)
+            self._h = None
+            self._ring._matrices.discard(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class _BorrowedNttContext(NttContext):
     """One of the two prime contexts of a RingMod: every member of NttContext, owned by the RingMod (close() only lets go)."""
 
@@ -963,6 +1047,7 @@ class RingMod:
             raise CoreError(f"lsr_ring_mod_create({q}, {n}) returned NULL: {_abi.last_error()}")
         self._primes = ring_mod_primes(self.n)
         self._contexts = [None, None]
+        self._matrices = weakref.WeakSet()
 
     @property
     def handle(self):
@@ -986,6 +1071,8 @@ class RingMod:
 
     def close(self):
         if getattr(self, "_h", None):
+            for mat in list(getattr(self, "_matrices", ())):   # a matrix must not outlive its handle
+                mat.close()
             for ctx in self._contexts:
                 if ctx is not None:
                     ctx.close()
@@ -999,6 +1086,35 @@ class RingMod:
 
     def __exit__(self, *exc):
         self.close()
+
+    def matrix(self, m):
+        """The resident RingModMatrix of the host array m [rows, cols, n], words in [0, q); complete on return."""
+        m_in = _u64_array(m)
+        if m_in.ndim != 3 or m_in.shape[-1] != self.n:
+            raise ValueError("m must be [rows, cols, n]")
+        m3 = np.ascontiguousarray(m_in)
+        handle = self._lib.lsr_ring_mod_matrix_create(self._h, m3.ctypes.data, m3.shape[0], m3.shape[1])
+        if not handle:
+            raise CoreError("lsr_ring_mod_matrix_create failed: " + _abi.last_error())
+        return RingModMatrix(self, handle)
+
+    def matrix_device(self, d_m, rows, cols, stream=0):
+        """The same from a device buffer [rows][cols][n], enqueued on `stream`; d_m is copied and may be reused behind the stream."""
+        handle = self._lib.lsr_ring_mod_matrix_create_device(self._h, d_m, rows, cols, stream)
+        if not handle:
+            raise CoreError("lsr_ring_mod_matrix_create_device failed: " + _abi.last_error())
+        return RingModMatrix(self, handle)
+
+    def matrix_seeded(self, key, domain, index_base, rows, cols):
+        """The RingModMatrix whose entry [r][c] is the UNIFORM element mod q of stream index index_base + r cols + c under `key` (four
+        uint64 words or 32 bytes), sampled on the device."""
+        k2 = _ring_keys(key)
+        if k2.shape[0] != 1:
+            raise ValueError("key must be one 256-bit key")
+        handle = self._lib.lsr_ring_mod_matrix_create_seeded(self._h, k2.ctypes.data, domain, index_base, rows, cols)
+        if not handle:
+            raise CoreError("lsr_ring_mod_matrix_create_seeded failed: " + _abi.last_error())
+        return RingModMatrix(self, handle)
 
     def lift_device(self, i, d_out, d_x, count, stream=0):
         """d_out[e] = the residue mod prime i of the centred representative of d_x[e], e < count words; d_out may be d_x."""

@@ -173,6 +173,18 @@ SIGNATURES = {
     "lsr_ring_mod_mul_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, vp]),
     "lsr_ring_mod_dot_batch": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size]),
     "lsr_ring_mod_dot_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, vp]),
+    "lsr_ring_mod_capacity_bounded": (c_size, [u64, u32, u64]),
+    "lsr_ring_mod_matrix_create": (vp, [vp, vp, c_size, c_size]),
+    "lsr_ring_mod_matrix_create_device": (vp, [vp, vp, c_size, c_size, vp]),
+    "lsr_ring_mod_matrix_create_seeded": (vp, [vp, vp, u32, u64, c_size, c_size]),
+    "lsr_ring_mod_matrix_free": (None, [vp]),
+    "lsr_ring_mod_matrix_rows": (c_size, [vp]),
+    "lsr_ring_mod_matrix_cols": (c_size, [vp]),
+    "lsr_ring_mod_matrix_row_block": (c_size, [vp]),
+    "lsr_ring_mod_matvec_batch": (c_int, [vp, vp, vp, c_size]),
+    "lsr_ring_mod_matvec_batch_device": (c_int, [vp, vp, vp, c_size, vp]),
+    "lsr_ring_mod_matvec_gadget_batch": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size]),
+    "lsr_ring_mod_matvec_gadget_batch_device": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size, vp]),
     "lsr_sample_gaussian_seeded": (c_int, [vp, c_size, c_double, u64, u32, u64]),
     "lsr_gaussian_cdf": (c_size, [c_double, vp, c_size]),
     "lsr_lwe_context_create_seeded": (vp, [ctypes.POINTER(PublicParams), u64, c_int]),

@@ -79,6 +79,10 @@ bool rns_moduli_for(uint32_t n, uint64_t out[2]);
 // (P = p1 p2): floor(((P - 1) / 2) / (n h^2)) with h = floor(q / 2), saturated at SIZE_MAX.  0: (q, n) is not admissible — q < 2, n
 // not a power of two in [2, 131072], no prime pair, or not even one product fits.
 size_t ring_mod_capacity(uint64_t q, uint32_t n);
+// The same count when one operand of every product is short, its centred magnitude at most `bound` (the digits of a gadget
+// decomposition: bound = B / 2; §5q): floor(((P - 1) / 2) / (n h bound)).  0 for bound == 0, for bound > h and wherever
+// ring_mod_capacity is 0; ring_mod_capacity_bounded(q, n, h) == ring_mod_capacity(q, n).
+size_t ring_mod_capacity_bounded(uint64_t q, uint32_t n, uint64_t bound);
 
 uint64_t os_entropy64();
 

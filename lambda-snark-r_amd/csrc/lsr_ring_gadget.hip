@@ -15,29 +15,7 @@ namespace lsr {
 
 static_assert(kGadgetMaxDigits == 64 / 2 + 1, "recompose takes b (D - 1) <= 64 with b >= 2");
 
-// B^D as a 128-bit integer (b D <= 64) and off = B/2 in every digit position
-static u128 gadget_span(unsigned b, uint64_t digits) { return (u128)1 << (b * digits); }
-static u128 gadget_offset(unsigned b, uint64_t digits) { return ((u128)1 << (b - 1)) * ((gadget_span(b, digits) - 1) / (((u128)1 << b) - 1)); }
-
-// the rules of batch.h that do not read q
-static bool gadget_shape_ok(unsigned b, uint64_t digits) { return b >= 2 && b <= 32 && digits >= 1 && digits <= 64 / b; }
-
-static bool gadget_admissible(uint64_t q, unsigned b, uint64_t digits) {
-    if (!gadget_shape_ok(b, digits) || q < 2) return false;
-    const u128 off = gadget_offset(b, digits);
-    return ((uint64_t)1 << (b - 1)) <= q / 2 && (q - 1) / 2 <= off && q / 2 <= gadget_span(b, digits) - 1 - off;
-}
-
-static GadgetParams gadget_params(uint64_t q, unsigned b, uint64_t digits) {
-    GadgetParams g{};
-    g.half_q = q / 2;
-    g.off = (uint64_t)gadget_offset(b, digits);   // below B^D <= 2^64
-    g.digit_mask = (uint32_t)(((uint64_t)1 << b) - 1);
-    g.half_base = 1u << (b - 1);
-    g.base_log2 = b;
-    g.digits = (uint32_t)digits;
-    return g;
-}
+// (gadget_admissible and gadget_params: lsr_ring_gadget_digits.hpp, shared with lsr_ring_mod_matvec.hip)
 
 static unsigned stream_grid(size_t total) { return static_cast<unsigned>(std::min<size_t>((total + kThreads - 1) / kThreads, 256 * 32)); }
 

@@ -2,28 +2,12 @@
 // their recomposition, the l-infinity norm, and y = M G^-1(x) with the digits extracted in the load stage of the mat-vec's tile kernel.
 #pragma once
 
+#include "lsr_ring_gadget_digits.hpp"
 #include "lsr_ring_matvec_kernels.hpp"
 
 namespace lsr {
 
-// (b, D) and what the host derives from them and q.  With B = 2^b: off = B/2 in each of the D digit positions.  A digit fits 32 bits
-// (b <= 32), so its arithmetic is 32-bit; q itself travels beside this struct (ModParams in the tile kernel).
-struct GadgetParams {
-    uint64_t off;
-    uint64_t half_q;         // floor(q / 2): the largest word that is its own centred representative
-    uint32_t digit_mask;     // B - 1
-    uint32_t half_base;      // B / 2
-    uint32_t base_log2, digits;
-};
-
-// u = centred(x) + off for a canonical x, in wrapping 64-bit arithmetic: 0 <= u < B^D <= 2^64 for an admissible (b, D)
-__device__ __forceinline__ uint64_t gadget_shifted(uint64_t x, uint64_t q, const GadgetParams& g) { return x + g.off - (x > g.half_q ? q : 0ull); }
-// digit d of the word behind u, as the canonical residue of z_d = ((u >> b d) & (B - 1)) - B/2 in [-B/2, B/2 - 1]
-__device__ __forceinline__ uint64_t gadget_digit(uint64_t u, uint32_t shift, uint64_t q, const GadgetParams& g) {
-    const uint32_t t = (uint32_t)(u >> shift) & g.digit_mask;
-    const uint32_t z = t - g.half_base;                        // two's complement of z_d in 32 bits (b = 32: B/2 = 2^31)
-    return (uint64_t)(int64_t)(int32_t)z + (t < g.half_base ? q : 0ull);
-}
+// (GadgetParams, gadget_shifted and gadget_digit: lsr_ring_gadget_digits.hpp)
 
 // out[j][d][k] = digit d of x[j][k]; `total` = count n words of x.  Each word is read once; its D digits leave from registers, each
 // store instruction of a wave covering 64 consecutive words of one digit polynomial.

@@ -15,33 +15,11 @@
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
 #include "lsr_ring_call.hpp"
-#include "lsr_ring_mod_kernels.hpp"
+#include "lsr_ring_mod.hpp"
 #include "lsr_ring_workspace.hpp"
 #include "lsr_runtime.hpp"
 
-struct LsrRingMod {
-    // the modulus stays the first field: lsr_ring_mod_modulus reads nothing else, and the refusals that precede device work read nothing
-    uint64_t q = 0;
-    uint32_t n = 0;
-    int logn = 0;
-    int device = 0;
-    size_t max_terms = 0;
-    lsr::NttContextPtr prime[2];
-    lsr::RingModConsts rc{};
-    lsr::ModParams pq{};             // of q: only q and floor(2^128 / q) are used
-    lsr::LiftSource lift[2]{};
-    // n <= 4096: [2][chunk][n] inverse-transformed sums, then [2][bhat_rows][n] transforms of a shared b.  Never resized.
-    size_t chunk = 0, bhat_rows = 0;
-    lsr::DeviceBuffer<uint64_t> ws;
-    // calls on one handle are ordered like the ring calls of a context (lsr_ring_call.hpp ring_call)
-    mutable std::mutex mutex;
-    mutable lsr::Event event;
-};
-
 namespace lsr {
-
-constexpr size_t kRingModSumWords = (size_t)1 << 22;    // per prime: 32 MiB, both arrays stay in the Infinity Cache for the reduce
-constexpr size_t kRingModBhatWords = (size_t)1 << 21;   // per prime
 
 // q and floor(2^128 / q) for any q >= 2 (mulmod_barrett128 and mod64_barrett use nothing else)
 static ModParams ring_mod_params(uint64_t q, int logn) {
@@ -64,7 +42,7 @@ static unsigned stream_grid(size_t count, bool vec) {
     return static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 8192)));
 }
 
-static void launch_lift(const LsrRingMod& h, int i, uint64_t* d_out, const uint64_t* d_x, size_t count, hipStream_t s) {
+void launch_lift(const LsrRingMod& h, int i, uint64_t* d_out, const uint64_t* d_x, size_t count, hipStream_t s) {
     const bool vec = aligned16(d_out) && aligned16(d_x);
     for_bool(vec, [&](auto v) {
         hipLaunchKernelGGL(ring_mod_lift_kernel<decltype(v)::value>, dim3(stream_grid(count, vec)), dim3(kRingModThreads), 0, s, d_out, d_x, count, h.lift[i]);
@@ -72,7 +50,7 @@ static void launch_lift(const LsrRingMod& h, int i, uint64_t* d_out, const uint6
     LSR_HIP(hipGetLastError());
 }
 
-static void launch_reduce(const LsrRingMod& h, uint64_t* d_out, const uint64_t* d_r0, const uint64_t* d_r1, size_t count, bool accumulate, hipStream_t s) {
+void launch_reduce(const LsrRingMod& h, uint64_t* d_out, const uint64_t* d_r0, const uint64_t* d_r1, size_t count, bool accumulate, hipStream_t s) {
     const bool vec = aligned16(d_out) && aligned16(d_r0) && aligned16(d_r1);
     for_bool(vec, [&](auto v) {
         for_bool(accumulate, [&](auto acc) {
@@ -216,6 +194,14 @@ int lsr_ring_mod_primes(uint32_t n, uint64_t primes[2]) noexcept {
 size_t lsr_ring_mod_capacity(uint64_t q, uint32_t n) noexcept {
     try {
         return lsr::ring_mod_capacity(q, n);
+    } catch (...) {
+        return 0;
+    }
+}
+
+size_t lsr_ring_mod_capacity_bounded(uint64_t q, uint32_t n, uint64_t bound) noexcept {
+    try {
+        return lsr::ring_mod_capacity_bounded(q, n, bound);
     } catch (...) {
         return 0;
     }

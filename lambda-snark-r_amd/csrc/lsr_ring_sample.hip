@@ -28,8 +28,15 @@ struct SampleCall {
 
 static unsigned bit_length(uint64_t v) { return v ? 64u - (unsigned)__builtin_clzll(v) : 0u; }
 
-// elements [first, first + count) of a call into d_out (element `first` at d_out); d_keys holds the key groups from group_base on
-static void sample_device(const NttContext& c, uint64_t* d_out, uint64_t first, uint64_t count, const SampleCall& call, const uint64_t* d_keys,
+// elements [first, first + count) of a call into d_out (element `first` at d_out); d_keys holds the key groups from group_base on.
+// The ring is given by its modulus and degree alone: any q >= 2, prime or not (the ring handles of lsr_ring_mod_matvec.hip sample
+// under a modulus no context has).
+struct SampleRing {
+    uint64_t modulus;
+    int logn;
+    uint32_t degree;
+};
+static void sample_device(const SampleRing& c, uint64_t* d_out, uint64_t first, uint64_t count, const SampleCall& call, const uint64_t* d_keys,
                           uint64_t group_base, hipStream_t s) {
     if (call.kind == LSR_RING_SAMPLE_BALL) {
         RingBallJob job{d_out, d_keys, call.index_base, call.components, group_base, first, count, c.modulus, (uint32_t)call.param, call.domain, (uint32_t)c.logn};
@@ -70,6 +77,16 @@ static void sample_device(const NttContext& c, uint64_t* d_out, uint64_t first, 
         else hipLaunchKernelGGL(ring_sample_small_kernel, dim3(grid), dim3(kRingSampleThreads), 0, s, job);
         LSR_HIP(hipGetLastError());
     }
+}
+
+static void sample_device(const NttContext& c, uint64_t* d_out, uint64_t first, uint64_t count, const SampleCall& call, const uint64_t* d_keys,
+                          uint64_t group_base, hipStream_t s) {
+    sample_device(SampleRing{c.modulus, c.logn, c.degree}, d_out, first, count, call, d_keys, group_base, s);
+}
+
+void sample_uniform_device(uint64_t q, int logn, uint64_t* d_out, uint64_t count, const uint64_t* d_key, uint32_t domain, uint64_t index_base,
+                           hipStream_t s) {
+    sample_device(SampleRing{q, logn, 1u << logn}, d_out, 0, count, SampleCall{LSR_RING_SAMPLE_UNIFORM, 0, count, domain, index_base}, d_key, 0, s);
 }
 
 // host buffers through bounded device chunks of whole elements on the context's work stream; each chunk brings its own key groups
