@@ -828,6 +828,66 @@ int lsr_ring_mod_matvec_gadget_batch(const LsrRingModMatrix* mat, uint64_t* y, c
 int lsr_ring_mod_matvec_gadget_batch_device(const LsrRingModMatrix* mat, uint64_t* d_y, const uint64_t* d_x, size_t batch, unsigned base_log2,
                                             size_t digits, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: Gram matrices under any modulus (bounded ring vectors on a ring handle) ---------------- */
+/* The garbage polynomials of a lattice argument — g_il = <s_i, s_l>, h_il = <phi_i, s_l> + <phi_l, s_i> — in Z_q[X]/(X^n + 1) for the
+ * q of an LsrRingMod, at every n the handle admits.  Shapes, packed layouts, limits and the three forms are those of
+ * lsr_ntt_ring_gram_batch and lsr_ntt_ring_gram_sym2_batch: a [batch][ra][width][n], b [batch][rb][width][n], g [batch][ra][rb][n]
+ * (cross); b == NULL: the packed upper triangle of a with itself, g [batch][r (r + 1) / 2][n] (symmetric, rb == ra); sym2: the
+ * symmetrised packed form of two families.  Limits: LSR_RING_GRAM_MAX_VECTORS, LSR_RING_DOT_MAX_TERMS, LSR_RING_GRAM_MAX_FAMILY_BYTES.
+ * The ring is negacyclic.  Every operand polynomial is lifted and transformed once per prime.
+ *
+ * Definition.  Every output word equals lsr_ring_mod_dot_batch on (a[j][i], b[j][l]) pair by pair — for sym2 the sum of two such
+ * results mod q — canonical in [0, q); inputs in [0, q).
+ *
+ * Capacity with two short operands (host only):
+ *   lsr_ring_mod_capacity_product(q, n, bound_a, bound_b) = floor(((P - 1)/2) / (n bound_a bound_b))
+ * counts the negacyclic products of an operand of centred magnitude <= bound_a and one of magnitude <= bound_b that one sum may hold.
+ * 128-bit host arithmetic, saturated at SIZE_MAX; 0 when a bound is 0, when a bound is above floor(q/2) and wherever
+ * lsr_ring_mod_capacity(q, n) is 0.  With h = floor(q/2): capacity_product(q, n, h, bound) == lsr_ring_mod_capacity_bounded(q, n, bound)
+ * and capacity_product(q, n, h, h) == lsr_ring_mod_capacity(q, n).
+ *
+ * Bounds.  bound_a and bound_b are the l-infinity bounds the caller asserts on the centred representatives of a and of b; 0 states
+ * none, which is floor(q/2).  The symmetric form (b == NULL) does not read bound_b and holds a against bound_a twice.  In the cross
+ * form with b == a the same words are held against both bounds.  The device VERIFIES the bounds:
+ * status is [batch] (int32), never NULL, and written for every family:
+ *    1   every operand word of family j was below q and within its bound: the family's outputs are exact;
+ *    0   some word's centred magnitude exceeded its bound;
+ *   -1   some word was >= q (-1 wins over 0).
+ * For a status 0 or -1 EVERY output word of that family is 0; the other families of the batch are unaffected.  With both bounds none
+ * only -1 can occur.
+ *
+ * Grouping rule: columns are taken in groups of at most capacity_product(q, n, bound_a, bound_b) (the symmetric form: bound_a twice;
+ * sym2: half of it, rounded down — an entry sums two products per column), every group after the first reduced into g with
+ * accumulate.  Exactness never depends on the caller knowing a capacity.
+ *
+ * Refusals (-1 and lsr_last_error, before any device work), in this order: NULL handle, g, status, a (sym2: or b); ra, width (b: rb)
+ * == 0; b == NULL with rb != ra; ra or rb above LSR_RING_GRAM_MAX_VECTORS; width above LSR_RING_DOT_MAX_TERMS; sizes overflowing
+ * size_t; a bound above floor(q/2) (bound_b only where b is read).  Then batch == 0 is a no-op that returns 0.  Then: one family's
+ * operands or outputs above LSR_RING_GRAM_MAX_FAMILY_BYTES; a family that does not fit the workspace even one column at a time
+ * (vectors + outputs polynomials per prime); sym2 where capacity_product is below 2 (the message names the cross form; q =
+ * 8246337208321 at n = 8 is such a ring); g or status overlapping an operand or each other; no visible device.
+ *
+ * Workspace, ordering and graph capture.  The workspace belongs to the handle: per prime max(2^23, LAMBDA_SNARK_NTT_CHUNK_MIB 2^20 / 32)
+ * 64-bit words — 2^23 words, 64 MiB, at the default chunk size of 256 MiB; a function of the process-wide chunk size alone — and
+ * 2^15 words of per-family flags behind the two halves.  A chunk of whole families holds, per prime, the families' lifted operands,
+ * and their outputs ((vectors width + outputs) n words a family); a family that does not fit, or whose width exceeds the capacity, is
+ * taken alone in column groups.  The first eager Gram call or lsr_ring_mod_gram_prepare(h) allocates it; it is never resized and
+ * lsr_ring_mod_free releases it; lsr_ring_mod_create allocates nothing for it.  A _device call on a capturing stream that finds it
+ * missing is refused (the message asks for one eager call first) and leaves the handle usable; after _prepare the _device forms
+ * capture into a HIP graph from the first call.  Calls on one handle are ordered by the handle's mutex and event; a captured call is
+ * not bracketed.  The plain forms take host buffers through bounded device chunks of whole families on the first prime context's
+ * work stream and return when g and status are complete; the _device forms enqueue only. */
+size_t lsr_ring_mod_capacity_product(uint64_t q, uint32_t n, uint64_t bound_a, uint64_t bound_b) LSR_NOEXCEPT;
+int lsr_ring_mod_gram_prepare(const LsrRingMod* h) LSR_NOEXCEPT;
+int lsr_ring_mod_gram_batch(const LsrRingMod* h, uint64_t* g, int32_t* status, const uint64_t* a, const uint64_t* b, size_t batch, size_t ra,
+                            size_t rb, size_t width, uint64_t bound_a, uint64_t bound_b) LSR_NOEXCEPT;
+int lsr_ring_mod_gram_batch_device(const LsrRingMod* h, uint64_t* d_g, int32_t* d_status, const uint64_t* d_a, const uint64_t* d_b, size_t batch,
+                                   size_t ra, size_t rb, size_t width, uint64_t bound_a, uint64_t bound_b, void* stream) LSR_NOEXCEPT;
+int lsr_ring_mod_gram_sym2_batch(const LsrRingMod* h, uint64_t* out, int32_t* status, const uint64_t* a, const uint64_t* b, size_t batch, size_t r,
+                                 size_t width, uint64_t bound_a, uint64_t bound_b) LSR_NOEXCEPT;
+int lsr_ring_mod_gram_sym2_batch_device(const LsrRingMod* h, uint64_t* d_out, int32_t* d_status, const uint64_t* d_a, const uint64_t* d_b,
+                                        size_t batch, size_t r, size_t width, uint64_t bound_a, uint64_t bound_b, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

@@ -27,7 +27,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PACK_CENTRED", "RING_PACK_RESIDUE", "ring_pack_words", "ring_pack_min_bits", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "RingMod", "ring_mod_primes", "ring_mod_capacity", "ring_mod_capacity_bounded", "RingModMatrix", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PACK_CENTRED", "RING_PACK_RESIDUE", "ring_pack_words", "ring_pack_min_bits", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "RingMod", "ring_mod_primes", "ring_mod_capacity", "ring_mod_capacity_bounded", "ring_mod_capacity_product", "RingModMatrix", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -945,6 +945,14 @@ def ring_mod_capacity_bounded(q, n, bound):
     return int(_abi.lib().lsr_ring_mod_capacity_bounded(int(q), int(n), int(bound)))
 
 
+def ring_mod_capacity_product(q, n, bound_a, bound_b):
+    """``lsr_ring_mod_capacity_product``: how many products of an element of centred magnitude <= bound_a with one of magnitude
+    <= bound_b, degree n, one sum mod q may hold; 0 for a bound of 0 or above q // 2 or an inadmissible (q, n) (host only)."""
+    if not (0 <= int(q) < 2**64 and 0 <= int(n) < 2**32 and 0 <= int(bound_a) < 2**64 and 0 <= int(bound_b) < 2**64):
+        return 0
+    return int(_abi.lib().lsr_ring_mod_capacity_product(int(q), int(n), int(bound_a), int(bound_b)))
+
+
 class RingModMatrix:
     """A rows x cols matrix over Z_q[X]/(X^n + 1) resident on a RingMod's device (``LsrRingModMatrix*``, batch.h "resident matrices
     under any modulus").  Made by ``RingMod.matrix`` (host array), ``matrix_device`` (device pointer) or
@@ -1156,6 +1164,68 @@ class RingMod:
     def dot_device(self, d_c, d_a, d_b, batch, terms, b_rows, stream=0):
         """Device buffers: c [batch][n], a [batch][terms][n], b [b_rows][terms][n] (b_rows 1 or batch), asynchronous on `stream`."""
         _check(self._lib.lsr_ring_mod_dot_batch_device(self._h, d_c, d_a, d_b, batch, terms, b_rows, stream), "lsr_ring_mod_dot_batch_device")
+
+    def gram_prepare(self):
+        """``lsr_ring_mod_gram_prepare``: allocates the Gram workspace, so that ``gram_device`` captures into a graph from the first call."""
+        _check(self._lib.lsr_ring_mod_gram_prepare(self._h), "lsr_ring_mod_gram_prepare")
+
+    def _gram_operands(self, a, b, same_shape):
+        n = self.n
+        a_in = _u64_array(a, "a")
+        if a_in.ndim not in (3, 4) or a_in.shape[-1] != n:
+            raise ValueError("a must be [ra, width, n] or [batch, ra, width, n]")
+        a4 = np.ascontiguousarray(a_in.reshape(-1, a_in.shape[-3], a_in.shape[-2], n))
+        if b is None:
+            return a_in, a4, None
+        b_in = a_in if b is a else _u64_array(b, "b")
+        if b_in.ndim != a_in.ndim or b_in.shape[-1] != n or b_in.shape[-2] != a_in.shape[-2] or (same_shape and b_in.shape != a_in.shape):
+            raise ValueError("b must have the shape of a" if same_shape else "b must be [rb, width, n] or [batch, rb, width, n], with the width and the rank of a")
+        b4 = a4 if b_in is a_in else np.ascontiguousarray(b_in.reshape(-1, b_in.shape[-3], b_in.shape[-2], n))
+        if b4.shape[0] != a4.shape[0]:
+            raise ValueError("a and b must hold the same number of families")
+        return a_in, a4, b4
+
+    def gram(self, a, b=None, bound_a=0, bound_b=0):
+        """g[j][i][l] = sum_c a[j][i][c] * b[j][l][c] mod (X^n + 1, q) (host arrays): a is [batch, ra, width, n], b is
+        [batch, rb, width, n]; returns (g [batch, ra, rb, n], status [batch]).  b=None: the family with itself, only i <= l, packed as
+        [batch, ra (ra + 1) / 2, n] (ring_gram_index).  bound_a, bound_b: the l-infinity bounds asserted on the centred operands (0:
+        none); status[j] is 1 where family j kept them (exact outputs), 0 where a word exceeded its bound, -1 where a word was >= q —
+        then every output word of the family is 0.  3-d operands are a batch of one, and so are the results."""
+        a_in, a4, b4 = self._gram_operands(a, b, False)
+        batch, ra, width = a4.shape[:3]
+        rb = ra if b4 is None else b4.shape[1]
+        out = np.empty((batch, ra * (ra + 1) // 2, self.n) if b4 is None else (batch, ra, rb, self.n), dtype=np.uint64)
+        status = np.empty(batch, dtype=np.int32)
+        _check(self._lib.lsr_ring_mod_gram_batch(self._h, out.ctypes.data, status.ctypes.data, a4.ctypes.data, None if b4 is None else b4.ctypes.data, batch,
+                                                 ra, rb, width, int(bound_a), int(bound_b)), "lsr_ring_mod_gram_batch")
+        return (out[0], status[0]) if a_in.ndim == 3 else (out, status)
+
+    def gram_device(self, d_g, d_status, d_a, d_b, batch, ra, rb, width, bound_a=0, bound_b=0, stream=0):
+        """Device buffers: a [batch][ra][width][n], b [batch][rb][width][n], g [batch][ra][rb][n], status [batch] int32; d_b of 0 or
+        None: the symmetric form, g [batch][ra (ra + 1) / 2][n].  Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ring_mod_gram_batch_device(self._h, d_g, d_status, d_a, d_b or None, batch, ra, rb, width, int(bound_a), int(bound_b), stream),
+               "lsr_ring_mod_gram_batch_device")
+
+    def gram_sym2(self, a, b, bound_a=0, bound_b=0):
+        """The symmetrised packed Gram matrix of two families mod (X^n + 1, q) (host arrays): a and b are [batch, r, width, n]; returns
+        (h [batch, r (r + 1) / 2, n], status [batch]) with h[j][(i, l)] = <a_i, b_l> + <a_l, b_i> for i < l and <a_i, b_i> on the
+        diagonal (ring_gram_index); bounds and status as ``gram``."""
+        if b is None:
+            raise ValueError("gram_sym2 takes two families")
+        a_in, a4, b4 = self._gram_operands(a, b, True)
+        batch, r, width = a4.shape[:3]
+        out = np.empty((batch, r * (r + 1) // 2, self.n), dtype=np.uint64)
+        status = np.empty(batch, dtype=np.int32)
+        _check(self._lib.lsr_ring_mod_gram_sym2_batch(self._h, out.ctypes.data, status.ctypes.data, a4.ctypes.data, b4.ctypes.data, batch, r, width,
+                                                      int(bound_a), int(bound_b)), "lsr_ring_mod_gram_sym2_batch")
+        return (out[0], status[0]) if a_in.ndim == 3 else (out, status)
+
+    def gram_sym2_device(self, d_h, d_status, d_a, d_b, batch, r, width, bound_a=0, bound_b=0, stream=0):
+        """Device buffers: a and b [batch][r][width][n] (d_b may be d_a), h [batch][r (r + 1) / 2][n], status [batch] int32.
+        Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ring_mod_gram_sym2_batch_device(self._h, d_h, d_status, d_a, d_b or None, batch, r, width, int(bound_a), int(bound_b), stream),
+               "lsr_ring_mod_gram_sym2_batch_device")
+
 
 
 class Params:

@@ -234,6 +234,16 @@ size_t ring_mod_capacity_bounded(uint64_t q, uint32_t n, uint64_t bound) {
     return terms > (u128)SIZE_MAX ? SIZE_MAX : (size_t)terms;
 }
 
+size_t ring_mod_capacity_product(uint64_t q, uint32_t n, uint64_t bound_a, uint64_t bound_b) {
+    uint64_t p[2];
+    if (q < 2 || !rns_moduli_for(n, p)) return 0;
+    const uint64_t h = q >> 1;
+    if (bound_a == 0 || bound_b == 0 || bound_a > h || bound_b > h || ring_mod_capacity(q, n) == 0) return 0;   // below: n a b <= n h^2 < 2^103
+    const u128 limit = ((u128)p[0] * p[1] - 1) / 2, term = (u128)n * bound_a * bound_b;
+    const u128 terms = limit / term;
+    return terms > (u128)SIZE_MAX ? SIZE_MAX : (size_t)terms;
+}
+
 uint64_t os_entropy64() {
     uint64_t v = 0;
     os_entropy_fill(&v, sizeof v);

@@ -83,6 +83,10 @@ size_t ring_mod_capacity(uint64_t q, uint32_t n);
 // decomposition: bound = B / 2; §5q): floor(((P - 1) / 2) / (n h bound)).  0 for bound == 0, for bound > h and wherever
 // ring_mod_capacity is 0; ring_mod_capacity_bounded(q, n, h) == ring_mod_capacity(q, n).
 size_t ring_mod_capacity_bounded(uint64_t q, uint32_t n, uint64_t bound);
+// The same count when BOTH operands of every product are short (the Gram matrices of bounded ring vectors, §5r):
+// floor(((P - 1) / 2) / (n bound_a bound_b)).  0 where a bound is 0 or above h and wherever ring_mod_capacity is 0;
+// ring_mod_capacity_product(q, n, h, b) == ring_mod_capacity_bounded(q, n, b), ring_mod_capacity_product(q, n, h, h) == ring_mod_capacity(q, n).
+size_t ring_mod_capacity_product(uint64_t q, uint32_t n, uint64_t bound_a, uint64_t bound_b);
 
 uint64_t os_entropy64();
 

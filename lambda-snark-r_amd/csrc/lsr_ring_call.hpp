@@ -56,6 +56,11 @@ decltype(auto) for_flavour(const NttContext& c, F&& f) {
 // n > 4096: the tile size of the middle pass, the low log n - 4 (n = 2^17: - 5) bits of a two-pass transform
 inline int mid_tile_log(const NttContext& c) { return c.logn - std::max(c.logn - kTileLog, 4); }
 
+// what a capturing call says when the workspace it needs was never allocated (also the Gram calls of a ring handle, lsr_ring_mod_gram.hip)
+constexpr const char* kWorkspaceBeforeCapture =
+    "this call needs the context's workspace, which the first such call allocates: make one eager (uncaptured) "
+    "call on this context before capturing";
+
 // The bracket of one ring call on the device (caller validated the arguments): under ring_mutex, `workspace` allocated at
 // `workspace_words` by the first call that needs it, the launches of `enqueue` on `s` behind the context's previous ring call, and
 // ring_event recorded behind them for the next one.  A capturing stream: no brackets (lsr_runtime.hpp, stream_is_capturing).
@@ -68,8 +73,7 @@ void ring_call(const NttContext& c, DeviceBuffer<uint64_t>& workspace, size_t wo
         // the workspace is allocated once and never resized, so a graph captured after one eager call keeps valid pointers; an
         // allocation inside the capture would not be part of the graph
         if (capturing)
-            throw std::runtime_error("this call needs the context's workspace, which the first such call allocates: make one eager (uncaptured) "
-                                     "call on this context before capturing");
+            throw std::runtime_error(kWorkspaceBeforeCapture);
         workspace.allocate(workspace_words);
     }
     if (!capturing) c.ring_event.wait(s);

@@ -18,19 +18,15 @@
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
 #include "lsr_ring_call.hpp"
+#include "lsr_ring_gram.hpp"
 #include "lsr_ring_gram_kernels.hpp"
 #include "lsr_ring_workspace.hpp"
 #include "lsr_runtime.hpp"
 
 namespace lsr {
 
-constexpr size_t kGramMaxGridZ = 65535;
-static_assert((LSR_RING_GRAM_MAX_VECTORS / 2) * (LSR_RING_GRAM_MAX_VECTORS / 2) <= 65535, "the block pairs of one family are one grid axis");
-
 // polynomials the workspace holds: both halves of the n > 4096 layout
 static size_t gram_workspace_polys(const NttContext& c) { return ring_dot_scratch_words(c) >> c.logn; }
-
-static size_t gram_outputs(size_t ra, size_t rb, bool sym) { return sym ? ra * (ra + 1) / 2 : ra * rb; }
 
 // sym: the packed upper triangle (b-hat == a-hat); sym2: the packed symmetrised form of two families
 template <class A>
@@ -140,22 +136,7 @@ namespace {
 int ring_gram_check(const char* where, const NttContext* ctx, const void* g, const void* a, const void* b, size_t batch, size_t ra, size_t rb,
                     size_t width, bool sym2 = false) {
     if (!ctx || !g || !a || (sym2 && !b)) return lsr::abi_refuse(where, "NULL context or buffer");
-    if (ra == 0 || width == 0 || (b && rb == 0)) return lsr::abi_refuse(where, "ra, rb and width must be at least 1");
-    if (!b && rb != ra)
-        return lsr::abi_refuse(where, "the symmetric form (b == NULL) takes rb == ra, got ra = " + std::to_string(ra) + ", rb = " + std::to_string(rb));
-    if (ra > LSR_RING_GRAM_MAX_VECTORS || rb > LSR_RING_GRAM_MAX_VECTORS)
-        return lsr::abi_refuse(where, "ra = " + std::to_string(ra) + ", rb = " + std::to_string(rb) + ": above LSR_RING_GRAM_MAX_VECTORS (" +
-                                          std::to_string(LSR_RING_GRAM_MAX_VECTORS) + ")");
-    if (width > LSR_RING_DOT_MAX_TERMS)
-        return lsr::abi_refuse(where, "width = " + std::to_string(width) + " is above LSR_RING_DOT_MAX_TERMS (" + std::to_string(LSR_RING_DOT_MAX_TERMS) + ")");
-    // every product a shape takes, in polynomials and then in bytes at the smallest ring (n = 2, 16 bytes a polynomial)
-    size_t vecs = 0, a_polys = 0, b_polys = 0, g_polys = 0, bytes = 0;
-    const size_t outs = lsr::gram_outputs(ra, rb, b == nullptr || sym2);
-    const bool overflow = __builtin_mul_overflow(batch, ra, &vecs) || __builtin_mul_overflow(vecs, width, &a_polys) ||
-                          __builtin_mul_overflow(batch, rb, &vecs) || __builtin_mul_overflow(vecs, width, &b_polys) ||
-                          __builtin_mul_overflow(batch, outs, &g_polys) || __builtin_mul_overflow(a_polys, (size_t)16, &bytes) ||
-                          __builtin_mul_overflow(b_polys, (size_t)16, &bytes) || __builtin_mul_overflow(g_polys, (size_t)16, &bytes);
-    if (overflow) return lsr::abi_refuse(where, "the sizes of a, b or g overflow size_t (batch, ra, rb, width)");
+    if (lsr::ring_gram_shape_check(where, b != nullptr, batch, ra, rb, width, sym2) != 0) return -1;
     return batch == 0 ? 1 : 0;
 }
 

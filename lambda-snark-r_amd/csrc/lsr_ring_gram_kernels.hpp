@@ -39,7 +39,7 @@ constexpr uint32_t kGramThreads = 256;
 
 // Edge E of the register block per arithmetic flavour (the resource table and the measurements: DESIGN.md §5j)
 template <class A> constexpr int kGramEdge = 4;
-template <> constexpr int kGramEdge<ArithF64> = LSR_RING_GRAM_EDGE_F64;
+template <> inline constexpr int kGramEdge<ArithF64> = LSR_RING_GRAM_EDGE_F64;
 
 struct GramShape {
     uint32_t logn, ra, rb, ncols, flags;   // flags: kRingDotFirst — start at zero (else: at the canonical words an earlier group left in g)
@@ -47,9 +47,12 @@ struct GramShape {
     size_t g_fam;                          // words of one family's outputs
 };
 
-template <class A, int E, bool SYM, bool SYM2 = false>
-__global__ void __launch_bounds__(kGramThreads) ring_gram_kernel(uint64_t* __restrict__ g, const uint64_t* __restrict__ ahat,
-                                                                   const uint64_t* __restrict__ bhat, GramShape s, ModParams p) {
+// The work of one workgroup: block pair `pair` (the grid's y of the layout above) of family `fam`, both workgroup-uniform.  The kernel
+// of a context passes its block indices; the kernel of a ring handle under an arbitrary modulus (lsr_ring_mod_gram_kernels.hpp) takes
+// the prime out of y first.
+template <class A, int E, bool SYM, bool SYM2>
+__device__ __forceinline__ void ring_gram_block(uint64_t* __restrict__ g, const uint64_t* __restrict__ ahat, const uint64_t* __restrict__ bhat,
+                                                const GramShape& s, const ModParams& p, uint32_t pair, uint32_t fam) {
     using elem = typename A::elem;
     const size_t n = (size_t)1 << s.logn;
     const size_t pos = (size_t)blockIdx.x * kGramThreads + threadIdx.x;
@@ -57,24 +60,24 @@ __global__ void __launch_bounds__(kGramThreads) ring_gram_kernel(uint64_t* __res
     const uint32_t nbl = (s.rb + E - 1) / E;
     uint32_t ib, lb;
     if constexpr (SYM) {
-        uint32_t rest = blockIdx.y;
+        uint32_t rest = pair;
         for (ib = 0; rest >= nbl - ib; ++ib) rest -= nbl - ib;
         lb = ib + rest;
     } else {
-        ib = blockIdx.y / nbl;
-        lb = blockIdx.y % nbl;
+        ib = pair / nbl;
+        lb = pair % nbl;
     }
     const uint32_t i0 = ib * E, l0 = lb * E;
     const uint32_t ni = min((uint32_t)E, s.ra - i0), nl = min((uint32_t)E, s.rb - l0);
     if (pos >= n) return;
-    const uint64_t* const ap = ahat + blockIdx.z * s.a_fam + i0 * s.a_vec;
-    const uint64_t* const bp = bhat + blockIdx.z * s.b_fam + l0 * s.b_vec;
-    uint64_t* const gp = g + blockIdx.z * s.g_fam;
+    const uint64_t* const ap = ahat + fam * s.a_fam + i0 * s.a_vec;
+    const uint64_t* const bp = bhat + fam * s.b_fam + l0 * s.b_vec;
+    uint64_t* const gp = g + fam * s.g_fam;
     // SYM2: the transposed operands a_L and b_I of the second product (a diagonal block has them in x and y)
     static_assert(SYM || !SYM2, "the symmetrised form is a mode of the packed form");
     const bool diag = SYM2 && ib == lb;
-    const uint64_t* const ap2 = ahat + blockIdx.z * s.a_fam + l0 * s.a_vec;
-    const uint64_t* const bp2 = bhat + blockIdx.z * s.b_fam + i0 * s.b_vec;
+    const uint64_t* const ap2 = ahat + fam * s.a_fam + l0 * s.a_vec;
+    const uint64_t* const bp2 = bhat + fam * s.b_fam + i0 * s.b_vec;
     constexpr uint32_t kPeriod = SYM2 ? kRingDotF64Period / 2 : kRingDotF64Period;
     // (ii, ll) of the block is an output of this workgroup; its polynomial within the family
     auto live = [&](int ii, int ll) { return (uint32_t)ii < ni && (uint32_t)ll < nl && (!SYM || i0 + ii <= l0 + ll); };
@@ -135,6 +138,12 @@ __global__ void __launch_bounds__(kGramThreads) ring_gram_kernel(uint64_t* __res
 #pragma unroll
         for (int ll = 0; ll < E; ++ll)
             if (live(ii, ll)) gp[slot(ii, ll) * n + pos] = A::store_reduced(acc[ii][ll], p);
+}
+
+template <class A, int E, bool SYM, bool SYM2 = false>
+__global__ void __launch_bounds__(kGramThreads) ring_gram_kernel(uint64_t* __restrict__ g, const uint64_t* __restrict__ ahat,
+                                                                   const uint64_t* __restrict__ bhat, GramShape s, ModParams p) {
+    ring_gram_block<A, E, SYM, SYM2>(g, ahat, bhat, s, p, blockIdx.y, blockIdx.z);
 }
 
 }  // namespace lsr

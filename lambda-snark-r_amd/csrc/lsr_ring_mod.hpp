@@ -1,5 +1,6 @@
 // The ring handle under an arbitrary modulus (LsrRingMod, batch.h) as the translation units that read it see it:
-// lsr_ring_mod.hip creates it and computes mul and dot, lsr_ring_mod_matvec.hip keeps resident matrices on it (§5q).
+// lsr_ring_mod.hip creates it and computes mul and dot, lsr_ring_mod_matvec.hip keeps resident matrices on it (§5q),
+// lsr_ring_mod_gram.hip computes Gram matrices of bounded vectors on it (§5r).
 #pragma once
 
 #include <mutex>
@@ -21,6 +22,10 @@ struct LsrRingMod {
     // n <= 4096: [2][chunk][n] inverse-transformed sums, then [2][bhat_rows][n] transforms of a shared b.  Never resized.
     size_t chunk = 0, bhat_rows = 0;
     lsr::DeviceBuffer<uint64_t> ws;
+    // the Gram calls (lsr_ring_mod_gram.hip): [2][ring_mod_gram_words()] lifted operands, their transforms and the outputs of one chunk
+    // per prime, then kRingModGramFlagWords words of per-family flags.  Allocated by the first eager Gram call or by
+    // lsr_ring_mod_gram_prepare under `mutex`, never resized.
+    mutable lsr::DeviceBuffer<uint64_t> gram_ws;
     // calls on one handle are ordered like the ring calls of a context (lsr_ring_call.hpp ring_call)
     mutable std::mutex mutex;
     mutable lsr::Event event;
@@ -30,6 +35,11 @@ namespace lsr {
 
 constexpr size_t kRingModSumWords = (size_t)1 << 22;    // per prime: 32 MiB, both arrays stay in the Infinity Cache for the reduce
 constexpr size_t kRingModBhatWords = (size_t)1 << 21;   // per prime
+
+// Gram workspace words per prime: a function of the process-wide chunk size alone (a quarter of it, 64 MiB of 256: the two halves stay in
+// the Infinity Cache between the passes of a chunk), at least 2^23 words
+size_t ring_mod_gram_words();
+constexpr size_t kRingModGramFlagWords = (size_t)1 << 15;   // 65536 32-bit flag words: the families of one chunk are one grid axis
 
 // the two streaming kernels on `s` (lsr_ring_mod.hip): no workspace, no ordering
 void launch_lift(const LsrRingMod& h, int i, uint64_t* d_out, const uint64_t* d_x, size_t count, hipStream_t s);

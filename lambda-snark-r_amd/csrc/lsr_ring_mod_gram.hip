@@ -1,0 +1,318 @@
+// Gram matrices of bounded ring vectors in Z_q[X]/(X^n + 1) for ANY modulus q >= 2 (batch.h "Gram matrices under any modulus",
+// DESIGN.md §5r): the cross, symmetric and symmetrised forms of lsr_ntt_ring_gram_batch / _sym2_batch on a ring handle (LsrRingMod,
+// lsr_ring_mod.hip), at every n the handle admits.  The caller states l-infinity bounds on the centred operands; the device verifies
+// them and reports per family (status), and the columns are taken in groups of what P = p1 p2 carries under those bounds
+// (ring_mod_capacity_product).  Per chunk of families and group of columns:
+//   1. ring_mod_gram_lift_kernel: every operand word read once, lifted for both primes into the two halves of the handle's Gram
+//      workspace, bounds and range folded into the family's flag word (families in several groups: one check pass over the chunk's
+//      whole families first, then lifts without the check);
+//   2. launch_ntt forward in place on each half (a-hat and b-hat are contiguous: one launch per prime);
+//   3. the register-blocked pointwise product of §5j into the workspace: ring_mod_gram_kernel for both primes in one launch, or — the
+//      FP64 flavour's cross and symmetric forms, where the second prime costs a wave — ring_gram_kernel once per prime;
+//   4. launch_ntt inverse in place on each half's outputs;
+//   5. ring_mod_gram_reduce_kernel: CRT and reduction mod q into g (accumulating from the second group on), zeros where the family's
+//      flags are set, and status.
+// The workspace is [2][ring_mod_gram_words()] words and the flag words: sized by the process-wide chunk size alone, allocated by the
+// first eager call or by lsr_ring_mod_gram_prepare, never resized.
+#include <algorithm>
+#include <cstring>
+
+#include "lambda_snark/batch.h"
+#include "lsr_flavour.hpp"
+#include "lsr_ring_call.hpp"
+#include "lsr_ring_gram.hpp"
+#include "lsr_ring_mod.hpp"
+#include "lsr_ring_mod_gram_kernels.hpp"
+#include "lsr_runtime.hpp"
+
+namespace lsr {
+
+size_t ring_mod_gram_words() { return std::max<size_t>((size_t)1 << 23, ntt_chunk_bytes() / 32); }
+
+static_assert(kGramMaxGridZ <= 2 * kRingModGramFlagWords, "one flag word per family of a chunk");
+static_assert(2 * (LSR_RING_GRAM_MAX_VECTORS / 4) * (LSR_RING_GRAM_MAX_VECTORS / 4) <= 65535, "block pairs and primes share one grid axis");
+
+struct ModGramCall {
+    uint64_t* g;
+    int32_t* status;
+    const uint64_t *a, *b;     // b == nullptr: the symmetric form
+    size_t batch, ra, rb, width;
+    bool sym2;
+    uint64_t bound_a, bound_b;   // as the caller gave them: 0 = none
+};
+
+// what a call takes of the workspace and of P
+struct ModGramPlan {
+    bool sym, one_set;           // one_set: b's transforms are a's (the symmetric form, or the cross form with b == a and rb == ra)
+    size_t vectors, outs;        // operand vectors lifted per family; output polynomials per family
+    uint64_t bound_a, bound_b;   // resolved: none -> floor(q / 2); the symmetric form holds a against bound_a twice
+    uint64_t check_a;            // what a's words are held against: both bounds where b is a itself
+    size_t capacity;             // columns per group that P carries (sym2: two products per column)
+};
+
+static ModGramPlan mod_gram_plan(const LsrRingMod& h, const ModGramCall& c) {
+    ModGramPlan p{};
+    const uint64_t half = h.q >> 1;
+    p.sym = c.b == nullptr;
+    p.one_set = p.sym || (c.b == c.a && c.rb == c.ra);
+    p.vectors = p.one_set ? c.ra : c.ra + c.rb;
+    p.outs = gram_outputs(c.ra, c.rb, p.sym || c.sym2);
+    p.bound_a = c.bound_a ? c.bound_a : half;
+    p.bound_b = p.sym ? p.bound_a : (c.bound_b ? c.bound_b : half);
+    p.check_a = !p.sym && c.b == c.a ? std::min(p.bound_a, p.bound_b) : p.bound_a;
+    p.capacity = ring_mod_capacity_product(h.q, h.n, p.bound_a, p.bound_b);
+    if (c.sym2) p.capacity /= 2;
+    return p;
+}
+
+// one operand of one chunk or group: `vectors` runs of `run` words per family
+struct LiftLaunch {
+    uint64_t* dst;
+    const uint64_t* src;
+    size_t vectors, families, run, src_vec, src_fam, dst_vec, dst_fam;
+    uint64_t bound;
+};
+
+template <bool CHECK, bool STORE>
+static void gram_lift(const LsrRingMod& h, const LiftLaunch& l, uint32_t* flags, hipStream_t s) {
+    const bool vec = (reinterpret_cast<uintptr_t>(l.src) & 15u) == 0;
+    const size_t items = vec ? l.run / 2 : l.run;
+    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))),
+                    static_cast<unsigned>(l.vectors), static_cast<unsigned>(l.families));
+    const GramLiftShape shape{l.run, l.src_vec, l.src_fam, l.dst_vec, l.dst_fam, ring_mod_gram_words(), h.q, l.bound};
+    for_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((ring_mod_gram_lift_kernel<decltype(v)::value, CHECK, STORE>), grid, dim3(kRingModThreads), 0, s, l.dst, l.src, flags, shape,
+                           h.lift[0], h.lift[1]);
+    });
+}
+
+// Both primes in one launch (the prime is the low bit of grid y), or one launch of the single-prime kernel per prime: decided per
+// instantiation by the compiler's resource report (profiles/r34_ring_mod_gram_resource_usage.txt).  Carrying the second
+// prime costs the FP64 flavour's cross and symmetric kernels a wave (70 VGPRs against 62: 7 waves per SIMD against 8).
+template <class A, bool SYM2>
+constexpr bool kModGramBothPrimes = !(std::is_same_v<A, ArithF64> && !SYM2);
+
+template <class A>
+static void gram_product(const LsrRingMod& h, uint64_t* ghat, const uint64_t* ahat, const uint64_t* bhat, const GramShape& shape, bool sym, bool sym2,
+                         size_t families, hipStream_t s) {
+    constexpr int E = kGramEdge<A>;
+    const unsigned bi = (shape.ra + E - 1) / E, bl = (shape.rb + E - 1) / E, pairs = sym || sym2 ? bi * (bi + 1) / 2 : bi * bl;
+    const size_t half = ring_mod_gram_words();
+    const unsigned runs = static_cast<unsigned>((h.n + kGramThreads - 1) / kGramThreads);
+    const GramModPrimes primes{{h.prime[0]->mod, h.prime[1]->mod}, half};
+    if (sym2) {
+        static_assert(kModGramBothPrimes<A, true>, "the symmetrised form runs both primes in one launch");
+        hipLaunchKernelGGL((ring_mod_gram_kernel<A, E, true, true>), dim3(runs, 2 * pairs, static_cast<unsigned>(families)), dim3(kGramThreads), 0, s, ghat, ahat,
+                           bhat, shape, primes);
+        return;
+    }
+    for_bool(sym, [&](auto y) {
+        constexpr bool kSym = decltype(y)::value;
+        if constexpr (kModGramBothPrimes<A, false>) {
+            hipLaunchKernelGGL((ring_mod_gram_kernel<A, E, kSym>), dim3(runs, 2 * pairs, static_cast<unsigned>(families)), dim3(kGramThreads), 0, s, ghat, ahat,
+                               bhat, shape, primes);
+        } else {
+            for (int i = 0; i < 2; ++i)
+                hipLaunchKernelGGL((ring_gram_kernel<A, E, kSym>), dim3(runs, pairs, static_cast<unsigned>(families)), dim3(kGramThreads), 0, s, ghat + i * half,
+                                   ahat + i * half, bhat + i * half, shape, h.prime[i]->mod);
+        }
+    });
+}
+
+static void gram_reduce(const LsrRingMod& h, uint64_t* g, int32_t* status, const uint64_t* ghat, const uint32_t* flags, size_t words, size_t families,
+                        bool accumulate, hipStream_t s) {
+    const bool vec = (reinterpret_cast<uintptr_t>(g) & 15u) == 0;
+    const size_t items = vec ? words / 2 : words;
+    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))),
+                    static_cast<unsigned>(families));
+    for_bool(vec, [&](auto v) {
+        for_bool(accumulate, [&](auto acc) {
+            hipLaunchKernelGGL((ring_mod_gram_reduce_kernel<decltype(v)::value, decltype(acc)::value>), grid, dim3(kRingModThreads), 0, s, g, status, ghat,
+                               ghat + ring_mod_gram_words(), flags, words, words, h.rc, h.prime[1]->mod, h.pq);
+        });
+    });
+}
+
+template <class A>
+static void mod_gram_enqueue(const LsrRingMod& h, const ModGramCall& c, hipStream_t s) {
+    const ModGramPlan p = mod_gram_plan(h, c);
+    const size_t n = h.n, half = ring_mod_gram_words(), polys = half >> h.logn;
+    const size_t a_fam = c.ra * c.width * n, b_fam = c.rb * c.width * n, g_fam = p.outs * n;
+    uint64_t* const ws = h.gram_ws.ptr;
+    uint32_t* const flags = reinterpret_cast<uint32_t*>(ws + 2 * half);
+    const uint64_t* const b = p.one_set ? c.a : c.b;
+    auto transforms = [&](uint64_t* data, size_t count, bool inverse) {
+        for (int i = 0; i < 2; ++i) launch_ntt(*h.prime[i], data + i * half, count, inverse, s);
+    };
+    // Columns per group: what P carries and what the workspace holds of one family (>= 1: mod_gram_call).  Families per chunk: what
+    // the workspace holds of such groups and their outputs, the chunks of a batch of equal size.  A family's flags must be complete
+    // before its first reduce: with one group the check rides in the lift, else a pass without stores over the chunk's whole
+    // families comes first.
+    const size_t wmax = std::min({c.width, p.capacity, (polys - p.outs) / p.vectors});
+    const size_t chunk_max = std::min(polys / (p.vectors * wmax + p.outs), kGramMaxGridZ);
+    const size_t chunks = (c.batch + chunk_max - 1) / chunk_max, chunk = (c.batch + chunks - 1) / chunks;
+    const bool one_group = wmax == c.width;
+    const size_t vec_words = c.width * n;
+    for (size_t j0 = 0; j0 < c.batch; j0 += chunk) {
+        const size_t now = std::min(chunk, c.batch - j0);
+        const uint64_t *aj = c.a + j0 * a_fam, *bj = b + j0 * b_fam;
+        zero_words_async(reinterpret_cast<uint64_t*>(flags), (now + 1) / 2, s);
+        if (!one_group) {
+            gram_lift<true, false>(h, {ws, aj, c.ra, now, vec_words, vec_words, a_fam, 0, 0, p.check_a}, flags, s);
+            if (!p.one_set) gram_lift<true, false>(h, {ws, bj, c.rb, now, vec_words, vec_words, b_fam, 0, 0, p.bound_b}, flags, s);
+        }
+        for (size_t c0 = 0; c0 < c.width; c0 += wmax) {
+            const size_t wnow = std::min(wmax, c.width - c0), run = wnow * n;
+            uint64_t* const bhat = p.one_set ? ws : ws + now * c.ra * run;
+            uint64_t* const ghat = ws + now * p.vectors * run;
+            const LiftLaunch la{ws, aj + c0 * n, c.ra, now, run, vec_words, a_fam, run, c.ra * run, p.check_a};
+            const LiftLaunch lb{bhat, bj + c0 * n, c.rb, now, run, vec_words, b_fam, run, c.rb * run, p.bound_b};
+            for_bool(one_group, [&](auto check) {
+                gram_lift<decltype(check)::value, true>(h, la, flags, s);
+                if (!p.one_set) gram_lift<decltype(check)::value, true>(h, lb, flags, s);
+            });
+            transforms(ws, now * p.vectors * wnow, false);
+            const GramShape shape{(uint32_t)h.logn, (uint32_t)c.ra, (uint32_t)c.rb, (uint32_t)wnow, kRingDotFirst | kRingDotLast,
+                                  run, c.ra * run, run, c.rb * run, g_fam};
+            gram_product<A>(h, ghat, ws, bhat, shape, p.sym, c.sym2, now, s);
+            transforms(ghat, now * p.outs, true);
+            gram_reduce(h, c.g + j0 * g_fam, c.status + j0, ghat, flags, g_fam, now, c0 > 0, s);
+        }
+    }
+}
+
+// One call on the device (caller validated the arguments): the handle's mutex and event as ring_mod_dot_device, the Gram workspace
+// as ring_call allocates a context's.
+static void mod_gram_device(const LsrRingMod& h, const ModGramCall& c, hipStream_t s) {
+    std::lock_guard<std::mutex> lock(h.mutex);
+    const bool capturing = stream_is_capturing(s);
+    if (!h.gram_ws.ptr) {
+        if (capturing) throw std::runtime_error(kWorkspaceBeforeCapture);
+        h.gram_ws.allocate(2 * ring_mod_gram_words() + kRingModGramFlagWords);
+    }
+    if (h.prime[0]->use_f64 != h.prime[1]->use_f64) throw std::runtime_error("the two prime contexts run different kernel flavours");
+    if (!capturing) h.event.wait(s);
+    if (h.prime[0]->use_f64) mod_gram_enqueue<ArithF64>(h, c, s);
+    else mod_gram_enqueue<ArithU64>(h, c, s);
+    LSR_HIP(hipGetLastError());
+    if (!capturing) h.event.record(s);
+}
+
+// host buffers through bounded device chunks of whole families on the first prime context's work stream; status comes back with g
+static void host_mod_gram(const LsrRingMod& h, const ModGramCall& c) {
+    const ModGramPlan p = mod_gram_plan(h, c);
+    const NttContext& ctx = *h.prime[0];
+    const size_t n = h.n, a_words = c.ra * c.width * n, b_words = p.one_set ? 0 : c.rb * c.width * n, g_words = p.outs * n;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(c.batch, (kStagingBytes / 8) / (a_words + b_words + g_words)));
+    DeviceBuffer<uint64_t> da(chunk * a_words), db(chunk * b_words), dg(chunk * g_words);
+    DeviceBuffer<int32_t> dstatus(chunk);
+    std::lock_guard<std::mutex> lock(ctx.staging_mutex);   // serialises use of work_stream(ctx)
+    hipStream_t s = work_stream(ctx);
+    for (size_t j0 = 0; j0 < c.batch; j0 += chunk) {
+        const size_t now = std::min(chunk, c.batch - j0);
+        LSR_HIP(hipMemcpyAsync(da.ptr, c.a + j0 * a_words, now * a_words * 8, hipMemcpyHostToDevice, s));
+        if (!p.one_set) LSR_HIP(hipMemcpyAsync(db.ptr, c.b + j0 * b_words, now * b_words * 8, hipMemcpyHostToDevice, s));
+        ModGramCall d = c;
+        d.g = dg.ptr;
+        d.status = dstatus.ptr;
+        d.a = da.ptr;
+        d.b = p.sym ? nullptr : (p.one_set ? da.ptr : db.ptr);
+        d.batch = now;
+        mod_gram_device(h, d, s);
+        LSR_HIP(hipMemcpyAsync(c.g + j0 * g_words, dg.ptr, now * g_words * 8, hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipMemcpyAsync(c.status + j0, dstatus.ptr, now * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        LSR_HIP(hipStreamSynchronize(s));
+    }
+}
+
+}  // namespace lsr
+
+// ------------------------------------------------------------------------------------------------
+// C-ABI
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// The refusals of batch.h in its order, all before any device work.  Up to the bounds they read nothing of the handle but q.
+int mod_gram_call(const char* where, const LsrRingMod* h, const lsr::ModGramCall& c, bool device, void* stream) noexcept {
+    if (!h || !c.g || !c.status || !c.a || (c.sym2 && !c.b)) return lsr::abi_refuse(where, "NULL handle, buffer or status");
+    if (lsr::ring_gram_shape_check(where, c.b != nullptr, c.batch, c.ra, c.rb, c.width, c.sym2) != 0) return -1;
+    const uint64_t half = h->q >> 1;
+    if (c.bound_a > half || (c.b && c.bound_b > half))
+        return lsr::abi_refuse(where, "bound_a = " + std::to_string(c.bound_a) + ", bound_b = " + std::to_string(c.bound_b) + ": a bound is above floor(q / 2) = " +
+                                          std::to_string(half) + " (0 states none)");
+    if (c.batch == 0) return 0;
+    return lsr::abi_guarded(where, [&] {
+        const lsr::ModGramPlan p = lsr::mod_gram_plan(*h, c);
+        const size_t poly_bytes = (size_t)h->n * 8, listed = p.sym ? c.ra : c.ra + c.rb;
+        // (at most 128 * 65536 and 4096 polynomials of at most 2^20 bytes: no overflow)
+        if (listed * c.width * poly_bytes > LSR_RING_GRAM_MAX_FAMILY_BYTES || p.outs * poly_bytes > LSR_RING_GRAM_MAX_FAMILY_BYTES)
+            throw std::runtime_error("one family takes " + std::to_string(listed * c.width * poly_bytes) + " bytes of operands and " +
+                                     std::to_string(p.outs * poly_bytes) + " bytes of outputs: above LSR_RING_GRAM_MAX_FAMILY_BYTES (" +
+                                     std::to_string((size_t)LSR_RING_GRAM_MAX_FAMILY_BYTES) + ")");
+        const size_t polys = lsr::ring_mod_gram_words() >> h->logn;
+        if (p.vectors + p.outs > polys)
+            throw std::runtime_error("a family of " + std::to_string(p.vectors) + " vectors and " + std::to_string(p.outs) +
+                                     " outputs needs a workspace of as many polynomials per prime even one column at a time; it holds " + std::to_string(polys) +
+                                     " at this ring degree (LAMBDA_SNARK_NTT_CHUNK_MIB sets the workspace size)");
+        if (c.sym2 && p.capacity == 0)
+            throw std::runtime_error("the symmetrised form sums two products per column and q = " + std::to_string(h->q) + ", n = " + std::to_string(h->n) +
+                                     " under these bounds carries one (lsr_ring_mod_capacity_product): take the cross form, lsr_ring_mod_gram_batch, "
+                                     "and add its (i, l) and (l, i) entries mod q");
+        size_t a_bytes = 0, b_bytes = 0, g_bytes = 0;
+        if (__builtin_mul_overflow(c.batch * c.ra * c.width, poly_bytes, &a_bytes) || __builtin_mul_overflow(c.batch * c.rb * c.width, poly_bytes, &b_bytes) ||
+            __builtin_mul_overflow(c.batch * p.outs, poly_bytes, &g_bytes))
+            throw std::runtime_error("the sizes of a, b or g overflow size_t at this ring degree");
+        const size_t status_bytes = c.batch * sizeof(int32_t);
+        lsr::require_apart(c.g, g_bytes, c.a, a_bytes, "g overlaps a: the output must not share memory with an operand");
+        if (c.b) lsr::require_apart(c.g, g_bytes, c.b, b_bytes, "g overlaps b: the output must not share memory with an operand");
+        lsr::require_apart(c.status, status_bytes, c.a, a_bytes, "status overlaps a: the output must not share memory with an operand");
+        if (c.b) lsr::require_apart(c.status, status_bytes, c.b, b_bytes, "status overlaps b: the output must not share memory with an operand");
+        lsr::require_apart(c.status, status_bytes, c.g, g_bytes, "status overlaps g: the two outputs must not share memory");
+        lsr::require_device();
+        lsr::DeviceGuard guard(h->device);
+        if (device) lsr::mod_gram_device(*h, c, static_cast<hipStream_t>(stream));
+        else lsr::host_mod_gram(*h, c);
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t lsr_ring_mod_capacity_product(uint64_t q, uint32_t n, uint64_t bound_a, uint64_t bound_b) noexcept {
+    try {
+        return lsr::ring_mod_capacity_product(q, n, bound_a, bound_b);
+    } catch (...) {
+        return 0;
+    }
+}
+
+int lsr_ring_mod_gram_prepare(const LsrRingMod* h) noexcept {
+    const char* const where = "lsr_ring_mod_gram_prepare";
+    if (!h) return lsr::abi_refuse(where, "NULL handle");
+    return lsr::abi_guarded(where, [&] {
+        lsr::require_device();
+        lsr::DeviceGuard guard(h->device);
+        std::lock_guard<std::mutex> lock(h->mutex);
+        if (!h->gram_ws.ptr) h->gram_ws.allocate(2 * lsr::ring_mod_gram_words() + lsr::kRingModGramFlagWords);
+    });
+}
+
+int lsr_ring_mod_gram_batch(const LsrRingMod* h, uint64_t* g, int32_t* status, const uint64_t* a, const uint64_t* b, size_t batch, size_t ra, size_t rb,
+                            size_t width, uint64_t bound_a, uint64_t bound_b) noexcept {
+    return mod_gram_call("lsr_ring_mod_gram_batch", h, {g, status, a, b, batch, ra, rb, width, false, bound_a, bound_b}, false, nullptr);
+}
+int lsr_ring_mod_gram_batch_device(const LsrRingMod* h, uint64_t* d_g, int32_t* d_status, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t ra,
+                                   size_t rb, size_t width, uint64_t bound_a, uint64_t bound_b, void* stream) noexcept {
+    return mod_gram_call("lsr_ring_mod_gram_batch_device", h, {d_g, d_status, d_a, d_b, batch, ra, rb, width, false, bound_a, bound_b}, true, stream);
+}
+int lsr_ring_mod_gram_sym2_batch(const LsrRingMod* h, uint64_t* out, int32_t* status, const uint64_t* a, const uint64_t* b, size_t batch, size_t r,
+                                 size_t width, uint64_t bound_a, uint64_t bound_b) noexcept {
+    return mod_gram_call("lsr_ring_mod_gram_sym2_batch", h, {out, status, a, b, batch, r, r, width, true, bound_a, bound_b}, false, nullptr);
+}
+int lsr_ring_mod_gram_sym2_batch_device(const LsrRingMod* h, uint64_t* d_out, int32_t* d_status, const uint64_t* d_a, const uint64_t* d_b, size_t batch,
+                                        size_t r, size_t width, uint64_t bound_a, uint64_t bound_b, void* stream) noexcept {
+    return mod_gram_call("lsr_ring_mod_gram_sym2_batch_device", h, {d_out, d_status, d_a, d_b, batch, r, r, width, true, bound_a, bound_b}, true, stream);
+}
+
+}  // extern "C"
