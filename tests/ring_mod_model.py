@@ -155,6 +155,59 @@ def largest_admissible(n):
     return lo
 
 
+def edge_words(q):
+    """the words at which lift and reduce decide: 0, 1, h = floor(q / 2) (the largest word that is its own centred representative),
+    h + 1 (the most negative one; q - 1 at q = 2) and q - 1"""
+    h = q // 2
+    return [0, 1, h, min(h + 1, q - 1), q - 1]
+
+
+def planted(rng, q, shape, fill=None):
+    """A uint64 array [vectors, ..., n] of uniform words mod q (rng: a numpy Generator) with planted edges.
+    fill {vector: word}: polynomial 0 of that vector is all `word` (the whole-polynomial extremes a caller pairs across two operands).
+    The five edge_words sit at distinct random positions in every polynomial of vector 0 that `fill` leaves alone — as many of them as
+    n holds, rotating through the five — and onward through the following free polynomials until each of the five has been planted."""
+    import numpy as np
+    fill = fill or {}
+    n = shape[-1]
+    x = rng.integers(0, q, size=shape, dtype=np.uint64)
+    polys = x.reshape(shape[0], -1, n)
+    per_vector, edges, take = polys.shape[1], edge_words(q), min(n, 5)
+    nxt, done = 0, set()
+    for k in range(shape[0] * per_vector):
+        v, i = divmod(k, per_vector)
+        if v >= 1 and len(done) == 5:
+            break
+        if i == 0 and v in fill:
+            continue
+        for pos in rng.choice(n, size=take, replace=False).tolist():
+            polys[v, i, pos] = edges[nxt % 5]
+            done.add(nxt % 5)
+            nxt += 1
+    for v, word in fill.items():
+        polys[v, 0, :] = word
+    if len(done) < 5:
+        raise ValueError("shape %r is too small for the five edge words" % (shape,))
+    return x
+
+
+def dot_through_primes(a_terms, b_terms, q, centre=centre, reduce=reduce):
+    """sum_i a_i b_i mod (X^n + 1, q) the way a handle computes it: the exact integer product of the centred operands (schoolbook),
+    its residues mod the two primes, and reduce.  `centre` and `reduce` are arguments so that a test can hand in a broken copy."""
+    n = len(a_terms[0])
+    p1, p2 = primes(n)
+    total = [0] * n
+    for a, b in zip(a_terms, b_terms):
+        a, b = [centre(int(v), q) for v in a], [centre(int(v), q) for v in b]
+        for i, ai in enumerate(a):
+            for j, bj in enumerate(b):
+                if i + j < n:
+                    total[i + j] += ai * bj
+                else:
+                    total[i + j - n] -= ai * bj
+    return [reduce(*residues(v, p1, p2), q, p1, p2) for v in total]
+
+
 # ---- the model's own tests (collected through tests/test_ring_mod_abi.py) --------------------------------------------------------
 def test_kronecker_equals_schoolbook():
     rng = random.Random(5)
@@ -192,3 +245,74 @@ def test_lift_and_reduce_round_trip():
     assert capacity(2, 64) == min((big - 1) // 2 // 64, 2**64 - 1) and capacity(1, 64) == 0 and capacity(3329, 3) == 0
     top = largest_admissible(64)
     assert capacity(top, 64) >= 1 and capacity(top + 1, 64) == 0
+
+
+def test_planted_arrays_hold_the_five_edge_words():
+    import numpy as np
+    rng = np.random.default_rng(9)
+    for n in (2, 4, 8, 64):
+        for q in (largest_admissible(n), prime_5_mod_8_below(1 << 32), 3329):
+            h, per_tile = q // 2, 4096 // n
+            fill = {0: h, 1: h, per_tile: h, per_tile + 2: min(h + 1, q - 1)}
+            for shape in [(per_tile + 3, n), (per_tile + 3, 3, n), (per_tile + 3, 2, 2, n)]:
+                for f in ({}, fill):
+                    x = planted(rng, q, shape, f)
+                    assert x.shape == shape and x.dtype == np.uint64 and int(x.max()) < q
+                    assert set(edge_words(q)) <= set(x.reshape(-1).tolist()), (n, q, shape)
+                    polys = x.reshape(shape[0], -1, n)
+                    for v, word in f.items():
+                        assert (polys[v, 0] == word).all()
+                    for i in range(polys.shape[1]):                                  # every free polynomial of vector 0 holds min(n, 5) of them
+                        if not (i == 0 and 0 in f):
+                            assert len(set(edge_words(q)) & set(polys[0, i].tolist())) >= min(n, 5), (n, q, i)
+    assert edge_words(2) == [0, 1, 1, 1, 1] and edge_words(7) == [0, 1, 3, 4, 6]
+    try:
+        planted(rng, 3329, (1, 2), {0: 1})
+    except ValueError:
+        pass
+    else:
+        raise AssertionError("a shape without room for the five words is refused")
+
+
+def test_planted_products_tell_broken_lift_and_reduce_apart():
+    """Under the largest admissible q the planted pairs — all h by all h, and all h by all h + 1 (-h: that q is odd) — put n h^2 and
+    -n h^2 into coefficient n - 1, within n (2 h + 1) of the ends of the CRT range.  A centre that sends h to h - q makes that
+    coefficient n (h + 1)^2, outside the range: the reference changes.  The sign decision of reduce is pinned from both sides: a
+    threshold n (2 h + 1) lower takes n h^2 for a negative, one as much higher takes -n h^2 for a positive.  `>` against `>=` differs
+    at the integer (P - 1) / 2 alone, and no admissible operands produce it: a coefficient is at most n h^2 < (P - 1) / 2 in
+    magnitude (asserted), so that one mistake is invisible through products — test_ring_mod_gpu.py's test_reduce_alone feeds the
+    residues of (P - 1) / 2 themselves."""
+    for n in (2, 4, 16):
+        q = largest_admissible(n)
+        h, (p1, p2) = q // 2, primes(n)
+        half_p = (p1 * p2 - 1) // 2
+        margin = n * (2 * h + 1)
+        assert q % 2 == 1 and capacity(q, n) == 1 and capacity(q + 1, n) == 0
+        assert 0 < half_p - n * h * h < margin
+        pairs = [([h] * n, [h] * n), ([h] * n, [h + 1] * n)]
+
+        def reference(centre_fn=centre, reduce_fn=reduce):
+            return [dot_through_primes([a], [b], q, centre_fn, reduce_fn) for a, b in pairs]
+
+        def reduce_with(threshold, strict=True):
+            def broken(r0, r1, q_, p1_, p2_):
+                big = p1_ * p2_
+                x = (r0 + p1_ * ((r1 - r0) * pow(p1_, -1, p2_) % p2_)) % big
+                if x > threshold or (not strict and x == threshold):
+                    x -= big
+                return x % q_
+            return broken
+
+        want = reference()
+        assert want == [negacyclic_mul(a, b, q) for a, b in pairs]
+        assert want[0][n - 1] == n * h * h % q and want[1][n - 1] == -n * h * h % q
+        assert reference(reduce_fn=reduce_with(half_p)) == want                     # (the local copy is the model's reduce)
+        assert reference(centre_fn=lambda x, q_: x if x < q_ // 2 else x - q_)[0] != want[0]
+        assert reference(reduce_fn=reduce_with(half_p - margin))[0] != want[0]
+        assert reference(reduce_fn=reduce_with(half_p + margin))[1] != want[1]
+        assert reference(reduce_fn=reduce_with(half_p, strict=False)) == want       # >= : the same function on every admissible product
+    rng = random.Random(11)
+    for n, q in [(4, 3329), (8, largest_admissible(8)), (4, 1 << 32)]:
+        a = [[rng.randrange(q) for _ in range(n)] for _ in range(1 if capacity(q, n) == 1 else 3)]
+        b = [[rng.randrange(q) for _ in range(n)] for _ in a]
+        assert dot_through_primes(a, b, q) == negacyclic_dot(a, b, q)

@@ -13,6 +13,8 @@ import pytest
 import ring_mod_model as model
 from ring_mod_model import (test_kronecker_equals_schoolbook,  # noqa: F401  (collected here: the model's own tests)
                             test_lift_and_reduce_round_trip,  # noqa: F401
+                            test_planted_arrays_hold_the_five_edge_words,  # noqa: F401
+                            test_planted_products_tell_broken_lift_and_reduce_apart,  # noqa: F401
                             test_primes_follow_the_rule)  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -222,6 +222,59 @@ def test_flags_are_complete_before_the_first_reduce_of_a_family_in_column_groups
         assert _same(ring.gram(a, b, 0, bound_b), want)
 
 
+# ---- 4b. operands and outputs off the vector alignment ---------------------------------------------------------------------------------
+def test_operands_and_outputs_off_the_vector_alignment(pkg):
+    """a, b and g start one word into their allocations: 8-byte but not 16-byte aligned, where the host takes the one-word-per-lane
+    variants of the lift and of the reduce.  Width 3 within 128 is one group (the check rides in the lift); width 9 without bounds
+    is above the capacity of 7 (a check-only pass, lifts without the check, a plain and an accumulating reduce); a word at
+    bound + 1 zeroes its family.  The words around g and behind status stay as they were."""
+    import torch
+    n, q, ra, rb, batch, bound = 64, Q40, 3, 2, 2, 128
+    sentinel, status_sentinel = 0x5A5A5A5A5A5A5A5A, 7
+    assert mod.capacity(q, n) == 7
+    rng = np.random.default_rng(816)
+
+    def off_alignment(x):
+        d = torch.full((x.size + 2,), sentinel, dtype=torch.int64, device="cuda")
+        d[1:1 + x.size].copy_(_dev(torch, x).reshape(-1))
+        assert (d.data_ptr() + 8) % 16 == 8
+        return d
+
+    def run(ring, a, b, bound_a, bound_b):
+        d_a, d_b = off_alignment(a), off_alignment(b)
+        words = batch * ra * rb * n
+        d_g = torch.full((words + 3,), sentinel, dtype=torch.int64, device="cuda")
+        d_status = torch.full((batch + 2,), status_sentinel, dtype=torch.int32, device="cuda")
+        assert (d_g.data_ptr() + 8) % 16 == 8
+        ring.gram_device(d_g.data_ptr() + 8, d_status.data_ptr(), d_a.data_ptr() + 8, d_b.data_ptr() + 8, batch, ra, rb, a.shape[2], bound_a, bound_b,
+                         stream=_stream(torch))
+        torch.cuda.synchronize()
+        g, status = _host(d_g), d_status.cpu().numpy()
+        assert g[0] == sentinel and (g[1 + words:] == sentinel).all(), "the words around g were written"
+        assert status[batch:].tolist() == [status_sentinel] * 2, "the words behind status were written"
+        for d, x in ((d_a, a), (d_b, b)):
+            assert np.array_equal(_host(d)[1:-1], x.reshape(-1)) and _host(d)[0] == sentinel == _host(d)[-1]
+        return g[1:1 + words].reshape(batch, ra, rb, n), status[:batch]
+
+    with pkg.RingMod(q, n, device=0) as ring:
+        a, b = _random(rng, q, (batch, ra, 3, n), bound=bound), _random(rng, q, (batch, rb, 3, n), bound=bound)
+        a[0, 0, 0, 0], a[1, 2, 2, n - 1], b[0, 1, 2, 5], b[1, 0, 0, 0] = bound, q - bound, q - bound, bound       # the bounds met exactly
+        assert pkg.ring_mod_capacity_product(q, n, bound, bound) >= 3
+        want = _want(model.gram(a, b, q, bound, bound), (batch, ra, rb, n))
+        assert want[1].tolist() == [1, 1] and _same(run(ring, a, b, bound, bound), want)
+
+        width = 9                                                                # 7 + 2
+        assert ring.max_terms == 7 == pkg.ring_mod_capacity_product(q, n, q // 2, q // 2) < width
+        wide_a, wide_b = _with_extremes(_random(rng, q, (batch, ra, width, n)), q), _with_extremes(_random(rng, q, (batch, rb, width, n)), q)
+        want = _want(model.gram(wide_a, wide_b, q), (batch, ra, rb, n))
+        assert want[1].tolist() == [1, 1] and _same(run(ring, wide_a, wide_b, 0, 0), want)
+
+        b[1, 1, 2, n - 1] = bound + 1
+        want = _want(model.gram(a, b, q, bound, bound), (batch, ra, rb, n))
+        got = run(ring, a, b, bound, bound)
+        assert want[1].tolist() == [1, 0] and want[0][0].any() and _same(got, want) and not got[0][1].any()
+
+
 # ---- 5. workspace edges -------------------------------------------------------------------------------------------------------------
 def _workspace_words():
     """per prime, as batch.h states it"""

@@ -245,7 +245,9 @@ def test_graph_capture_straight_after_create(pkg):
 # ---- the integer flavour of the prime contexts ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [64, 2048])
 def test_integer_flavour_equals_the_fp64_flavour(pkg, lib, n):
-    """a process that forces the integer kernels: row blocks of 2, and at n = 2048 the gadget product launches once per prime"""
+    """a process that forces the integer kernels: row blocks of 2, and at n = 2048 the gadget product launches once per prime.  Both
+    flavours are held to the model as well as to each other: a mistake they share (the loader, the column-range addressing, the
+    reduce pass) does not cancel."""
     import torch
     q, b, xcols, batch = P5, 8, 3, 3                                                         # (2^40 + 15 is not admissible at n = 2048)
     digits = gadget.min_digits(q, b)
@@ -253,7 +255,8 @@ def test_integer_flavour_equals_the_fp64_flavour(pkg, lib, n):
     assert mod.capacity(q, n) >= 1 and digits >= 4
     rng = np.random.default_rng(n + 11)
     m = _random(rng, q, (ROWS, cols, n))
-    x, xg = _random(rng, q, (batch, cols, n)), _with_extremes(_random(rng, q, (batch, xcols, n)), q)
+    x, xg = _with_extremes(_random(rng, q, (batch, cols, n)), q), _with_extremes(_random(rng, q, (batch, xcols, n)), q)
+    want, want_gadget = model.matvec(m, x, q), model.matvec_gadget(m, xg, q, b, digits)
     lib.lsr_set_arith_mode(1)
     try:
         integer = pkg.RingMod(q, n, device=0)
@@ -265,6 +268,9 @@ def test_integer_flavour_equals_the_fp64_flavour(pkg, lib, n):
             assert (mi.row_block, mf.row_block) == (2, 4)
             assert np.array_equal(_matvec_device(torch, mi, x), _matvec_device(torch, mf, x))
             assert np.array_equal(_matvec_device(torch, mi, xg, (b, digits)), _matvec_device(torch, mf, xg, (b, digits)))
+            for name, mat in (("integer", mi), ("fp64", mf)):
+                assert np.array_equal(_matvec_device(torch, mat, x), want), name
+                assert np.array_equal(_matvec_device(torch, mat, xg, (b, digits)), want_gadget), name
 
 
 # ---- 10. an NTT prime the handle admits ---------------------------------------------------------------------------------------------
