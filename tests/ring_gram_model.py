@@ -3,9 +3,16 @@ g[j][i][l] = sum_{c < width} a[j][i][c] * b[j][l][c] in Z_q[X]/(X^n + 1) (sign =
 
   * packed_index:     the polynomial of the pair (i, l), i <= l, in the packed upper triangle of the symmetric form;
   * schoolbook_gram:  the definition on Python integers, cross form ([batch][ra][rb][n]) or, b=None, packed ([batch][r (r + 1) / 2][n]);
-  * dot_pairs:        the gathered operands of the route the call replaces, [batch * pairs][width][n] each, pairs in output order.
-The tests at the bottom (no GPU) pin the index against enumeration, the packed form against the cross form and one case by hand."""
+  * dot_pairs:        the gathered operands of the route the call replaces, [batch * pairs][width][n] each, pairs in output order;
+  * oracle_gram:      a second reference that shares nothing with the schoolbook — the CPU oracle's transforms (every operand polynomial
+                      once) around pointwise sums, ring_tile_model's _transform / _pointwise_sum: Goldilocks and the cyclic rings go
+                      through Python integers, the negacyclic ones through the oracle's mul_pointwise.
+The tests at the bottom (no GPU) pin the index against enumeration, the packed form against the cross form and one case by hand, and
+hold the two references against each other in every flavour of ring_tile_model.FLAVOURS before either judges a kernel."""
 import numpy as np
+import pytest
+
+from ring_tile_model import FLAVOURS, GOLDILOCKS, _pointwise_sum, _transform, goldilocks_lazy_carry, omega_for, planted
 
 
 def packed_index(r, i, l):
@@ -59,7 +66,43 @@ def dot_pairs(a, b):
             np.ascontiguousarray(b[:, ll]).reshape(batch * len(idx), width, n))
 
 
+# ---- the oracle's transforms around pointwise sums ------------------------------------------------------------------------------------
+def oracle_pair_sums(oracle, q, n, fa, fb, idx, cyclic):
+    """fa [batch, ra, terms, n], fb [batch, rb, terms, n] in the evaluation domain, idx a list of (i, l) -> [batch, len(idx), n]:
+    sum_c fa[j][i][c] . fb[j][l][c] per pair, canonical."""
+    ii, ll = [i for i, _ in idx], [l for _, l in idx]
+    return _pointwise_sum(oracle, q, n, np.ascontiguousarray(fa[:, ii]), np.ascontiguousarray(fb[:, ll]), cyclic)
+
+
+def oracle_gram(oracle, q, n, a, b, cyclic, omega):
+    """a: [batch, ra, width, n], b: [batch, rb, width, n] or None -> uint64 [batch, ra, rb, n], or packed [batch, r (r + 1) / 2, n]:
+    INTT(sum_c NTT(a_i[c]) . NTT(b_l[c])), every operand polynomial transformed once."""
+    fa = _transform(oracle, q, n, a, cyclic, omega)
+    symmetric = b is None
+    fb = fa if symmetric else _transform(oracle, q, n, b, cyclic, omega)
+    batch, ra, rb = fa.shape[0], fa.shape[1], fb.shape[1]
+    sums = oracle_pair_sums(oracle, q, n, fa, fb, pairs(ra, rb, symmetric), cyclic)
+    out = _transform(oracle, q, n, sums, cyclic, omega, inverse=True)
+    return out if symmetric else out.reshape(batch, ra, rb, n)
+
+
 # ---- the model's own tests (CPU only; collected through tests/test_ring_gram_abi.py) ----------------------------------------------------
+@pytest.mark.parametrize("n", [2, 16])
+@pytest.mark.parametrize("flavour", list(FLAVOURS))
+def test_oracle_gram_equals_schoolbook(oracle, flavour, n):
+    (q, cyclic), omega = FLAVOURS[flavour], omega_for(oracle, flavour, n)
+    sign = 1 if cyclic else -1
+    rng = np.random.default_rng(n + len(flavour))
+    batch, r, rb, width = 2, 5, 3, 2
+    a = planted(rng, q, batch * r * width, n).reshape(batch, r, width, n)
+    b = planted(rng, q, batch * rb * width, n).reshape(batch, rb, width, n)
+    if q == GOLDILOCKS and n >= 4:
+        a[0, 1, 0] = b[1, 2, 0] = goldilocks_lazy_carry(n)
+    assert oracle_gram(oracle, q, n, a, b, cyclic, omega).tolist() == schoolbook_gram(a, b, q, sign), (flavour, n, "cross")
+    assert oracle_gram(oracle, q, n, a, None, cyclic, omega).tolist() == schoolbook_gram(a, None, q, sign), (flavour, n, "symmetric")
+    assert oracle_gram(oracle, q, n, a, a, cyclic, omega).tolist() == schoolbook_gram(a, a, q, sign), (flavour, n, "b is a")
+
+
 def test_packed_index_matches_enumeration():
     for r in range(1, 7):
         order = pairs(r, r, True)

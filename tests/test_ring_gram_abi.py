@@ -9,6 +9,7 @@ import re
 import pytest
 
 from ring_gram_model import (test_gram_by_hand,  # noqa: F401  (collected here: the model's own tests)
+                             test_oracle_gram_equals_schoolbook,  # noqa: F401
                              test_packed_index_matches_enumeration,  # noqa: F401
                              test_symmetric_form_is_the_upper_triangle_of_the_cross_form)  # noqa: F401
 

@@ -1,7 +1,8 @@
 """GPU suite: the ring Gram matrices g[j][i][l] = sum_c a[j][i][c] b[j][l][c] (lsr_ntt_ring_gram_batch / _device).
 Pinned against the schoolbook definition, word for word against the ring inner product pair by pair in every arithmetic flavour on
 every edge of the register block, in where the outputs land, at the accumulators' worst case, under a shrunken workspace (column
-groups, family chunks), in the refusals that read the context, and in the device form across streams and under graph capture."""
+groups, family chunks), in the refusals that read the context, and in the device form across streams and under graph capture.
+The sweep against models that share nothing with the library, in every flavour, lives in tests/test_ring_gram_sweep_gpu.py."""
 import os
 import subprocess
 import sys

@@ -8,7 +8,9 @@ import re
 
 import pytest
 
-from ring_quadform_model import (test_quadform_by_hand,  # noqa: F401  (collected here: the model's own tests)
+from ring_quadform_model import (test_flat_spectrum_closed_forms_equal_schoolbook,  # noqa: F401  (collected here: the model's own tests)
+                                 test_oracle_references_equal_schoolbook,  # noqa: F401
+                                 test_quadform_by_hand,  # noqa: F401
                                  test_quadform_of_a_gram_matrix_is_the_norm_of_the_fold,  # noqa: F401
                                  test_sym2_is_the_cross_form_plus_its_transpose)  # noqa: F401
 

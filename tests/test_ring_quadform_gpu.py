@@ -4,7 +4,8 @@ Pinned against the schoolbook definitions, word for word against the composed ro
 product; ring inner products per pair added mod q) in every arithmetic flavour, at the accumulators' worst case and on either side
 of the FP64 re-centring period, in where the outputs land, under a shrunken workspace (groups of pairs, family chunks, column
 groups), in the refusals that read the context, in the device form across streams and under graph capture, and in the verifier's
-two closing identities of a folded witness."""
+two closing identities of a folded witness.
+The sweep against models that share nothing with the library, in every flavour, lives in tests/test_ring_gram_sweep_gpu.py."""
 import os
 import subprocess
 import sys
