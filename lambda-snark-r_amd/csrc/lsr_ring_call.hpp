@@ -1,14 +1,21 @@
-// The host call path shared by the fused ring operations (lsr_ring_mul.hip, lsr_ring_dot.hip, lsr_ring_fold.hip, lsr_ring_matvec.hip,
-// lsr_ring_gadget.hip, lsr_ring_galois.hip, lsr_ring_sample.hip, lsr_ring_challenge.hip and the ring combination of lsr_commit.hip): the dispatch from a context to a kernel
-// instantiation, the bracket that keeps the context's workspaces safe across streams and threads, the argument checks
-// the entry points have in common and the staging of host buffers.  The dispatch helpers (for_tile_log, for_rank, for_top_bits,
-// for_bool, for_flavour) also serve the commitment pipelines of lsr_commit.hip.  Host code only.
+// The host call path shared by the ring operations (lsr_ring_mul.hip, lsr_ring_dot.hip, lsr_ring_fold.hip, lsr_ring_matvec.hip,
+// lsr_ring_gadget.hip, lsr_ring_galois.hip, lsr_ring_sample.hip, lsr_ring_challenge.hip, lsr_ring_pack.hip, lsr_ring_norm.hip,
+// lsr_ring_scalar.hip, lsr_ring_gram.hip, lsr_ring_quadform.hip, the ring handles of lsr_ring_mod.hip, lsr_ring_mod_matvec.hip and
+// lsr_ring_mod_gram.hip, and the ring combination of lsr_commit.hip): the dispatch from a context to a kernel instantiation, the
+// bracket that keeps the context's workspaces safe across streams and threads, the argument checks the entry points
+// have in common and the one loop that stages host buffers through bounded device chunks (host_staged; its arithmetic:
+// lsr_staging_plan.hpp).  The dispatch helpers (for_tile_log, for_rank, for_top_bits, for_bool, for_flavour) also serve the commitment
+// pipelines of lsr_commit.hip.  Host code only.
 #pragma once
 #include <algorithm>
+#include <cstdlib>
+#include <initializer_list>
+#include <stdexcept>
 #include <type_traits>
 
 #include "lsr_ntt_kernels.hpp"
 #include "lsr_runtime.hpp"
+#include "lsr_staging_plan.hpp"
 
 namespace lsr {
 
@@ -98,25 +105,79 @@ inline void refuse_above_two_pass(const NttContext& c, const char* message) {
     if (c.logn > kTwoPassMaxLog2) throw std::runtime_error(message);
 }
 
-// bytes of device memory one host-pointer call stages at a time
-constexpr size_t kStagingBytes = 256ull << 20;
+// bytes of device memory one host-pointer call stages at a time: LAMBDA_SNARK_STAGING_MIB (a positive integer, read once per
+// process; a test and tuning knob as LAMBDA_SNARK_NTT_CHUNK_MIB is), 256 MiB when unset or unparsable
+inline size_t staging_bytes() {
+    static const size_t bytes = [] {
+        if (const char* e = std::getenv("LAMBDA_SNARK_STAGING_MIB")) {
+            const long v = std::atol(e);
+            if (v > 0) return static_cast<size_t>(v) << 20;
+        }
+        return static_cast<size_t>(256) << 20;
+    }();
+    return bytes;
+}
 
-// Host buffers through bounded device chunks on the context's work stream: `in_words` words go up and `out_words` words come back
-// per item, `run(d_out, d_in, now, s)` enqueues the work of `now` items.
+// the items of a call that fit the staging bound at `words_per_item` staged words each: at least 1, at most `count`
+inline size_t staging_chunk(size_t count, size_t words_per_item) {
+    return std::max<size_t>(1, std::min<size_t>(count, (staging_bytes() / 8) / words_per_item));
+}
+
+// what `run` sees of one chunk: items [first, first + now) of the call, the device buffer of each lane in the order the lanes were
+// declared (an absent lane: NULL), and group_first, the group the group lanes' buffers start at
+constexpr size_t kStagedMaxLanes = 4;
+struct StagedChunk {
+    size_t first, now, group_first;
+    void* buffer[kStagedMaxLanes];
+    template <class T>
+    T* lane(size_t i) const { return static_cast<T*>(buffer[i]); }
+};
+
+// The host buffers of a call of `count` items through bounded device chunks of `chunk` items on the context's work stream (DESIGN.md
+// §5c; the lanes and their arithmetic: lsr_staging_plan.hpp).  Per chunk, in stream order: the uploads, `run(chunk, s)`, which
+// enqueues the device work of the chunk's items and nothing else, the downloads, one synchronisation.  The group lanes of a call
+// share one `components`.
 template <class Run>
-void host_staged(const NttContext& c, uint64_t* out, const uint64_t* in, size_t count, size_t out_words, size_t in_words, Run&& run) {
+void host_staged(const NttContext& c, size_t count, size_t chunk, std::initializer_list<StagedLane> lanes, Run&& run) {
+    if (lanes.size() > kStagedMaxLanes) throw std::logic_error("host_staged: more lanes than kStagedMaxLanes");
     DeviceGuard guard(c.device);
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(count, (kStagingBytes / 8) / (in_words + out_words)));
-    DeviceBuffer<uint64_t> din(chunk * in_words), dout(chunk * out_words);
+    DeviceBuffer<unsigned char> device[kStagedMaxLanes];
+    StagedChunk k{};
+    size_t components = 0;
+    for (size_t i = 0; i < lanes.size(); ++i) {
+        const StagedLane& l = lanes.begin()[i];
+        device[i].allocate(staged_allocation(l, count, chunk));
+        k.buffer[i] = device[i].ptr;
+        if (l.components) components = l.components;
+    }
     std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
     hipStream_t s = work_stream(c);
-    for (size_t j0 = 0; j0 < count; j0 += chunk) {
-        const size_t now = std::min(chunk, count - j0);
-        LSR_HIP(hipMemcpyAsync(din.ptr, in + j0 * in_words, now * in_words * 8, hipMemcpyHostToDevice, s));
-        run(dout.ptr, din.ptr, now, s);
-        LSR_HIP(hipMemcpyAsync(out + j0 * out_words, dout.ptr, now * out_words * 8, hipMemcpyDeviceToHost, s));
+    for (k.first = 0; k.first < count; k.first += chunk) {
+        k.now = std::min(chunk, count - k.first);
+        k.group_first = components ? staged_group_first(k.first, components) : 0;
+        for (size_t i = 0; i < lanes.size(); ++i) {
+            const StagedLane& l = lanes.begin()[i];
+            const StagedCopy copy = staged_copy(l, k.first, k.now);
+            if (staged_uploads(l, k.first))
+                LSR_HIP(hipMemcpyAsync(device[i].ptr, static_cast<const unsigned char*>(l.up) + copy.host_offset, copy.bytes, hipMemcpyHostToDevice, s));
+        }
+        run(k, s);
+        for (size_t i = 0; i < lanes.size(); ++i) {
+            const StagedLane& l = lanes.begin()[i];
+            const StagedCopy copy = staged_copy(l, k.first, k.now);
+            if (l.down && l.extent != 0)
+                LSR_HIP(hipMemcpyAsync(static_cast<unsigned char*>(l.down) + copy.host_offset, device[i].ptr, copy.bytes, hipMemcpyDeviceToHost, s));
+        }
         LSR_HIP(hipStreamSynchronize(s));
     }
+}
+
+// one operand up, one result down: `in_words` words go up and `out_words` words come back per item, `run(d_out, d_in, now, s)`
+// enqueues the work of `now` items
+template <class Run>
+void host_staged(const NttContext& c, uint64_t* out, const uint64_t* in, size_t count, size_t out_words, size_t in_words, Run&& run) {
+    host_staged(c, count, staging_chunk(count, in_words + out_words), {staged_items(in, nullptr, in_words * 8), staged_items(nullptr, out, out_words * 8)},
+                [&](const StagedChunk& k, hipStream_t s) { run(k.lane<uint64_t>(1), k.lane<const uint64_t>(0), k.now, s); });
 }
 
 // The host buffers of a ring inner product c_j = sum_i f(a_{j,i}) b_{j,i} ([batch][terms][n] against [b_rows][terms][n]) through
@@ -129,7 +190,7 @@ void host_staged_dot(const NttContext& c, uint64_t* out, const uint64_t* a, cons
     DeviceGuard guard(c.device);
     const size_t n = c.degree;
     const bool shared_b = b_rows == 1 && batch > 1;
-    const size_t bound = std::max<size_t>(1, kStagingBytes / (n * 8));          // polynomials per staged operand
+    const size_t bound = std::max<size_t>(1, staging_bytes() / (n * 8));          // polynomials per staged operand
     const size_t group_max = std::min(terms, bound), chunk = group_max == terms ? std::max<size_t>(1, std::min(batch, bound / terms)) : 1;
     DeviceBuffer<uint64_t> da(chunk * group_max * n), db((shared_b ? 1 : chunk) * group_max * n), dc(chunk * n);
     std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)

@@ -100,27 +100,6 @@ static void challenge_device(const NttContext& c, uint64_t* d_out, int32_t* d_tr
     LSR_HIP(hipGetLastError());
 }
 
-// host buffers through bounded device chunks of whole elements on the context's work stream; each chunk brings its own key groups
-static void host_challenge(const NttContext& c, uint64_t* out, int32_t* tries, uint64_t count, const ChallengeCall& call, const uint64_t* keys,
-                           const int32_t* d_table) {
-    const size_t n = c.degree;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, (kStagingBytes / 8) / (n + 1)));
-    const uint64_t chunk_groups = chunk / call.components + 2;
-    DeviceBuffer<uint64_t> d_out(chunk * n), d_keys(chunk_groups * 4);
-    DeviceBuffer<int32_t> d_tries(chunk);
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    for (uint64_t e0 = 0; e0 < count; e0 += chunk) {
-        const uint64_t now = std::min(chunk, count - e0);
-        const uint64_t g0 = e0 / call.components, g1 = (e0 + now - 1) / call.components;
-        LSR_HIP(hipMemcpyAsync(d_keys.ptr, keys + 4 * g0, (g1 - g0 + 1) * 32, hipMemcpyHostToDevice, s));
-        challenge_device(c, d_out.ptr, d_tries.ptr, e0, now, call, d_keys.ptr, g0, d_table, s);
-        LSR_HIP(hipMemcpyAsync(out + e0 * n, d_out.ptr, now * n * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipMemcpyAsync(tries + e0, d_tries.ptr, now * 4, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
-}
-
 }  // namespace lsr
 
 // ------------------------------------------------------------------------------------------------
@@ -178,7 +157,13 @@ int challenge_call(const char* where, const NttContext* ctx, uint64_t* out, int3
             lsr::challenge_device(*ctx, out, tries, 0, count, call, keys, 0, d_table, s);
         } else {
             const int32_t* d_table = opnorm_bound ? lsr::resident_table(*ctx, nullptr) : nullptr;
-            lsr::host_challenge(*ctx, out, tries, count, call, keys, d_table);
+            // host buffers through bounded device chunks of whole elements; each chunk brings its own key groups and takes its tries back
+            const size_t n = ctx->degree;
+            lsr::host_staged(*ctx, count, lsr::staging_chunk(count, n + 1),
+                             {lsr::staged_groups(keys, 32, call.components), lsr::staged_items(nullptr, out, n * 8), lsr::staged_items(nullptr, tries, 4)},
+                             [&](const lsr::StagedChunk& k, hipStream_t s) {
+                                 lsr::challenge_device(*ctx, k.lane<uint64_t>(1), k.lane<int32_t>(2), k.first, k.now, call, k.lane<const uint64_t>(0), k.group_first, d_table, s);
+                             });
         }
     });
 }

@@ -125,25 +125,21 @@ static void ring_fold_device(const NttContext& c, uint64_t* d_out, const uint64_
 // groups (the accumulator stays on the device between groups)
 static void host_ring_fold(const NttContext& c, uint64_t* out, const uint64_t* v, const uint64_t* p, size_t outputs, size_t terms, size_t ts,
                            size_t width) {
-    DeviceGuard guard(c.device);
     const size_t n = c.degree, vec = width * n;
-    const size_t bound = std::max<size_t>(1, kStagingBytes / (n * 8));          // polynomials per staged operand
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
+    const size_t bound = std::max<size_t>(1, staging_bytes() / (n * 8));          // polynomials per staged operand
     if (width <= bound && terms <= bound / width) {
         const size_t fit_v = ts == 0 ? outputs : (bound / width - terms) / ts + 1;     // (now - 1) ts + terms vectors within the bound
         const size_t chunk = std::max<size_t>(1, std::min({outputs, fit_v, bound / terms, bound / width}));
-        DeviceBuffer<uint64_t> dv(((chunk - 1) * ts + terms) * vec), dp(chunk * terms * n), dout(chunk * vec);
-        for (size_t j0 = 0; j0 < outputs; j0 += chunk) {
-            const size_t now = std::min(chunk, outputs - j0);
-            if (ts != 0 || j0 == 0) LSR_HIP(hipMemcpyAsync(dv.ptr, v + j0 * ts * vec, ((now - 1) * ts + terms) * vec * 8, hipMemcpyHostToDevice, s));
-            LSR_HIP(hipMemcpyAsync(dp.ptr, p + j0 * terms * n, now * terms * n * 8, hipMemcpyHostToDevice, s));
-            ring_fold_device(c, dout.ptr, dv.ptr, dp.ptr, now, terms, ts, width, s);
-            LSR_HIP(hipMemcpyAsync(out + j0 * vec, dout.ptr, now * vec * 8, hipMemcpyDeviceToHost, s));
-            LSR_HIP(hipStreamSynchronize(s));
-        }
+        host_staged(c, outputs, chunk,
+                    {staged_items(v, nullptr, ts * vec * 8, terms * vec * 8), staged_items(p, nullptr, terms * n * 8), staged_items(nullptr, out, vec * 8)},
+                    [&](const StagedChunk& k, hipStream_t s) {
+                        ring_fold_device(c, k.lane<uint64_t>(2), k.lane<const uint64_t>(0), k.lane<const uint64_t>(1), k.now, terms, ts, width, s);
+                    });
         return;
     }
+    DeviceGuard guard(c.device);
+    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
+    hipStream_t s = work_stream(c);
     const size_t group_max = std::min(terms, bound), wmax = std::min(width, std::max<size_t>(1, bound / group_max));
     DeviceBuffer<uint64_t> dv(group_max * wmax * n), dp(group_max * n), dout(wmax * n);
     for (size_t j = 0; j < outputs; ++j)

@@ -97,31 +97,19 @@ static void ring_gram_device(const NttContext& c, uint64_t* d_g, const uint64_t*
     });
 }
 
-// host buffers through bounded device chunks of whole families on the context's work stream (host_staged with two operands; b == a
-// with rb == ra goes up once)
+// host buffers through bounded device chunks of whole families on the context's work stream; the b lane is absent in the symmetric
+// form and when b == a with rb == ra, where a goes up once and serves as both
 static void host_ring_gram(const NttContext& c, uint64_t* g, const uint64_t* a, const uint64_t* b, size_t batch, size_t ra, size_t rb, size_t width,
                            bool sym2) {
     const size_t n = c.degree;
     const bool sym = b == nullptr, one_set = sym || (b == a && rb == ra);
     const size_t a_words = ra * width * n, b_words = one_set ? 0 : rb * width * n, g_words = gram_outputs(ra, rb, sym || sym2) * n;
-    if (sym) {
-        host_staged(c, g, a, batch, g_words, a_words,
-                    [&](uint64_t* d_g, const uint64_t* d_a, size_t now, hipStream_t s) { ring_gram_device(c, d_g, d_a, nullptr, now, ra, rb, width, false, s); });
-        return;
-    }
-    DeviceGuard guard(c.device);
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, (kStagingBytes / 8) / (a_words + b_words + g_words)));
-    DeviceBuffer<uint64_t> da(chunk * a_words), db(chunk * b_words), dg(chunk * g_words);
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    for (size_t j0 = 0; j0 < batch; j0 += chunk) {
-        const size_t now = std::min(chunk, batch - j0);
-        LSR_HIP(hipMemcpyAsync(da.ptr, a + j0 * a_words, now * a_words * 8, hipMemcpyHostToDevice, s));
-        if (!one_set) LSR_HIP(hipMemcpyAsync(db.ptr, b + j0 * b_words, now * b_words * 8, hipMemcpyHostToDevice, s));
-        ring_gram_device(c, dg.ptr, da.ptr, one_set ? da.ptr : db.ptr, now, ra, rb, width, sym2, s);
-        LSR_HIP(hipMemcpyAsync(g + j0 * g_words, dg.ptr, now * g_words * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
+    host_staged(c, batch, staging_chunk(batch, a_words + b_words + g_words),
+                {staged_items(a, nullptr, a_words * 8), staged_items(b, nullptr, b_words * 8), staged_items(nullptr, g, g_words * 8)},
+                [&](const StagedChunk& k, hipStream_t s) {
+                    const uint64_t* const d_a = k.lane<const uint64_t>(0);
+                    ring_gram_device(c, k.lane<uint64_t>(2), d_a, sym ? nullptr : (one_set ? d_a : k.lane<const uint64_t>(1)), k.now, ra, rb, width, sym2, s);
+                });
 }
 
 }  // namespace lsr

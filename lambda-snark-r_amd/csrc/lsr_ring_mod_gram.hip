@@ -203,26 +203,18 @@ static void host_mod_gram(const LsrRingMod& h, const ModGramCall& c) {
     const ModGramPlan p = mod_gram_plan(h, c);
     const NttContext& ctx = *h.prime[0];
     const size_t n = h.n, a_words = c.ra * c.width * n, b_words = p.one_set ? 0 : c.rb * c.width * n, g_words = p.outs * n;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(c.batch, (kStagingBytes / 8) / (a_words + b_words + g_words)));
-    DeviceBuffer<uint64_t> da(chunk * a_words), db(chunk * b_words), dg(chunk * g_words);
-    DeviceBuffer<int32_t> dstatus(chunk);
-    std::lock_guard<std::mutex> lock(ctx.staging_mutex);   // serialises use of work_stream(ctx)
-    hipStream_t s = work_stream(ctx);
-    for (size_t j0 = 0; j0 < c.batch; j0 += chunk) {
-        const size_t now = std::min(chunk, c.batch - j0);
-        LSR_HIP(hipMemcpyAsync(da.ptr, c.a + j0 * a_words, now * a_words * 8, hipMemcpyHostToDevice, s));
-        if (!p.one_set) LSR_HIP(hipMemcpyAsync(db.ptr, c.b + j0 * b_words, now * b_words * 8, hipMemcpyHostToDevice, s));
-        ModGramCall d = c;
-        d.g = dg.ptr;
-        d.status = dstatus.ptr;
-        d.a = da.ptr;
-        d.b = p.sym ? nullptr : (p.one_set ? da.ptr : db.ptr);
-        d.batch = now;
-        mod_gram_device(h, d, s);
-        LSR_HIP(hipMemcpyAsync(c.g + j0 * g_words, dg.ptr, now * g_words * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipMemcpyAsync(c.status + j0, dstatus.ptr, now * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
+    host_staged(ctx, c.batch, staging_chunk(c.batch, a_words + b_words + g_words),
+                {staged_items(c.a, nullptr, a_words * 8), staged_items(c.b, nullptr, b_words * 8), staged_items(nullptr, c.g, g_words * 8),
+                 staged_items(nullptr, c.status, sizeof(int32_t))},
+                [&](const StagedChunk& k, hipStream_t s) {
+                    ModGramCall d = c;
+                    d.g = k.lane<uint64_t>(2);
+                    d.status = k.lane<int32_t>(3);
+                    d.a = k.lane<const uint64_t>(0);
+                    d.b = p.sym ? nullptr : (p.one_set ? d.a : k.lane<const uint64_t>(1));
+                    d.batch = k.now;
+                    mod_gram_device(h, d, s);
+                });
 }
 
 }  // namespace lsr

@@ -86,22 +86,13 @@ static void ring_mul_device(const NttContext& c, uint64_t* d_c, const uint64_t* 
 // host buffers through bounded device chunks on the context's work stream
 static void host_ring_mul(const NttContext& c, uint64_t* out, const uint64_t* a, const uint64_t* b, size_t batch, size_t b_rows) {
     refuse_large(c);
-    DeviceGuard guard(c.device);
     const size_t n = c.degree;
     const bool shared_b = b_rows == 1 && batch > 1;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, kStagingBytes / (n * 8)));
-    DeviceBuffer<uint64_t> da(chunk * n), db(shared_b ? n : chunk * n);
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    if (shared_b) LSR_HIP(hipMemcpyAsync(db.ptr, b, n * 8, hipMemcpyHostToDevice, s));
-    for (size_t done = 0; done < batch; done += chunk) {
-        const size_t now = std::min(chunk, batch - done);
-        LSR_HIP(hipMemcpyAsync(da.ptr, a + done * n, now * n * 8, hipMemcpyHostToDevice, s));
-        if (!shared_b) LSR_HIP(hipMemcpyAsync(db.ptr, b + done * n, now * n * 8, hipMemcpyHostToDevice, s));
-        ring_mul_device(c, da.ptr, da.ptr, db.ptr, now, shared_b ? 1 : now, s);
-        LSR_HIP(hipMemcpyAsync(out + done * n, da.ptr, now * n * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
+    // each operand within the bound; the product comes back in a's buffer
+    host_staged(c, batch, staging_chunk(batch, n), {staged_items(a, out, n * 8), staged_items(b, nullptr, shared_b ? 0 : n * 8, n * 8)},
+                [&](const StagedChunk& k, hipStream_t s) {
+                    ring_mul_device(c, k.lane<uint64_t>(0), k.lane<const uint64_t>(0), k.lane<const uint64_t>(1), k.now, shared_b ? 1 : k.now, s);
+                });
 }
 
 }  // namespace lsr

@@ -66,23 +66,13 @@ static void project_device(const NttContext& c, int64_t* d_out, int32_t* d_statu
 // host buffers through bounded device chunks of whole vectors on the context's work stream; each chunk brings its own key groups
 static void host_project(const NttContext& c, int64_t* out, int32_t* status, const uint64_t* x, uint64_t count, const ProjectCall& call,
                          const uint64_t* keys) {
-    DeviceGuard guard(c.device);
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, (kStagingBytes / 8) / (call.len + kProjectRows)));
-    const uint64_t chunk_groups = chunk / call.components + 2;
-    DeviceBuffer<uint64_t> d_x(chunk * call.len), d_out(chunk * kProjectRows), d_keys(chunk_groups * 4);
-    DeviceBuffer<int32_t> d_status(chunk);
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    for (uint64_t j0 = 0; j0 < count; j0 += chunk) {
-        const uint64_t now = std::min(chunk, count - j0);
-        const uint64_t g0 = j0 / call.components, g1 = (j0 + now - 1) / call.components;
-        LSR_HIP(hipMemcpyAsync(d_keys.ptr, keys + 4 * g0, (g1 - g0 + 1) * 32, hipMemcpyHostToDevice, s));
-        LSR_HIP(hipMemcpyAsync(d_x.ptr, x + j0 * call.len, now * call.len * 8, hipMemcpyHostToDevice, s));
-        project_device(c, reinterpret_cast<int64_t*>(d_out.ptr), d_status.ptr, d_x.ptr, j0, now, call, d_keys.ptr, g0, s);
-        LSR_HIP(hipMemcpyAsync(out + j0 * kProjectRows, d_out.ptr, now * kProjectRows * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipMemcpyAsync(status + j0, d_status.ptr, now * 4, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
+    host_staged(c, count, staging_chunk(count, call.len + kProjectRows),
+                {staged_groups(keys, 32, call.components), staged_items(x, nullptr, call.len * 8), staged_items(nullptr, out, kProjectRows * 8),
+                 staged_items(nullptr, status, 4)},
+                [&](const StagedChunk& k, hipStream_t s) {
+                    project_device(c, k.lane<int64_t>(2), k.lane<int32_t>(3), k.lane<const uint64_t>(1), k.first, k.now, call, k.lane<const uint64_t>(0),
+                                   k.group_first, s);
+                });
 }
 
 // rows [rows_first, rows_first + rows) of the matrix of (d_key, index_base) into d_out [rows][len]
@@ -98,22 +88,6 @@ static void project_matrix_device(const NttContext& c, uint64_t* d_out, uint64_t
     job.index = index_base + rows_first;
     hipLaunchKernelGGL(ring_project_matrix_kernel, dim3(static_cast<unsigned>(rows * job.chunks)), dim3(kNormThreads), 0, s, job);
     LSR_HIP(hipGetLastError());
-}
-
-static void host_project_matrix(const NttContext& c, uint64_t* out, uint64_t rows_first, uint64_t rows, uint64_t len, const uint64_t* key, uint32_t domain,
-                                uint64_t index_base) {
-    DeviceGuard guard(c.device);
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(rows, (kStagingBytes / 8) / len));
-    DeviceBuffer<uint64_t> d_out(chunk * len), d_key(4);
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    LSR_HIP(hipMemcpyAsync(d_key.ptr, key, 32, hipMemcpyHostToDevice, s));
-    for (uint64_t r0 = 0; r0 < rows; r0 += chunk) {
-        const uint64_t now = std::min(chunk, rows - r0);
-        project_matrix_device(c, d_out.ptr, rows_first + r0, now, len, d_key.ptr, domain, index_base, s);
-        LSR_HIP(hipMemcpyAsync(out + r0 * len, d_out.ptr, now * len * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
 }
 
 struct ProjectAdjointCall {
@@ -161,24 +135,14 @@ static void project_adjoint_device(const NttContext& c, uint64_t* d_out, int32_t
 // weight groups
 static void host_project_adjoint(const NttContext& c, uint64_t* out, int32_t* status, const uint64_t* weights, uint64_t count,
                                  const ProjectAdjointCall& call, const uint64_t* keys) {
-    DeviceGuard guard(c.device);
     const uint64_t per_vector = call.sets * call.len, per_group = call.sets * kProjectRows;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, (kStagingBytes / 8) / per_vector));
-    const uint64_t chunk_groups = chunk / call.components + 2;
-    DeviceBuffer<uint64_t> d_out(chunk * per_vector), d_weights(chunk_groups * per_group), d_keys(chunk_groups * 4);
-    DeviceBuffer<int32_t> d_status(chunk);
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    for (uint64_t j0 = 0; j0 < count; j0 += chunk) {
-        const uint64_t now = std::min(chunk, count - j0);
-        const uint64_t g0 = j0 / call.components, g1 = (j0 + now - 1) / call.components;
-        LSR_HIP(hipMemcpyAsync(d_keys.ptr, keys + 4 * g0, (g1 - g0 + 1) * 32, hipMemcpyHostToDevice, s));
-        LSR_HIP(hipMemcpyAsync(d_weights.ptr, weights + g0 * per_group, (g1 - g0 + 1) * per_group * 8, hipMemcpyHostToDevice, s));
-        project_adjoint_device(c, d_out.ptr, d_status.ptr, d_weights.ptr, j0, now, call, d_keys.ptr, g0, s);
-        LSR_HIP(hipMemcpyAsync(out + j0 * per_vector, d_out.ptr, now * per_vector * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipMemcpyAsync(status + j0, d_status.ptr, now * 4, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
+    host_staged(c, count, staging_chunk(count, per_vector),
+                {staged_groups(keys, 32, call.components), staged_groups(weights, per_group * 8, call.components),
+                 staged_items(nullptr, out, per_vector * 8), staged_items(nullptr, status, 4)},
+                [&](const StagedChunk& k, hipStream_t s) {
+                    project_adjoint_device(c, k.lane<uint64_t>(2), k.lane<int32_t>(3), k.lane<const uint64_t>(1), k.first, k.now, call,
+                                           k.lane<const uint64_t>(0), k.group_first, s);
+                });
 }
 
 }  // namespace lsr
@@ -281,7 +245,11 @@ int project_matrix_call(const char* where, const NttContext* ctx, uint64_t* out,
             lsr::DeviceGuard guard(ctx->device);
             lsr::project_matrix_device(*ctx, out, rows_first, rows, len, key, domain, index_base, static_cast<hipStream_t>(stream));
         } else {
-            lsr::host_project_matrix(*ctx, out, rows_first, rows, len, key, domain, index_base);
+            // host rows through bounded device chunks; the key goes up once
+            lsr::host_staged(*ctx, rows, lsr::staging_chunk(rows, len), {lsr::staged_items(key, nullptr, 0, 32), lsr::staged_items(nullptr, out, len * 8)},
+                             [&](const lsr::StagedChunk& k, hipStream_t s) {
+                                 lsr::project_matrix_device(*ctx, k.lane<uint64_t>(1), rows_first + k.first, k.now, len, k.lane<const uint64_t>(0), domain, index_base, s);
+                             });
         }
     });
 }

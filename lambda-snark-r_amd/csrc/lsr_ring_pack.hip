@@ -100,22 +100,13 @@ static void unpack_device(const NttContext& c, uint64_t* d_out, int32_t* d_statu
 // Host buffers through bounded device chunks of whole elements on the context's work stream: `in_words` words per element go up,
 // `out_words` words and a status come back.
 static void host_pack(const NttContext& c, uint64_t* out, int32_t* status, const uint64_t* in, uint64_t count, const PackCall& call, bool unpack) {
-    DeviceGuard guard(c.device);
     const uint64_t in_words = unpack ? call.wpe : call.n, out_words = unpack ? call.n : call.wpe;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, (kStagingBytes / 8) / (in_words + out_words)));
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    DeviceBuffer<uint64_t> d_in(chunk * in_words), d_out(chunk * out_words);
-    DeviceBuffer<int32_t> d_status(chunk);
-    for (uint64_t j0 = 0; j0 < count; j0 += chunk) {
-        const uint64_t now = std::min(chunk, count - j0);
-        LSR_HIP(hipMemcpyAsync(d_in.ptr, in + j0 * in_words, now * in_words * 8, hipMemcpyHostToDevice, s));
-        if (unpack) unpack_device(c, d_out.ptr, d_status.ptr, d_in.ptr, now, call, s);
-        else pack_device(c, d_out.ptr, d_status.ptr, d_in.ptr, now, call, s);
-        LSR_HIP(hipMemcpyAsync(out + j0 * out_words, d_out.ptr, now * out_words * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipMemcpyAsync(status + j0, d_status.ptr, now * 4, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
+    host_staged(c, count, staging_chunk(count, in_words + out_words),
+                {staged_items(in, nullptr, in_words * 8), staged_items(nullptr, out, out_words * 8), staged_items(nullptr, status, 4)},
+                [&](const StagedChunk& k, hipStream_t s) {
+                    if (unpack) unpack_device(c, k.lane<uint64_t>(1), k.lane<int32_t>(2), k.lane<const uint64_t>(0), k.now, call, s);
+                    else pack_device(c, k.lane<uint64_t>(1), k.lane<int32_t>(2), k.lane<const uint64_t>(0), k.now, call, s);
+                });
 }
 
 }  // namespace lsr

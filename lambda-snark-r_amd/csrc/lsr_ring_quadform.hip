@@ -114,20 +114,11 @@ static void host_ring_quadform(const NttContext& c, uint64_t* out, const uint64_
     const size_t n = c.degree;
     const bool shared = c_rows == 1;
     const size_t g_words = r * (r + 1) / 2 * n, c_words = r * n;
-    DeviceGuard guard(c.device);
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(batch, (kStagingBytes / 8) / (g_words + c_words + n)));
-    DeviceBuffer<uint64_t> dg(chunk * g_words), dc((shared ? 1 : chunk) * c_words), dout(chunk * n);
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    if (shared) LSR_HIP(hipMemcpyAsync(dc.ptr, cc, c_words * 8, hipMemcpyHostToDevice, s));
-    for (size_t j0 = 0; j0 < batch; j0 += chunk) {
-        const size_t now = std::min(chunk, batch - j0);
-        LSR_HIP(hipMemcpyAsync(dg.ptr, g + j0 * g_words, now * g_words * 8, hipMemcpyHostToDevice, s));
-        if (!shared) LSR_HIP(hipMemcpyAsync(dc.ptr, cc + j0 * c_words, now * c_words * 8, hipMemcpyHostToDevice, s));
-        ring_quadform_device(c, dout.ptr, dg.ptr, dc.ptr, now, r, shared ? 1 : now, offdiag, s);
-        LSR_HIP(hipMemcpyAsync(out + j0 * n, dout.ptr, now * n * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
+    host_staged(c, batch, staging_chunk(batch, g_words + c_words + n),
+                {staged_items(g, nullptr, g_words * 8), staged_items(cc, nullptr, shared ? 0 : c_words * 8, c_words * 8), staged_items(nullptr, out, n * 8)},
+                [&](const StagedChunk& k, hipStream_t s) {
+                    ring_quadform_device(c, k.lane<uint64_t>(2), k.lane<const uint64_t>(0), k.lane<const uint64_t>(1), k.now, r, shared ? 1 : k.now, offdiag, s);
+                });
 }
 
 }  // namespace lsr

@@ -89,25 +89,6 @@ void sample_uniform_device(uint64_t q, int logn, uint64_t* d_out, uint64_t count
     sample_device(SampleRing{q, logn, 1u << logn}, d_out, 0, count, SampleCall{LSR_RING_SAMPLE_UNIFORM, 0, count, domain, index_base}, d_key, 0, s);
 }
 
-// host buffers through bounded device chunks of whole elements on the context's work stream; each chunk brings its own key groups
-static void host_sample(const NttContext& c, uint64_t* out, uint64_t count, const SampleCall& call, const uint64_t* keys) {
-    DeviceGuard guard(c.device);
-    const size_t n = c.degree;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(count, (kStagingBytes / 8) / n));
-    const uint64_t chunk_groups = chunk / call.components + 2;
-    DeviceBuffer<uint64_t> d_out(chunk * n), d_keys(chunk_groups * 4);
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
-    for (uint64_t e0 = 0; e0 < count; e0 += chunk) {
-        const uint64_t now = std::min(chunk, count - e0);
-        const uint64_t g0 = e0 / call.components, g1 = (e0 + now - 1) / call.components;
-        LSR_HIP(hipMemcpyAsync(d_keys.ptr, keys + 4 * g0, (g1 - g0 + 1) * 32, hipMemcpyHostToDevice, s));
-        sample_device(c, d_out.ptr, e0, now, call, d_keys.ptr, g0, s);
-        LSR_HIP(hipMemcpyAsync(out + e0 * n, d_out.ptr, now * n * 8, hipMemcpyDeviceToHost, s));
-        LSR_HIP(hipStreamSynchronize(s));
-    }
-}
-
 }  // namespace lsr
 
 // ------------------------------------------------------------------------------------------------
@@ -134,7 +115,12 @@ static int sample_call(const char* where, const NttContext* ctx, uint64_t* out, 
             lsr::DeviceGuard guard(ctx->device);
             lsr::sample_device(*ctx, out, 0, count, call, keys, 0, static_cast<hipStream_t>(stream));
         } else {
-            lsr::host_sample(*ctx, out, count, call, keys);
+            // host buffers through bounded device chunks of whole elements; each chunk brings its own key groups
+            lsr::host_staged(*ctx, count, lsr::staging_chunk(count, ctx->degree),
+                             {lsr::staged_groups(keys, 32, call.components), lsr::staged_items(nullptr, out, (size_t)ctx->degree * 8)},
+                             [&](const lsr::StagedChunk& k, hipStream_t s) {
+                                 lsr::sample_device(*ctx, k.lane<uint64_t>(1), k.first, k.now, call, k.lane<const uint64_t>(0), k.group_first, s);
+                             });
         }
     });
 }

@@ -80,30 +80,24 @@ static void scalar_combine_device(const NttContext& c, uint64_t* d_out, int32_t*
 // group to the next.  There the status is decided here, from the host's copy of the weights: a refused output runs no device work.
 static void host_scalar_combine(const NttContext& c, uint64_t* out, int32_t* status, const uint64_t* v, const uint64_t* weights, const uint64_t* addend,
                                 uint64_t count, const ScalarCombineCall& call) {
-    DeviceGuard guard(c.device);
     const uint64_t len = call.len, sets = call.sets, terms = call.terms, ts = call.term_stride, per_group = sets * terms;
-    const uint64_t fit = std::max<uint64_t>(1, (kStagingBytes / 8) / len);             // vectors of len words within the bound
-    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
-    hipStream_t s = work_stream(c);
+    const uint64_t fit = std::max<uint64_t>(1, (staging_bytes() / 8) / len);             // vectors of len words within the bound
     if (terms + sets <= fit) {
         // (chunk - 1) ts + terms vectors of v and chunk sets vectors of out within the bound
         const uint64_t chunk = std::min(count, (fit - terms + ts) / (ts + sets));
-        const uint64_t chunk_groups = std::min((count - 1) / call.components + 1, chunk / call.components + 2);
-        DeviceBuffer<uint64_t> d_v(((chunk - 1) * ts + terms) * len), d_out(chunk * sets * len), d_weights(chunk_groups * per_group);
-        DeviceBuffer<int32_t> d_status(chunk);
-        for (uint64_t j0 = 0; j0 < count; j0 += chunk) {
-            const uint64_t now = std::min(chunk, count - j0);
-            const uint64_t g0 = j0 / call.components, g1 = (j0 + now - 1) / call.components;
-            if (ts != 0 || j0 == 0) LSR_HIP(hipMemcpyAsync(d_v.ptr, v + j0 * ts * len, ((now - 1) * ts + terms) * len * 8, hipMemcpyHostToDevice, s));
-            LSR_HIP(hipMemcpyAsync(d_weights.ptr, weights + g0 * per_group, (g1 - g0 + 1) * per_group * 8, hipMemcpyHostToDevice, s));
-            if (addend) LSR_HIP(hipMemcpyAsync(d_out.ptr, addend + j0 * sets * len, now * sets * len * 8, hipMemcpyHostToDevice, s));
-            scalar_combine_device(c, d_out.ptr, d_status.ptr, d_v.ptr, d_weights.ptr, addend ? d_out.ptr : nullptr, j0, now, call, g0, s);
-            LSR_HIP(hipMemcpyAsync(out + j0 * sets * len, d_out.ptr, now * sets * len * 8, hipMemcpyDeviceToHost, s));
-            LSR_HIP(hipMemcpyAsync(status + j0, d_status.ptr, now * 4, hipMemcpyDeviceToHost, s));
-            LSR_HIP(hipStreamSynchronize(s));
-        }
+        host_staged(c, count, chunk,
+                    {staged_items(v, nullptr, ts * len * 8, terms * len * 8), staged_groups(weights, per_group * 8, call.components),
+                     staged_items(addend, out, sets * len * 8), staged_items(nullptr, status, 4)},
+                    [&](const StagedChunk& k, hipStream_t s) {
+                        uint64_t* const d_out = k.lane<uint64_t>(2);
+                        scalar_combine_device(c, d_out, k.lane<int32_t>(3), k.lane<const uint64_t>(0), k.lane<const uint64_t>(1), addend ? d_out : nullptr,
+                                              k.first, k.now, call, k.group_first, s);
+                    });
         return;
     }
+    DeviceGuard guard(c.device);
+    std::lock_guard<std::mutex> lock(c.staging_mutex);   // serialises use of work_stream(c)
+    hipStream_t s = work_stream(c);
     const uint64_t group_max = std::min(terms, fit > sets ? fit - sets : 1);
     DeviceBuffer<uint64_t> d_v(group_max * len), d_out(sets * len), d_weights(sets * group_max);
     DeviceBuffer<int32_t> d_status(1);
