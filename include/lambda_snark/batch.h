@@ -888,6 +888,54 @@ int lsr_ring_mod_gram_sym2_batch(const LsrRingMod* h, uint64_t* out, int32_t* st
 int lsr_ring_mod_gram_sym2_batch_device(const LsrRingMod* h, uint64_t* d_out, int32_t* d_status, const uint64_t* d_a, const uint64_t* d_b,
                                         size_t batch, size_t r, size_t width, uint64_t bound_a, uint64_t bound_b, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: fold under any modulus (ring vectors by ring-valued challenges on a ring handle) ---------------- */
+/* The fold z_j = sum_i c_{j,i} s_{j term_stride + i} of a lattice argument — the prover's fold of the witness, the verifier's fold of
+ * the commitments — in Z_q[X]/(X^n + 1) for the q of an LsrRingMod, n <= 4096:
+ *   out[j][c] = sum_{i < terms} p[j][i] * v[j term_stride + i][c].
+ * Shapes, layouts and term_stride (0, terms, or anything else) are those of lsr_ntt_ring_fold_batch: v [vectors][width][n] with
+ * vectors = (outputs - 1) term_stride + terms, p [outputs][terms][n], out [outputs][width][n].  The ring is negacyclic.
+ *
+ * Definition.  Every output polynomial out[j][c] equals lsr_ring_mod_dot_batch on the gathered operands a_i = v[j term_stride + i][c],
+ * b_i = p[j][i], word for word: canonical in [0, q); inputs in [0, q); a challenge's -1 is q - 1.
+ * Limits: terms <= LSR_RING_DOT_MAX_TERMS, width <= LSR_RING_FOLD_MAX_WIDTH.
+ *
+ * Bounds and status: those of the Gram matrices above.  bound_v and bound_p are the l-infinity bounds the caller asserts on the
+ * centred representatives of v and of p; 0 states none, which is floor(q/2).  The device VERIFIES them: status is [outputs] (int32),
+ * never NULL, and written for every output:
+ *    1   every word output j reads — the terms width n words of its term vectors and the terms n words of p[j] — was below q and
+ *        within its bound: out[j] is exact;
+ *    0   some such word's centred magnitude exceeded its bound;
+ *   -1   some such word was >= q (-1 wins over 0).
+ * For a status 0 or -1 EVERY word of out[j] is 0; the other outputs are unaffected.  With term_stride == 0 every output reads the same
+ * vectors, so a bad word in v gates every output, while a bad word in p[j] gates output j alone.
+ *
+ * Grouping rule: terms are taken in groups of at most lsr_ring_mod_capacity_product(q, n, bound_v, bound_p) (0 -> floor(q/2)), every
+ * group after the first reduced into out with accumulate.  Exactness never depends on the caller knowing a capacity: q = 2^40 + 15 at
+ * n = 64 carries 7 unbounded products and 2199021131876 with the challenges declared within 2.  A violation found in a later group
+ * still leaves out[j] all zero.
+ *
+ * Range: n <= 4096, as lsr_ring_mod_dot_batch.  Above it the call is refused and the message names the composed route: lift v and p
+ * per prime, lsr_ntt_ring_fold_batch_device on lsr_ring_mod_prime_context(h, i), reduce, the terms in groups of max_terms.
+ *
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL handle, out, status, v or
+ * p; (2) terms == 0.  (3) Then outputs == 0 or width == 0 is a no-op that returns 0.  Then (4) terms above LSR_RING_DOT_MAX_TERMS;
+ * (5) width above LSR_RING_FOLD_MAX_WIDTH; (6) a size that overflows size_t, as lsr_ntt_ring_fold_batch lists them; (7) a bound above
+ * floor(q/2); (8) n above 4096; (9) the byte size of v, p or out overflowing size_t at the handle's n; (10) out overlapping v, then
+ * p, status overlapping v, p, then out, in address range; (11) no visible device.
+ *
+ * Workspace, ordering and graph capture.  The workspace is the handle's own, the one of the fused products with the per-output flag
+ * words behind it: its size depends on n alone and lsr_ring_mod_create allocates it — there is no _prepare — so the _device form
+ * enqueues only and captures into a HIP graph from the first call, without a hidden allocation.  Per prime it holds 2^22 words of
+ * sums and min(4096, 2^21 / n) challenge transforms: outputs are taken in chunks of whole outputs that fit both (an output of more
+ * than 2^22 / n components alone, its components in chunks).  Calls on one handle are ordered by the handle's mutex and event; a
+ * captured call is not bracketed.  The plain form takes host buffers through bounded device chunks on the first prime context's work
+ * stream — whole outputs together with the span of vectors they read, each operand within LAMBDA_SNARK_STAGING_MIB where one output's
+ * is (a shared v, term_stride == 0, goes up once) — and returns when out and status are complete. */
+int lsr_ring_mod_fold_batch(const LsrRingMod* h, uint64_t* out, int32_t* status, const uint64_t* v, const uint64_t* p, size_t outputs, size_t terms,
+                            size_t term_stride, size_t width, uint64_t bound_v, uint64_t bound_p) LSR_NOEXCEPT;
+int lsr_ring_mod_fold_batch_device(const LsrRingMod* h, uint64_t* d_out, int32_t* d_status, const uint64_t* d_v, const uint64_t* d_p, size_t outputs,
+                                   size_t terms, size_t term_stride, size_t width, uint64_t bound_v, uint64_t bound_p, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

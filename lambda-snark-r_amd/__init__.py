@@ -1226,6 +1226,37 @@ class RingMod:
         _check(self._lib.lsr_ring_mod_gram_sym2_batch_device(self._h, d_h, d_status, d_a, d_b or None, batch, r, width, int(bound_a), int(bound_b), stream),
                "lsr_ring_mod_gram_sym2_batch_device")
 
+    def fold(self, v, p, term_stride=0, bound_v=0, bound_p=0):
+        """out[j][c] = sum_i p[j][i] * v[j term_stride + i][c] mod (X^n + 1, q) (host arrays, n <= 4096): v is [vectors, width, n], p is
+        [outputs, terms, n] (or [terms, n]: one output) with vectors >= (outputs - 1) term_stride + terms, as ``NttContext.ring_fold``.
+        Returns (out [outputs, width, n], status [outputs]) — ([width, n], status) for a 2-d p.  bound_v, bound_p: the l-infinity
+        bounds asserted on the centred words of v and p (0: none); status[j] is 1 where every word output j reads kept them (exact
+        output), 0 where one exceeded its bound, -1 where one was >= q — then every word of out[j] is 0."""
+        n = self.n
+        v_in, p_in = _u64_array(v, "v"), _u64_array(p, "p")
+        if v_in.ndim != 3 or v_in.shape[-1] != n:
+            raise ValueError("v must be [vectors, width, n]")
+        if p_in.ndim not in (2, 3) or p_in.shape[-1] != n:
+            raise ValueError("p must be [terms, n] or [outputs, terms, n]")
+        terms, term_stride = p_in.shape[-2], int(term_stride)
+        if terms == 0:
+            raise ValueError("terms must be at least 1")
+        v3, p3 = np.ascontiguousarray(v_in), np.ascontiguousarray(p_in.reshape(-1, terms, n))
+        outputs, width = p3.shape[0], v3.shape[1]
+        if term_stride < 0 or (outputs and v3.shape[0] < (outputs - 1) * term_stride + terms):
+            raise ValueError("v must hold (outputs - 1) * term_stride + terms vectors")
+        out = np.empty((outputs, width, n), dtype=np.uint64)
+        status = np.empty(outputs, dtype=np.int32)
+        _check(self._lib.lsr_ring_mod_fold_batch(self._h, out.ctypes.data, status.ctypes.data, v3.ctypes.data, p3.ctypes.data, outputs, terms, term_stride,
+                                                 width, int(bound_v), int(bound_p)), "lsr_ring_mod_fold_batch")
+        return (out[0], status[0]) if p_in.ndim == 2 else (out, status)
+
+    def fold_device(self, d_out, d_status, d_v, d_p, outputs, terms, term_stride, width, bound_v=0, bound_p=0, stream=0):
+        """Device buffers: out [outputs][width][n], status [outputs] int32, v [(outputs - 1) term_stride + terms][width][n],
+        p [outputs][terms][n].  Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ring_mod_fold_batch_device(self._h, d_out, d_status, d_v, d_p, outputs, terms, term_stride, width, int(bound_v), int(bound_p),
+                                                        stream), "lsr_ring_mod_fold_batch_device")
+
 
 
 class Params:

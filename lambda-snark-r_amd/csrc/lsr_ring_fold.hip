@@ -15,6 +15,7 @@
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
 #include "lsr_ring_call.hpp"
+#include "lsr_ring_fold.hpp"
 #include "lsr_ring_fold_kernels.hpp"
 #include "lsr_ring_workspace.hpp"
 #include "lsr_runtime.hpp"
@@ -167,29 +168,14 @@ static void host_ring_fold(const NttContext& c, uint64_t* out, const uint64_t* v
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-struct FoldCounts {
-    size_t vectors = 0, v_polys = 0, p_polys = 0, out_polys = 0;   // (outputs - 1) term_stride + terms; and the polynomials of v, p, out
-};
+using lsr::FoldCounts;
 
 // Argument checks that read no context (and never dereference ctx), in the documented order: -1 and a message, 1 for the empty call
 // (a no-op), 0 to go on.
 int ring_fold_check(const char* where, const NttContext* ctx, const void* out, const void* v, const void* p, size_t outputs, size_t terms,
                     size_t ts, size_t width, FoldCounts& k) {
     if (!ctx || !out || !v || !p) return lsr::abi_refuse(where, "NULL context or buffer");
-    if (terms == 0) return lsr::abi_refuse(where, "terms must be at least 1");
-    if (outputs == 0 || width == 0) return 1;
-    if (terms > LSR_RING_DOT_MAX_TERMS)
-        return lsr::abi_refuse(where, "terms = " + std::to_string(terms) + " is above LSR_RING_DOT_MAX_TERMS (" + std::to_string(LSR_RING_DOT_MAX_TERMS) + ")");
-    if (width > LSR_RING_FOLD_MAX_WIDTH)
-        return lsr::abi_refuse(where, "width = " + std::to_string(width) + " is above LSR_RING_FOLD_MAX_WIDTH (" + std::to_string(LSR_RING_FOLD_MAX_WIDTH) + ")");
-    // every product a shape takes, in polynomials and then in bytes at the smallest ring (n = 2, 16 bytes a polynomial)
-    size_t span = 0;
-    const bool overflow = __builtin_mul_overflow(outputs - 1, ts, &span) || __builtin_add_overflow(span, terms, &k.vectors) ||
-                          __builtin_mul_overflow(k.vectors, width, &k.v_polys) || __builtin_mul_overflow(outputs, terms, &k.p_polys) ||
-                          __builtin_mul_overflow(outputs, width, &k.out_polys) || __builtin_mul_overflow(k.v_polys, (size_t)16, &span) ||
-                          __builtin_mul_overflow(k.p_polys, (size_t)16, &span) || __builtin_mul_overflow(k.out_polys, (size_t)16, &span);
-    if (overflow) return lsr::abi_refuse(where, "the sizes of v, p or out overflow size_t (outputs, terms, term_stride, width)");
-    return 0;
+    return lsr::ring_fold_shape_check(where, outputs, terms, ts, width, k);
 }
 
 // The checks of a non-empty call that read the context, still before any device work.

@@ -244,8 +244,8 @@ LsrRingMod* lsr_ring_mod_create(uint64_t q, uint32_t n, int device) noexcept {
         h->rc.big_mod_q = (uint64_t)(big % q);
         if (h->logn <= lsr::kTileLog) {
             h->chunk = lsr::kRingModSumWords >> h->logn;
-            h->bhat_rows = std::min<size_t>(4096, lsr::kRingModBhatWords >> h->logn);
-            h->ws.allocate(2 * (h->chunk + h->bhat_rows) * n);
+            h->bhat_rows = std::min<size_t>(lsr::kRingModBhatMaxRows, lsr::kRingModBhatWords >> h->logn);
+            h->ws.allocate(2 * (h->chunk + h->bhat_rows) * n + lsr::kRingModFoldFlagWords);
         }
         return h.release();
     } catch (const std::exception& e) {

@@ -1,6 +1,6 @@
 // The ring handle under an arbitrary modulus (LsrRingMod, batch.h) as the translation units that read it see it:
 // lsr_ring_mod.hip creates it and computes mul and dot, lsr_ring_mod_matvec.hip keeps resident matrices on it (§5q),
-// lsr_ring_mod_gram.hip computes Gram matrices of bounded vectors on it (§5r).
+// lsr_ring_mod_gram.hip computes Gram matrices of bounded vectors on it (§5r), lsr_ring_mod_fold.hip folds vectors by challenges on it (§5s).
 #pragma once
 
 #include <mutex>
@@ -19,7 +19,8 @@ struct LsrRingMod {
     lsr::RingModConsts rc{};
     lsr::ModParams pq{};             // of q: only q and floor(2^128 / q) are used
     lsr::LiftSource lift[2]{};
-    // n <= 4096: [2][chunk][n] inverse-transformed sums, then [2][bhat_rows][n] transforms of a shared b.  Never resized.
+    // n <= 4096: [2][chunk][n] inverse-transformed sums, then [2][bhat_rows][n] transforms of a shared b or of a fold's challenges, then
+    // kRingModFoldFlagWords words of a fold's per-output flags.  Never resized.
     size_t chunk = 0, bhat_rows = 0;
     lsr::DeviceBuffer<uint64_t> ws;
     // the Gram calls (lsr_ring_mod_gram.hip): [2][ring_mod_gram_words()] lifted operands, their transforms and the outputs of one chunk
@@ -35,6 +36,8 @@ namespace lsr {
 
 constexpr size_t kRingModSumWords = (size_t)1 << 22;    // per prime: 32 MiB, both arrays stay in the Infinity Cache for the reduce
 constexpr size_t kRingModBhatWords = (size_t)1 << 21;   // per prime
+constexpr size_t kRingModBhatMaxRows = 4096;            // bhat_rows = min(this, kRingModBhatWords / n)
+constexpr size_t kRingModFoldFlagWords = kRingModBhatMaxRows / 2;   // 32-bit flag words: one per challenge row
 
 // Gram workspace words per prime: a function of the process-wide chunk size alone (a quarter of it, 64 MiB of 256: the two halves stay in
 // the Infinity Cache between the passes of a chunk), at least 2^23 words
