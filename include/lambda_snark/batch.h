@@ -725,12 +725,14 @@ int lsr_ntt_ring_unpack_batch_device(const NttContext* ctx, uint64_t* d_out, int
  * buffer; (lift) i outside {0, 1}; then count == 0 is a no-op that returns 0; then count * 8 overflowing size_t, a buffer that is
  * not 8-byte aligned, an output that overlaps an operand without being it; no visible device.
  *
- * Composition.  Together with lsr_ring_mod_prime_context these two calls put every bilinear call of the toolkit under q: lift the
- * operands for prime 0 and for prime 1, run the call on each prime's context, reduce the two results.  That covers
- * lsr_ntt_ring_mul_batch, lsr_ntt_ring_dot_batch, lsr_ntt_ring_fold_batch, lsr_ntt_ring_matvec_batch, lsr_ntt_ring_gram_batch,
- * lsr_ntt_ring_gram_sym2_batch and lsr_ntt_ring_dot_galois_batch, at every n.  The caller keeps ONE bound: the number of products
- * summed per output must not exceed max_terms (a gram_sym2 entry sums two).  Longer sums are split by the caller and the parts
- * reduced with `accumulate`.
+ * Composition.  Together with lsr_ring_mod_prime_context these two calls put every bilinear call of the toolkit under q at EVERY n
+ * the handle admits: lift the operands for prime 0 and for prime 1, run the call on each prime's context, reduce the two results.
+ * That covers lsr_ntt_ring_mul_batch, lsr_ntt_ring_dot_batch, lsr_ntt_ring_fold_batch, lsr_ntt_ring_matvec_batch,
+ * lsr_ntt_ring_gram_batch, lsr_ntt_ring_gram_sym2_batch and lsr_ntt_ring_dot_galois_batch.  The caller keeps ONE bound: the number of
+ * products summed per output must not exceed max_terms (a gram_sym2 entry sums two).  Longer sums are split by the caller and the
+ * parts reduced with `accumulate`.  At n <= 4096 each of these has a fused call on the handle (mul, dot and dot_galois here; matvec,
+ * gram and fold in the sections below) and the composed route is only the way above 4096.  The calls that are not bilinear — sampling,
+ * norms, projections, automorphisms, digits, packing — need no primes at all: they run on the handle's coefficient context, below.
  *
  * The fused calls, n <= 4096:
  *   c_j = a_j b_j (mul) and c_j = sum_{i < terms} a_{j,i} b_{j,i} (dot) in Z_q[X]/(X^n + 1), canonical; inputs in [0, q).
@@ -744,13 +746,47 @@ int lsr_ntt_ring_unpack_batch_device(const NttContext* ctx, uint64_t* d_out, int
  * above LSR_RING_DOT_MAX_TERMS; sizes overflowing size_t; c overlapping an operand; no visible device.
  * Workspace, ordering and graph capture: the workspace belongs to the handle, its size depends on n alone and lsr_ring_mod_create
  * allocates it, so the _device forms capture into a HIP graph from the first call.  The batch is taken in chunks.  Calls on one
- * handle are ordered by an event of the handle's own (as a context's ring calls are); a captured call is not bracketed. */
+ * handle are ordered by an event of the handle's own (as a context's ring calls are); a captured call is not bracketed.
+ *
+ * The twisted inner product, n <= 4096:
+ *   lsr_ring_mod_dot_galois_batch(h, c, a, b, batch, terms, b_rows, g):  c_j = sum_{i < terms} sigma_g(a_{j,i}) b_{j,i} in
+ *   Z_q[X]/(X^n + 1), canonical, sigma_g: X -> X^g for odd g < 2n.  Every output equals lsr_ring_mod_dot_batch on the materialised
+ *   sigma_g(a) word for word; g = 1 is lsr_ring_mod_dot_batch.  With g = 2n - 1 coefficient 0 of c_j is <a_j, b_j> mod q, the inner
+ *   product of the coefficient vectors.  The tile kernel of dot fetches the words of a through the permutation before it lifts them;
+ *   sigma_g only permutes and negates centred coefficients, so the capacity is max_terms unchanged and the terms go in the same groups.
+ *   Shapes, b_rows, the host-staged form, workspace, ordering and graph capture are those of lsr_ring_mod_dot_batch.  Refusals, in this
+ *   order: NULL handle or buffer; b_rows not in {1, batch}; terms == 0; g even.  Then batch == 0 is a no-op that returns 0.  Then:
+ *   g >= 2n; n above 4096 (the message names the composed route: lift, lsr_ntt_ring_dot_galois_batch_device on each prime context,
+ *   reduce); terms above LSR_RING_DOT_MAX_TERMS; sizes overflowing size_t; c overlapping an operand; no visible device.
+ *
+ * The coefficient context:
+ *   lsr_ring_mod_coeff_context(h) lends an NttContext of (q, n) that is negacyclic and has NO twiddle tables (NULL on a NULL handle).
+ *   The handle creates it in lsr_ring_mod_create and frees it with itself: never free it (ntt_context_free on it does nothing).  Its
+ *   flavour follows lsr_set_arith_mode like any context's (every admissible q is below 2^45: FP64 by default).
+ *   Accessors: lsr_ntt_context_device the device, lsr_ntt_context_root 0, lsr_ntt_context_uses_f64 the flavour, lsr_ntt_handoff_bytes 8,
+ *   lsr_ntt_context_is_cyclic 0.
+ *   SERVED on it, host and _device forms, signatures and contracts unchanged, exact for every admissible q (even, 2, 3, the largest
+ *   the handle admits), centred by the convention above: lsr_ntt_ring_sample_batch, lsr_ntt_ring_challenge_batch,
+ *   lsr_ntt_ring_opnorm_batch, lsr_ntt_ring_opnorm_prepare, lsr_ntt_ring_pack_batch, lsr_ntt_ring_unpack_batch,
+ *   lsr_ntt_ring_decompose_batch, lsr_ntt_ring_recompose_batch, lsr_ntt_ring_linf_batch, lsr_ntt_ring_automorphism_batch,
+ *   lsr_ntt_ring_l2sq_batch, lsr_ntt_ring_project_batch, lsr_ntt_ring_project_matrix_batch, lsr_ntt_ring_project_adjoint_batch,
+ *   lsr_ntt_ring_scalar_combine_batch, and the word-by-word products mod q ntt_mul_pointwise, ntt_mul_pointwise_batch,
+ *   lsr_ntt_mul_pointwise_device (they run no transform).
+ *   REFUSED on it: every other function that takes an NttContext (or an array of them) — ntt_forward, ntt_inverse, ntt_forward_batch,
+ *   ntt_inverse_batch, lsr_ntt_forward_batch_device, lsr_ntt_inverse_batch_device, lsr_ntt_forward_batch_sharded,
+ *   lsr_ntt_inverse_batch_sharded, lsr_cyclic_ntt_forward_batch, lsr_cyclic_ntt_inverse_batch, lsr_ntt_ring_matrix_create_seeded,
+ *   lsr_ntt_ring_gram_block, and with their _device forms lsr_ntt_ring_mul_batch, lsr_ntt_ring_dot_batch, lsr_ntt_ring_fold_batch,
+ *   lsr_ntt_ring_dot_galois_batch, lsr_ntt_ring_matrix_create, lsr_ntt_ring_gram_batch, lsr_ntt_ring_gram_sym2_batch,
+ *   lsr_ntt_ring_quadform_batch.  Each returns -1, NULL or 0 according to its type; lsr_last_error names the
+ *   entry point, contains "coefficient context" and names the lsr_ring_mod_* call to use where one exists.  The refusal is the first
+ *   check after the context's own NULL check: it precedes every look at a buffer (a sharded call looks at its `shards` contexts). */
 typedef struct LsrRingMod LsrRingMod;
 LsrRingMod* lsr_ring_mod_create(uint64_t q, uint32_t n, int device) LSR_NOEXCEPT;
 void lsr_ring_mod_free(LsrRingMod* h) LSR_NOEXCEPT;
 uint64_t lsr_ring_mod_modulus(const LsrRingMod* h) LSR_NOEXCEPT;
 const NttContext* lsr_ring_mod_prime_context(const LsrRingMod* h, int i) LSR_NOEXCEPT;
 size_t lsr_ring_mod_max_terms(const LsrRingMod* h) LSR_NOEXCEPT;
+const NttContext* lsr_ring_mod_coeff_context(const LsrRingMod* h) LSR_NOEXCEPT;
 int lsr_ring_mod_primes(uint32_t n, uint64_t primes[2]) LSR_NOEXCEPT;
 size_t lsr_ring_mod_capacity(uint64_t q, uint32_t n) LSR_NOEXCEPT;
 int lsr_ring_mod_lift_batch_device(const LsrRingMod* h, int i, uint64_t* d_out, const uint64_t* d_x, size_t count, void* stream) LSR_NOEXCEPT;
@@ -763,6 +799,10 @@ int lsr_ring_mod_dot_batch(const LsrRingMod* h, uint64_t* c, const uint64_t* a, 
                            size_t b_rows) LSR_NOEXCEPT;
 int lsr_ring_mod_dot_batch_device(const LsrRingMod* h, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms,
                                   size_t b_rows, void* stream) LSR_NOEXCEPT;
+int lsr_ring_mod_dot_galois_batch(const LsrRingMod* h, uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t terms,
+                                  size_t b_rows, uint64_t g) LSR_NOEXCEPT;
+int lsr_ring_mod_dot_galois_batch_device(const LsrRingMod* h, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch,
+                                         size_t terms, size_t b_rows, uint64_t g, void* stream) LSR_NOEXCEPT;
 
 /* ---------------- NTT: resident matrices under any modulus (y = M x and y = M G^-1(x) on a ring handle) ---------------- */
 /* The module product with a public matrix — an Ajtai commitment t = A s, Kyber's A s, a commitment to the digits of a long witness —

@@ -1029,7 +1029,8 @@ class RingModMatrix:
 
 
 class _BorrowedNttContext(NttContext):
-    """One of the two prime contexts of a RingMod: every member of NttContext, owned by the RingMod (close() only lets go)."""
+    """A context a RingMod lends (a prime context or the coefficient context): every member of NttContext, owned by the RingMod
+    (close() only lets go)."""
 
     def __init__(self, owner, handle, q, n):   # pylint: disable=super-init-not-called
         self._lib, self._h, self._owner = owner._lib, handle, owner
@@ -1054,7 +1055,7 @@ class RingMod:
         if not self._h:
             raise CoreError(f"lsr_ring_mod_create({q}, {n}) returned NULL: {_abi.last_error()}")
         self._primes = ring_mod_primes(self.n)
-        self._contexts = [None, None]
+        self._contexts = [None, None, None]      # prime 0, prime 1, the coefficient context
         self._matrices = weakref.WeakSet()
 
     @property
@@ -1076,6 +1077,15 @@ class RingMod:
         if self._contexts[i] is None:
             self._contexts[i] = _BorrowedNttContext(self, self._lib.lsr_ring_mod_prime_context(self._h, i), self._primes[i], self.n)
         return self._contexts[i]
+
+    def coeff_context(self):
+        """The handle's NttContext of (q, n) itself, without twiddle tables, borrowed like the prime contexts: the coefficient-wise
+        members (ring_sample, ring_challenge, ring_opnorm, ring_pack, ring_unpack, ring_decompose, ring_recompose, ring_linf,
+        ring_automorphism, ring_l2sq, ring_project, ring_project_matrix, ring_project_adjoint, ring_scalar_combine, mul_pointwise) work
+        on it under any q; every member that transforms raises CoreError naming the RingMod call to use."""
+        if self._contexts[2] is None:
+            self._contexts[2] = _BorrowedNttContext(self, self._lib.lsr_ring_mod_coeff_context(self._h), self.q, self.n)
+        return self._contexts[2]
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1164,6 +1174,27 @@ class RingMod:
     def dot_device(self, d_c, d_a, d_b, batch, terms, b_rows, stream=0):
         """Device buffers: c [batch][n], a [batch][terms][n], b [b_rows][terms][n] (b_rows 1 or batch), asynchronous on `stream`."""
         _check(self._lib.lsr_ring_mod_dot_batch_device(self._h, d_c, d_a, d_b, batch, terms, b_rows, stream), "lsr_ring_mod_dot_batch_device")
+
+    def ring_dot_galois(self, a, b, g):
+        """sum_i sigma_g(a_i) * b_i mod (X^n + 1, q), sigma_g: X -> X^g for odd g < 2n (n <= 4096): equal to dot on the materialised
+        sigma_g(a) word for word; shapes as dot.  With g = 2n - 1, coefficient 0 is the inner product of the coefficient vectors."""
+        a_in = _u64_array(a)
+        if a_in.ndim < 2 or a_in.shape[-1] != self.n:
+            raise ValueError("a must be [terms, n] or [batch, terms, n]")
+        terms = a_in.shape[-2]
+        if terms == 0:
+            raise ValueError("terms must be at least 1")
+        a3 = np.ascontiguousarray(a_in.reshape(-1, terms, self.n))
+        b3 = np.ascontiguousarray(_u64_array(b).reshape(-1, terms, self.n))
+        out = np.empty((a3.shape[0], self.n), dtype=np.uint64)
+        _check(self._lib.lsr_ring_mod_dot_galois_batch(self._h, out.ctypes.data, a3.ctypes.data, b3.ctypes.data, a3.shape[0], terms, b3.shape[0], int(g)),
+               "lsr_ring_mod_dot_galois_batch")
+        return out[0] if a_in.ndim == 2 else out
+
+    def ring_dot_galois_device(self, d_c, d_a, d_b, batch, terms, b_rows, g, stream=0):
+        """Device buffers, shapes as dot_device.  Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ring_mod_dot_galois_batch_device(self._h, d_c, d_a, d_b, batch, terms, b_rows, int(g), stream),
+               "lsr_ring_mod_dot_galois_batch_device")
 
     def gram_prepare(self):
         """``lsr_ring_mod_gram_prepare``: allocates the Gram workspace, so that ``gram_device`` captures into a graph from the first call."""

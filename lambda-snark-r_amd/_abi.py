@@ -165,6 +165,7 @@ SIGNATURES = {
     "lsr_ring_mod_modulus": (u64, [vp]),
     "lsr_ring_mod_prime_context": (vp, [vp, c_int]),
     "lsr_ring_mod_max_terms": (c_size, [vp]),
+    "lsr_ring_mod_coeff_context": (vp, [vp]),
     "lsr_ring_mod_primes": (c_int, [u32, vp]),
     "lsr_ring_mod_capacity": (c_size, [u64, u32]),
     "lsr_ring_mod_lift_batch_device": (c_int, [vp, c_int, vp, vp, c_size, vp]),
@@ -173,6 +174,8 @@ SIGNATURES = {
     "lsr_ring_mod_mul_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, vp]),
     "lsr_ring_mod_dot_batch": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size]),
     "lsr_ring_mod_dot_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, vp]),
+    "lsr_ring_mod_dot_galois_batch": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, u64]),
+    "lsr_ring_mod_dot_galois_batch_device": (c_int, [vp, vp, vp, vp, c_size, c_size, c_size, u64, vp]),
     "lsr_ring_mod_capacity_bounded": (c_size, [u64, u32, u64]),
     "lsr_ring_mod_matrix_create": (vp, [vp, vp, c_size, c_size]),
     "lsr_ring_mod_matrix_create_device": (vp, [vp, vp, c_size, c_size, vp]),

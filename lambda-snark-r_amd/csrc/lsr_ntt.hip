@@ -85,19 +85,6 @@ DeviceGuard::~DeviceGuard() {
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
-static ModParams make_mod_params(uint64_t q, int logn) {
-    ModParams p{};
-    p.q = q;
-    p.two_q = 2 * q;
-    p.qd = static_cast<double>(q);
-    p.inv_qd = 1.0 / static_cast<double>(q);
-    const u128 ratio = ~static_cast<u128>(0) / q;   // floor((2^128-1)/q) == floor(2^128/q) for odd q > 1
-    p.barrett_hi = static_cast<uint64_t>(ratio >> 64);
-    p.barrett_lo = static_cast<uint64_t>(ratio);
-    p.logn = logn;
-    return p;
-}
-
 int resolve_device(const char* where, int device, bool announce) {
     const int devices = visible_device_count();
     if (devices <= 0) {
@@ -138,12 +125,14 @@ static NttContext* build_context(const char* where, uint64_t q, uint32_t n, int 
         ctx->device = device;
         ctx->psi = tw.psi;
         ctx->cyclic = cyclic;
-        ctx->gold = (q == kProverModulus);
+        ctx->coeff = tw.fwd.empty();   // no tables: a ring handle's coefficient context (create_coeff_context), any q >= 2 below 2^45
+        ctx->gold = !ctx->coeff && (q == kProverModulus);
         ctx->mod = make_mod_params(q, logn);
         ctx->use_f64 = !ctx->gold && (q < (1ull << 45)) && arith_mode() != 1;
-        ctx->handoff_bytes = handoff_is_packed(q, logn, ctx->use_f64) ? 6 : 8;
-        const uint64_t w_last_scaled = mulmod(tw.inv[n > 1 ? 1 : 0], tw.n_inv, q);
-        if (ctx->gold) {   // multipliers in Montgomery form (gold_mul_mont)
+        ctx->handoff_bytes = !ctx->coeff && handoff_is_packed(q, logn, ctx->use_f64) ? 6 : 8;
+        const uint64_t w_last_scaled = ctx->coeff ? 0 : mulmod(tw.inv[n > 1 ? 1 : 0], tw.n_inv, q);
+        if (ctx->coeff) {              // nothing to upload, and no transform ever reads the round constants
+        } else if (ctx->gold) {   // multipliers in Montgomery form (gold_mul_mont)
             std::vector<uint64_t> f(n), g(n);
             for (uint32_t i = 0; i < n; ++i) {
                 f[i] = prover_montgomery(tw.fwd[i]);
@@ -195,6 +184,10 @@ NttContext* create_ntt_context(uint64_t q, uint32_t n, int device) {
         return nullptr;
     }
     return build_context("ntt_context_create", q, n, logn, device, build_twiddles(q, n, logn, psi), false);
+}
+
+NttContext* create_coeff_context(const char* where, uint64_t q, uint32_t n, int logn, int device) {
+    return build_context(where, q, n, logn, device, TwiddleTables{}, false);
 }
 
 NttContext* create_cyclic_ntt_context(uint64_t q, uint32_t n, uint64_t omega, int device, bool large, const char* where) {
@@ -655,17 +648,22 @@ NttContext* lsr_ntt_context_create_on(uint64_t q, uint32_t n, int device) noexce
         return nullptr;
     }
 }
-void ntt_context_free(NttContext* ctx) noexcept { lsr::destroy_ntt_context(ctx); }
+void ntt_context_free(NttContext* ctx) noexcept {
+    if (ctx && ctx->coeff) return;   // lent by a ring handle and freed with it
+    lsr::destroy_ntt_context(ctx);
+}
 int lsr_ntt_context_device(const NttContext* ctx) noexcept { return ctx ? ctx->device : -1; }
 uint64_t lsr_ntt_context_root(const NttContext* ctx) noexcept { return ctx ? ctx->psi : 0; }
 int lsr_ntt_context_uses_f64(const NttContext* ctx) noexcept { return ctx && ctx->use_f64 ? 1 : 0; }
 int lsr_ntt_handoff_bytes(const NttContext* ctx) noexcept { return ctx ? ctx->handoff_bytes : -1; }
 
 int ntt_forward(const NttContext* ctx, uint64_t* coeffs, uint32_t n) noexcept {
+    if (lsr::refuse_coeff_context("ntt_forward", ctx)) return -1;
     if (!ctx || !coeffs || n != ctx->degree) return -1;   // ntt.cpp:81
     return abi_guarded("ntt_forward", [&] { lsr::host_ntt(*ctx, coeffs, 1, false); });
 }
 int ntt_inverse(const NttContext* ctx, uint64_t* evals, uint32_t n) noexcept {
+    if (lsr::refuse_coeff_context("ntt_inverse", ctx)) return -1;
     if (!ctx || !evals || n != ctx->degree) return -1;    // ntt.cpp:96
     return abi_guarded("ntt_inverse", [&] { lsr::host_ntt(*ctx, evals, 1, true); });
 }
@@ -675,11 +673,13 @@ void ntt_mul_pointwise(const NttContext* ctx, uint64_t* result, const uint64_t* 
 }
 
 int ntt_forward_batch(const NttContext* ctx, uint64_t* polys, size_t batch) noexcept {
+    if (lsr::refuse_coeff_context("ntt_forward_batch", ctx)) return -1;
     if (!ctx || !polys) return -1;
     if (batch == 0) return 0;
     return abi_guarded("ntt_forward_batch", [&] { lsr::host_ntt(*ctx, polys, batch, false); });
 }
 int ntt_inverse_batch(const NttContext* ctx, uint64_t* polys, size_t batch) noexcept {
+    if (lsr::refuse_coeff_context("ntt_inverse_batch", ctx)) return -1;
     if (!ctx || !polys) return -1;
     if (batch == 0) return 0;
     return abi_guarded("ntt_inverse_batch", [&] { lsr::host_ntt(*ctx, polys, batch, true); });
@@ -690,6 +690,7 @@ int ntt_mul_pointwise_batch(const NttContext* ctx, uint64_t* result, const uint6
 }
 
 int lsr_ntt_forward_batch_device(const NttContext* ctx, uint64_t* d_polys, size_t batch, void* stream) noexcept {
+    if (lsr::refuse_coeff_context("lsr_ntt_forward_batch_device", ctx)) return -1;
     if (!ctx || !d_polys) return -1;
     return abi_guarded("lsr_ntt_forward_batch_device", [&] {
         lsr::DeviceGuard guard(ctx->device);
@@ -697,6 +698,7 @@ int lsr_ntt_forward_batch_device(const NttContext* ctx, uint64_t* d_polys, size_
     });
 }
 int lsr_ntt_inverse_batch_device(const NttContext* ctx, uint64_t* d_polys, size_t batch, void* stream) noexcept {
+    if (lsr::refuse_coeff_context("lsr_ntt_inverse_batch_device", ctx)) return -1;
     if (!ctx || !d_polys) return -1;
     return abi_guarded("lsr_ntt_inverse_batch_device", [&] {
         lsr::DeviceGuard guard(ctx->device);
@@ -734,7 +736,10 @@ void lsr_host_free_pinned(void* p) noexcept {
 }
 
 static int ntt_batch_sharded(const char* where, const NttContext* const* ctxs, int shards, uint64_t* polys, size_t batch, bool inverse) noexcept {
-    if (!ctxs || shards <= 0 || !polys) return -1;
+    if (!ctxs || shards <= 0) return -1;
+    for (int g = 0; g < shards; ++g)
+        if (lsr::refuse_coeff_context(where, ctxs[g])) return -1;
+    if (!polys) return -1;
     for (int g = 0; g < shards; ++g)
         if (!ctxs[g] || ctxs[g]->degree != ctxs[0]->degree || ctxs[g]->modulus != ctxs[0]->modulus) return -1;
     if (batch == 0) return 0;

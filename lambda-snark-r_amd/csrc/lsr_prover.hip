@@ -642,11 +642,13 @@ uint32_t lsr_prover_max_log2_size(void) noexcept { return lsr::kProverMaxLog2; }
 int lsr_ntt_context_is_cyclic(const NttContext* ctx) noexcept { return ctx && ctx->cyclic ? 1 : 0; }
 
 int lsr_cyclic_ntt_forward_batch(const NttContext* ctx, uint64_t* values, size_t batch) noexcept {
+    if (lsr::refuse_coeff_context("lsr_cyclic_ntt_forward_batch", ctx)) return -1;
     if (!ctx || !values || !ctx->cyclic) return -1;
     if (batch == 0) return 0;
     return abi_guarded("lsr_cyclic_ntt_forward_batch", [&] { lsr::cyclic_host(*ctx, values, batch, false); });
 }
 int lsr_cyclic_ntt_inverse_batch(const NttContext* ctx, uint64_t* values, size_t batch) noexcept {
+    if (lsr::refuse_coeff_context("lsr_cyclic_ntt_inverse_batch", ctx)) return -1;
     if (!ctx || !values || !ctx->cyclic) return -1;
     if (batch == 0) return 0;
     return abi_guarded("lsr_cyclic_ntt_inverse_batch", [&] { lsr::cyclic_host(*ctx, values, batch, true); });

@@ -174,6 +174,7 @@ using lsr::FoldCounts;
 // (a no-op), 0 to go on.
 int ring_fold_check(const char* where, const NttContext* ctx, const void* out, const void* v, const void* p, size_t outputs, size_t terms,
                     size_t ts, size_t width, FoldCounts& k) {
+    if (lsr::refuse_coeff_context(where, ctx)) return -1;
     if (!ctx || !out || !v || !p) return lsr::abi_refuse(where, "NULL context or buffer");
     return lsr::ring_fold_shape_check(where, outputs, terms, ts, width, k);
 }

@@ -145,6 +145,7 @@ int automorphism_call(const char* where, const NttContext* ctx, uint64_t* out, c
 
 int dot_galois_call(const char* where, const NttContext* ctx, uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t terms, size_t b_rows,
                     uint64_t g, bool device, void* stream) noexcept {
+    if (lsr::refuse_coeff_context(where, ctx)) return -1;
     if (!ctx || !c || !a || !b) return lsr::abi_refuse(where, "NULL context or buffer");
     if (b_rows != 1 && b_rows != batch)
         return lsr::abi_refuse(where, "b_rows must be 1 or batch (" + std::to_string(batch) + "), got " + std::to_string(b_rows));

@@ -89,11 +89,13 @@ __global__ void __launch_bounds__(kThreads) ring_automorphism_kernel(uint64_t* _
 // split in the SOURCE offset, which is one per-lane byte offset.  The ragged-tile clips survive: the resource spans the outputs the
 // tile has, and a word of an absent output gets the out-of-range lane offset (reads 0; -0 = 0).
 //
-// The body is shared with the lift-on-load family below through a word source `Src`:
-//   Src::kPermuted   the words of a are fetched through src.g (GaloisSource) or at the plain kernel's addresses (LiftSource);
-//   src.word(x)      (not kPermuted) what becomes of a raw operand word of a or b before A::load.
+// The body is shared with the lift-on-load families below through a word source `Src`:
+//   Src::kPermuted   the words of a are fetched through src.g (GaloisSource, LiftGaloisSource) or at the plain kernel's addresses
+//                    (LiftSource);
+//   Src::kLifted     every raw operand word of a and b goes through src.word(x) before A::load (LiftSource, LiftGaloisSource).
 struct GaloisSource {
     static constexpr bool kPermuted = true;
+    static constexpr bool kLifted = false;
     GaloisParams g;
     __device__ __forceinline__ uint32_t lane_product(uint32_t j) const { return j * g.h; }   // the lane part of j h
 };
@@ -102,9 +104,24 @@ struct GaloisSource {
 // which lies in (p - half, p) because half < 2^43 < p.
 struct LiftSource {
     static constexpr bool kPermuted = false;
+    static constexpr bool kLifted = true;
     uint64_t half, rebase;
     __device__ __forceinline__ uint32_t lane_product(uint32_t) const { return 0u; }
     __device__ __forceinline__ uint64_t word(uint64_t x) const { return x <= half ? x : x + rebase; }
+};
+// Both at once (lsr_ring_mod_dot_galois_batch): the words of a mod q are fetched through the permutation and lifted,
+// the words of b are lifted.  The sign of sigma_g is applied AFTER the lift, against the prime: the lifted word y is the canonical
+// residue of the centred v, |v| <= floor(q / 2), and galois_negate(y, p) is the canonical residue of -v, of the same magnitude — the
+// operand bound the handle's capacity rests on.  (At an even q the word q / 2 lifts to +q / 2 and its negation is the residue of
+// -q / 2, where the materialised sigma_g(a) holds the word q / 2 again, lifted to +q / 2: the two integers differ by q in that
+// coefficient, so the integer products differ by a multiple of q, which the reduce removes.)  A clipped word reads 0 and stays 0.
+struct LiftGaloisSource {
+    static constexpr bool kPermuted = true;
+    static constexpr bool kLifted = true;
+    GaloisParams g;
+    LiftSource lift;
+    __device__ __forceinline__ uint32_t lane_product(uint32_t j) const { return j * g.h; }
+    __device__ __forceinline__ uint64_t word(uint64_t x) const { return lift.word(x); }
 };
 
 template <class A, int LT, bool BHAT, class Src>
@@ -144,8 +161,8 @@ __device__ __forceinline__ void tile_ring_dot_from_source(uint64_t* c, const uin
         const uint32_t reg = reg_offset<LO0, R0>(k);
         const bool present = !kStrided || (base0 >> LT) + (reg >> LT) < outputs;
         const uint64_t raw = buf_load64<kAuxStream>(r, present ? operand_bytes(base0, os) : kRingDotOutOfRange, operand_bytes(reg, os));
-        if constexpr (Src::kPermuted) return raw;
-        else return src.word(raw);
+        if constexpr (Src::kLifted) return src.word(raw);
+        else return raw;
     };
     // Word k of round 0 of a.  kPermuted, sigma_g(a): the same clips, the source word s & (n - 1) of the word's own output, negated
     // where s & n
@@ -157,7 +174,9 @@ __device__ __forceinline__ void tile_ring_dot_from_source(uint64_t* c, const uin
             const uint32_t s = (lane_jh + (reg & nmask) * src.g.h) & src.g.mask;
             const uint32_t from = kStrided ? ((s & nmask) + output * os) * 8u : (s & nmask) * 8u;
             // (not a streaming load: the eight words of a cache line go to eight different lanes)
-            const uint64_t word = buf_load64(r, output < outputs ? from : kRingDotOutOfRange, 0);
+            const uint64_t raw = buf_load64(r, output < outputs ? from : kRingDotOutOfRange, 0);
+            uint64_t word = raw;
+            if constexpr (Src::kLifted) word = src.word(raw);
             return (s & n) ? galois_negate(word, p.q) : word;
         } else {
             return operand_word(r, os, k);
@@ -286,6 +305,18 @@ __global__ void __launch_bounds__(kThreads) ntt_tile_ring_dot_lift(uint64_t* c, 
                                                                      LiftSource lift, ModParams p, const typename A::twid* __restrict__ fwd,
                                                                      const typename A::twid* __restrict__ inv, RoundConsts<A> cs) {
     tile_ring_dot_from_source<A, LT, BHAT>(c, a, b, total, nterms, a_os, b_os, flags, lift, p, fwd, inv, cs);
+}
+
+// c_j = sum_{i < nterms} sigma_g(a_{j,i}) b_{j,i} mod the prime of `p` on operands mod another modulus q (LiftGaloisSource): one of
+// the two launches of lsr_ring_mod_dot_galois_batch (lsr_ring_mod.hip).  Behind the load this is ntt_tile_ring_dot_galois on lift(a),
+// lift(b).  BHAT: b holds transforms mod the prime and is read as it is.
+template <class A, int LT, bool BHAT>
+__global__ void __launch_bounds__(kThreads) ntt_tile_ring_dot_lift_galois(uint64_t* c, const uint64_t* __restrict__ a, const uint64_t* __restrict__ b,
+                                                                            size_t total, uint32_t nterms, size_t a_os, size_t b_os, uint32_t flags,
+                                                                            GaloisParams g, LiftSource lift, ModParams p,
+                                                                            const typename A::twid* __restrict__ fwd,
+                                                                            const typename A::twid* __restrict__ inv, RoundConsts<A> cs) {
+    tile_ring_dot_from_source<A, LT, BHAT>(c, a, b, total, nterms, a_os, b_os, flags, LiftGaloisSource{g, lift}, p, fwd, inv, cs);
 }
 
 }  // namespace lsr

@@ -123,6 +123,7 @@ namespace {
 // (a no-op), 0 to go on.  sym2: the symmetrised form, whose b must not be NULL.
 int ring_gram_check(const char* where, const NttContext* ctx, const void* g, const void* a, const void* b, size_t batch, size_t ra, size_t rb,
                     size_t width, bool sym2 = false) {
+    if (lsr::refuse_coeff_context(where, ctx)) return -1;
     if (!ctx || !g || !a || (sym2 && !b)) return lsr::abi_refuse(where, "NULL context or buffer");
     if (lsr::ring_gram_shape_check(where, b != nullptr, batch, ra, rb, width, sym2) != 0) return -1;
     return batch == 0 ? 1 : 0;
@@ -199,7 +200,7 @@ int lsr_ntt_ring_gram_sym2_batch_device(const NttContext* ctx, uint64_t* d_h, co
 }
 
 size_t lsr_ntt_ring_gram_block(const NttContext* ctx) noexcept {
-    if (!ctx) return 0;
+    if (!ctx || lsr::refuse_coeff_context("lsr_ntt_ring_gram_block", ctx)) return 0;
     return lsr::for_flavour(*ctx, [](auto a) -> size_t { return lsr::kGramEdge<decltype(a)>; });
 }
 

@@ -125,6 +125,7 @@ static LsrRingMatrix* matrix_create(const NttContext& c, const uint64_t* m, size
 // ------------------------------------------------------------------------------------------------
 // Argument checks of create that need no device and no dereference of ctx, in the documented order: -1 and a message, or 0 to go on.
 static int matrix_check(const char* where, const NttContext* ctx, const void* m, size_t rows, size_t cols) {
+    if (lsr::refuse_coeff_context(where, ctx)) return -1;
     if (!ctx || !m) return lsr::abi_refuse(where, "NULL context or matrix buffer m");
     if (rows == 0) return lsr::abi_refuse(where, "rows must be at least 1");
     if (cols == 0) return lsr::abi_refuse(where, "cols must be at least 1");

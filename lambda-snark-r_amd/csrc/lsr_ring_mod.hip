@@ -8,6 +8,10 @@
 //                   [2][chunk][n], then one reduce launch into c.  A shared b is lifted into the workspace and transformed once per
 //                   prime and group (launch_ntt; at n <= 4096 a transform needs none of the prime context's scratch).  Groups hold at
 //                   most max_terms terms — what P can carry — and every group after the first is reduced with `accumulate`.
+//   dot_galois      c_j = sum_i sigma_g(a_{j,i}) b_{j,i}: dot with ntt_tile_ring_dot_lift_galois in place of the tile
+//                   kernel, which fetches the words of a through the permutation before it lifts them; same groups, same workspace.
+//   coeff context   an NttContext of (q, n) without twiddle tables, owned by the handle (create_coeff_context, lsr_ntt.hip): the
+//                   coefficient-wise calls of the toolkit run on it under q, every call that transforms refuses it (§5t).
 // The workspace is sized by n alone and allocated with the handle, so the device forms capture into a graph from the first call.
 #include <algorithm>
 #include <cstring>
@@ -20,21 +24,6 @@
 #include "lsr_runtime.hpp"
 
 namespace lsr {
-
-// q and floor(2^128 / q) for any q >= 2 (mulmod_barrett128 and mod64_barrett use nothing else)
-static ModParams ring_mod_params(uint64_t q, int logn) {
-    ModParams p{};
-    p.q = q;
-    p.two_q = 2 * q;
-    p.qd = static_cast<double>(q);
-    p.inv_qd = 1.0 / p.qd;
-    u128 ratio = ~static_cast<u128>(0) / q;             // floor((2^128 - 1) / q): one short of floor(2^128 / q) exactly when q | 2^128
-    if ((q & (q - 1)) == 0) ratio += 1;
-    p.barrett_hi = static_cast<uint64_t>(ratio >> 64);
-    p.barrett_lo = static_cast<uint64_t>(ratio);
-    p.logn = logn;
-    return p;
-}
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static unsigned stream_grid(size_t count, bool vec) {
@@ -69,15 +58,21 @@ struct DotLiftOperands {
     size_t a_os, b_os;   // words between consecutive outputs' term-i polynomials
 };
 
-// one prime's launch: the flavour of that prime's context (FP64 unless the process forces the integer kernels)
+// one prime's launch: the flavour of that prime's context (FP64 unless the process forces the integer kernels).  g: the words of a
+// go through sigma_g (the twisted inner product), NULL for the plain one
 template <bool BHAT>
-static void dot_lift_tile(const NttContext& c, const LiftSource& lift, const DotLiftOperands& o, hipStream_t s) {
+static void dot_lift_tile(const NttContext& c, const LiftSource& lift, const GaloisParams* g, const DotLiftOperands& o, hipStream_t s) {
     const unsigned grid = static_cast<unsigned>((o.total + kTile - 1) / kTile);
     auto launch = [&](auto a) {
         using A = decltype(a);
         for_tile_log<1, 12>(c.logn, [&](auto t) {
-            hipLaunchKernelGGL((ntt_tile_ring_dot_lift<A, decltype(t)::value, BHAT>), dim3(grid), dim3(kThreads), 0, s, o.c, o.a, o.b, o.total, o.nterms, o.a_os,
-                               o.b_os, kRingDotFirst | kRingDotLast, lift, c.mod, Flavour<A>::fwd(c), Flavour<A>::inv(c), Flavour<A>::consts(c));
+            constexpr int LT = decltype(t)::value;
+            if (g)
+                hipLaunchKernelGGL((ntt_tile_ring_dot_lift_galois<A, LT, BHAT>), dim3(grid), dim3(kThreads), 0, s, o.c, o.a, o.b, o.total, o.nterms, o.a_os, o.b_os,
+                                   kRingDotFirst | kRingDotLast, *g, lift, c.mod, Flavour<A>::fwd(c), Flavour<A>::inv(c), Flavour<A>::consts(c));
+            else
+                hipLaunchKernelGGL((ntt_tile_ring_dot_lift<A, LT, BHAT>), dim3(grid), dim3(kThreads), 0, s, o.c, o.a, o.b, o.total, o.nterms, o.a_os, o.b_os,
+                                   kRingDotFirst | kRingDotLast, lift, c.mod, Flavour<A>::fwd(c), Flavour<A>::inv(c), Flavour<A>::consts(c));
         });
     };
     if (c.use_f64) launch(ArithF64{});
@@ -85,8 +80,9 @@ static void dot_lift_tile(const NttContext& c, const LiftSource& lift, const Dot
 }
 
 // n <= 4096.  a: [batch][terms][n] with `terms` the stride of an output's terms; accumulate: c already holds partial sums mod q.
+// g (or NULL): sigma_g on the words of a.  It permutes and negates the centred coefficients, so a group carries what it carries without.
 static void ring_mod_dot_enqueue(const LsrRingMod& h, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms, bool shared_b,
-                                 bool accumulate, hipStream_t s) {
+                                 bool accumulate, const GaloisParams* g, hipStream_t s) {
     const size_t n = h.n;
     uint64_t* const sums[2] = {h.ws.ptr, h.ws.ptr + h.chunk * n};
     uint64_t* const bhat[2] = {h.ws.ptr + 2 * h.chunk * n, h.ws.ptr + (2 * h.chunk + h.bhat_rows) * n};
@@ -102,21 +98,26 @@ static void ring_mod_dot_enqueue(const LsrRingMod& h, uint64_t* d_c, const uint6
         for (size_t j0 = 0; j0 < batch; j0 += h.chunk) {
             const size_t now = std::min(h.chunk, batch - j0), off = (j0 * terms + i0) * n;
             for (int i = 0; i < 2; ++i) {
-                if (shared_b) dot_lift_tile<true>(*h.prime[i], h.lift[i], {sums[i], d_a + off, bhat[i], now * n, (uint32_t)group, terms * n, 0}, s);
-                else dot_lift_tile<false>(*h.prime[i], h.lift[i], {sums[i], d_a + off, d_b + off, now * n, (uint32_t)group, terms * n, terms * n}, s);
+                if (shared_b) dot_lift_tile<true>(*h.prime[i], h.lift[i], g, {sums[i], d_a + off, bhat[i], now * n, (uint32_t)group, terms * n, 0}, s);
+                else dot_lift_tile<false>(*h.prime[i], h.lift[i], g, {sums[i], d_a + off, d_b + off, now * n, (uint32_t)group, terms * n, terms * n}, s);
             }
             launch_reduce(h, d_c + j0 * n, sums[0], sums[1], now * n, accumulate || i0 > 0, s);
         }
     }
 }
 
-// One call on the device (caller validated the arguments): ring_call's brackets on the handle's own mutex and event.
+// One call on the device (caller validated the arguments): ring_call's brackets on the handle's own mutex and event.  g: 0 for the
+// plain product, else the odd Galois element below 2 n applied to a
 static void ring_mod_dot_device(const LsrRingMod& h, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms, size_t b_rows,
-                                bool accumulate, hipStream_t s) {
+                                bool accumulate, uint64_t g, hipStream_t s) {
+    // g^-1 mod 2 n by Newton's iteration, which doubles the correct low bits (g is its own inverse mod 8), as lsr_ring_galois.hip
+    uint32_t inv = (uint32_t)g;
+    for (int i = 0; i < 4; ++i) inv *= 2u - (uint32_t)g * inv;
+    const GaloisParams gp{inv & (2u * h.n - 1u), 2u * h.n - 1u};
     std::lock_guard<std::mutex> lock(h.mutex);
     const bool capturing = stream_is_capturing(s);
     if (!capturing) h.event.wait(s);
-    ring_mod_dot_enqueue(h, d_c, d_a, d_b, batch, terms, b_rows == 1 && batch > 1, accumulate, s);
+    ring_mod_dot_enqueue(h, d_c, d_a, d_b, batch, terms, b_rows == 1 && batch > 1, accumulate, g ? &gp : nullptr, s);
     if (!capturing) h.event.record(s);
 }
 
@@ -132,16 +133,23 @@ static size_t mul_or_max(size_t x, size_t y) {
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-// mul is dot with terms == 1, except that c may be a or b itself.  Refusals in batch.h's order.
+// mul is dot with terms == 1, except that c may be a or b itself.  g: 0 for mul and dot, else the Galois element of dot_galois (1 is
+// the plain product through the same kernel).  Refusals in batch.h's order.
 int ring_mod_dot_call(const char* where, const LsrRingMod* h, uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t terms, size_t b_rows,
-                      bool is_mul, bool device, void* stream) noexcept {
+                      bool is_mul, bool device, void* stream, bool galois = false, uint64_t g = 0) noexcept {
     if (!h || !c || !a || !b) return lsr::abi_refuse(where, "NULL handle or buffer");
     if (b_rows != 1 && b_rows != batch)
         return lsr::abi_refuse(where, "b_rows must be 1 or batch (" + std::to_string(batch) + "), got " + std::to_string(b_rows));
     if (terms == 0) return lsr::abi_refuse(where, "terms must be at least 1");
+    if (galois && (g & 1) == 0) return lsr::abi_refuse(where, "g = " + std::to_string(g) + " is even: a Galois element is odd");
     if (batch == 0) return 0;
     return lsr::abi_guarded(where, [&] {
         const size_t n = h->n, poly_bytes = n * 8;
+        if (galois && g >= 2 * (uint64_t)n) throw std::runtime_error("g = " + std::to_string(g) + " is not below 2 n = " + std::to_string(2 * (uint64_t)n));
+        if (galois && h->logn > lsr::kTileLog)
+            throw std::runtime_error("n = " + std::to_string(n) + " is above 4096, where the twisted inner product has no fused form: "
+                                     "lsr_ring_mod_lift_batch_device both operands for each prime, run lsr_ntt_ring_dot_galois_batch_device on "
+                                     "lsr_ring_mod_prime_context(h, 0) and (h, 1), and pass the two results to lsr_ring_mod_reduce_batch_device");
         if (h->logn > lsr::kTileLog)
             throw std::runtime_error("n = " + std::to_string(n) + " is above 4096, where the product has no fused form: lsr_ring_mod_lift_batch_device "
                                      "both operands for each prime, run lsr_ntt_ring_" + (is_mul ? "mul" : "dot") + "_batch_device on "
@@ -156,11 +164,11 @@ int ring_mod_dot_call(const char* where, const LsrRingMod* h, uint64_t* c, const
         lsr::require_device();
         if (device) {
             lsr::DeviceGuard guard(h->device);
-            lsr::ring_mod_dot_device(*h, c, a, b, batch, terms, b_rows, false, static_cast<hipStream_t>(stream));
+            lsr::ring_mod_dot_device(*h, c, a, b, batch, terms, b_rows, false, g, static_cast<hipStream_t>(stream));
         } else {
             lsr::host_staged_dot(*h->prime[0], c, a, b, batch, terms, b_rows,
                                  [&](uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t now, size_t group, size_t rows, hipStream_t s, bool first,
-                                     bool) { lsr::ring_mod_dot_device(*h, d_c, d_a, d_b, now, group, rows, !first, s); });
+                                     bool) { lsr::ring_mod_dot_device(*h, d_c, d_a, d_b, now, group, rows, !first, g, s); });
         }
     });
 }
@@ -233,7 +241,9 @@ LsrRingMod* lsr_ring_mod_create(uint64_t q, uint32_t n, int device) noexcept {
             h->lift[i] = lsr::LiftSource{q >> 1, p[i] - q};
         }
         h->logn = h->prime[0]->logn;
-        h->pq = lsr::ring_mod_params(q, h->logn);
+        h->coeff.reset(lsr::create_coeff_context(where, q, n, h->logn, device));
+        if (!h->coeff) return nullptr;   // (create_coeff_context set lsr_last_error)
+        h->pq = lsr::make_mod_params(q, h->logn);
         const lsr::u128 big = (lsr::u128)p[0] * p[1], half = (big - 1) / 2;
         h->rc.p[0] = p[0];
         h->rc.p[1] = p[1];
@@ -269,6 +279,7 @@ void lsr_ring_mod_free(LsrRingMod* h) noexcept {
 uint64_t lsr_ring_mod_modulus(const LsrRingMod* h) noexcept { return h ? h->q : 0; }
 const NttContext* lsr_ring_mod_prime_context(const LsrRingMod* h, int i) noexcept { return h && (i == 0 || i == 1) ? h->prime[i].get() : nullptr; }
 size_t lsr_ring_mod_max_terms(const LsrRingMod* h) noexcept { return h ? h->max_terms : 0; }
+const NttContext* lsr_ring_mod_coeff_context(const LsrRingMod* h) noexcept { return h ? h->coeff.get() : nullptr; }
 
 int lsr_ring_mod_lift_batch_device(const LsrRingMod* h, int i, uint64_t* d_out, const uint64_t* d_x, size_t count, void* stream) noexcept {
     const char* const where = "lsr_ring_mod_lift_batch_device";
@@ -314,6 +325,14 @@ int lsr_ring_mod_dot_batch(const LsrRingMod* h, uint64_t* c, const uint64_t* a, 
 int lsr_ring_mod_dot_batch_device(const LsrRingMod* h, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms, size_t b_rows,
                                   void* stream) noexcept {
     return ring_mod_dot_call("lsr_ring_mod_dot_batch_device", h, d_c, d_a, d_b, batch, terms, b_rows, false, true, stream);
+}
+int lsr_ring_mod_dot_galois_batch(const LsrRingMod* h, uint64_t* c, const uint64_t* a, const uint64_t* b, size_t batch, size_t terms, size_t b_rows,
+                                  uint64_t g) noexcept {
+    return ring_mod_dot_call("lsr_ring_mod_dot_galois_batch", h, c, a, b, batch, terms, b_rows, false, false, nullptr, true, g);
+}
+int lsr_ring_mod_dot_galois_batch_device(const LsrRingMod* h, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms,
+                                         size_t b_rows, uint64_t g, void* stream) noexcept {
+    return ring_mod_dot_call("lsr_ring_mod_dot_galois_batch_device", h, d_c, d_a, d_b, batch, terms, b_rows, false, true, stream, true, g);
 }
 
 }  // extern "C"

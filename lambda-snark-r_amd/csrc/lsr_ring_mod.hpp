@@ -1,6 +1,6 @@
 // The ring handle under an arbitrary modulus (LsrRingMod, batch.h) as the translation units that read it see it:
-// lsr_ring_mod.hip creates it and computes mul and dot, lsr_ring_mod_matvec.hip keeps resident matrices on it (§5q),
-// lsr_ring_mod_gram.hip computes Gram matrices of bounded vectors on it (§5r), lsr_ring_mod_fold.hip folds vectors by challenges on it (§5s).
+// lsr_ring_mod.hip creates it, computes mul, dot and dot_galois and lends its coefficient context (§5t), lsr_ring_mod_matvec.hip keeps
+// resident matrices on it (§5q), lsr_ring_mod_gram.hip computes Gram matrices of bounded vectors on it (§5r), lsr_ring_mod_fold.hip folds vectors by challenges on it (§5s).
 #pragma once
 
 #include <mutex>
@@ -16,6 +16,7 @@ struct LsrRingMod {
     int device = 0;
     size_t max_terms = 0;
     lsr::NttContextPtr prime[2];
+    lsr::NttContextPtr coeff;        // (q, n) without tables: lent out by lsr_ring_mod_coeff_context
     lsr::RingModConsts rc{};
     lsr::ModParams pq{};             // of q: only q and floor(2^128 / q) are used
     lsr::LiftSource lift[2]{};

@@ -102,6 +102,7 @@ static void host_ring_mul(const NttContext& c, uint64_t* out, const uint64_t* a,
 // ------------------------------------------------------------------------------------------------
 // Argument checks that need no device (and no dereference of ctx): -1 and a message, or 0 to go on.
 static int ring_mul_check(const char* where, const NttContext* ctx, const void* c, const void* a, const void* b, size_t batch, size_t b_rows) {
+    if (lsr::refuse_coeff_context(where, ctx)) return -1;
     if (!ctx || !c || !a || !b) return lsr::abi_refuse(where, "NULL context or buffer");
     if (b_rows != 1 && b_rows != batch)
         return lsr::abi_refuse(where, "b_rows must be 1 or batch (" + std::to_string(batch) + "), got " + std::to_string(b_rows));

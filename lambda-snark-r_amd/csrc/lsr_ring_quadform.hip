@@ -132,6 +132,7 @@ namespace {
 // (a no-op), 0 to go on.
 int ring_quadform_check(const char* where, const NttContext* ctx, const void* out, const void* g, const void* c, size_t batch, size_t r,
                         size_t c_rows) {
+    if (lsr::refuse_coeff_context(where, ctx)) return -1;
     if (!ctx || !out || !g || !c) return lsr::abi_refuse(where, "NULL context or buffer");
     if (r == 0) return lsr::abi_refuse(where, "r must be at least 1");
     if (c_rows != 1 && c_rows != batch)

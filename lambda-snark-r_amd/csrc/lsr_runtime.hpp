@@ -192,6 +192,9 @@ struct NttContext {
     // tests/test_ring_challenge_abi.py checks their order on a handle that holds only these
     uint64_t modulus = 0;
     uint32_t degree = 0;
+    // the coefficient context of a ring handle under any modulus (lsr_ring_mod_coeff_context): no twiddle tables, so
+    // the coefficient-wise calls run on it and every call that transforms refuses it first (refuse_coeff_context below)
+    bool coeff = false;
     int logn = 0;
     int device = 0;
     bool use_f64 = false;
@@ -239,7 +242,45 @@ struct NttContext {
 
 namespace lsr {
 
+// q, 2 q, the doubles and floor(2^128 / q) for any q >= 2, prime or not (mulmod_barrett128 and mod64_barrett use nothing else of q)
+inline ModParams make_mod_params(uint64_t q, int logn) {
+    ModParams p{};
+    p.q = q;
+    p.two_q = 2 * q;
+    p.qd = static_cast<double>(q);
+    p.inv_qd = 1.0 / p.qd;
+    u128 ratio = ~static_cast<u128>(0) / q;             // floor((2^128 - 1) / q): one short of floor(2^128 / q) exactly when q | 2^128
+    if ((q & (q - 1)) == 0) ratio += 1;
+    p.barrett_hi = static_cast<uint64_t>(ratio >> 64);
+    p.barrett_lo = static_cast<uint64_t>(ratio);
+    p.logn = logn;
+    return p;
+}
+
 NttContext* create_ntt_context(uint64_t q, uint32_t n, int device);
+// the negacyclic context of (q, n) without twiddle tables that a ring handle lends out (lsr_ring_mod_coeff_context): any q >= 2 and any
+// n = 2^logn the handle admits; psi = 0, the 8-byte hand-off, the flavour of lsr_set_arith_mode.  `where` names the entry point
+NttContext* create_coeff_context(const char* where, uint64_t q, uint32_t n, int logn, int device);
+// The refusal every entry point that transforms makes first after its context's own NULL check: true, with lsr_last_error "<where>:
+// ... coefficient context ...", when ctx is a coefficient context.  An entry lsr_ntt_ring_X whose product the handle computes itself
+// is pointed to lsr_ring_mod_X.
+inline bool refuse_coeff_context(const char* where, const NttContext* ctx) {
+    if (!ctx || !ctx->coeff) return false;
+    static const char* const kOnHandle[] = {"mul_batch", "dot_batch", "dot_galois_batch", "fold_batch", "gram_batch", "gram_sym2_batch",
+                                            "matrix_create", "matrix_create_seeded"};
+    const std::string name(where), prefix("lsr_ntt_ring_"), device("_device");
+    std::string instead;
+    if (name.compare(0, prefix.size(), prefix) == 0) {
+        std::string rest = name.substr(prefix.size());
+        const bool dev = rest.size() > device.size() && rest.compare(rest.size() - device.size(), device.size(), device) == 0;
+        if (dev) rest.resize(rest.size() - device.size());
+        for (const char* k : kOnHandle)
+            if (rest == k) instead = std::string(": use lsr_ring_mod_") + rest + (dev ? "_device" : "") + " on the handle";
+    }
+    set_last_error(name + ": the context is the coefficient context of a ring handle (lsr_ring_mod_coeff_context), which has no twiddle tables and "
+                          "serves the coefficient-wise calls only" + instead);
+    return true;
+}
 // cyclic transform over F_q with the given primitive n-th root (0 = the reference's root for NTT_MODULUS)
 // large: the ceiling is 2^22 instead of 2^17 (lsr_cyclic_ntt_context_create_large; above 2^17 only q = NTT_MODULUS); `where` names
 // the entry point in lsr_last_error
