@@ -976,6 +976,70 @@ int lsr_ring_mod_fold_batch(const LsrRingMod* h, uint64_t* out, int32_t* status,
 int lsr_ring_mod_fold_batch_device(const LsrRingMod* h, uint64_t* d_out, int32_t* d_status, const uint64_t* d_v, const uint64_t* d_p, size_t outputs,
                                    size_t terms, size_t term_stride, size_t width, uint64_t bound_v, uint64_t bound_p, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: quadratic forms under any modulus (a packed Gram triangle in ring-valued challenges on a ring handle) -------- */
+/* The verifier's closing equations of a lattice argument — <z, z> = sum g_il c_i c_l and sum_i <phi_i, z> c_i = sum h_il c_i c_l — in
+ * Z_q[X]/(X^n + 1) for the q of an LsrRingMod, at every n the handle admits.  This is the call to take where
+ * lsr_ntt_ring_quadform_batch is refused on the handle's coefficient context.  Shapes are those of lsr_ntt_ring_quadform_batch: g
+ * [batch][r (r + 1) / 2][n] in the packed order lsr_ring_mod_gram_batch (b == NULL) and lsr_ring_mod_gram_sym2_batch write, c
+ * [c_rows][r][n] with c_rows == batch or 1 (one set of challenges for every family), out [batch][n], status [batch].  The ring is
+ * negacyclic.  Limits: r <= LSR_RING_GRAM_MAX_VECTORS, one family's g <= LSR_RING_GRAM_MAX_FAMILY_BYTES.
+ *
+ * Definition.  out[j] = sum_i g[j][(i,i)] c_i c_i + offdiag * sum_{i < l} g[j][(i,l)] c_i c_l in Z_q[X]/(X^n + 1): canonical in
+ * [0, q), exact, and independent of the kernel flavour and of how the call slices, groups and chunks its work; inputs in [0, q).
+ * Word for word it is lsr_ring_mod_mul_batch on every pair (c_i, c_l), the off-diagonal products scaled by offdiag mod q, and
+ * lsr_ring_mod_dot_batch of the r (r + 1) / 2 products against g[j].  offdiag is a word below q — 2 for a lsr_ring_mod_gram_batch(s),
+ * 1 for a lsr_ring_mod_gram_sym2_batch(phi, s) — and acts through its centred representative w: the kernels multiply by the residues
+ * of w mod p1 and mod p2.  g and c are never written.
+ *
+ * Capacity of a cubic sum (host only).  The form is CUBIC in its operands, so neither max_terms nor lsr_ring_mod_capacity_product,
+ * which count bilinear products, cover it:
+ *   lsr_ring_mod_capacity_quadform(q, n, bound_g, bound_c) = floor(((P - 1)/2) / (n^2 bound_g bound_c^2))
+ * counts the triple negacyclic products g c c' of operands of centred magnitude |g| <= bound_g and |c|, |c'| <= bound_c that one sum
+ * may hold.  A bound of 0 states none, which is floor(q/2); 0 for a bound above floor(q/2) and wherever lsr_ring_mod_capacity(q, n) is
+ * 0; saturated at SIZE_MAX.  (The divisor can exceed 128 bits: (P - 1)/2 is divided by n, n, bound_g, bound_c, bound_c in turn.)
+ * q = 4294967197 at n = 64 carries 0 such products of unbounded operands and 4398042366208 with the challenges declared within 2.
+ *
+ * Bounds and status: those of the Gram matrices above.  bound_g and bound_c are the l-infinity bounds the caller asserts on the
+ * centred representatives of g and of c; 0 states none.  The device VERIFIES them: status is [batch] (int32), never NULL, and written
+ * for every family:
+ *    1   every word family j reads — its g[j] and the c it takes — was below q and within its bound: out[j] is exact;
+ *    0   some such word's centred magnitude exceeded its bound;
+ *   -1   some such word was >= q (-1 wins over 0).
+ * For a status 0 or -1 EVERY word of out[j] is 0.  With c_rows == 1 every family reads the same c, so a bad word in c gates every
+ * family, while a bad word in g[j] gates family j alone.
+ *
+ * Grouping rule: with W = max(1, |w|), the packed pairs are taken in runs of the packed order of at most
+ * floor(lsr_ring_mod_capacity_quadform(q, n, bound_g, bound_c) / W) pairs (the workspace may cut the runs shorter); every group goes
+ * all the way to out — inverse transform, CRT, reduction mod q — and every group after the first is added to out mod q.  A violation
+ * found in a later group still leaves out[j] all zero.  Where not even one pair fits — unbounded challenges at any modulus of 32 bits
+ * or more, an offdiag such as (q + 1)/2 at a large q — the call is refused before any device work; the message names bound_c and the
+ * route that always works because it reduces mod q between the two products: lsr_ring_mod_mul_batch per pair, a scaling by offdiag,
+ * lsr_ring_mod_dot_batch.
+ *
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL h, out, status, g or c;
+ * (2) r == 0; (3) c_rows neither 1 nor batch; (4) r above LSR_RING_GRAM_MAX_VECTORS; (5) a size that overflows size_t, as
+ * lsr_ntt_ring_quadform_batch lists them; (6) offdiag >= q; (7) a bound above floor(q/2).  (8) Then batch == 0 is a no-op that returns
+ * 0.  Then (9) one family's g above LSR_RING_GRAM_MAX_FAMILY_BYTES; (10) the capacity refusal above; (11) r + 3 polynomials per prime
+ * (the transformed c of one family, one of g, one partial sum, one sum) not fitting the workspace — the message names
+ * LAMBDA_SNARK_NTT_CHUNK_MIB, which sizes it (at the present limits no call reaches this one: a prime's half holds at least 64
+ * polynomials at n = 131072, and a family of r >= 62 there is above LSR_RING_GRAM_MAX_FAMILY_BYTES); (12) out overlapping g, then c, status overlapping g, c, then out, in address range;
+ * (13) no visible device; (14) a capturing stream with the workspace not yet allocated (the message asks for one eager call first;
+ * the handle stays usable).
+ *
+ * Workspace, ordering and graph capture: the Gram matrices' — the handle's Gram workspace and its flag words, allocated by the first
+ * eager Gram or quadratic-form call or by lsr_ring_mod_gram_prepare(h), never resized; there is no workspace of this call's own.  A chunk
+ * of whole families holds, per prime, the transformed c (r polynomials a family, or r once when shared: a shared c is lifted, checked
+ * and transformed once per call), a group of transformed g, the slices' partial sums and one sum a family.  After _prepare the _device
+ * form captures into a HIP graph from the first call (one chain of kernels).  Calls on one handle are ordered by the handle's mutex
+ * and event; a captured call is not bracketed.  The plain form takes host buffers through bounded device chunks of whole families on
+ * the first prime context's work stream (a shared c goes up once) and returns when out and status are complete; the _device form
+ * enqueues only. */
+size_t lsr_ring_mod_capacity_quadform(uint64_t q, uint32_t n, uint64_t bound_g, uint64_t bound_c) LSR_NOEXCEPT;
+int lsr_ring_mod_quadform_batch(const LsrRingMod* h, uint64_t* out, int32_t* status, const uint64_t* g, const uint64_t* c, size_t batch, size_t r,
+                                size_t c_rows, uint64_t offdiag, uint64_t bound_g, uint64_t bound_c) LSR_NOEXCEPT;
+int lsr_ring_mod_quadform_batch_device(const LsrRingMod* h, uint64_t* d_out, int32_t* d_status, const uint64_t* d_g, const uint64_t* d_c, size_t batch,
+                                       size_t r, size_t c_rows, uint64_t offdiag, uint64_t bound_g, uint64_t bound_c, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

@@ -27,7 +27,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PACK_CENTRED", "RING_PACK_RESIDUE", "ring_pack_words", "ring_pack_min_bits", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "RingMod", "ring_mod_primes", "ring_mod_capacity", "ring_mod_capacity_bounded", "ring_mod_capacity_product", "RingModMatrix", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PACK_CENTRED", "RING_PACK_RESIDUE", "ring_pack_words", "ring_pack_min_bits", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "RingMod", "ring_mod_primes", "ring_mod_capacity", "ring_mod_capacity_bounded", "ring_mod_capacity_product", "ring_mod_capacity_quadform", "RingModMatrix", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -953,6 +953,15 @@ def ring_mod_capacity_product(q, n, bound_a, bound_b):
     return int(_abi.lib().lsr_ring_mod_capacity_product(int(q), int(n), int(bound_a), int(bound_b)))
 
 
+def ring_mod_capacity_quadform(q, n, bound_g, bound_c):
+    """``lsr_ring_mod_capacity_quadform``: how many triple products g c c' of an element of centred magnitude <= bound_g with two of
+    magnitude <= bound_c, degree n, one sum mod q may hold (a bound of 0: none, q // 2); 0 for a bound above q // 2 or an inadmissible
+    (q, n) (host only)."""
+    if not (0 <= int(q) < 2**64 and 0 <= int(n) < 2**32 and 0 <= int(bound_g) < 2**64 and 0 <= int(bound_c) < 2**64):
+        return 0
+    return int(_abi.lib().lsr_ring_mod_capacity_quadform(int(q), int(n), int(bound_g), int(bound_c)))
+
+
 class RingModMatrix:
     """A rows x cols matrix over Z_q[X]/(X^n + 1) resident on a RingMod's device (``LsrRingModMatrix*``, batch.h "resident matrices
     under any modulus").  Made by ``RingMod.matrix`` (host array), ``matrix_device`` (device pointer) or
@@ -1287,6 +1296,39 @@ class RingMod:
         p [outputs][terms][n].  Asynchronous on `stream`; enqueues only."""
         _check(self._lib.lsr_ring_mod_fold_batch_device(self._h, d_out, d_status, d_v, d_p, outputs, terms, term_stride, width, int(bound_v), int(bound_p),
                                                         stream), "lsr_ring_mod_fold_batch_device")
+
+    def quadform(self, g, c, offdiag=2, bound_g=0, bound_c=0):
+        """out[j] = sum_i g[j][(i, i)] c_i c_i + offdiag * sum_{i < l} g[j][(i, l)] c_i c_l mod (X^n + 1, q) (host arrays, DESIGN.md
+        §5u): g is [batch, r (r + 1) / 2, n] in the packed order of ``gram(s)`` and ``gram_sym2`` (ring_gram_index), c is [batch, r, n],
+        or [r, n]: one set of challenges shared by every family.  Returns (out [batch, n], status [batch]) — ([n], status) for a 2-d g.
+        offdiag: a word below q — 2 for a gram(s), 1 for a gram_sym2(phi, s).  bound_g, bound_c: the l-infinity bounds asserted on the
+        centred words of g and c (0: none); status[j] is 1 where every word family j reads kept them (exact output), 0 where one
+        exceeded its bound, -1 where one was >= q — then every word of out[j] is 0."""
+        n = self.n
+        g_in, c_in = _u64_array(g, "g"), _u64_array(c, "c")
+        if g_in.ndim not in (2, 3) or g_in.shape[-1] != n:
+            raise ValueError("g must be [pairs, n] or [batch, pairs, n]")
+        if c_in.ndim not in (2, 3) or c_in.shape[-1] != n:
+            raise ValueError("c must be [r, n] or [batch, r, n]")
+        r, pairs = c_in.shape[-2], g_in.shape[-2]
+        if pairs != r * (r + 1) // 2:
+            raise ValueError("g must hold r (r + 1) / 2 polynomials per family for the r polynomials of c")
+        g3 = np.ascontiguousarray(g_in.reshape(-1, pairs, n))
+        c3 = np.ascontiguousarray(c_in.reshape(-1, r, n))
+        batch, c_rows = g3.shape[0], (1 if c_in.ndim == 2 else c3.shape[0])
+        if c_rows not in (1, batch):
+            raise ValueError("c must hold one set of challenges ([r, n]) or one per family of g")
+        out = np.empty((batch, n), dtype=np.uint64)
+        status = np.empty(batch, dtype=np.int32)
+        _check(self._lib.lsr_ring_mod_quadform_batch(self._h, out.ctypes.data, status.ctypes.data, g3.ctypes.data, c3.ctypes.data, batch, r, c_rows,
+                                                     int(offdiag), int(bound_g), int(bound_c)), "lsr_ring_mod_quadform_batch")
+        return (out[0], status[0]) if g_in.ndim == 2 else (out, status)
+
+    def quadform_device(self, d_out, d_status, d_g, d_c, batch, r, c_rows, offdiag=2, bound_g=0, bound_c=0, stream=0):
+        """Device buffers: g [batch][r (r + 1) / 2][n], c [c_rows][r][n] with c_rows 1 or batch, out [batch][n], status [batch] int32.
+        Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ring_mod_quadform_batch_device(self._h, d_out, d_status, d_g, d_c, batch, r, c_rows, int(offdiag), int(bound_g), int(bound_c),
+                                                            stream), "lsr_ring_mod_quadform_batch_device")
 
 
 

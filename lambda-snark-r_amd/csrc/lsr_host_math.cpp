@@ -244,6 +244,17 @@ size_t ring_mod_capacity_product(uint64_t q, uint32_t n, uint64_t bound_a, uint6
     return terms > (u128)SIZE_MAX ? SIZE_MAX : (size_t)terms;
 }
 
+size_t ring_mod_capacity_quadform(uint64_t q, uint32_t n, uint64_t bound_g, uint64_t bound_c) {
+    uint64_t p[2];
+    if (q < 2 || !rns_moduli_for(n, p)) return 0;
+    const uint64_t h = q >> 1;
+    if (bound_g > h || bound_c > h || ring_mod_capacity(q, n) == 0) return 0;
+    const uint64_t g = bound_g ? bound_g : h, c = bound_c ? bound_c : h;    // h >= 1: q >= 2
+    // nested floor divisions by positive integers are the floor of the one division
+    const u128 terms = ((u128)p[0] * p[1] - 1) / 2 / n / n / g / c / c;
+    return terms > (u128)SIZE_MAX ? SIZE_MAX : (size_t)terms;
+}
+
 uint64_t os_entropy64() {
     uint64_t v = 0;
     os_entropy_fill(&v, sizeof v);

@@ -87,6 +87,10 @@ size_t ring_mod_capacity_bounded(uint64_t q, uint32_t n, uint64_t bound);
 // floor(((P - 1) / 2) / (n bound_a bound_b)).  0 where a bound is 0 or above h and wherever ring_mod_capacity is 0;
 // ring_mod_capacity_product(q, n, h, b) == ring_mod_capacity_bounded(q, n, b), ring_mod_capacity_product(q, n, h, h) == ring_mod_capacity(q, n).
 size_t ring_mod_capacity_product(uint64_t q, uint32_t n, uint64_t bound_a, uint64_t bound_b);
+// Triple negacyclic products g c c' with |g| <= bound_g and |c|, |c'| <= bound_c that one sum may hold:
+// floor(((P - 1) / 2) / (n^2 bound_g bound_c^2)), the divisions taken one after the other (the divisor can exceed 128 bits).  A bound
+// of 0 states none: h.  0 where a bound is above h and wherever ring_mod_capacity is 0; saturated at SIZE_MAX.
+size_t ring_mod_capacity_quadform(uint64_t q, uint32_t n, uint64_t bound_g, uint64_t bound_c);
 
 uint64_t os_entropy64();
 

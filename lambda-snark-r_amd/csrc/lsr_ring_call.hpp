@@ -1,7 +1,7 @@
 // The host call path shared by the ring operations (lsr_ring_mul.hip, lsr_ring_dot.hip, lsr_ring_fold.hip, lsr_ring_matvec.hip,
 // lsr_ring_gadget.hip, lsr_ring_galois.hip, lsr_ring_sample.hip, lsr_ring_challenge.hip, lsr_ring_pack.hip, lsr_ring_norm.hip,
 // lsr_ring_scalar.hip, lsr_ring_gram.hip, lsr_ring_quadform.hip, the ring handles of lsr_ring_mod.hip, lsr_ring_mod_matvec.hip,
-// lsr_ring_mod_gram.hip and lsr_ring_mod_fold.hip, and the ring combination of lsr_commit.hip): the dispatch from a context to a kernel instantiation, the
+// lsr_ring_mod_gram.hip, lsr_ring_mod_fold.hip and lsr_ring_mod_quadform.hip, and the ring combination of lsr_commit.hip): the dispatch from a context to a kernel instantiation, the
 // bracket that keeps the context's workspaces safe across streams and threads, the argument checks the entry points
 // have in common and the one loop that stages host buffers through bounded device chunks (host_staged; its arithmetic:
 // lsr_staging_plan.hpp).  The dispatch helpers (for_tile_log, for_rank, for_top_bits, for_bool, for_flavour) also serve the commitment

@@ -1,6 +1,7 @@
 // The ring handle under an arbitrary modulus (LsrRingMod, batch.h) as the translation units that read it see it:
 // lsr_ring_mod.hip creates it, computes mul, dot and dot_galois and lends its coefficient context (§5t), lsr_ring_mod_matvec.hip keeps
-// resident matrices on it (§5q), lsr_ring_mod_gram.hip computes Gram matrices of bounded vectors on it (§5r), lsr_ring_mod_fold.hip folds vectors by challenges on it (§5s).
+// resident matrices on it (§5q), lsr_ring_mod_gram.hip computes Gram matrices of bounded vectors on it (§5r), lsr_ring_mod_fold.hip folds vectors by challenges on it (§5s),
+// lsr_ring_mod_quadform.hip evaluates quadratic forms of a packed Gram triangle on it (§5u).
 #pragma once
 
 #include <mutex>
@@ -24,7 +25,7 @@ struct LsrRingMod {
     // kRingModFoldFlagWords words of a fold's per-output flags.  Never resized.
     size_t chunk = 0, bhat_rows = 0;
     lsr::DeviceBuffer<uint64_t> ws;
-    // the Gram calls (lsr_ring_mod_gram.hip): [2][ring_mod_gram_words()] lifted operands, their transforms and the outputs of one chunk
+    // the Gram calls and the quadratic forms (lsr_ring_mod_gram.hip, lsr_ring_mod_quadform.hip): [2][ring_mod_gram_words()] lifted operands, their transforms and the outputs of one chunk
     // per prime, then kRingModGramFlagWords words of per-family flags.  Allocated by the first eager Gram call or by
     // lsr_ring_mod_gram_prepare under `mutex`, never resized.
     mutable lsr::DeviceBuffer<uint64_t> gram_ws;
