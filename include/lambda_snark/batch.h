@@ -850,7 +850,34 @@ int lsr_ring_mod_dot_galois_batch_device(const LsrRingMod* h, uint64_t* d_c, con
  * complete; the _device forms enqueue only.  Workspace, ordering and graph capture are the fused products': no allocation after
  * create (the per-prime sums go to the handle's workspace in chunks of whole vectors or, where rows n exceeds 2^22 words, of one
  * vector and a range of rows), calls on one handle are ordered by the handle's event, a captured call is not bracketed and the
- * _device forms capture into a HIP graph from the first call. */
+ * _device forms capture into a HIP graph from the first call.
+ *
+ * The bounded product: the plain product with a bound on x that the device VERIFIES — the commitment t = A s
+ * and the verifier's A z, whose operand is short by construction.
+ *   lsr_ring_mod_matvec_bounded_batch: x [batch][cols][n], y [batch][rows][n], status [batch] (int32), never NULL.
+ * bound_x is the l-infinity bound the caller asserts on the centred representatives of x; 0 states none, which is floor(q/2): then
+ * only -1 can occur and the call is the plain product with a canonicity check.  status is written for every vector, with the values
+ * and the precedence of the Gram and fold calls below:
+ *    1   every one of the cols n words of x[j] was below q and within the bound: y[j] equals lsr_ring_mod_matvec_batch on the same
+ *        operands word for word, canonical in [0, q);
+ *    0   some word's centred magnitude exceeded the bound;
+ *   -1   some word was >= q (-1 wins over 0).
+ * For a status 0 or -1 EVERY word of y[j] is 0; the other vectors of the batch are unaffected.
+ * Grouping rule: matrix columns are taken in groups of at most lsr_ring_mod_capacity_bounded(q, n, bound_x) (0 -> floor(q/2), which
+ * gives max_terms), every group after the first reduced into y with accumulate: q = 2^40 + 15 at n = 64 takes 258 columns in 37
+ * groups unbounded and in one with x declared within 128.  Exactness never depends on the caller knowing the capacity — the bound is
+ * verified, not promised.  A violation found in a later group still leaves y[j] all zero.
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work), in this order: (1) NULL mat, y, status or x;
+ * (2) bound_x above floor(q/2).  (3) Then batch == 0 is a no-op that returns 0.  Then (4) y overlapping x; (5) status overlapping
+ * x, then y, in address range; (6) no visible device.
+ * Range: n <= 4096, as the matrix handle itself.
+ * Workspace, ordering and graph capture are the plain product's: the per-vector flag words are the 4096 32-bit words behind the
+ * handle's workspace, which lsr_ring_mod_create allocates, so they exist before lsr_ring_mod_matrix_create returns; a chunk of
+ * whole vectors is capped at 4096 vectors by them.  The _device form allocates nothing, is ordered by the handle's mutex and event
+ * and captures into a HIP graph from the first call; the plain form takes host buffers through bounded device chunks, status staged
+ * alongside y, and returns when both are complete.
+ * The bounded inner product with a per-output b is lsr_ring_mod_fold_batch at width = 1, term_stride = terms (out[j] = sum_i
+ * p[j][i] v[j terms + i]); lsr_ring_mod_dot_batch takes no bound. */
 typedef struct LsrRingModMatrix LsrRingModMatrix;
 size_t lsr_ring_mod_capacity_bounded(uint64_t q, uint32_t n, uint64_t bound) LSR_NOEXCEPT;
 LsrRingModMatrix* lsr_ring_mod_matrix_create(const LsrRingMod* h, const uint64_t* m, size_t rows, size_t cols) LSR_NOEXCEPT;
@@ -867,6 +894,10 @@ int lsr_ring_mod_matvec_gadget_batch(const LsrRingModMatrix* mat, uint64_t* y, c
                                      size_t digits) LSR_NOEXCEPT;
 int lsr_ring_mod_matvec_gadget_batch_device(const LsrRingModMatrix* mat, uint64_t* d_y, const uint64_t* d_x, size_t batch, unsigned base_log2,
                                             size_t digits, void* stream) LSR_NOEXCEPT;
+int lsr_ring_mod_matvec_bounded_batch(const LsrRingModMatrix* mat, uint64_t* y, int32_t* status, const uint64_t* x, size_t batch,
+                                      uint64_t bound_x) LSR_NOEXCEPT;
+int lsr_ring_mod_matvec_bounded_batch_device(const LsrRingModMatrix* mat, uint64_t* d_y, int32_t* d_status, const uint64_t* d_x, size_t batch,
+                                             uint64_t bound_x, void* stream) LSR_NOEXCEPT;
 
 /* ---------------- NTT: Gram matrices under any modulus (bounded ring vectors on a ring handle) ---------------- */
 /* The garbage polynomials of a lattice argument — g_il = <s_i, s_l>, h_il = <phi_i, s_l> + <phi_l, s_i> — in Z_q[X]/(X^n + 1) for the

@@ -1018,9 +1018,31 @@ class RingModMatrix:
         _check(self._lib.lsr_ring_mod_matvec_gadget_batch_device(self._h, d_y, d_x, batch, base_log2, digits, stream),
                "lsr_ring_mod_matvec_gadget_batch_device")
 
+    def matvec_bounded(self, x, bound_x=0):
+        """y = M x with the bound on x verified on the device: x is [cols, n] or [batch, cols, n].  Returns
+        (y [batch, rows, n], status [batch]) — ([rows, n], status) for a 2-d x.  bound_x: the l-infinity bound asserted on the centred
+        words of x (0: none); status[j] is 1 where every word of x[j] kept it (y[j] is ``matvec``'s), 0 where one exceeded the bound,
+        -1 where one was >= q — then every word of y[j] is 0."""
+        x_in = _u64_array(x)
+        if x_in.ndim not in (2, 3) or x_in.shape[-2:] != (self.cols, self.n):
+            raise ValueError("x must be [cols, n] or [batch, cols, n]")
+        if not 0 <= int(bound_x) < 2**64:
+            raise ValueError("bound_x must be a 64-bit word")
+        x3 = np.ascontiguousarray(x_in.reshape(-1, self.cols, self.n))
+        out = np.empty((x3.shape[0], self.rows, self.n), dtype=np.uint64)
+        status = np.empty(x3.shape[0], dtype=np.int32)
+        _check(self._lib.lsr_ring_mod_matvec_bounded_batch(self._h, out.ctypes.data, status.ctypes.data, x3.ctypes.data, x3.shape[0], int(bound_x)),
+               "lsr_ring_mod_matvec_bounded_batch")
+        return (out[0], status[0]) if x_in.ndim == 2 else (out, status)
+
+    def matvec_bounded_device(self, d_y, d_status, d_x, batch, bound_x=0, stream=0):
+        """Device buffers: y [batch][rows][n], status [batch] int32, x [batch][cols][n].  Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ring_mod_matvec_bounded_batch_device(self._h, d_y, d_status, d_x, batch, int(bound_x), stream),
+               "lsr_ring_mod_matvec_bounded_batch_device")
+
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.lsr_ring_mod_matrix_free(self._h)      # (reads the RingMod's handle: still open, see RingMod.close)
+            self._lib.lsr_ring_mod_matrix_free(self._h)     # (reads the RingMod's handle: still open, see RingMod.close)
             self._h = None
             self._ring._matrices.discard(self)
 

@@ -188,6 +188,8 @@ SIGNATURES = {
     "lsr_ring_mod_matvec_batch_device": (c_int, [vp, vp, vp, c_size, vp]),
     "lsr_ring_mod_matvec_gadget_batch": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size]),
     "lsr_ring_mod_matvec_gadget_batch_device": (c_int, [vp, vp, vp, c_size, ctypes.c_uint, c_size, vp]),
+    "lsr_ring_mod_matvec_bounded_batch": (c_int, [vp, vp, vp, vp, c_size, u64]),
+    "lsr_ring_mod_matvec_bounded_batch_device": (c_int, [vp, vp, vp, vp, c_size, u64, vp]),
     "lsr_ring_mod_capacity_product": (c_size, [u64, u32, u64, u64]),
     "lsr_ring_mod_gram_prepare": (c_int, [vp]),
     "lsr_ring_mod_gram_batch": (c_int, [vp, vp, vp, vp, vp, c_size, c_size, c_size, c_size, u64, u64]),

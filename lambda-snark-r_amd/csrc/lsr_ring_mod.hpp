@@ -41,6 +41,12 @@ constexpr size_t kRingModBhatWords = (size_t)1 << 21;   // per prime
 constexpr size_t kRingModBhatMaxRows = 4096;            // bhat_rows = min(this, kRingModBhatWords / n)
 constexpr size_t kRingModFoldFlagWords = kRingModBhatMaxRows / 2;   // 32-bit flag words: one per challenge row
 
+// n <= 4096: the 2 kRingModFoldFlagWords 32-bit flag words behind the workspace's sums and challenge transforms — a fold's per-output
+// flags, a bounded matrix product's per-vector flags (lsr_ring_mod_matvec.hip); whoever holds the handle's mutex owns them
+inline uint32_t* ring_mod_flag_words(const LsrRingMod& h) {
+    return reinterpret_cast<uint32_t*>(h.ws.ptr + 2 * (h.chunk + h.bhat_rows) * h.n);
+}
+
 // Gram workspace words per prime: a function of the process-wide chunk size alone (a quarter of it, 64 MiB of 256: the two halves stay in
 // the Infinity Cache between the passes of a chunk), at least 2^23 words
 size_t ring_mod_gram_words();

@@ -7,6 +7,14 @@
 //             or, where one vector's rows n words exceed it, one vector and a range of rows.  Per chunk and group ONE launch of
 //             ntt_tile_ring_mod_matvec covers both primes (grid z; one instantiation launches per prime instead, kModMatvecBothPrimes),
 //             then one reduce launch into y, accumulating from the second group on.
+//   bounded   lsr_ring_mod_matvec_bounded_batch: the plain product with the caller's l-infinity bound on x VERIFIED on
+//             the device and a status per vector.  The groups are capacity_bounded(q, n, bound_x) columns; the kernel's checking
+//             instantiation holds every word it loads against q and the bound and ORs violations into one flag word per vector of the
+//             chunk (the handle's flag words, cleared per chunk: a chunk is at most kRingModMatvecFlagWords vectors); the reduce is
+//             ring_mod_gram_reduce_kernel, vector = grid y, which writes zeros over a flagged vector — whatever the earlier groups
+//             wrote — and status.  A vector taken in row ranges is checked whole by one storeless pass of ring_mod_gram_lift_kernel
+//             before its first reduce, and its tile launches are the unchecked ones; so is a chunk at the sizes where that
+//             measured faster or the checking instantiation is a wave short (kModMatvecCheckInTile).
 // No allocation after create: the device forms capture into a graph from the first call.
 #include <algorithm>
 #include <memory>
@@ -52,8 +60,34 @@ struct ModMatvecLaunch {
 template <class A, int LT, bool GADGET>
 constexpr bool kModMatvecBothPrimes = !(std::is_same_v<A, ArithU64> && GADGET && LT == 11);
 
-template <class A, bool GADGET>
-static void mod_matvec_tile(const LsrRingModMatrix& m, const ModMatvecLaunch& l, const GadgetParams& g, hipStream_t s) {
+// Where the bounded product's check runs, decided per instantiation by the compiler's resource report and by measurement
+// (profiles/r38_ring_mod_matvec_bounded_resource_usage.txt, profiles/r38_ring_mod_matvec_bounded_bench.json): in the
+// tile kernel from n = 512 on, except in the integer flavour at n = 4096, whose checking instantiation is a wave short of its
+// unchecked twin.  Elsewhere the chunk's x goes through one storeless check pass and the tile launches are the unchecked ones: at
+// n = 64, 128 and 256 the pass measured faster than the check in the tile (n = 256, where the FP64 checking instantiation is a wave
+// short as well: 512 us against 589, the plain product 470), at n = 4096 the tile is no slower (2055 against 2074); the sizes between
+// follow their neighbours unmeasured.  LSR_MOD_MATVEC_CHECK_IN_TILE = 1 / 0: an experiment build that checks in the tile everywhere /
+// nowhere.
+#ifndef LSR_MOD_MATVEC_CHECK_IN_TILE
+#define LSR_MOD_MATVEC_CHECK_IN_TILE (-1)
+#endif
+template <class A, int LT>
+constexpr bool kModMatvecCheckInTile = LSR_MOD_MATVEC_CHECK_IN_TILE >= 0 ? LSR_MOD_MATVEC_CHECK_IN_TILE != 0
+                                                                         : LT >= 9 && !(std::is_same_v<A, ArithU64> && LT == 12);
+
+static bool mod_matvec_checks_in_tile(bool f64, int logn) {
+    bool in_tile = false;
+    for_tile_log<1, 12>(logn, [&](auto t) {
+        constexpr int LT = decltype(t)::value;
+        in_tile = f64 ? kModMatvecCheckInTile<ArithF64, LT> : kModMatvecCheckInTile<ArithU64, LT>;
+    });
+    return in_tile;
+}
+
+// CHECK: the launch holds x against q and `bound` and ORs violations into flags[vector of the chunk]
+template <class A, bool GADGET, bool CHECK = false>
+static void mod_matvec_tile(const LsrRingModMatrix& m, const ModMatvecLaunch& l, const GadgetParams& g, hipStream_t s, uint32_t* flags = nullptr,
+                            uint64_t bound = 0) {
     const LsrRingMod& h = *m.h;
     constexpr int RB = MatvecRowBlock<A>::value;
     const size_t n = h.n, total = l.vectors * n, m_row_words = m.cols * n;
@@ -66,11 +100,16 @@ static void mod_matvec_tile(const LsrRingModMatrix& m, const ModMatvecLaunch& l,
     for_tile_log<1, 12>(h.logn, [&](auto t) {
         constexpr int LT = decltype(t)::value;
         constexpr bool kBoth = kModMatvecBothPrimes<A, LT, GADGET>;
-        const dim3 grid(static_cast<unsigned>((total + kTile - 1) / kTile), static_cast<unsigned>((l.nr + RB - 1) / RB), kBoth ? 2 : 1);
-        for (int i = 0; i < (kBoth ? 1 : 2); ++i) {
-            if (i) both.prime[0] = both.prime[1];
-            hipLaunchKernelGGL((ntt_tile_ring_mod_matvec<A, LT, RB, GADGET, kBoth>), grid, dim3(kThreads), 0, s, both, l.x, total, (uint32_t)l.nr,
-                               (uint32_t)l.xcols, (uint32_t)l.col0, (uint32_t)l.ncols, m_row_words, h.q, g);
+        static_assert(!CHECK || kBoth, "the checking launch takes both primes: the workgroups of prime 0 check");
+        if constexpr (CHECK && !kModMatvecCheckInTile<A, LT>) {
+            throw std::logic_error("mod_matvec_tile: this size checks in a pass of its own");   // (and its checking instantiation is not built)
+        } else {
+            const dim3 grid(static_cast<unsigned>((total + kTile - 1) / kTile), static_cast<unsigned>((l.nr + RB - 1) / RB), kBoth ? 2 : 1);
+            for (int i = 0; i < (kBoth ? 1 : 2); ++i) {
+                if (i) both.prime[0] = both.prime[1];
+                hipLaunchKernelGGL((ntt_tile_ring_mod_matvec<A, LT, RB, GADGET, kBoth, CHECK>), grid, dim3(kThreads), 0, s, both, l.x, total,
+                                   (uint32_t)l.nr, (uint32_t)l.xcols, (uint32_t)l.col0, (uint32_t)l.ncols, m_row_words, h.q, g, flags, bound);
+            }
         }
     });
 }
@@ -113,8 +152,77 @@ static void mod_matvec_enqueue(const LsrRingModMatrix& m, uint64_t* d_y, const u
     }
 }
 
+// The vectors of one chunk of a bounded product: one flag word each
+constexpr size_t kRingModMatvecFlagWords = 2 * kRingModFoldFlagWords;
+static_assert(kRingModMatvecFlagWords <= 65535, "the vectors of a chunk are one grid axis of the reduce");
+
+// [vectors][words] of y (one chunk of whole vectors, or one row range of one vector) from the two primes' sums, gated by the flags
+static void bounded_reduce(const LsrRingMod& h, uint64_t* y, int32_t* status, const uint32_t* flags, size_t words, size_t vectors, bool accumulate,
+                           hipStream_t s) {
+    const bool vec = (reinterpret_cast<uintptr_t>(y) & 15u) == 0;
+    const size_t items = vec ? words / 2 : words;
+    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))),
+                    static_cast<unsigned>(vectors));
+    for_bool(vec, [&](auto v) {
+        for_bool(accumulate, [&](auto acc) {
+            hipLaunchKernelGGL((ring_mod_gram_reduce_kernel<decltype(v)::value, decltype(acc)::value>), grid, dim3(kRingModThreads), 0, s, y, status, h.ws.ptr,
+                               h.ws.ptr + kRingModSumWords, flags, words, words, h.rc, h.prime[1]->mod, h.pq);
+        });
+    });
+}
+
+// the `words` contiguous words of each of `vectors` vectors of x held against q and `bound` into flags[vector]; nothing is stored
+static void bounded_check_pass(const LsrRingMod& h, const uint64_t* x, uint32_t* flags, size_t words, size_t vectors, uint64_t bound, hipStream_t s) {
+    const bool vec = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
+    const size_t items = vec ? words / 2 : words;
+    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))), 1u,
+                    static_cast<unsigned>(vectors));
+    const GramLiftShape shape{words, 0, words, 0, 0, 0, h.q, bound};
+    for_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((ring_mod_gram_lift_kernel<decltype(v)::value, true, false>), grid, dim3(kRingModThreads), 0, s, static_cast<uint64_t*>(nullptr), x,
+                           flags, shape, h.lift[0], h.lift[1]);
+    });
+}
+
+// The bounded plain product: x [batch][cols][n] held against q and bound_x (0: none), status [batch].  mod_matvec_enqueue's loops with
+// the groups of the verified bound, the chunk capped by the flag words and the gated reduce.
+static void mod_matvec_bounded_enqueue(const LsrRingModMatrix& m, uint64_t* d_y, int32_t* d_status, const uint64_t* d_x, size_t batch, uint64_t bound_x,
+                                       hipStream_t s) {
+    const LsrRingMod& h = *m.h;
+    const bool f64 = primes_use_f64(h);
+    const size_t n = h.n;
+    const uint64_t bound = bound_x ? bound_x : h.q >> 1;
+    const size_t group_max = std::min(m.cols, ring_mod_capacity_bounded(h.q, h.n, bound));    // the capacity is >= max_terms >= 1
+    const size_t vector_words = m.rows * n;
+    const bool whole = vector_words <= kRingModSumWords;
+    const size_t chunk = whole ? std::min(kRingModSumWords / vector_words, kRingModMatvecFlagWords) : 1, nr_max = whole ? m.rows : kRingModSumWords / n;
+    uint32_t* const flags = ring_mod_flag_words(h);
+    // a vector in row ranges (now == 1) needs its flags before its first reduce: the check pass, whatever the instantiation
+    const bool in_tile = whole && mod_matvec_checks_in_tile(f64, h.logn);
+    for (size_t j0 = 0; j0 < batch; j0 += chunk) {
+        const size_t now = std::min(chunk, batch - j0);
+        const uint64_t* const xj = d_x + j0 * m.cols * n;
+        zero_words_async(reinterpret_cast<uint64_t*>(flags), (now + 1) / 2, s);
+        if (!in_tile) bounded_check_pass(h, xj, flags, m.cols * n, now, bound, s);
+        for (size_t r0 = 0; r0 < m.rows; r0 += nr_max) {
+            const size_t nr = std::min(nr_max, m.rows - r0);
+            for (size_t c0 = 0; c0 < m.cols; c0 += group_max) {
+                const ModMatvecLaunch l{xj, now, r0, nr, c0, std::min(group_max, m.cols - c0), m.cols};
+                for_bool(in_tile, [&](auto check) {
+                    if (f64) mod_matvec_tile<ArithF64, false, decltype(check)::value>(m, l, GadgetParams{}, s, flags, bound);
+                    else mod_matvec_tile<ArithU64, false, decltype(check)::value>(m, l, GadgetParams{}, s, flags, bound);
+                });
+                LSR_HIP(hipGetLastError());
+                bounded_reduce(h, d_y + (j0 * m.rows + r0) * n, d_status + j0, flags, nr * n, now, c0 > 0, s);
+            }
+        }
+    }
+}
+
 // One call on the device (caller validated the arguments): ring_mod_dot_device's brackets on the handle's mutex and event.
-static void mod_matvec_device(const LsrRingModMatrix& m, uint64_t* d_y, const uint64_t* d_x, size_t batch, unsigned b, size_t digits, hipStream_t s) {
+// d_status: the bounded product (b and digits 0), else the plain or the gadget product.
+static void mod_matvec_device(const LsrRingModMatrix& m, uint64_t* d_y, const uint64_t* d_x, size_t batch, unsigned b, size_t digits, hipStream_t s,
+                              int32_t* d_status = nullptr, uint64_t bound_x = 0) {
     const LsrRingMod& h = *m.h;
     std::lock_guard<std::mutex> lock(h.mutex);
     const bool capturing = stream_is_capturing(s);
@@ -122,7 +230,8 @@ static void mod_matvec_device(const LsrRingModMatrix& m, uint64_t* d_y, const ui
         m.ready.wait(s);
         h.event.wait(s);
     }
-    mod_matvec_enqueue(m, d_y, d_x, batch, b, digits, s);
+    if (d_status) mod_matvec_bounded_enqueue(m, d_y, d_status, d_x, batch, bound_x, s);
+    else mod_matvec_enqueue(m, d_y, d_x, batch, b, digits, s);
     if (!capturing) h.event.record(s);
 }
 
@@ -251,6 +360,35 @@ int matvec_call(const char* where, const LsrRingModMatrix* mat, uint64_t* y, con
     });
 }
 
+// batch.h's refusals of the bounded product in its order
+int matvec_bounded_call(const char* where, const LsrRingModMatrix* mat, uint64_t* y, int32_t* status, const uint64_t* x, size_t batch, uint64_t bound_x,
+                        bool device, void* stream) noexcept {
+    if (!mat || !y || !status || !x) return lsr::abi_refuse(where, "NULL matrix, buffer or status");
+    const uint64_t half = mat->q >> 1;
+    if (bound_x > half)
+        return lsr::abi_refuse(where, "bound_x = " + std::to_string(bound_x) + " is above floor(q / 2) = " + std::to_string(half) + " (0 states none)");
+    if (batch == 0) return 0;
+    return lsr::abi_guarded(where, [&] {
+        const size_t n = mat->n, x_bytes = batch * mat->cols * n * 8, y_bytes = batch * mat->rows * n * 8, status_bytes = batch * sizeof(int32_t);
+        lsr::require_apart(y, y_bytes, x, x_bytes, "y overlaps x: the output must not share memory with the operand");
+        lsr::require_apart(status, status_bytes, x, x_bytes, "status overlaps x: the output must not share memory with the operand");
+        lsr::require_apart(status, status_bytes, y, y_bytes, "status overlaps y: the two outputs must not share memory");
+        lsr::require_device();
+        if (device) {
+            lsr::DeviceGuard guard(mat->device);
+            lsr::mod_matvec_device(*mat, y, x, batch, 0, 0, static_cast<hipStream_t>(stream), status, bound_x);
+            return;
+        }
+        const size_t x_words = mat->cols * n, y_words = mat->rows * n;
+        lsr::host_staged(*mat->h->prime[0], batch, lsr::staging_chunk(batch, x_words + y_words + 1),
+                         {lsr::staged_items(x, nullptr, x_words * 8), lsr::staged_items(nullptr, y, y_words * 8),
+                          lsr::staged_items(nullptr, status, sizeof(int32_t))},
+                         [&](const lsr::StagedChunk& k, hipStream_t s) {
+                             lsr::mod_matvec_device(*mat, k.lane<uint64_t>(1), k.lane<const uint64_t>(0), k.now, 0, 0, s, k.lane<int32_t>(2), bound_x);
+                         });
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -297,6 +435,14 @@ int lsr_ring_mod_matvec_gadget_batch(const LsrRingModMatrix* mat, uint64_t* y, c
 int lsr_ring_mod_matvec_gadget_batch_device(const LsrRingModMatrix* mat, uint64_t* d_y, const uint64_t* d_x, size_t batch, unsigned base_log2, size_t digits,
                                             void* stream) noexcept {
     return matvec_call("lsr_ring_mod_matvec_gadget_batch_device", mat, d_y, d_x, batch, true, base_log2, digits, true, stream);
+}
+int lsr_ring_mod_matvec_bounded_batch(const LsrRingModMatrix* mat, uint64_t* y, int32_t* status, const uint64_t* x, size_t batch,
+                                      uint64_t bound_x) noexcept {
+    return matvec_bounded_call("lsr_ring_mod_matvec_bounded_batch", mat, y, status, x, batch, bound_x, false, nullptr);
+}
+int lsr_ring_mod_matvec_bounded_batch_device(const LsrRingModMatrix* mat, uint64_t* d_y, int32_t* d_status, const uint64_t* d_x, size_t batch,
+                                             uint64_t bound_x, void* stream) noexcept {
+    return matvec_bounded_call("lsr_ring_mod_matvec_bounded_batch_device", mat, d_y, d_status, d_x, batch, bound_x, true, stream);
 }
 
 }  // extern "C"
