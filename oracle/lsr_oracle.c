@@ -660,14 +660,14 @@ static int parse(const oracle_lwe* c, const uint64_t* comm, size_t len, const ui
     return 1;
 }
 
-int oracle_lwe_verify(const oracle_lwe* c, const uint64_t* comm, size_t comm_len, const uint64_t* msg, size_t msg_len) {
-    if (!c || !comm || !msg) return -1;
+/* the opened polynomial w = v - INTT(<s_hat, NTT(u)>) mod q of a well-formed row, before any rounding: w_out[n] */
+int oracle_lwe_open(const oracle_lwe* c, const uint64_t* comm, size_t comm_len, uint64_t* w_out) {
+    if (!c || !comm || !w_out) return -1;
     const uint64_t *u, *v;
     if (!parse(c, comm, comm_len, &u, &v)) return -1;
     const uint32_t n = c->n, k = c->k;
     const uint64_t q = c->q;
-    if (msg_len > n) return 0;                                      /* commitment.cpp:219-221 */
-    uint64_t* w = (uint64_t*)malloc(sizeof(uint64_t) * n);
+    uint64_t* w = w_out;
     uint64_t* tmp = (uint64_t*)malloc(sizeof(uint64_t) * n);
     memcpy(w, v, sizeof(uint64_t) * n);
     fwd_core(c->ntt, w);
@@ -677,12 +677,23 @@ int oracle_lwe_verify(const oracle_lwe* c, const uint64_t* comm, size_t comm_len
         for (uint32_t x = 0; x < n; ++x) w[x] = (w[x] + q - oracle_mulmod(c->s_hat[(size_t)j * n + x], tmp[x], q)) % q;
     }
     inv_core(c->ntt, w);
+    free(tmp);
+    return 0;
+}
+
+int oracle_lwe_verify(const oracle_lwe* c, const uint64_t* comm, size_t comm_len, const uint64_t* msg, size_t msg_len) {
+    if (!c || !comm || !msg) return -1;
+    const uint32_t n = c->n;
+    const uint64_t q = c->q;
+    uint64_t* w = (uint64_t*)malloc(sizeof(uint64_t) * n);
+    if (oracle_lwe_open(c, comm, comm_len, w) != 0) { free(w); return -1; }
+    if (msg_len > n) { free(w); return 0; }                         /* commitment.cpp:219-221 */
     uint64_t diff = 0;
     for (size_t i = 0; i < msg_len; ++i) {
         uint64_t dec = (uint64_t)((((u128)w[i] * c->t) + (q >> 1)) / q) % c->t;
         diff |= dec ^ msg[i];                                       /* raw message word, commitment.cpp:224 */
     }
-    free(w); free(tmp);
+    free(w);
     return diff == 0 ? 1 : 0;
 }
 

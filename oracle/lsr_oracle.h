@@ -96,6 +96,8 @@ uint64_t    oracle_lwe_t(const oracle_lwe* c);
 size_t      oracle_lwe_commit_words(const oracle_lwe* c);       /* total words incl. data[0] */
 /* writes commitment words (data[0] = payload byte length) into out; 0 ok / -1 error */
 int  oracle_lwe_commit(const oracle_lwe* c, const uint64_t* msg, size_t msg_len, uint64_t seed, uint64_t* out);
+/* the opened polynomial w = v - INTT(<s_hat, NTT(u)>) mod q, before rounding, into w_out[n]; 0 ok / -1 malformed row */
+int  oracle_lwe_open(const oracle_lwe* c, const uint64_t* comm, size_t comm_len, uint64_t* w_out);
 int  oracle_lwe_verify(const oracle_lwe* c, const uint64_t* comm, size_t comm_len, const uint64_t* msg, size_t msg_len);
 int  oracle_lwe_linear_combine(const oracle_lwe* c, const uint64_t* const* comms, const size_t* comm_lens,
                                const uint64_t* coeffs, size_t count, uint64_t* out);

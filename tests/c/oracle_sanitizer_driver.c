@@ -51,6 +51,8 @@ int main(void) {
     CHECK(oracle_lwe_linear_combine(c, both, lens, cf, 2, c3) == 0);
     CHECK(oracle_lwe_verify(c, c3, w, comb, 4) == 1);
     CHECK(oracle_lwe_verify(c, c3, 3, comb, 4) == -1);
+    uint64_t opened[256];
+    CHECK(oracle_lwe_open(c, c3, w, opened) == 0 && oracle_lwe_open(c, c3, 3, opened) == -1 && oracle_lwe_open(c, c3, w, NULL) == -1);
     uint64_t long_msg[300];
     for (int i = 0; i < 300; ++i) long_msg[i] = (uint64_t)i;
     CHECK(oracle_lwe_commit(c, long_msg, 300, 5, c1) == 0 && oracle_lwe_verify(c, c1, w, long_msg, 256) == 1 && oracle_lwe_verify(c, c1, w, long_msg, 300) == 0);

@@ -45,6 +45,7 @@ class Oracle:
         L.oracle_lwe_t.restype = u64; L.oracle_lwe_t.argtypes = [vp]
         L.oracle_lwe_commit_words.restype = sz; L.oracle_lwe_commit_words.argtypes = [vp]
         L.oracle_lwe_commit.restype = ci; L.oracle_lwe_commit.argtypes = [vp, vp, sz, u64, vp]
+        L.oracle_lwe_open.restype = ci; L.oracle_lwe_open.argtypes = [vp, vp, sz, vp]
         L.oracle_lwe_verify.restype = ci; L.oracle_lwe_verify.argtypes = [vp, vp, sz, vp, sz]
         L.oracle_lwe_linear_combine.restype = ci; L.oracle_lwe_linear_combine.argtypes = [vp, vp, vp, vp, sz, vp]
         L.oracle_lwe_public_matrix.argtypes = [vp, vp]
@@ -165,6 +166,15 @@ class Oracle:
         c = np.ascontiguousarray(comm_words, dtype=np.uint64)
         m = np.array([int(x) for x in msg], dtype=np.uint64)
         return self.L.oracle_lwe_verify(h, c.ctypes.data, c.size, m.ctypes.data, m.size)
+
+    def lwe_open(self, q, n, k, sigma, key_seed, comm_words):
+        """-> (rc, w [n]): w = v - INTT(<s_hat, NTT(u)>) mod q of a well-formed row (rc 0); rc -1 and zeros for a malformed one"""
+        h = self.lwe_handle(q, n, k, sigma, key_seed)
+        assert h
+        c = np.ascontiguousarray(comm_words, dtype=np.uint64)
+        w = np.zeros(n, dtype=np.uint64)
+        rc = self.L.oracle_lwe_open(h, c.ctypes.data, c.size, w.ctypes.data)
+        return rc, w
 
     def lwe_linear_combine(self, q, n, k, sigma, key_seed, comms, coeffs):
         h = self.lwe_handle(q, n, k, sigma, key_seed)

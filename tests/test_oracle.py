@@ -230,6 +230,45 @@ def test_verify_opening(oracle):
     assert oracle.lwe_verify(comm_words=c[:100], msg=msg, **P) == -1
 
 
+def test_open_hands_out_the_polynomial_verify_rounds(oracle):
+    """oracle_lwe_open at the odd rank (256, 3): w = v - <s, u> decodes, through the big-integer model of tests/decode_model.py, to the
+    embedded message in every slot and to 0 beyond it; oracle_lwe_verify (which goes through it) agrees; a malformed row gives -1."""
+    import decode_model
+    q, n, k, key = Q44, 256, 3, 31
+    t = oracle.L.oracle_lwe_t(oracle.lwe_handle(q, n, k, 3.19, key))
+    msg = [2**63 + 5, t, 2**64 - 1, 0, t - 1, 12345, 1]
+    c = oracle.lwe_commit(q, n, k, 3.19, key, msg, 99)
+    rc, w = oracle.lwe_open(q, n, k, 3.19, key, c)
+    assert rc == 0 and w.shape == (n,) and int(w.max()) < q
+    model = [decode_model.slot_and_rho(int(x), t, q) for x in w]
+    slots = [s for s, _ in model]
+    embedded = [m % t for m in msg]
+    assert slots == embedded + [0] * (n - len(msg))
+    assert 0 < max(r for _, r in model) < q // 2                              # a fresh row has noise, and headroom
+    assert decode_model.noise_bits(w, t, q) == max(r for _, r in model).bit_length()
+    assert oracle.lwe_verify(q, n, k, 3.19, key, c, embedded) == 1
+    assert oracle.lwe_verify(q, n, k, 3.19, key, c, slots) == 1               # every slot
+    assert oracle.lwe_verify(q, n, k, 3.19, key, c, slots[:n - 1] + [1]) == 0
+    # the two other ranks of the same key open their own rows only: the sum over all k polynomials of u is in w
+    c1 = oracle.lwe_commit(q, n, 1, 3.19, key, msg, 99)
+    assert [decode_model.slot_and_rho(int(x), t, q)[0] for x in oracle.lwe_open(q, n, 1, 3.19, key, c1)[1]] == slots
+    dropped = c.copy()
+    dropped[5 + 2 * n:5 + 3 * n] = 0                                          # without u_2 the row no longer decodes
+    rc, w2 = oracle.lwe_open(q, n, k, 3.19, key, dropped)
+    assert rc == 0 and [decode_model.slot_and_rho(int(x), t, q)[0] for x in w2] != slots
+    # malformed rows: header, length, a word >= q in the last u polynomial and in v
+    for bad in (_changed(c, 1, int(c[1]) ^ 1), _changed(c, 0, 0), _changed(c, 5 + k * n - 1, q), _changed(c, c.size - 1, q), c[:100]):
+        rc, w3 = oracle.lwe_open(q, n, k, 3.19, key, bad)
+        assert rc == -1 and not w3.any()
+        assert oracle.lwe_verify(q, n, k, 3.19, key, bad, embedded) == -1
+
+
+def _changed(row, index, value):
+    out = row.copy()
+    out[index] = value
+    return out
+
+
 def test_linear_combination(oracle):
     m1, m2 = [1, 2, 3, 4], [5, 6, 7, 8]
     c1 = oracle.lwe_commit(msg=m1, seed=1, **P)

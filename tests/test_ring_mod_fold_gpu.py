@@ -254,6 +254,75 @@ def test_a_violation_in_the_last_group_zeroes_the_whole_output(pkg):
         assert _same(_device_fold(torch, ring, v, bad, terms, 0, h - 1), want)
 
 
+# ---- 5b. operands and outputs off the vector alignment ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["top", "P5"])
+@pytest.mark.parametrize("flavour", ["f64", "u64"])
+def test_operands_and_outputs_off_the_vector_alignment(pkg, lib, flavour, name):
+    """v, p and out start one word into their allocations: 8-byte but not 16-byte aligned, where the host takes the one-word-per-lane
+    variants of the challenge lift and of the reduce (the tile kernel reads v where it lies).  n = 64, width 2, 3 outputs of 3 terms:
+    under `top` with bound_p = floor(q/2) - 1 the capacity is 1, so every term is its own group — a plain and two accumulating
+    reduces; under P5 with short operands the call is one group.  Output 1 holds a challenge word one over its bound and output 2 a
+    word >= q, each in its LAST term: both come back as zeros, whatever the earlier groups wrote, by the one-word zero-fill.  The word
+    before out, the word behind it and the words behind status stay as they were, and so do the operands."""
+    import torch
+    n, width, outputs, terms = 64, 2, 3, 3
+    if name == "top":
+        q = model.largest_admissible(n)
+        bound_v, bound_p = 0, q // 2 - 1
+        assert fold_model.groups(q, n, terms, bound_v, bound_p) == [1, 1, 1]
+    else:
+        q, bound_v, bound_p = P5, 1 << 20, 2
+        assert fold_model.groups(q, n, terms, bound_v, bound_p) == [3]
+    rng = np.random.default_rng(814 + (name == "top"))
+    f64 = flavour == "f64"
+    lib.lsr_set_arith_mode(0 if f64 else 1)
+    try:
+        ring = pkg.RingMod(q, n, device=0)
+    finally:
+        lib.lsr_set_arith_mode(0)
+
+    def off_alignment(x):
+        d = torch.full((x.size + 2,), SENTINEL, dtype=torch.int64, device="cuda")
+        d[1:1 + x.size].copy_(_dev(torch, x).reshape(-1))
+        assert (d.data_ptr() + 8) % 16 == 8
+        return d
+
+    def run(v, p, stride):
+        d_v, d_p = off_alignment(v), off_alignment(p)
+        words = outputs * width * n
+        d_out = torch.full((words + 3,), SENTINEL, dtype=torch.int64, device="cuda")
+        d_status = torch.full((outputs + 2,), STATUS_SENTINEL, dtype=torch.int32, device="cuda")
+        assert (d_out.data_ptr() + 8) % 16 == 8
+        ring.fold_device(d_out.data_ptr() + 8, d_status.data_ptr(), d_v.data_ptr() + 8, d_p.data_ptr() + 8, outputs, terms, stride, width, bound_v, bound_p,
+                         stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        out, status = _host(d_out), d_status.cpu().numpy()
+        assert out[0] == SENTINEL and (out[1 + words:] == SENTINEL).all(), "the words around out were written"
+        assert status[outputs:].tolist() == [STATUS_SENTINEL] * 2, "the words behind status were written"
+        for d, x in ((d_v, v), (d_p, p)):
+            assert np.array_equal(_host(d)[1:-1], x.reshape(-1)) and _host(d)[0] == SENTINEL == _host(d)[-1], "an operand was written"
+        return out[1:1 + words].reshape(outputs, width, n), status[:outputs]
+
+    with ring:
+        assert ring.prime_context(0).uses_f64 == f64 == ring.prime_context(1).uses_f64
+        for stride in (terms, 0, 1):
+            vectors = _vectors(outputs, terms, stride)
+            v = _short(rng, q, (vectors, width, n), bound_v) if bound_v else model.planted(rng, q, (vectors, width, n), {0: q // 2})
+            p = _short(rng, q, (outputs, terms, n), bound_p)
+            p[0, 0, 0], p[2, terms - 1, n - 1] = bound_p, q - bound_p                     # the bound met from both sides
+            want = _model(v, p, q, stride, bound_v, bound_p)
+            assert want[1].tolist() == [1, 1, 1] and all(want[0][j].any() for j in range(outputs))
+            assert _same(run(v, p, stride), want), (name, flavour, stride)
+        # (stride 1) output 1: its last challenge one over the bound; output 2: a word >= q in the last vector it reads
+        bad_v, bad_p = v.copy(), p.copy()
+        bad_p[1, terms - 1, n - 1] = q - bound_p - 1
+        bad_v[2 + terms - 1, width - 1, n - 1] = q
+        want = _model(bad_v, bad_p, q, 1, bound_v, bound_p)
+        got = run(bad_v, bad_p, 1)
+        assert want[1].tolist() == [1, 0, -1] and _same(got, want), (name, flavour)
+        assert got[0][0].any() and not got[0][1:].any()
+
+
 # ---- 6. chunks ---------------------------------------------------------------------------------------------------------------------
 def test_one_output_past_every_chunk_limit(pkg):
     """The limits of lsr_ring_mod_fold.hip, each crossed by one output or one component:

@@ -303,6 +303,77 @@ def test_every_tile_size_and_both_flavours(pkg, lib, logn):
                     assert np.array_equal(y, _gated(plain, status)), (name, j)
 
 
+# ---- 7b. operands and outputs off the vector alignment ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [64, 512])
+@pytest.mark.parametrize("flavour", ["f64", "u64"])
+def test_operands_and_outputs_off_the_vector_alignment(pkg, lib, flavour, n):
+    """x and y start one word into their allocations: 8-byte but not 16-byte aligned, where the host takes the one-word-per-lane
+    variants of the check pass and of the reduces (the tile kernels read x where it lies).  q is the largest admissible modulus at
+    this n: within floor(q/2) / 2 two columns are a group, so three columns are a plain and an accumulating gated reduce — behind a
+    check pass of its own at n = 64, with the check in the tile at n = 512.  Vector 1 holds a word one over the bound and vector 2 a
+    word >= q, both in the last column, which the second group alone reads: they come back as zeros by the one-word zero-fill.  The
+    plain product of the same matrix takes its columns one at a time (three reduces, two accumulating), the gadget product in one
+    group.  The word before y, the word behind it and the words behind status stay as they were, and so does x."""
+    import torch
+    import ring_mod_matvec_model as plain_model
+    rows, cols, batch, base_log2, digits = 3, 3, 4, 14, 3
+    q = mod.largest_admissible(n)
+    bound = q // 2 // 2
+    assert model.groups(q, n, cols, bound) == [2, 1] and model.groups(q, n, cols) == [1, 1, 1] == [mod.capacity(q, n)] * cols
+    assert plain_model.capacity_bounded(q, n, 1 << (base_log2 - 1)) >= cols
+    rng = np.random.default_rng(817 + n)
+    lib.lsr_set_arith_mode(0 if flavour == "f64" else 1)
+    try:
+        ring = pkg.RingMod(q, n, device=0)
+    finally:
+        lib.lsr_set_arith_mode(0)
+
+    def run(call, x, with_status):
+        d_x = torch.full((x.size + 2,), SENTINEL, dtype=torch.int64, device="cuda")
+        d_x[1:1 + x.size].copy_(_dev(torch, x).reshape(-1))
+        words = batch * rows * n
+        d_y = torch.full((words + 3,), SENTINEL, dtype=torch.int64, device="cuda")
+        d_status = torch.full((batch + 2,), STATUS_SENTINEL, dtype=torch.int32, device="cuda")
+        assert (d_x.data_ptr() + 8) % 16 == 8 and (d_y.data_ptr() + 8) % 16 == 8
+        call(d_y.data_ptr() + 8, d_status.data_ptr(), d_x.data_ptr() + 8)
+        torch.cuda.synchronize()
+        y, status = _host(d_y), d_status.cpu().numpy()
+        assert y[0] == SENTINEL and (y[1 + words:] == SENTINEL).all(), "the words around y were written"
+        assert status[batch if with_status else 0:].tolist() == [STATUS_SENTINEL] * (2 if with_status else batch + 2), "status was written past the call's"
+        assert np.array_equal(_host(d_x)[1:-1], x.reshape(-1)) and _host(d_x)[0] == SENTINEL == _host(d_x)[-1], "x was written"
+        return y[1:1 + words].reshape(batch, rows, n), status[:batch]
+
+    with ring:
+        assert ring.prime_context(0).uses_f64 == (flavour == "f64") == ring.prime_context(1).uses_f64
+        m = _random(rng, q, (rows, cols, n))
+        with ring.matrix(m) as mat:
+            s = _stream(torch)
+            x = _short(rng, q, (batch, cols, n), bound)
+            x[0, 0, :], x[3, cols - 1, :] = bound, q - bound                                  # whole polynomials at the bound
+            want = model.matvec_bounded(m, x, q, bound)
+            assert want[1].tolist() == [1] * batch and all(want[0][j].any() for j in range(batch))
+            assert _same(run(lambda y, st, dx: mat.matvec_bounded_device(y, st, dx, batch, bound, stream=s), x, True), want)
+            bad = x.copy()
+            bad[1, cols - 1, n - 1], bad[2, cols - 1, n - 1] = bound + 1, q
+            want = model.matvec_bounded(m, bad, q, bound)
+            got = run(lambda y, st, dx: mat.matvec_bounded_device(y, st, dx, batch, bound, stream=s), bad, True)
+            assert want[1].tolist() == [1, 0, -1, 1] and _same(got, want)
+            assert not got[0][1:3].any() and got[0][0].any() and got[0][3].any()
+            # no bound stated: three groups of one column, and only -1 can occur
+            want = model.matvec_bounded(m, bad, q)
+            got = run(lambda y, st, dx: mat.matvec_bounded_device(y, st, dx, batch, 0, stream=s), bad, True)
+            assert want[1].tolist() == [1, 1, -1, 1] and _same(got, want) and not got[0][2].any()
+            # the plain and the gadget product of the same matrix
+            full = _random(rng, q, (batch, cols, n))
+            full[0, 0, :], full[1, 0, :] = q // 2, q // 2 + 1
+            got = run(lambda y, st, dx: mat.matvec_device(y, dx, batch, stream=s), full, False)
+            assert np.array_equal(got[0], plain_model.matvec(m, full, q))
+            narrow = _random(rng, q, (batch, cols // digits, n))
+            narrow[0, 0, :3] = [q // 2, q // 2 + 1, q - 1]
+            got = run(lambda y, st, dx: mat.matvec_gadget_device(y, dx, batch, base_log2, digits, stream=s), narrow, False)
+            assert np.array_equal(got[0], plain_model.matvec_gadget(m, narrow, q, base_log2, digits))
+
+
 # ---- 8. capture ------------------------------------------------------------------------------------------------------------------------
 def test_graph_capture_straight_after_create(pkg):
     """no eager bounded call first: the flag words exist since the handle's create.  Three groups inside the graph; two replays on

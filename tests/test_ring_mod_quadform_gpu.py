@@ -308,6 +308,71 @@ def test_bounds_are_verified_per_family_across_groups(pkg, flavour):
         assert _same(_device(torch, ring, clean_g, clean_c, offdiag, bound_g, bound_c), clean)
 
 
+# ---- 5b. operands and outputs off the vector alignment ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("flavour", FLAVOURS)
+def test_operands_and_outputs_off_the_vector_alignment(pkg, flavour):
+    """g, c and out start one word into their allocations: 8-byte but not 16-byte aligned, where the host takes the one-word-per-lane
+    variants of the lift and of the reduce.  28 pairs against a capacity of 7 are four groups: a check of the whole g without stores,
+    lifts of g without the check, a plain and three accumulating reduces; r = 2 is one group, the check riding in the lift.  Family 1
+    holds a word over bound_g in its last pair, family 2 a word >= q: both come back as zeros, whatever the earlier groups wrote, by
+    the one-word zero-fill.  The word before out, the word behind it and the words behind status stay as they were, and so do the
+    operands."""
+    import torch
+    q, n, r, batch = P5, 64, 7, 4
+    h = q // 2
+    bound_g, bound_c = h - 1, GROUP_BOUND_C
+    sentinel, status_sentinel = 0x5A5A5A5A5A5A5A5A, 7
+    assert model.groups(q, n, r, 1, bound_g, bound_c) == [7, 7, 7, 7] and model.groups(q, n, 2, 2, bound_g, bound_c) == [3]
+    rng = np.random.default_rng(815)
+
+    def off_alignment(x):
+        d = torch.full((x.size + 2,), sentinel, dtype=torch.int64, device="cuda")
+        d[1:1 + x.size].copy_(_dev(torch, x).reshape(-1))
+        assert (d.data_ptr() + 8) % 16 == 8
+        return d
+
+    def run(ring, g, c, offdiag):
+        d_g, d_c = off_alignment(g), off_alignment(c)
+        d_out = torch.full((batch * n + 3,), sentinel, dtype=torch.int64, device="cuda")
+        d_status = torch.full((batch + 2,), status_sentinel, dtype=torch.int32, device="cuda")
+        assert (d_out.data_ptr() + 8) % 16 == 8
+        ring.quadform_device(d_out.data_ptr() + 8, d_status.data_ptr(), d_g.data_ptr() + 8, d_c.data_ptr() + 8, batch, c.shape[-2],
+                             1 if c.ndim == 2 else batch, offdiag, bound_g, bound_c, stream=_stream(torch))
+        torch.cuda.synchronize()
+        out, status = _host(d_out), d_status.cpu().numpy()
+        assert out[0] == sentinel and (out[1 + batch * n:] == sentinel).all(), "the words around out were written"
+        assert status[batch:].tolist() == [status_sentinel] * 2, "the words behind status were written"
+        for d, x in ((d_g, g), (d_c, c)):
+            assert np.array_equal(_host(d)[1:-1], x.reshape(-1)) and _host(d)[0] == sentinel == _host(d)[-1], "an operand was written"
+        return out[1:1 + batch * n].reshape(batch, n), status[:batch]
+
+    def check(ring, g, c, offdiag, statuses):
+        want = _want(g, c, q, offdiag, bound_g, bound_c)
+        assert want[1].tolist() == statuses
+        got = run(ring, g, c, offdiag)
+        assert _same(got, want)
+        for j, st in enumerate(statuses):
+            assert bool(got[0][j].any()) == (st == 1), j
+
+    with _ring(pkg, q, n, flavour) as ring:
+        g, c = _bounded(rng, q, (batch, 28, n), bound_g), _bounded(rng, q, (batch, r, n), bound_c)
+        check(ring, g, c, 1, [1, 1, 1, 1])
+        check(ring, g, c[0], 1, [1, 1, 1, 1])                                   # a shared c
+        bad_g, bad_c = g.copy(), c.copy()
+        bad_g[1, 27, n - 1], bad_c[2, r - 1, 0] = h, q                          # the last group's last pair; a challenge word >= q
+        check(ring, bad_g, bad_c, 1, [1, 0, -1, 1])
+        bad_g[2, 27, 0] = q + 5
+        check(ring, bad_g, c[0], 1, [1, 0, -1, 1])                              # a shared c: the families' own g words
+        shared = c[0].copy()
+        shared[r - 1, n - 1] = bound_c + 1                                      # ... and a shared word over its bound gates them all
+        check(ring, g, shared, 1, [0, 0, 0, 0])
+        # r = 2 with offdiag 2: three pairs in one group
+        g2, c2 = _bounded(rng, q, (batch, 3, n), bound_g), _bounded(rng, q, (batch, 2, n), bound_c)
+        check(ring, g2, c2, 2, [1, 1, 1, 1])
+        g2[3, 2, n - 1], c2[0, 0, n - 1] = q - h, 2**64 - 1
+        check(ring, g2, c2, 2, [-1, 1, 1, 0])
+
+
 # ---- 6. refusals that read the handle -----------------------------------------------------------------------------------------------
 def test_refusals_on_a_real_handle(pkg):
     import torch
