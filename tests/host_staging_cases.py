@@ -3,7 +3,10 @@ process under the default staging bound (one chunk) and in a fresh child under L
 
 At 1 MiB the bound is 131072 words.  Each case states the chunk its call's formula gives there and is sized for at
 least three chunks with a ragged last one; where a call has key or weight groups, `components` does not divide the chunk, so a group
-straddles a chunk boundary; where it has a status, a refused item sits inside a later chunk, not at its start."""
+straddles a chunk boundary; where it has a status, a refused item sits inside a later chunk, not at its start.
+
+The cases from `gadget` on (and `matvec`) also leave their operands in INPUTS: the test's own process holds their one-chunk results to
+the integer models (host_staging_refs.py); the child never reads it."""
 import numpy as np
 
 Q14 = 12289                    # n = 64 challenges
@@ -11,6 +14,15 @@ Q_NORTH = 17592169062401       # 44-bit NTT prime for n <= 4096 (FP64 kernels)
 Q60 = 1152921504606584833      # 60-bit NTT prime (u64 Shoup kernels)
 GOLD = 18446744069414584321    # CyclicNtt's modulus (Goldilocks kernels)
 Q36 = (1 << 36) + 31           # RingMod: any modulus (odd, not NTT-friendly; n = 1024 carries it)
+GADGET_BASE = {Q_NORTH: 12, Q60: 16, Q36: 10}      # base_log2 whose smallest admissible digit count under q is GADGET_DIGITS
+GADGET_DIGITS = 4
+UINT64_MAX = 2**64 - 1
+
+INPUTS = {}                    # case name -> {key: operands} of the case's last run in this process
+
+
+def _record(case, key, **operands):
+    INPUTS.setdefault(case, {})[key] = operands
 
 
 def _rand(rng, q, shape):
@@ -288,14 +300,184 @@ def ring_dot(pkg):
 def matvec(pkg):
     """a 2 x 3 matrix at n = 1024: chunk 131072 / (3072 + 2048) = 25, batch 60 = 25 + 25 + 10"""
     out, rng = {}, np.random.default_rng(19)
-    for name, ctx, q in _contexts(pkg, 1024, ("f64", "u64")):
-        mat = ctx.ring_matrix(_rand(rng, q, (2, 3, 1024)))
-        out[name] = mat.matvec(_rand(rng, q, (60, 3, 1024)))
+    for name, ctx, q in _contexts(pkg, 1024, ("f64", "u64", "gold")):
+        m, x = _rand(rng, q, (2, 3, 1024)), _rand(rng, q, (60, 3, 1024))
+        mat = ctx.ring_matrix(m)
+        out[name] = mat.matvec(x)
+        _record("matvec", name, q=q, m=m, x=x, omega=ctx.omega if name == "gold" else 0)
         mat.close()
         ctx.close()
     return out
 
 
+def _gadget_base(pkg, q):
+    b = GADGET_BASE[q]
+    assert pkg.ring_gadget_min_digits(q, b) == GADGET_DIGITS
+    return b
+
+
+def gadget(pkg):
+    """n = 1024, 4 digits.  Decompose and recompose: chunk 131072 / (4096 + 1024) = 25, count 60 = 25 + 25 + 10.  linf: chunk 131072 /
+    (1024 + 1) = 127, count 300 = 127 + 127 + 46; element 260 holds a word >= q (reported as 2^64 - 1)"""
+    out, rng = {}, np.random.default_rng(20)
+    for name, ctx, q in _contexts(pkg, 1024, ("f64", "u64")):
+        b = _gadget_base(pkg, q)
+        x, z, y = _rand(rng, q, (60, 1024)), _rand(rng, q, (60, GADGET_DIGITS, 1024)), _rand(rng, q, (300, 1024))
+        y[260, 5] = q
+        digits = ctx.ring_decompose(x, b, GADGET_DIGITS)
+        assert np.array_equal(ctx.ring_recompose(digits, b), x)
+        linf = ctx.ring_linf(y)
+        assert np.flatnonzero(linf == np.uint64(UINT64_MAX)).tolist() == [260]
+        out[name + " digits"], out[name + " recomposed"], out[name + " linf"] = digits, ctx.ring_recompose(z, b), linf
+        _record("gadget", name, q=q, b=b, x=x, z=z, y=y)
+        ctx.close()
+    return out
+
+
+def matvec_gadget(pkg):
+    """a 2 x (2 * 4) matrix at n = 1024 against x of 2 columns: chunk 131072 / (2048 + 2048) = 32, batch 70 = 32 + 32 + 6"""
+    out, rng = {}, np.random.default_rng(21)
+    for name, ctx, q in _contexts(pkg, 1024, ("f64", "u64")):
+        b = _gadget_base(pkg, q)
+        m, x = _rand(rng, q, (2, 2 * GADGET_DIGITS, 1024)), _rand(rng, q, (70, 2, 1024))
+        mat = ctx.ring_matrix(m)
+        out[name] = mat.matvec_gadget(x, b, GADGET_DIGITS)
+        _record("matvec_gadget", name, q=q, b=b, m=m, x=x)
+        mat.close()
+        ctx.close()
+    return out
+
+
+def automorphism(pkg):
+    """n = 1024: chunk 131072 / (1024 + 1024) = 64, count 150 = 64 + 64 + 22; g = 5 and the conjugation g = N - 1 (N = 2 n; N = n on
+    the cyclic ring)"""
+    out, rng = {}, np.random.default_rng(22)
+    for name, ctx, q in _contexts(pkg, 1024, ("f64", "gold")):
+        assert ctx.galois_conjugation == (1023 if name == "gold" else 2047)
+        x = _rand(rng, q, (150, 1024))
+        for g in (5, ctx.galois_conjugation):
+            out[f"{name} g {g}"] = ctx.ring_automorphism(x, g)
+        _record("automorphism", name, q=q, x=x, cyclic=name == "gold")
+        ctx.close()
+    return out
+
+
+def dot_galois(pkg):
+    """n = 1024, g = 2 n - 1: 128 polynomials per operand; terms 4: chunk 32, batch 100 = 3 * 32 + 4; terms 130: one output at a time
+    in groups of 128 + 2 terms, the sums waiting on the device in between; each with b per output and with one shared b row (which
+    goes up with chunk 0 only while all its terms fit)"""
+    out, rng = {}, np.random.default_rng(23)
+    for name, ctx, q in _contexts(pkg, 1024, ("f64", "u64")):
+        g = ctx.galois_conjugation
+        for tag, batch, terms in (("", 100, 4), (" groups", 3, 130)):
+            a, b = _rand(rng, q, (batch, terms, 1024)), _rand(rng, q, (batch, terms, 1024))
+            twisted = ctx.ring_automorphism(a, g)
+            for form, rows in ((" each", b), (" shared", b[1])):
+                got = ctx.ring_dot_galois(a, rows, g)
+                assert np.array_equal(got, ctx.ring_dot(twisted, rows)), (name, tag, form)
+                out[name + tag + form] = got
+            _record("dot_galois", name + tag, q=q, g=g, a=a, b=b)
+        ctx.close()
+    return out
+
+
+def opnorm(pkg):
+    """n = 64: chunk 131072 / (64 + 2) = 1985, count 4100 = 1985 + 1985 + 130.  The inputs are first candidates (T = 0) of ring_challenge
+    at four weight pairs, interleaved, so that the norms vary inside every chunk."""
+    out, rng = {}, np.random.default_rng(24)
+    keys = _keys(rng, 4)
+    for name, ctx in (("negacyclic", pkg.NttContext(Q14, 64, device=0)), ("cyclic", pkg.CyclicNtt(64))):
+        parts = [ctx.ring_challenge(1025, k1, k2, 0, keys[i])[0] for i, (k1, k2) in enumerate(((31, 10), (16, 4), (8, 0), (40, 20)))]
+        x = np.ascontiguousarray(np.stack(parts, axis=1).reshape(4100, 64))
+        norms = ctx.ring_opnorm(x)
+        assert len(set(norms[1985:].tolist())) > 2, "the norms must vary past the first chunk"
+        out[name] = _wide(norms)
+        _record("opnorm", name, q=GOLD if name == "cyclic" else Q14, x=x, cyclic=name == "cyclic")
+        ctx.close()
+    return out
+
+
+def _ring_mod_products(ring, rng, q, n, case, shapes, g):
+    """dot and ring_dot_galois of a RingMod at every (tag, batch, terms) of `shapes`, with b per output and with one shared b row"""
+    out = {}
+    for tag, batch, terms in shapes:
+        a, b = _rand(rng, q, (batch, terms, n)), _rand(rng, q, (batch, terms, n))
+        for form, rows in ((" each", b), (" shared", b[1])):
+            out["dot" + tag + form], out["galois" + tag + form] = ring.dot(a, rows), ring.ring_dot_galois(a, rows, g)
+        _record(case, "dot" + tag, q=q, g=g, a=a, b=b)
+    return out
+
+
+def ring_mod_mul_dot(pkg):
+    """RingMod(Q36, 1024): 128 polynomials per staged operand.  mul: chunk 128, batch 300 = 128 + 128 + 44.  dot and ring_dot_galois
+    (g = 2 n - 1): terms 4: chunk 32, batch 100 = 3 * 32 + 4; terms 130: one output at a time in staged groups of 128 + 2 terms, every
+    group after the first accumulated into c (and the group of 128 split again at max_terms = 127 on the device)"""
+    rng = np.random.default_rng(25)
+    with pkg.RingMod(Q36, 1024, device=0) as ring:
+        assert ring.max_terms == 127
+        a, b = _rand(rng, Q36, (300, 1024)), _rand(rng, Q36, (300, 1024))
+        out = {"mul each": ring.mul(a, b), "mul shared": ring.mul(a, b[3])}
+        _record("ring_mod_mul_dot", "mul", q=Q36, a=a, b=b)
+        out.update(_ring_mod_products(ring, rng, Q36, 1024, "ring_mod_mul_dot", (("", 100, 4), (" groups", 3, 130)), 2047))
+    return out
+
+
+def ring_mod_nested_groups(pkg):
+    """RingMod(Q36, 4096), terms 70, batch 2: an operand holds 32 polynomials, so each output goes in staged groups of 32 + 32 + 6
+    terms, and max_terms = 31 splits each group of 32 again into 31 + 1 inside ring_mod_dot_enqueue: the two groupings nest and the
+    partial sums wait in c across both"""
+    rng = np.random.default_rng(26)
+    with pkg.RingMod(Q36, 4096, device=0) as ring:
+        assert 2 <= ring.max_terms < 32 and 32 % ring.max_terms != 0
+        return _ring_mod_products(ring, rng, Q36, 4096, "ring_mod_nested_groups", ((" nested", 2, 70),), 8191)
+
+
+def ring_mod_matvec(pkg):
+    """RingMod(Q36, 1024).  A 2 x 3 matrix: chunk 131072 / (3072 + 2048) = 25, batch 60 = 25 + 25 + 10.  The gadget product of a
+    2 x (2 * 4) matrix with x of 2 columns: chunk 131072 / (2048 + 2048) = 32, batch 70 = 32 + 32 + 6"""
+    out, rng = {}, np.random.default_rng(27)
+    b = _gadget_base(pkg, Q36)
+    with pkg.RingMod(Q36, 1024, device=0) as ring:
+        m, x = _rand(rng, Q36, (2, 3, 1024)), _rand(rng, Q36, (60, 3, 1024))
+        with ring.matrix(m) as mat:
+            out["plain"] = mat.matvec(x)
+        _record("ring_mod_matvec", "plain", q=Q36, m=m, x=x)
+        m, x = _rand(rng, Q36, (2, 2 * GADGET_DIGITS, 1024)), _rand(rng, Q36, (70, 2, 1024))
+        with ring.matrix(m) as mat:
+            out["gadget"] = mat.matvec_gadget(x, b, GADGET_DIGITS)
+        _record("ring_mod_matvec", "gadget", q=Q36, b=b, m=m, x=x)
+    return out
+
+
+def ring_mod_coeff(pkg):
+    """the coefficient context of RingMod(2^32, 1024).  l2sq, width 4: chunk 131072 / (4096 + 2) = 31, count 70 = 31 + 31 + 8; vector
+    47 holds a word >= q (2^128 - 1).  Pack, 10 bits: chunk 131072 / (1024 + 160) = 110, count 250 = 110 + 110 + 30; element 170 holds
+    a coefficient of 600 > 511 (status 0), element 240 a word >= q (status -1).  Unpack, RESIDUE at 33 bits: chunk 131072 / (528 +
+    1024) = 84, count 250 = 84 + 84 + 82; element 200 holds the field 2^32 >= q (status 0)."""
+    q, rng = 1 << 32, np.random.default_rng(28)
+    with pkg.RingMod(q, 1024, device=0) as ring:
+        ctx = ring.coeff_context()
+        v = _rand(rng, q, (70, 4, 1024))
+        v[47, 2, 100] = q
+        norms = ctx.ring_l2sq(v)
+        assert [j for j, s in enumerate(norms.tolist()) if s == 2**128 - 1] == [47]
+        x = _small(rng, q, (250, 1024), 500)
+        x[170, 7] = 600
+        x[240, 9] = q
+        words, status = ctx.ring_pack(x, 10)
+        assert status.tolist() == [1] * 170 + [0] + [1] * 69 + [-1] + [1] * 9
+        back, back_status = ctx.ring_unpack(words, 10)
+        y = _rand(rng, q, (250, 1024))
+        residues, residue_status = ctx.ring_pack(y, 33, pkg.RING_PACK_RESIDUE)
+        residues[200, 0] |= np.uint64(1 << 32)
+        unpacked, unpacked_status = ctx.ring_unpack(residues, 33, pkg.RING_PACK_RESIDUE)
+        assert unpacked_status.tolist() == [1] * 200 + [0] + [1] * 49
+    _record("ring_mod_coeff", "all", q=q, v=v, x=x, y=y)
+    return {"l2sq": _wide(norms), "words": words, "status": status, "back": back, "back status": back_status, "residues": residues,
+            "residue status": residue_status, "unpacked": unpacked, "unpacked status": unpacked_status}
+
+
 CASES = {f.__name__: f for f in (sample, sample_small, challenge, pack, pack_small, l2sq, project, project_matrix, project_adjoint, scalar_combine,
                                  scalar_combine_term_groups, ring_mul, ring_gram, ring_quadform, ring_mod_gram, ring_fold, ring_fold_term_groups,
-                                 ring_dot, matvec)}
+                                 ring_dot, matvec, gadget, matvec_gadget, automorphism, dot_galois, opnorm, ring_mod_mul_dot,
+                                 ring_mod_nested_groups, ring_mod_matvec, ring_mod_coeff)}
