@@ -970,6 +970,7 @@ class RingModMatrix:
     def __init__(self, ring, handle):
         self._ring, self._lib, self._h, self.n = ring, ring._lib, handle, ring.n
         ring._matrices.add(self)
+        ring._matrix_handles.add(handle)
 
     @property
     def handle(self):
@@ -1041,10 +1042,15 @@ class RingModMatrix:
                "lsr_ring_mod_matvec_bounded_batch_device")
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.lsr_ring_mod_matrix_free(self._h)     # (reads the RingMod's handle: still open, see RingMod.close)
+        handle = getattr(self, "_h", None)
+        if handle:
             self._h = None
             self._ring._matrices.discard(self)
+            # lsr_ring_mod_matrix_free reads the RingMod's handle.  A RingMod closed first has freed this matrix itself and emptied
+            # the set (RingMod.close): then there is nothing left to free, and the handle must not be touched.
+            if handle in self._ring._matrix_handles:
+                self._ring._matrix_handles.discard(handle)
+                self._lib.lsr_ring_mod_matrix_free(handle)
 
     def __del__(self):
         try:
@@ -1088,6 +1094,10 @@ class RingMod:
         self._primes = ring_mod_primes(self.n)
         self._contexts = [None, None, None]      # prime 0, prime 1, the coefficient context
         self._matrices = weakref.WeakSet()
+        # the native handles of the matrices still to be freed.  The WeakSet alone does not find them all: when a RingMod and its
+        # matrices are collected as cyclic garbage (the frames of a traceback hold both), the weak references are cleared before any
+        # finalizer runs, and the RingMod's may run first.
+        self._matrix_handles = set()
 
     @property
     def handle(self):
@@ -1122,6 +1132,9 @@ class RingMod:
         if getattr(self, "_h", None):
             for mat in list(getattr(self, "_matrices", ())):   # a matrix must not outlive its handle
                 mat.close()
+            handles = getattr(self, "_matrix_handles", set())
+            while handles:                                     # matrices the WeakSet no longer names (see __init__): freed here,
+                self._lib.lsr_ring_mod_matrix_free(handles.pop())   # and their close() finds the set empty
             for ctx in self._contexts:
                 if ctx is not None:
                     ctx.close()

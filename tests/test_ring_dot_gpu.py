@@ -138,7 +138,9 @@ def _recentring_terms(pkg):
 @pytest.mark.parametrize("which", range(5))
 def test_f64_accumulator_is_recentred(pkg, which):
     """n = 1024: four outputs per tile, operand tiles strided by terms * n.  3001 is odd and 3001 q / 2 > 2^54: a sum kept in a double
-    without reduction cannot be exact."""
+    without reduction cannot be exact.  All 3001 terms reach ONE launch: host_staged_dot stages 256 MiB / 8 n = 32768 polynomials per
+    operand, so the four outputs go up whole, and ring_dot_enqueue hands a per-output b over in one launch and a shared b in groups of
+    ring_dot_chunk_polys = 4096 b-hat rows.  (Which positions can tell a lost periodic re-centre: tests/test_f64_long_sums_gpu.py.)"""
     terms = _recentring_terms(pkg)[which]
     assert which != 4 or terms * Q_NORTH // 2 > 2**54
     ctx = pkg.NttContext(Q_NORTH, 1024, device=0)

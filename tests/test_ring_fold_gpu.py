@@ -128,7 +128,9 @@ def _all_minus_one_case(ctx, q, n, terms, sign):
 @pytest.mark.parametrize("terms", [2, 32, 33, 65, 3001])
 def test_f64_accumulator_is_recentred(pkg, terms):
     """32 is the re-centring period (33, 65: one product past it); 3001 (q - 1)^2-sized summands cannot stay exact in a double
-    without reduction."""
+    without reduction.  All 3001 terms reach ONE launch: the one output fits the staging bound (256 MiB / 8 n = 131072 polynomials)
+    and ring_fold_enqueue takes whole outputs while terms <= ring_dot_chunk_polys = 4096.  (Which positions can tell a lost periodic
+    re-centre: tests/test_f64_long_sums_gpu.py.)"""
     assert pkg.RING_DOT_F64_RECENTRE_PERIOD == 32
     ctx = pkg.NttContext(Q44, 256, device=0)
     assert ctx.uses_f64

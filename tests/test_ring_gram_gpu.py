@@ -10,7 +10,9 @@ import sys
 import numpy as np
 import pytest
 
+from f64_walk_model import discriminating_positions
 from ring_gram_model import dot_pairs, packed_index, pairs, schoolbook_gram
+from ring_tile_model import oracle_product
 from test_ring_matvec_gpu import _flavour_context
 
 pytestmark = pytest.mark.gpu
@@ -155,13 +157,35 @@ def _identical_columns_case(ctx, q, n, width, seed):
     assert np.array_equal(ctx.ring_gram(a), want_sym), (width, "symmetric")
 
 
-def test_f64_accumulators_are_recentred_over_3001_columns(pkg):
+def _cross_pair_at_launch_capacity(ctx, oracle, q, n, seed):
+    """The cross form of ONE vector against one, over as many identical columns as the cross form ever gives one launch: the
+    workspace holds 4096 polynomials at every n <= 4096 (gram_workspace_polys) and a launch takes polys / (ra + rb) columns of a
+    family, 2048 at ra = rb = 1.  Before the call the walk model is asked which evaluation positions lose a bit over 2048 unreduced
+    additions under every representative of the product: without one the call could not tell a lost periodic re-centre."""
+    width = 4096 // 2
+    rng = np.random.default_rng(seed)
+    pa, pb = _rand(rng, q, (1, n)), _rand(rng, q, (1, n))
+    fa, fb = (np.array(oracle.ntt_forward(q, n, p).tolist(), dtype=object) for p in (pa, pb))
+    telling = len(discriminating_positions(fa * fb % q, q, width))
+    assert telling >= 1, "no position of %d can tell a lost re-centre over %d columns" % (n, width)
+    a = np.ascontiguousarray(np.broadcast_to(pa[None, :, None, :], (1, 1, width, n)))
+    b = np.ascontiguousarray(np.broadcast_to(pb[None, :, None, :], (1, 1, width, n)))
+    want = _to_u64(oracle_product(oracle, q, n, pa, pb, False, 0).astype(object) * width % q).reshape(1, 1, 1, n)
+    assert np.array_equal(ctx.ring_gram(a, b), want), (width, "cross, one pair", telling)
+
+
+def test_f64_accumulators_are_recentred_over_3001_columns(pkg, oracle):
     """3001 q / 2 > 2^54: a sum kept in a double without reduction cannot be exact.  (2 + 2) * 3001 polynomials are more than the
-    workspace holds at n = 1024, so the sums are also carried between column groups."""
+    workspace holds at n = 1024, so the sums are also carried between column groups: the cross form of two vectors against two runs
+    as launches of 4096 / 4 = 1024 columns with canonical words handed over, and 1024 * 0.875 q < 2^54 additions cannot lose a bit
+    that both representatives lose (tests/f64_walk_model.py) — those launches check the hand-over, not the periodic re-centre.  The
+    symmetric form of two vectors gets 2048 columns into its first launch, and so does the cross form of one vector against one, which
+    _cross_pair_at_launch_capacity adds with the positions that can tell counted first."""
     assert 3001 * Q_NORTH // 2 > 2**54
     ctx = pkg.NttContext(Q_NORTH, 1024, device=0)
     assert ctx.uses_f64
     _identical_columns_case(ctx, Q_NORTH, 1024, 3001, 1)
+    _cross_pair_at_launch_capacity(ctx, oracle, Q_NORTH, 1024, 2)
     ctx.close()
 
 

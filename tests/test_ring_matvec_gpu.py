@@ -153,7 +153,9 @@ def test_every_row_count_across_two_row_blocks(pkg, lib, flavour):
 def test_accumulator_worst_case(pkg, lib, flavour, cols):
     """Every entry of M is one polynomial m0 and every column of x one polynomial x0: each of the rows' accumulators receives the same
     product cols times, so y = cols (m0 x0).  cols straddles the FP64 re-centring period (32); 3001 q / 2 > 2^54 is beyond any
-    unreduced double, and 41 or more canonical 60-bit summands overflow 64 bits unless each sum is reduced."""
+    unreduced double, and 41 or more canonical 60-bit summands overflow 64 bits unless each sum is reduced.  All 3001 columns reach
+    ONE launch: at n <= 4096 matvec_device is a single ntt_tile_ring_matvec launch over every column of the resident matrix.  (Which
+    positions can tell a lost periodic re-centre: tests/test_f64_long_sums_gpu.py.)"""
     n = 64
     q, ctx = _flavour_context(pkg, lib, flavour, n)
     assert pkg.RING_DOT_F64_RECENTRE_PERIOD == 32

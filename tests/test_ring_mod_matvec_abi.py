@@ -238,3 +238,49 @@ def test_python_wrappers_check_the_shapes(pkg):
         ring.matrix(np.zeros((3, 16), dtype=np.uint64))
     with pytest.raises(ValueError, match="256-bit"):
         ring.matrix_seeded(np.zeros(8, dtype=np.uint64), 16, 0, 1, 1)
+
+
+class _RecordingLib:
+    """stands in for the library: records which handle each free receives, in order"""
+
+    def __init__(self):
+        self.calls = []
+
+    def lsr_ring_mod_matrix_free(self, handle):
+        self.calls.append(("matrix", handle))
+
+    def lsr_ring_mod_free(self, handle):
+        self.calls.append(("ring", handle))
+
+
+def _recorded_ring(pkg):
+    import weakref
+    lib = _RecordingLib()
+    ring = pkg.RingMod.__new__(pkg.RingMod)
+    ring.n, ring._h, ring._lib = 16, 1000, lib
+    ring._contexts, ring._matrices, ring._matrix_handles = [None, None, None], weakref.WeakSet(), set()
+    return lib, ring
+
+
+def test_every_matrix_is_freed_once_and_before_its_ring_in_either_close_order(pkg):
+    """lsr_ring_mod_matrix_free reads the ring's handle, so no matrix may be freed after lsr_ring_mod_free.  The ring finds live matrices
+    through a WeakSet; when ring and matrices are collected as cyclic garbage (a failed test's traceback holds both) the weak references
+    are cleared before any finalizer runs and the ring's may run first: cleared here by hand, as the collector does."""
+    lib, ring = _recorded_ring(pkg)                      # the usual order: matrix, then ring
+    a, b = pkg.RingModMatrix(ring, 1), pkg.RingModMatrix(ring, 2)
+    a.close()
+    a.close()
+    ring.close()
+    b.close()
+    assert lib.calls == [("matrix", 1), ("matrix", 2), ("ring", 1000)] and a.handle is None and b.handle is None
+
+    lib, ring = _recorded_ring(pkg)                      # the collector's order: weak references gone, the ring's finalizer first
+    a, b = pkg.RingModMatrix(ring, 1), pkg.RingModMatrix(ring, 2)
+    ring._matrices.clear()
+    ring.close()
+    assert sorted(lib.calls[:2]) == [("matrix", 1), ("matrix", 2)] and lib.calls[2:] == [("ring", 1000)]
+    a.close()
+    del b                                                # RingModMatrix.__del__
+    assert len(lib.calls) == 3 and a.handle is None
+    ring.close()
+    assert len(lib.calls) == 3
