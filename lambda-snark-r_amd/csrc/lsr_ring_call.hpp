@@ -1,7 +1,7 @@
 // The host call path shared by the ring operations (lsr_ring_mul.hip, lsr_ring_dot.hip, lsr_ring_fold.hip, lsr_ring_matvec.hip,
 // lsr_ring_gadget.hip, lsr_ring_galois.hip, lsr_ring_sample.hip, lsr_ring_challenge.hip, lsr_ring_pack.hip, lsr_ring_norm.hip,
-// lsr_ring_scalar.hip, lsr_ring_gram.hip, lsr_ring_quadform.hip, the ring handles of lsr_ring_mod.hip, lsr_ring_mod_matvec.hip,
-// lsr_ring_mod_gram.hip, lsr_ring_mod_fold.hip and lsr_ring_mod_quadform.hip, and the ring combination of lsr_commit.hip): the dispatch from a context to a kernel instantiation, the
+// lsr_ring_scalar.hip, lsr_ring_gram.hip, lsr_ring_quadform.hip, and the ring combination of lsr_commit.hip; the operations on a ring
+// handle under any modulus reach it through lsr_ring_mod_call.hpp, which holds the handle's own bracket): the dispatch from a context to a kernel instantiation, the
 // bracket that keeps the context's workspaces safe across streams and threads, the argument checks the entry points
 // have in common and the one loop that stages host buffers through bounded device chunks (host_staged; its arithmetic:
 // lsr_staging_plan.hpp).  The dispatch helpers (for_tile_log, for_rank, for_top_bits, for_bool, for_flavour) also serve the commitment
@@ -63,7 +63,7 @@ decltype(auto) for_flavour(const NttContext& c, F&& f) {
 // n > 4096: the tile size of the middle pass, the low log n - 4 (n = 2^17: - 5) bits of a two-pass transform
 inline int mid_tile_log(const NttContext& c) { return c.logn - std::max(c.logn - kTileLog, 4); }
 
-// what a capturing call says when the workspace it needs was never allocated (also the Gram calls of a ring handle, lsr_ring_mod_gram.hip)
+// what a capturing call says when the workspace it needs was never allocated (also the Gram workspace of a ring handle, lsr_ring_mod_call.hpp)
 constexpr const char* kWorkspaceBeforeCapture =
     "this call needs the context's workspace, which the first such call allocates: make one eager (uncaptured) "
     "call on this context before capturing";
@@ -93,11 +93,15 @@ inline void require_device() {
     if (visible_device_count() <= 0) throw std::runtime_error("no HIP device visible — this library has no CPU fallback");
 }
 
-// `message` when [out, out + out_bytes) and [in, in + in_bytes) share memory
-inline void require_apart(const void* out, size_t out_bytes, const void* in, size_t in_bytes, const char* message) {
+// [out, out + out_bytes) and [in, in + in_bytes) share memory
+inline bool ranges_overlap(const void* out, size_t out_bytes, const void* in, size_t in_bytes) {
     const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + out_bytes;
     const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + in_bytes;
-    if (o0 < i1 && i0 < o1) throw std::runtime_error(message);
+    return o0 < i1 && i0 < o1;
+}
+// `message` when they do
+inline void require_apart(const void* out, size_t out_bytes, const void* in, size_t in_bytes, const char* message) {
+    if (ranges_overlap(out, out_bytes, in, in_bytes)) throw std::runtime_error(message);
 }
 
 // the middle pass of a fused ring operation assumes ONE strided round on either side

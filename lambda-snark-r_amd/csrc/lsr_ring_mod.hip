@@ -13,13 +13,13 @@
 //   coeff context   an NttContext of (q, n) without twiddle tables, owned by the handle (create_coeff_context, lsr_ntt.hip): the
 //                   coefficient-wise calls of the toolkit run on it under q, every call that transforms refuses it (§5t).
 // The workspace is sized by n alone and allocated with the handle, so the device forms capture into a graph from the first call.
+// Its layout (ring_mod_workspace) and the bracket of a call (ring_mod_call): lsr_ring_mod_call.hpp.
 #include <algorithm>
 #include <cstring>
 
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
-#include "lsr_ring_call.hpp"
-#include "lsr_ring_mod.hpp"
+#include "lsr_ring_mod_call.hpp"
 #include "lsr_ring_workspace.hpp"
 #include "lsr_runtime.hpp"
 
@@ -84,41 +84,36 @@ static void dot_lift_tile(const NttContext& c, const LiftSource& lift, const Gal
 static void ring_mod_dot_enqueue(const LsrRingMod& h, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms, bool shared_b,
                                  bool accumulate, const GaloisParams* g, hipStream_t s) {
     const size_t n = h.n;
-    uint64_t* const sums[2] = {h.ws.ptr, h.ws.ptr + h.chunk * n};
-    uint64_t* const bhat[2] = {h.ws.ptr + 2 * h.chunk * n, h.ws.ptr + (2 * h.chunk + h.bhat_rows) * n};
+    const RingModWorkspace w = ring_mod_workspace(h);
     const size_t group_max = std::min({terms, h.max_terms, shared_b ? h.bhat_rows : terms});
     for (size_t i0 = 0; i0 < terms; i0 += group_max) {
         const size_t group = std::min(group_max, terms - i0);
         if (shared_b) {
             for (int i = 0; i < 2; ++i) {
-                launch_lift(h, i, bhat[i], d_b + i0 * n, group * n, s);
-                launch_ntt(*h.prime[i], bhat[i], group, false, s);
+                launch_lift(h, i, w.bhat[i], d_b + i0 * n, group * n, s);
+                launch_ntt(*h.prime[i], w.bhat[i], group, false, s);
             }
         }
         for (size_t j0 = 0; j0 < batch; j0 += h.chunk) {
             const size_t now = std::min(h.chunk, batch - j0), off = (j0 * terms + i0) * n;
             for (int i = 0; i < 2; ++i) {
-                if (shared_b) dot_lift_tile<true>(*h.prime[i], h.lift[i], g, {sums[i], d_a + off, bhat[i], now * n, (uint32_t)group, terms * n, 0}, s);
-                else dot_lift_tile<false>(*h.prime[i], h.lift[i], g, {sums[i], d_a + off, d_b + off, now * n, (uint32_t)group, terms * n, terms * n}, s);
+                if (shared_b) dot_lift_tile<true>(*h.prime[i], h.lift[i], g, {w.sums[i], d_a + off, w.bhat[i], now * n, (uint32_t)group, terms * n, 0}, s);
+                else dot_lift_tile<false>(*h.prime[i], h.lift[i], g, {w.sums[i], d_a + off, d_b + off, now * n, (uint32_t)group, terms * n, terms * n}, s);
             }
-            launch_reduce(h, d_c + j0 * n, sums[0], sums[1], now * n, accumulate || i0 > 0, s);
+            launch_reduce(h, d_c + j0 * n, w.sums[0], w.sums[1], now * n, accumulate || i0 > 0, s);
         }
     }
 }
 
-// One call on the device (caller validated the arguments): ring_call's brackets on the handle's own mutex and event.  g: 0 for the
-// plain product, else the odd Galois element below 2 n applied to a
+// One call on the device (caller validated the arguments) in the handle's bracket (ring_mod_call).  g: 0 for the plain product, else
+// the odd Galois element below 2 n applied to a
 static void ring_mod_dot_device(const LsrRingMod& h, uint64_t* d_c, const uint64_t* d_a, const uint64_t* d_b, size_t batch, size_t terms, size_t b_rows,
                                 bool accumulate, uint64_t g, hipStream_t s) {
     // g^-1 mod 2 n by Newton's iteration, which doubles the correct low bits (g is its own inverse mod 8), as lsr_ring_galois.hip
     uint32_t inv = (uint32_t)g;
     for (int i = 0; i < 4; ++i) inv *= 2u - (uint32_t)g * inv;
     const GaloisParams gp{inv & (2u * h.n - 1u), 2u * h.n - 1u};
-    std::lock_guard<std::mutex> lock(h.mutex);
-    const bool capturing = stream_is_capturing(s);
-    if (!capturing) h.event.wait(s);
-    ring_mod_dot_enqueue(h, d_c, d_a, d_b, batch, terms, b_rows == 1 && batch > 1, accumulate, g ? &gp : nullptr, s);
-    if (!capturing) h.event.record(s);
+    ring_mod_call(h, s, false, [&] { ring_mod_dot_enqueue(h, d_c, d_a, d_b, batch, terms, b_rows == 1 && batch > 1, accumulate, g ? &gp : nullptr, s); });
 }
 
 static size_t mul_or_max(size_t x, size_t y) {

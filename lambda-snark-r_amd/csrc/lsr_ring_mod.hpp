@@ -1,7 +1,8 @@
 // The ring handle under an arbitrary modulus (LsrRingMod, batch.h) as the translation units that read it see it:
 // lsr_ring_mod.hip creates it, computes mul, dot and dot_galois and lends its coefficient context (§5t), lsr_ring_mod_matvec.hip keeps
 // resident matrices on it (§5q), lsr_ring_mod_gram.hip computes Gram matrices of bounded vectors on it (§5r), lsr_ring_mod_fold.hip folds vectors by challenges on it (§5s),
-// lsr_ring_mod_quadform.hip evaluates quadratic forms of a packed Gram triangle on it (§5u).
+// lsr_ring_mod_quadform.hip evaluates quadratic forms of a packed Gram triangle on it (§5u).  The call path they share — the bracket
+// of a call, the views of the two workspaces, the checked lift and the gated reduce — is lsr_ring_mod_call.hpp.
 #pragma once
 
 #include <mutex>
@@ -22,14 +23,15 @@ struct LsrRingMod {
     lsr::ModParams pq{};             // of q: only q and floor(2^128 / q) are used
     lsr::LiftSource lift[2]{};
     // n <= 4096: [2][chunk][n] inverse-transformed sums, then [2][bhat_rows][n] transforms of a shared b or of a fold's challenges, then
-    // kRingModFoldFlagWords words of a fold's per-output flags.  Never resized.
+    // kRingModFoldFlagWords words of flags, a fold's per output or a bounded matrix product's per vector (ring_mod_workspace,
+    // lsr_ring_mod_call.hpp).  Never resized.
     size_t chunk = 0, bhat_rows = 0;
     lsr::DeviceBuffer<uint64_t> ws;
     // the Gram calls and the quadratic forms (lsr_ring_mod_gram.hip, lsr_ring_mod_quadform.hip): [2][ring_mod_gram_words()] lifted operands, their transforms and the outputs of one chunk
     // per prime, then kRingModGramFlagWords words of per-family flags.  Allocated by the first eager Gram call or by
     // lsr_ring_mod_gram_prepare under `mutex`, never resized.
     mutable lsr::DeviceBuffer<uint64_t> gram_ws;
-    // calls on one handle are ordered like the ring calls of a context (lsr_ring_call.hpp ring_call)
+    // calls on one handle are ordered like the ring calls of a context (lsr_ring_mod_call.hpp ring_mod_call)
     mutable std::mutex mutex;
     mutable lsr::Event event;
 };
@@ -40,12 +42,6 @@ constexpr size_t kRingModSumWords = (size_t)1 << 22;    // per prime: 32 MiB, bo
 constexpr size_t kRingModBhatWords = (size_t)1 << 21;   // per prime
 constexpr size_t kRingModBhatMaxRows = 4096;            // bhat_rows = min(this, kRingModBhatWords / n)
 constexpr size_t kRingModFoldFlagWords = kRingModBhatMaxRows / 2;   // 32-bit flag words: one per challenge row
-
-// n <= 4096: the 2 kRingModFoldFlagWords 32-bit flag words behind the workspace's sums and challenge transforms — a fold's per-output
-// flags, a bounded matrix product's per-vector flags (lsr_ring_mod_matvec.hip); whoever holds the handle's mutex owns them
-inline uint32_t* ring_mod_flag_words(const LsrRingMod& h) {
-    return reinterpret_cast<uint32_t*>(h.ws.ptr + 2 * (h.chunk + h.bhat_rows) * h.n);
-}
 
 // Gram workspace words per prime: a function of the process-wide chunk size alone (a quarter of it, 64 MiB of 256: the two halves stay in
 // the Infinity Cache between the passes of a chunk), at least 2^23 words

@@ -15,15 +15,15 @@
 // and a large one fewer outputs (mod_fold_enqueue).  An output too wide for the sums (width n above 2^22 words) is taken alone, its components in chunks; its flags are
 // then completed by a check pass without stores before its first reduce.
 // The workspace is the handle's, allocated by lsr_ring_mod_create: [2][chunk][n] sums, [2][bhat_rows][n] challenge transforms, and
-// kRingModFoldFlagWords words of per-output flags behind them.
+// kRingModFoldFlagWords words of per-output flags behind them (ring_mod_workspace, lsr_ring_mod_call.hpp, which also holds the
+// launchers of the lift and of the reduce).
 #include <algorithm>
 #include <cstring>
 
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
-#include "lsr_ring_call.hpp"
 #include "lsr_ring_fold.hpp"
-#include "lsr_ring_mod.hpp"
+#include "lsr_ring_mod_call.hpp"
 #include "lsr_ring_mod_fold_kernels.hpp"
 #include "lsr_runtime.hpp"
 
@@ -43,52 +43,20 @@ struct ModFoldCall {
     uint64_t bound_v, bound_p;   // as the caller gave them: 0 = none
 };
 
-// `families` runs of `run` contiguous words, `src_fam` words apart: checked against `bound` and q into flags[family] and (STORE)
-// lifted to dst + family dst_fam for prime 0, `half` words behind that for prime 1
-template <bool STORE>
-static void fold_lift(const LsrRingMod& h, uint64_t* dst, const uint64_t* src, uint32_t* flags, size_t run, size_t families, size_t src_fam, size_t dst_fam,
-                      size_t half, uint64_t bound, hipStream_t s) {
-    const bool vec = (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
-    const size_t items = vec ? run / 2 : run;
-    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))), 1u,
-                    static_cast<unsigned>(families));
-    const GramLiftShape shape{run, 0, src_fam, 0, dst_fam, half, h.q, bound};
-    for_bool(vec, [&](auto v) {
-        hipLaunchKernelGGL((ring_mod_gram_lift_kernel<decltype(v)::value, true, STORE>), grid, dim3(kRingModThreads), 0, s, dst, src, flags, shape, h.lift[0],
-                           h.lift[1]);
-    });
-}
-
 // Both primes in one launch, the prime as grid z: in this form the check costs no registers over ntt_tile_ring_fold, where a launch
 // per prime with the check as a template argument costs the checking launch 20 to 34 VGPRs in the FP64 flavour and a wave
 // (profiles/r35_ring_mod_fold_resource_usage.txt).
 template <class A>
-static void fold_tiles(const LsrRingMod& h, uint64_t* const (&sums)[2], const uint64_t* const (&bhat)[2], const uint64_t* v, uint32_t* flags,
-                       const RingModFoldShape& shape, size_t outputs, hipStream_t s) {
+static void fold_tiles(const LsrRingMod& h, const RingModWorkspace& w, const uint64_t* v, const RingModFoldShape& shape, size_t outputs, hipStream_t s) {
     const unsigned tiles = static_cast<unsigned>((shape.total + kTile - 1) / kTile);
     RingModFoldPrimes<A> both;
     for (int i = 0; i < 2; ++i) {
         const NttContext& c = *h.prime[i];
-        both.prime[i] = {sums[i], bhat[i], Flavour<A>::fwd(c), Flavour<A>::inv(c), c.mod, Flavour<A>::consts(c), h.lift[i]};
+        both.prime[i] = {w.sums[i], w.bhat[i], Flavour<A>::fwd(c), Flavour<A>::inv(c), c.mod, Flavour<A>::consts(c), h.lift[i]};
     }
     for_tile_log<1, 12>(h.logn, [&](auto t) {
         constexpr int LT = decltype(t)::value;
-        hipLaunchKernelGGL((ntt_tile_ring_mod_fold<A, LT>), dim3(tiles, static_cast<unsigned>(outputs), 2), dim3(kThreads), 0, s, both, v, flags, shape);
-    });
-}
-
-// out: [outputs][words] (one chunk of whole outputs, or one component range of one output)
-static void fold_reduce(const LsrRingMod& h, uint64_t* out, int32_t* status, const uint64_t* r0, const uint64_t* r1, const uint32_t* flags, size_t words,
-                        size_t outputs, bool accumulate, hipStream_t s) {
-    const bool vec = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
-    const size_t items = vec ? words / 2 : words;
-    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))),
-                    static_cast<unsigned>(outputs));
-    for_bool(vec, [&](auto v) {
-        for_bool(accumulate, [&](auto acc) {
-            hipLaunchKernelGGL((ring_mod_gram_reduce_kernel<decltype(v)::value, decltype(acc)::value>), grid, dim3(kRingModThreads), 0, s, out, status, r0, r1,
-                               flags, words, words, h.rc, h.prime[1]->mod, h.pq);
-        });
+        hipLaunchKernelGGL((ntt_tile_ring_mod_fold<A, LT>), dim3(tiles, static_cast<unsigned>(outputs), 2), dim3(kThreads), 0, s, both, v, w.flags, shape);
     });
 }
 
@@ -97,10 +65,7 @@ static void mod_fold_enqueue(const LsrRingMod& h, const ModFoldCall& c, hipStrea
     const size_t n = h.n, vec = c.width * n;
     const uint64_t half = h.q >> 1, bound_v = c.bound_v ? c.bound_v : half, bound_p = c.bound_p ? c.bound_p : half;
     const size_t capacity = ring_mod_capacity_product(h.q, h.n, bound_v, bound_p);    // >= max_terms >= 1
-    uint64_t* const sums[2] = {h.ws.ptr, h.ws.ptr + h.chunk * n};
-    uint64_t* const bhat_rw[2] = {h.ws.ptr + 2 * h.chunk * n, h.ws.ptr + (2 * h.chunk + h.bhat_rows) * n};
-    const uint64_t* const bhat[2] = {bhat_rw[0], bhat_rw[1]};
-    uint32_t* const flags = reinterpret_cast<uint32_t*>(h.ws.ptr + 2 * (h.chunk + h.bhat_rows) * n);
+    const RingModWorkspace w = ring_mod_workspace(h);
     // An output wider than the sums goes alone, `wmax` components at a time.  Else a chunk holds whole outputs, as many as the sums
     // hold, and its groups as many terms as P carries; where the challenge rows do not hold that many transforms, a chunk that fills
     // the device (kRingModFoldFillTiles tiles per prime) keeps its full groups and takes fewer outputs, and a smaller one keeps its
@@ -116,35 +81,30 @@ static void mod_fold_enqueue(const LsrRingMod& h, const ModFoldCall& c, hipStrea
         const size_t now = std::min(chunk, c.outputs - j0);
         const uint64_t* const vj = c.v + j0 * c.ts * vec;
         const uint64_t* const pj = c.p + j0 * c.terms * n;
-        zero_words_async(reinterpret_cast<uint64_t*>(flags), (now + 1) / 2, s);
+        zero_words_async(reinterpret_cast<uint64_t*>(w.flags), (now + 1) / 2, s);
         if (!whole) {   // (now == 1) the output's flags before its first reduce: its term vectors are contiguous in v
-            fold_lift<false>(h, nullptr, vj, flags, c.terms * vec, 1, 0, 0, 0, bound_v, s);
-            fold_lift<false>(h, nullptr, pj, flags, c.terms * n, 1, 0, 0, 0, bound_p, s);
+            ring_mod_check_pass(h, vj, w.flags, c.terms * vec, 1, 0, bound_v, s);
+            ring_mod_check_pass(h, pj, w.flags, c.terms * n, 1, 0, bound_p, s);
         }
         for (size_t c0 = 0; c0 < c.width; c0 += wmax) {
             const size_t wnow = std::min(wmax, c.width - c0), words = wnow * n;
             for (size_t i0 = 0; i0 < c.terms; i0 += group_max) {
                 const size_t group = std::min(group_max, c.terms - i0);
-                fold_lift<true>(h, bhat_rw[0], pj + i0 * n, flags, group * n, now, c.terms * n, group * n, h.bhat_rows * n, bound_p, s);
-                for (int i = 0; i < 2; ++i) launch_ntt(*h.prime[i], bhat_rw[i], now * group, false, s);
+                // the group's challenges, contiguous per output, into the b-hat rows of both primes
+                ring_mod_checked_lift<true, true>(h, {w.bhat[0], pj + i0 * n, 1, now, group * n, 0, c.terms * n, 0, group * n, h.bhat_rows * n, bound_p}, w.flags, s);
+                for (int i = 0; i < 2; ++i) launch_ntt(*h.prime[i], w.bhat[i], now * group, false, s);
                 const RingModFoldShape shape{words, (uint32_t)group, vec, c.ts * vec, h.q, bound_v};
-                fold_tiles<A>(h, sums, bhat, vj + i0 * vec + c0 * n, flags, shape, now, s);
-                fold_reduce(h, c.out + j0 * vec + c0 * n, c.status + j0, sums[0], sums[1], flags, words, now, i0 > 0, s);
+                fold_tiles<A>(h, w, vj + i0 * vec + c0 * n, shape, now, s);
+                // out: [now][words] (one chunk of whole outputs, or one component range of one output)
+                ring_mod_gated_reduce(h, c.out + j0 * vec + c0 * n, c.status + j0, w.sums[0], w.sums[1], w.flags, words, now, i0 > 0, s);
             }
         }
     }
 }
 
-// One call on the device (caller validated the arguments): the handle's mutex and event as ring_mod_dot_device.
+// One call on the device (caller validated the arguments) in the handle's bracket (ring_mod_call)
 static void mod_fold_device(const LsrRingMod& h, const ModFoldCall& c, hipStream_t s) {
-    std::lock_guard<std::mutex> lock(h.mutex);
-    const bool capturing = stream_is_capturing(s);
-    if (h.prime[0]->use_f64 != h.prime[1]->use_f64) throw std::runtime_error("the two prime contexts run different kernel flavours");
-    if (!capturing) h.event.wait(s);
-    if (h.prime[0]->use_f64) mod_fold_enqueue<ArithF64>(h, c, s);
-    else mod_fold_enqueue<ArithU64>(h, c, s);
-    LSR_HIP(hipGetLastError());
-    if (!capturing) h.event.record(s);
+    ring_mod_call(h, s, false, [&] { for_ring_mod_flavour(h, [&](auto a) { mod_fold_enqueue<decltype(a)>(h, c, s); }); });
 }
 
 // host buffers through bounded device chunks on the first prime context's work stream: whole outputs with the span of vectors they
@@ -181,10 +141,7 @@ int mod_fold_call(const char* where, const LsrRingMod* h, const lsr::ModFoldCall
     lsr::FoldCounts k;
     const int rc = lsr::ring_fold_shape_check(where, c.outputs, c.terms, c.ts, c.width, k);
     if (rc != 0) return rc < 0 ? -1 : 0;
-    const uint64_t half = h->q >> 1;
-    if (c.bound_v > half || c.bound_p > half)
-        return lsr::abi_refuse(where, "bound_v = " + std::to_string(c.bound_v) + ", bound_p = " + std::to_string(c.bound_p) + ": a bound is above floor(q / 2) = " +
-                                          std::to_string(half) + " (0 states none)");
+    if (lsr::ring_mod_bounds_check(where, h->q, "bound_v", c.bound_v, "bound_p", c.bound_p) != 0) return -1;
     return lsr::abi_guarded(where, [&] {
         if (h->n > lsr::kTile)
             throw std::runtime_error("n = " + std::to_string(h->n) + " is above 4096, where the fold has no fused form: lsr_ring_mod_lift_batch_device v and p for "
@@ -196,12 +153,7 @@ int mod_fold_call(const char* where, const LsrRingMod* h, const lsr::ModFoldCall
         if (__builtin_mul_overflow(k.v_polys, poly_bytes, &v_bytes) || __builtin_mul_overflow(k.p_polys, poly_bytes, &p_bytes) ||
             __builtin_mul_overflow(k.out_polys, poly_bytes, &out_bytes))
             throw std::runtime_error("the sizes of v, p or out overflow size_t at this ring degree");
-        const size_t status_bytes = c.outputs * sizeof(int32_t);
-        lsr::require_apart(c.out, out_bytes, c.v, v_bytes, "out overlaps v: the output must not share memory with an operand");
-        lsr::require_apart(c.out, out_bytes, c.p, p_bytes, "out overlaps p: the output must not share memory with an operand");
-        lsr::require_apart(c.status, status_bytes, c.v, v_bytes, "status overlaps v: the output must not share memory with an operand");
-        lsr::require_apart(c.status, status_bytes, c.p, p_bytes, "status overlaps p: the output must not share memory with an operand");
-        lsr::require_apart(c.status, status_bytes, c.out, out_bytes, "status overlaps out: the two outputs must not share memory");
+        lsr::require_outputs_apart({"out", c.out, out_bytes}, {"status", c.status, c.outputs * sizeof(int32_t)}, {{"v", c.v, v_bytes}, {"p", c.p, p_bytes}});
         lsr::require_device();
         lsr::DeviceGuard guard(h->device);
         if (device) lsr::mod_fold_device(*h, c, static_cast<hipStream_t>(stream));

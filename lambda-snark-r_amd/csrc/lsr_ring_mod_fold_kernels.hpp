@@ -8,7 +8,7 @@
 //            and lift(0) = 0.
 //   Check    the same word is held against q and against bound_v: "over the bound" / ">= q" are collected per lane over all terms,
 //            OR-ed across the wave by ballot, and at most one atomic OR per wave goes to the output's flag word (the bits and the
-//            flag layout of ring_mod_gram_lift_kernel, lsr_ring_mod_gram_kernels.hpp).  Only one prime's workgroups check: the
+//            flag layout of ring_mod_gram_lift_kernel, lsr_ring_mod_kernels.hpp).  Only one prime's workgroups check: the
 //            other prime reads the same words.
 //   Output   the launch's sums are complete (a group of terms is one whole sum: the groups are joined mod q by the reduce pass, not
 //            in the accumulator), so there is no kRingDotFirst / kRingDotLast hand-over.
@@ -23,7 +23,7 @@
 // >= q may lift to anything: its output is flagged and the reduce pass writes zeros over whatever the sums hold.)
 #pragma once
 
-#include "lsr_ring_mod_gram_kernels.hpp"
+#include "lsr_ring_mod_kernels.hpp"
 
 namespace lsr {
 

@@ -3,25 +3,24 @@
 // lsr_ring_mod.hip), at every n the handle admits.  The caller states l-infinity bounds on the centred operands; the device verifies
 // them and reports per family (status), and the columns are taken in groups of what P = p1 p2 carries under those bounds
 // (ring_mod_capacity_product).  Per chunk of families and group of columns:
-//   1. ring_mod_gram_lift_kernel: every operand word read once, lifted for both primes into the two halves of the handle's Gram
+//   1. ring_mod_gram_lift_kernel (ring_mod_checked_lift, lsr_ring_mod_call.hpp): every operand word read once, lifted for both primes into the two halves of the handle's Gram
 //      workspace, bounds and range folded into the family's flag word (families in several groups: one check pass over the chunk's
 //      whole families first, then lifts without the check);
 //   2. launch_ntt forward in place on each half (a-hat and b-hat are contiguous: one launch per prime);
 //   3. the register-blocked pointwise product of §5j into the workspace: ring_mod_gram_kernel for both primes in one launch, or — the
 //      FP64 flavour's cross and symmetric forms, where the second prime costs a wave — ring_gram_kernel once per prime;
 //   4. launch_ntt inverse in place on each half's outputs;
-//   5. ring_mod_gram_reduce_kernel: CRT and reduction mod q into g (accumulating from the second group on), zeros where the family's
+//   5. ring_mod_gram_reduce_kernel (ring_mod_gated_reduce): CRT and reduction mod q into g (accumulating from the second group on), zeros where the family's
 //      flags are set, and status.
 // The workspace is [2][ring_mod_gram_words()] words and the flag words: sized by the process-wide chunk size alone, allocated by the
-// first eager call or by lsr_ring_mod_gram_prepare, never resized.
+// first eager call or by lsr_ring_mod_gram_prepare, never resized (ring_mod_call, lsr_ring_mod_call.hpp).
 #include <algorithm>
 #include <cstring>
 
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
-#include "lsr_ring_call.hpp"
 #include "lsr_ring_gram.hpp"
-#include "lsr_ring_mod.hpp"
+#include "lsr_ring_mod_call.hpp"
 #include "lsr_ring_mod_gram_kernels.hpp"
 #include "lsr_runtime.hpp"
 
@@ -65,27 +64,6 @@ static ModGramPlan mod_gram_plan(const LsrRingMod& h, const ModGramCall& c) {
     return p;
 }
 
-// one operand of one chunk or group: `vectors` runs of `run` words per family
-struct LiftLaunch {
-    uint64_t* dst;
-    const uint64_t* src;
-    size_t vectors, families, run, src_vec, src_fam, dst_vec, dst_fam;
-    uint64_t bound;
-};
-
-template <bool CHECK, bool STORE>
-static void gram_lift(const LsrRingMod& h, const LiftLaunch& l, uint32_t* flags, hipStream_t s) {
-    const bool vec = (reinterpret_cast<uintptr_t>(l.src) & 15u) == 0;
-    const size_t items = vec ? l.run / 2 : l.run;
-    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))),
-                    static_cast<unsigned>(l.vectors), static_cast<unsigned>(l.families));
-    const GramLiftShape shape{l.run, l.src_vec, l.src_fam, l.dst_vec, l.dst_fam, ring_mod_gram_words(), h.q, l.bound};
-    for_bool(vec, [&](auto v) {
-        hipLaunchKernelGGL((ring_mod_gram_lift_kernel<decltype(v)::value, CHECK, STORE>), grid, dim3(kRingModThreads), 0, s, l.dst, l.src, flags, shape,
-                           h.lift[0], h.lift[1]);
-    });
-}
-
 // Both primes in one launch (the prime is the low bit of grid y), or one launch of the single-prime kernel per prime: decided per
 // instantiation by the compiler's resource report (profiles/r34_ring_mod_gram_resource_usage.txt).  Carrying the second
 // prime costs the FP64 flavour's cross and symmetric kernels a wave (70 VGPRs against 62: 7 waves per SIMD against 8).
@@ -119,31 +97,14 @@ static void gram_product(const LsrRingMod& h, uint64_t* ghat, const uint64_t* ah
     });
 }
 
-static void gram_reduce(const LsrRingMod& h, uint64_t* g, int32_t* status, const uint64_t* ghat, const uint32_t* flags, size_t words, size_t families,
-                        bool accumulate, hipStream_t s) {
-    const bool vec = (reinterpret_cast<uintptr_t>(g) & 15u) == 0;
-    const size_t items = vec ? words / 2 : words;
-    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))),
-                    static_cast<unsigned>(families));
-    for_bool(vec, [&](auto v) {
-        for_bool(accumulate, [&](auto acc) {
-            hipLaunchKernelGGL((ring_mod_gram_reduce_kernel<decltype(v)::value, decltype(acc)::value>), grid, dim3(kRingModThreads), 0, s, g, status, ghat,
-                               ghat + ring_mod_gram_words(), flags, words, words, h.rc, h.prime[1]->mod, h.pq);
-        });
-    });
-}
-
 template <class A>
 static void mod_gram_enqueue(const LsrRingMod& h, const ModGramCall& c, hipStream_t s) {
     const ModGramPlan p = mod_gram_plan(h, c);
     const size_t n = h.n, half = ring_mod_gram_words(), polys = half >> h.logn;
     const size_t a_fam = c.ra * c.width * n, b_fam = c.rb * c.width * n, g_fam = p.outs * n;
     uint64_t* const ws = h.gram_ws.ptr;
-    uint32_t* const flags = reinterpret_cast<uint32_t*>(ws + 2 * half);
+    uint32_t* const flags = ring_mod_gram_flags(h);
     const uint64_t* const b = p.one_set ? c.a : c.b;
-    auto transforms = [&](uint64_t* data, size_t count, bool inverse) {
-        for (int i = 0; i < 2; ++i) launch_ntt(*h.prime[i], data + i * half, count, inverse, s);
-    };
     // Columns per group: what P carries and what the workspace holds of one family (>= 1: mod_gram_call).  Families per chunk: what
     // the workspace holds of such groups and their outputs, the chunks of a batch of equal size.  A family's flags must be complete
     // before its first reduce: with one group the check rides in the lift, else a pass without stores over the chunk's whole
@@ -158,44 +119,32 @@ static void mod_gram_enqueue(const LsrRingMod& h, const ModGramCall& c, hipStrea
         const uint64_t *aj = c.a + j0 * a_fam, *bj = b + j0 * b_fam;
         zero_words_async(reinterpret_cast<uint64_t*>(flags), (now + 1) / 2, s);
         if (!one_group) {
-            gram_lift<true, false>(h, {ws, aj, c.ra, now, vec_words, vec_words, a_fam, 0, 0, p.check_a}, flags, s);
-            if (!p.one_set) gram_lift<true, false>(h, {ws, bj, c.rb, now, vec_words, vec_words, b_fam, 0, 0, p.bound_b}, flags, s);
+            ring_mod_checked_lift<true, false>(h, {ws, aj, c.ra, now, vec_words, vec_words, a_fam, 0, 0, half, p.check_a}, flags, s);
+            if (!p.one_set) ring_mod_checked_lift<true, false>(h, {ws, bj, c.rb, now, vec_words, vec_words, b_fam, 0, 0, half, p.bound_b}, flags, s);
         }
         for (size_t c0 = 0; c0 < c.width; c0 += wmax) {
             const size_t wnow = std::min(wmax, c.width - c0), run = wnow * n;
             uint64_t* const bhat = p.one_set ? ws : ws + now * c.ra * run;
             uint64_t* const ghat = ws + now * p.vectors * run;
-            const LiftLaunch la{ws, aj + c0 * n, c.ra, now, run, vec_words, a_fam, run, c.ra * run, p.check_a};
-            const LiftLaunch lb{bhat, bj + c0 * n, c.rb, now, run, vec_words, b_fam, run, c.rb * run, p.bound_b};
+            const LiftLaunch la{ws, aj + c0 * n, c.ra, now, run, vec_words, a_fam, run, c.ra * run, half, p.check_a};
+            const LiftLaunch lb{bhat, bj + c0 * n, c.rb, now, run, vec_words, b_fam, run, c.rb * run, half, p.bound_b};
             for_bool(one_group, [&](auto check) {
-                gram_lift<decltype(check)::value, true>(h, la, flags, s);
-                if (!p.one_set) gram_lift<decltype(check)::value, true>(h, lb, flags, s);
+                ring_mod_checked_lift<decltype(check)::value, true>(h, la, flags, s);
+                if (!p.one_set) ring_mod_checked_lift<decltype(check)::value, true>(h, lb, flags, s);
             });
-            transforms(ws, now * p.vectors * wnow, false);
+            ring_mod_gram_transforms(h, ws, now * p.vectors * wnow, false, s);
             const GramShape shape{(uint32_t)h.logn, (uint32_t)c.ra, (uint32_t)c.rb, (uint32_t)wnow, kRingDotFirst | kRingDotLast,
                                   run, c.ra * run, run, c.rb * run, g_fam};
             gram_product<A>(h, ghat, ws, bhat, shape, p.sym, c.sym2, now, s);
-            transforms(ghat, now * p.outs, true);
-            gram_reduce(h, c.g + j0 * g_fam, c.status + j0, ghat, flags, g_fam, now, c0 > 0, s);
+            ring_mod_gram_transforms(h, ghat, now * p.outs, true, s);
+            ring_mod_gated_reduce(h, c.g + j0 * g_fam, c.status + j0, ghat, ghat + half, flags, g_fam, now, c0 > 0, s);
         }
     }
 }
 
-// One call on the device (caller validated the arguments): the handle's mutex and event as ring_mod_dot_device, the Gram workspace
-// as ring_call allocates a context's.
+// One call on the device (caller validated the arguments) in the handle's bracket (ring_mod_call), on its Gram workspace
 static void mod_gram_device(const LsrRingMod& h, const ModGramCall& c, hipStream_t s) {
-    std::lock_guard<std::mutex> lock(h.mutex);
-    const bool capturing = stream_is_capturing(s);
-    if (!h.gram_ws.ptr) {
-        if (capturing) throw std::runtime_error(kWorkspaceBeforeCapture);
-        h.gram_ws.allocate(2 * ring_mod_gram_words() + kRingModGramFlagWords);
-    }
-    if (h.prime[0]->use_f64 != h.prime[1]->use_f64) throw std::runtime_error("the two prime contexts run different kernel flavours");
-    if (!capturing) h.event.wait(s);
-    if (h.prime[0]->use_f64) mod_gram_enqueue<ArithF64>(h, c, s);
-    else mod_gram_enqueue<ArithU64>(h, c, s);
-    LSR_HIP(hipGetLastError());
-    if (!capturing) h.event.record(s);
+    ring_mod_call(h, s, true, [&] { for_ring_mod_flavour(h, [&](auto a) { mod_gram_enqueue<decltype(a)>(h, c, s); }); });
 }
 
 // host buffers through bounded device chunks of whole families on the first prime context's work stream; status comes back with g
@@ -228,10 +177,7 @@ namespace {
 int mod_gram_call(const char* where, const LsrRingMod* h, const lsr::ModGramCall& c, bool device, void* stream) noexcept {
     if (!h || !c.g || !c.status || !c.a || (c.sym2 && !c.b)) return lsr::abi_refuse(where, "NULL handle, buffer or status");
     if (lsr::ring_gram_shape_check(where, c.b != nullptr, c.batch, c.ra, c.rb, c.width, c.sym2) != 0) return -1;
-    const uint64_t half = h->q >> 1;
-    if (c.bound_a > half || (c.b && c.bound_b > half))
-        return lsr::abi_refuse(where, "bound_a = " + std::to_string(c.bound_a) + ", bound_b = " + std::to_string(c.bound_b) + ": a bound is above floor(q / 2) = " +
-                                          std::to_string(half) + " (0 states none)");
+    if (lsr::ring_mod_bounds_check(where, h->q, "bound_a", c.bound_a, "bound_b", c.bound_b, c.b != nullptr) != 0) return -1;
     if (c.batch == 0) return 0;
     return lsr::abi_guarded(where, [&] {
         const lsr::ModGramPlan p = lsr::mod_gram_plan(*h, c);
@@ -254,12 +200,7 @@ int mod_gram_call(const char* where, const LsrRingMod* h, const lsr::ModGramCall
         if (__builtin_mul_overflow(c.batch * c.ra * c.width, poly_bytes, &a_bytes) || __builtin_mul_overflow(c.batch * c.rb * c.width, poly_bytes, &b_bytes) ||
             __builtin_mul_overflow(c.batch * p.outs, poly_bytes, &g_bytes))
             throw std::runtime_error("the sizes of a, b or g overflow size_t at this ring degree");
-        const size_t status_bytes = c.batch * sizeof(int32_t);
-        lsr::require_apart(c.g, g_bytes, c.a, a_bytes, "g overlaps a: the output must not share memory with an operand");
-        if (c.b) lsr::require_apart(c.g, g_bytes, c.b, b_bytes, "g overlaps b: the output must not share memory with an operand");
-        lsr::require_apart(c.status, status_bytes, c.a, a_bytes, "status overlaps a: the output must not share memory with an operand");
-        if (c.b) lsr::require_apart(c.status, status_bytes, c.b, b_bytes, "status overlaps b: the output must not share memory with an operand");
-        lsr::require_apart(c.status, status_bytes, c.g, g_bytes, "status overlaps g: the two outputs must not share memory");
+        lsr::require_outputs_apart({"g", c.g, g_bytes}, {"status", c.status, c.batch * sizeof(int32_t)}, {{"a", c.a, a_bytes}, {"b", c.b, b_bytes}});
         lsr::require_device();
         lsr::DeviceGuard guard(h->device);
         if (device) lsr::mod_gram_device(*h, c, static_cast<hipStream_t>(stream));
@@ -286,7 +227,7 @@ int lsr_ring_mod_gram_prepare(const LsrRingMod* h) noexcept {
         lsr::require_device();
         lsr::DeviceGuard guard(h->device);
         std::lock_guard<std::mutex> lock(h->mutex);
-        if (!h->gram_ws.ptr) h->gram_ws.allocate(2 * lsr::ring_mod_gram_words() + lsr::kRingModGramFlagWords);
+        lsr::ring_mod_gram_workspace(*h);
     });
 }
 

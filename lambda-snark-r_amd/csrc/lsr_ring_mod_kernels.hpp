@@ -4,6 +4,9 @@
 // [-(P - 1) / 2, (P - 1) / 2], P = p1 p2.  Both are one pass without a workspace, at any count (they run no transform): 16 bytes per
 // lane and access where every buffer is 16-byte aligned, 8 bytes otherwise.  (The fused inner product lifts as it loads:
 // ntt_tile_ring_dot_lift, lsr_ring_galois_kernels.hpp.)
+// Behind them the two kernels that the bounded calls of a handle share (Gram, fold, quadratic forms, the bounded matrix product;
+// launched by lsr_ring_mod_call.hpp): ring_mod_gram_lift_kernel, the lift for both primes with the caller's bound
+// verified into a flag word per family, and ring_mod_gram_reduce_kernel, the reduce gated by those flags.
 #pragma once
 
 #include "lsr_ring_galois_kernels.hpp"
@@ -98,6 +101,108 @@ __global__ void __launch_bounds__(kRingModThreads) ring_mod_reduce_kernel(uint64
         if ((count & 1) && first == 0) word(count - 1);
     } else {
         for (size_t e = first; e < count; e += stride) word(e);
+    }
+}
+
+// The checked lift: one read of every operand word, its centred representative as the canonical residue mod p1 and mod p2 into the
+// two halves of a workspace, and "over the bound" / ">= q" folded into one flag word per family.  Grid: x = runs of a vector's words
+// (grid-stride), y = vectors, z = families — every stride is a scalar offset, no lane divides.  16 bytes per lane and access where the
+// source is 16-byte aligned (the workspace always is; every run and stride is a multiple of n >= 2 words).  CHECK: fold the flags (a
+// wave ORs its lanes' bits first, then at most one atomic OR per wave); STORE: write the residues.  A family taken in several groups
+// is checked whole by a pass without STORE before its first group, so that its flags are complete before any reduce reads them.
+constexpr uint32_t kGramFlagOverBound = 1u, kGramFlagNotBelowQ = 2u;
+
+struct GramLiftShape {
+    size_t run;                 // words of one vector taken by this launch (columns n): even
+    size_t src_vec, src_fam;    // words between consecutive vectors / families of the operand
+    size_t dst_vec, dst_fam;    // the same in a prime's half of the workspace
+    size_t half;                // words between the two halves
+    uint64_t q, bound;          // a word x < q passes when its centred magnitude min(x, q - x) <= bound
+};
+
+template <bool VEC, bool CHECK, bool STORE>
+__global__ void __launch_bounds__(kRingModThreads) ring_mod_gram_lift_kernel(uint64_t* __restrict__ dst, const uint64_t* __restrict__ x,
+                                                                              uint32_t* __restrict__ flags, GramLiftShape s, LiftSource l0,
+                                                                              LiftSource l1) {
+    const size_t stride = (size_t)gridDim.x * kRingModThreads, first = (size_t)blockIdx.x * kRingModThreads + threadIdx.x;
+    const uint64_t* const src = x + blockIdx.z * s.src_fam + blockIdx.y * s.src_vec;
+    uint64_t* const d0 = dst + blockIdx.z * s.dst_fam + blockIdx.y * s.dst_vec;
+    uint64_t* const d1 = d0 + s.half;
+    uint32_t bits = 0;
+    auto check = [&](uint64_t w) {
+        if constexpr (CHECK) {
+            const uint64_t mag = w <= l0.half ? w : s.q - w;
+            bits |= w >= s.q ? kGramFlagNotBelowQ : (mag > s.bound ? kGramFlagOverBound : 0u);
+        }
+    };
+    if constexpr (VEC) {
+        const size_t pairs = s.run >> 1;
+        for (size_t e = first; e < pairs; e += stride) {
+            const ulonglong2 v = reinterpret_cast<const ulonglong2*>(src)[e];
+            check(v.x);
+            check(v.y);
+            if constexpr (STORE) {
+                reinterpret_cast<ulonglong2*>(d0)[e] = make_ulonglong2(l0.word(v.x), l0.word(v.y));
+                reinterpret_cast<ulonglong2*>(d1)[e] = make_ulonglong2(l1.word(v.x), l1.word(v.y));
+            }
+        }
+    } else {
+        for (size_t e = first; e < s.run; e += stride) {
+            const uint64_t w = src[e];
+            check(w);
+            if constexpr (STORE) {
+                d0[e] = l0.word(w);
+                d1[e] = l1.word(w);
+            }
+        }
+    }
+    if constexpr (CHECK) {
+        // every lane of the workgroup arrives here: the ballots see whole waves
+        const uint32_t wave_bits = (__ballot(bits & kGramFlagOverBound) ? kGramFlagOverBound : 0u) | (__ballot(bits & kGramFlagNotBelowQ) ? kGramFlagNotBelowQ : 0u);
+        if (wave_bits && (threadIdx.x & (warpSize - 1)) == 0) atomicOr(&flags[blockIdx.z], wave_bits);
+    }
+}
+
+// The gated reduce: ring_mod_reduce_kernel with the family as grid y — the word mod q of the integer a pair of residues determines
+// (ACC: added to what g holds), or 0 — whatever ACC says — where the family's flags are set; lane 0 of a family's first workgroup
+// writes status[family].  g: [families][words] (words even), r0 / r1: the families `r_fam` words apart
+template <bool VEC, bool ACC>
+__global__ void __launch_bounds__(kRingModThreads) ring_mod_gram_reduce_kernel(uint64_t* __restrict__ g, int32_t* __restrict__ status,
+                                                                                const uint64_t* __restrict__ r0, const uint64_t* __restrict__ r1,
+                                                                                const uint32_t* __restrict__ flags, size_t words, size_t r_fam,
+                                                                                RingModConsts rc, ModParams p2, ModParams pq) {
+    const size_t stride = (size_t)gridDim.x * kRingModThreads, first = (size_t)blockIdx.x * kRingModThreads + threadIdx.x;
+    const uint32_t bits = flags[blockIdx.y];
+    uint64_t* const out = g + blockIdx.y * words;
+    const uint64_t* const a = r0 + blockIdx.y * r_fam;
+    const uint64_t* const b = r1 + blockIdx.y * r_fam;
+    if (first == 0) status[blockIdx.y] = (bits & kGramFlagNotBelowQ) ? -1 : (bits & kGramFlagOverBound) ? 0 : 1;
+    if (bits) {
+        if constexpr (VEC) {
+            for (size_t e = first; e < (words >> 1); e += stride) reinterpret_cast<ulonglong2*>(out)[e] = make_ulonglong2(0, 0);
+        } else {
+            for (size_t e = first; e < words; e += stride) out[e] = 0;
+        }
+        return;
+    }
+    if constexpr (VEC) {
+        for (size_t e = first; e < (words >> 1); e += stride) {
+            const ulonglong2 x = reinterpret_cast<const ulonglong2*>(a)[e], y = reinterpret_cast<const ulonglong2*>(b)[e];
+            ulonglong2 v;
+            v.x = ring_mod_reduce_word(x.x, y.x, rc, p2, pq);
+            v.y = ring_mod_reduce_word(x.y, y.y, rc, p2, pq);
+            if constexpr (ACC) {
+                const ulonglong2 old = reinterpret_cast<const ulonglong2*>(out)[e];
+                v.x = ring_mod_add(old.x, v.x, pq.q);
+                v.y = ring_mod_add(old.y, v.y, pq.q);
+            }
+            reinterpret_cast<ulonglong2*>(out)[e] = v;
+        }
+    } else {
+        for (size_t e = first; e < words; e += stride) {
+            const uint64_t v = ring_mod_reduce_word(a[e], b[e], rc, p2, pq);
+            out[e] = ACC ? ring_mod_add(out[e], v, pq.q) : v;
+        }
     }
 }
 

@@ -15,15 +15,15 @@
 //             wrote — and status.  A vector taken in row ranges is checked whole by one storeless pass of ring_mod_gram_lift_kernel
 //             before its first reduce, and its tile launches are the unchecked ones; so is a chunk at the sizes where that
 //             measured faster or the checking instantiation is a wave short (kModMatvecCheckInTile).
-// No allocation after create: the device forms capture into a graph from the first call.
+// The bracket of a call, the view of the handle's workspace and the launchers of the check pass and of the gated reduce:
+// lsr_ring_mod_call.hpp.  No allocation after create: the device forms capture into a graph from the first call.
 #include <algorithm>
 #include <memory>
 
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
-#include "lsr_ring_call.hpp"
 #include "lsr_ring_matrix.hpp"
-#include "lsr_ring_mod.hpp"
+#include "lsr_ring_mod_call.hpp"
 #include "lsr_ring_mod_matvec_kernels.hpp"
 #include "lsr_runtime.hpp"
 
@@ -75,12 +75,10 @@ template <class A, int LT>
 constexpr bool kModMatvecCheckInTile = LSR_MOD_MATVEC_CHECK_IN_TILE >= 0 ? LSR_MOD_MATVEC_CHECK_IN_TILE != 0
                                                                          : LT >= 9 && !(std::is_same_v<A, ArithU64> && LT == 12);
 
-static bool mod_matvec_checks_in_tile(bool f64, int logn) {
+template <class A>
+static bool mod_matvec_checks_in_tile(int logn) {
     bool in_tile = false;
-    for_tile_log<1, 12>(logn, [&](auto t) {
-        constexpr int LT = decltype(t)::value;
-        in_tile = f64 ? kModMatvecCheckInTile<ArithF64, LT> : kModMatvecCheckInTile<ArithU64, LT>;
-    });
+    for_tile_log<1, 12>(logn, [&](auto t) { in_tile = kModMatvecCheckInTile<A, decltype(t)::value>; });
     return in_tile;
 }
 
@@ -91,10 +89,11 @@ static void mod_matvec_tile(const LsrRingModMatrix& m, const ModMatvecLaunch& l,
     const LsrRingMod& h = *m.h;
     constexpr int RB = MatvecRowBlock<A>::value;
     const size_t n = h.n, total = l.vectors * n, m_row_words = m.cols * n;
+    const RingModWorkspace w = ring_mod_workspace(h);
     RingModMatvecPrimes<A> both{};
     for (int i = 0; i < 2; ++i) {
         const NttContext& c = *h.prime[i];
-        both.prime[i] = {h.ws.ptr + i * kRingModSumWords, m.data[i].ptr + l.row0 * m_row_words, Flavour<A>::fwd(c), Flavour<A>::inv(c), c.mod,
+        both.prime[i] = {w.sums[i], m.data[i].ptr + l.row0 * m_row_words, Flavour<A>::fwd(c), Flavour<A>::inv(c), c.mod,
                          Flavour<A>::consts(c), h.lift[i]};
     }
     for_tile_log<1, 12>(h.logn, [&](auto t) {
@@ -114,18 +113,13 @@ static void mod_matvec_tile(const LsrRingModMatrix& m, const ModMatvecLaunch& l,
     });
 }
 
-// the flavour of the prime contexts: FP64 unless the process forces the integer kernels, the same for both (one process-wide switch)
-static bool primes_use_f64(const LsrRingMod& h) {
-    if (h.prime[0]->use_f64 != h.prime[1]->use_f64) throw std::runtime_error("the two prime contexts run different kernel flavours");
-    return h.prime[0]->use_f64;
-}
-
 static int mod_row_block(const LsrRingMod& h) { return h.prime[0]->use_f64 ? MatvecRowBlock<ArithF64>::value : MatvecRowBlock<ArithU64>::value; }
 
 // x: [batch][xcols][n]; digits == 0: the plain product (xcols == cols)
+template <class A>
 static void mod_matvec_enqueue(const LsrRingModMatrix& m, uint64_t* d_y, const uint64_t* d_x, size_t batch, unsigned b, size_t digits, hipStream_t s) {
     const LsrRingMod& h = *m.h;
-    const bool gadget = digits != 0, f64 = primes_use_f64(h);
+    const bool gadget = digits != 0;
     const size_t n = h.n, xcols = gadget ? m.cols / digits : m.cols;
     const GadgetParams g = gadget ? gadget_params(h.q, b, digits) : GadgetParams{};
     const size_t capacity = gadget ? ring_mod_capacity_bounded(h.q, h.n, (uint64_t)1 << (b - 1)) : h.max_terms;
@@ -133,20 +127,17 @@ static void mod_matvec_enqueue(const LsrRingModMatrix& m, uint64_t* d_y, const u
     const size_t vector_words = m.rows * n;
     const bool whole = vector_words <= kRingModSumWords;
     const size_t chunk = whole ? kRingModSumWords / vector_words : 1, nr_max = whole ? m.rows : kRingModSumWords / n;
-    const uint64_t *sum0 = h.ws.ptr, *sum1 = h.ws.ptr + kRingModSumWords;
+    const RingModWorkspace w = ring_mod_workspace(h);
     for (size_t j0 = 0; j0 < batch; j0 += chunk) {
         const size_t now = std::min(chunk, batch - j0);
         for (size_t r0 = 0; r0 < m.rows; r0 += nr_max) {
             const size_t nr = std::min(nr_max, m.rows - r0);
             for (size_t c0 = 0; c0 < m.cols; c0 += group_max) {
                 const ModMatvecLaunch l{d_x + j0 * xcols * n, now, r0, nr, c0, std::min(group_max, m.cols - c0), xcols};
-                for_bool(gadget, [&](auto ga) {
-                    if (f64) mod_matvec_tile<ArithF64, decltype(ga)::value>(m, l, g, s);
-                    else mod_matvec_tile<ArithU64, decltype(ga)::value>(m, l, g, s);
-                });
+                for_bool(gadget, [&](auto ga) { mod_matvec_tile<A, decltype(ga)::value>(m, l, g, s); });
                 LSR_HIP(hipGetLastError());
                 // (the chunk's words are contiguous in y: whole vectors, or rows r0 .. r0 + nr of one)
-                launch_reduce(h, d_y + (j0 * m.rows + r0) * n, sum0, sum1, now * nr * n, c0 > 0, s);
+                launch_reduce(h, d_y + (j0 * m.rows + r0) * n, w.sums[0], w.sums[1], now * nr * n, c0 > 0, s);
             }
         }
     }
@@ -156,83 +147,50 @@ static void mod_matvec_enqueue(const LsrRingModMatrix& m, uint64_t* d_y, const u
 constexpr size_t kRingModMatvecFlagWords = 2 * kRingModFoldFlagWords;
 static_assert(kRingModMatvecFlagWords <= 65535, "the vectors of a chunk are one grid axis of the reduce");
 
-// [vectors][words] of y (one chunk of whole vectors, or one row range of one vector) from the two primes' sums, gated by the flags
-static void bounded_reduce(const LsrRingMod& h, uint64_t* y, int32_t* status, const uint32_t* flags, size_t words, size_t vectors, bool accumulate,
-                           hipStream_t s) {
-    const bool vec = (reinterpret_cast<uintptr_t>(y) & 15u) == 0;
-    const size_t items = vec ? words / 2 : words;
-    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))),
-                    static_cast<unsigned>(vectors));
-    for_bool(vec, [&](auto v) {
-        for_bool(accumulate, [&](auto acc) {
-            hipLaunchKernelGGL((ring_mod_gram_reduce_kernel<decltype(v)::value, decltype(acc)::value>), grid, dim3(kRingModThreads), 0, s, y, status, h.ws.ptr,
-                               h.ws.ptr + kRingModSumWords, flags, words, words, h.rc, h.prime[1]->mod, h.pq);
-        });
-    });
-}
-
-// the `words` contiguous words of each of `vectors` vectors of x held against q and `bound` into flags[vector]; nothing is stored
-static void bounded_check_pass(const LsrRingMod& h, const uint64_t* x, uint32_t* flags, size_t words, size_t vectors, uint64_t bound, hipStream_t s) {
-    const bool vec = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
-    const size_t items = vec ? words / 2 : words;
-    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))), 1u,
-                    static_cast<unsigned>(vectors));
-    const GramLiftShape shape{words, 0, words, 0, 0, 0, h.q, bound};
-    for_bool(vec, [&](auto v) {
-        hipLaunchKernelGGL((ring_mod_gram_lift_kernel<decltype(v)::value, true, false>), grid, dim3(kRingModThreads), 0, s, static_cast<uint64_t*>(nullptr), x,
-                           flags, shape, h.lift[0], h.lift[1]);
-    });
-}
-
 // The bounded plain product: x [batch][cols][n] held against q and bound_x (0: none), status [batch].  mod_matvec_enqueue's loops with
 // the groups of the verified bound, the chunk capped by the flag words and the gated reduce.
+template <class A>
 static void mod_matvec_bounded_enqueue(const LsrRingModMatrix& m, uint64_t* d_y, int32_t* d_status, const uint64_t* d_x, size_t batch, uint64_t bound_x,
                                        hipStream_t s) {
     const LsrRingMod& h = *m.h;
-    const bool f64 = primes_use_f64(h);
     const size_t n = h.n;
     const uint64_t bound = bound_x ? bound_x : h.q >> 1;
     const size_t group_max = std::min(m.cols, ring_mod_capacity_bounded(h.q, h.n, bound));    // the capacity is >= max_terms >= 1
     const size_t vector_words = m.rows * n;
     const bool whole = vector_words <= kRingModSumWords;
     const size_t chunk = whole ? std::min(kRingModSumWords / vector_words, kRingModMatvecFlagWords) : 1, nr_max = whole ? m.rows : kRingModSumWords / n;
-    uint32_t* const flags = ring_mod_flag_words(h);
+    const RingModWorkspace w = ring_mod_workspace(h);
     // a vector in row ranges (now == 1) needs its flags before its first reduce: the check pass, whatever the instantiation
-    const bool in_tile = whole && mod_matvec_checks_in_tile(f64, h.logn);
+    const bool in_tile = whole && mod_matvec_checks_in_tile<A>(h.logn);
     for (size_t j0 = 0; j0 < batch; j0 += chunk) {
         const size_t now = std::min(chunk, batch - j0);
         const uint64_t* const xj = d_x + j0 * m.cols * n;
-        zero_words_async(reinterpret_cast<uint64_t*>(flags), (now + 1) / 2, s);
-        if (!in_tile) bounded_check_pass(h, xj, flags, m.cols * n, now, bound, s);
+        zero_words_async(reinterpret_cast<uint64_t*>(w.flags), (now + 1) / 2, s);
+        if (!in_tile) ring_mod_check_pass(h, xj, w.flags, m.cols * n, now, m.cols * n, bound, s);
         for (size_t r0 = 0; r0 < m.rows; r0 += nr_max) {
             const size_t nr = std::min(nr_max, m.rows - r0);
             for (size_t c0 = 0; c0 < m.cols; c0 += group_max) {
                 const ModMatvecLaunch l{xj, now, r0, nr, c0, std::min(group_max, m.cols - c0), m.cols};
-                for_bool(in_tile, [&](auto check) {
-                    if (f64) mod_matvec_tile<ArithF64, false, decltype(check)::value>(m, l, GadgetParams{}, s, flags, bound);
-                    else mod_matvec_tile<ArithU64, false, decltype(check)::value>(m, l, GadgetParams{}, s, flags, bound);
-                });
+                for_bool(in_tile, [&](auto check) { mod_matvec_tile<A, false, decltype(check)::value>(m, l, GadgetParams{}, s, w.flags, bound); });
                 LSR_HIP(hipGetLastError());
-                bounded_reduce(h, d_y + (j0 * m.rows + r0) * n, d_status + j0, flags, nr * n, now, c0 > 0, s);
+                // [now][nr n] of y: one chunk of whole vectors, or one row range of one vector
+                ring_mod_gated_reduce(h, d_y + (j0 * m.rows + r0) * n, d_status + j0, w.sums[0], w.sums[1], w.flags, nr * n, now, c0 > 0, s);
             }
         }
     }
 }
 
-// One call on the device (caller validated the arguments): ring_mod_dot_device's brackets on the handle's mutex and event.
+// One call on the device (caller validated the arguments) in the handle's bracket (ring_mod_call), behind the matrix's ready event.
 // d_status: the bounded product (b and digits 0), else the plain or the gadget product.
 static void mod_matvec_device(const LsrRingModMatrix& m, uint64_t* d_y, const uint64_t* d_x, size_t batch, unsigned b, size_t digits, hipStream_t s,
                               int32_t* d_status = nullptr, uint64_t bound_x = 0) {
-    const LsrRingMod& h = *m.h;
-    std::lock_guard<std::mutex> lock(h.mutex);
-    const bool capturing = stream_is_capturing(s);
-    if (!capturing) {
-        m.ready.wait(s);
-        h.event.wait(s);
-    }
-    if (d_status) mod_matvec_bounded_enqueue(m, d_y, d_status, d_x, batch, bound_x, s);
-    else mod_matvec_enqueue(m, d_y, d_x, batch, b, digits, s);
-    if (!capturing) h.event.record(s);
+    ring_mod_call(*m.h, s, false, [&] {
+        if (!stream_is_capturing(s)) m.ready.wait(s);
+        for_ring_mod_flavour(*m.h, [&](auto a) {
+            if (d_status) mod_matvec_bounded_enqueue<decltype(a)>(m, d_y, d_status, d_x, batch, bound_x, s);
+            else mod_matvec_enqueue<decltype(a)>(m, d_y, d_x, batch, b, digits, s);
+        });
+    });
 }
 
 enum class MatrixSource { kHost, kDevice, kSeeded };

@@ -20,7 +20,6 @@
 #pragma once
 
 #include "lsr_ring_gadget_digits.hpp"
-#include "lsr_ring_mod_gram_kernels.hpp"
 #include "lsr_ring_mod_kernels.hpp"
 
 namespace lsr {

@@ -16,6 +16,7 @@
 //   5. launch_ntt inverse in place on each half's sums;
 //   6. ring_mod_gram_reduce_kernel: CRT and reduction mod q into out (accumulating from the second group on), zeros where the family's
 //      flags are set, and status.
+// The lift and the reduce are launched by lsr_ring_mod_call.hpp, which also holds the bracket of a call and the Gram workspace.
 // Every group goes all the way to out: the sums of two groups are joined mod q, never in the evaluation domain, so a group's integer
 // stays within what P carries whatever the number of groups.
 #include <algorithm>
@@ -23,8 +24,7 @@
 
 #include "lambda_snark/batch.h"
 #include "lsr_flavour.hpp"
-#include "lsr_ring_call.hpp"
-#include "lsr_ring_mod.hpp"
+#include "lsr_ring_mod_call.hpp"
 #include "lsr_ring_mod_quadform_kernels.hpp"
 #include "lsr_runtime.hpp"
 
@@ -77,20 +77,13 @@ static size_t mod_quad_slices(const LsrRingMod& h, size_t families, size_t count
     return std::max<size_t>(1, std::min({want, most, cap, kModQuadMaxSlices}));
 }
 
-// `families` runs of `run` contiguous words, `src_fam` words apart: (CHECK) held against `bound` and q into flags[family] and (STORE)
-// lifted to dst + family dst_fam for prime 0, half a workspace behind that for prime 1
+// the checked lift (lsr_ring_mod_call.hpp) as the form takes it, one vector per family on the Gram workspace: `families` runs of `run`
+// contiguous words, `src_fam` words apart, (CHECK) held against `bound` and q into flags[family] and (STORE) lifted to dst + family
+// dst_fam for prime 0, half a workspace behind that for prime 1
 template <bool CHECK, bool STORE>
 static void quad_lift(const LsrRingMod& h, uint64_t* dst, const uint64_t* src, uint32_t* flags, size_t run, size_t families, size_t src_fam, size_t dst_fam,
                       uint64_t bound, hipStream_t s) {
-    const bool vec = (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
-    const size_t items = vec ? run / 2 : run;
-    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))), 1u,
-                    static_cast<unsigned>(families));
-    const GramLiftShape shape{run, 0, src_fam, 0, dst_fam, ring_mod_gram_words(), h.q, bound};
-    for_bool(vec, [&](auto v) {
-        hipLaunchKernelGGL((ring_mod_gram_lift_kernel<decltype(v)::value, CHECK, STORE>), grid, dim3(kRingModThreads), 0, s, dst, src, flags, shape, h.lift[0],
-                           h.lift[1]);
-    });
+    ring_mod_checked_lift<CHECK, STORE>(h, {dst, src, 1, families, run, 0, src_fam, 0, dst_fam, ring_mod_gram_words(), bound}, flags, s);
 }
 
 // One launch over the packed pairs [p0, p1) of `families` families for both primes (g-hat holds them from p0 on), and the sum of its
@@ -114,21 +107,6 @@ static void quad_evaluate(const LsrRingMod& h, uint64_t* sum, uint64_t* part, co
     }
 }
 
-static void quad_reduce(const LsrRingMod& h, uint64_t* out, int32_t* status, const uint64_t* sum, const uint32_t* flags, size_t families, bool accumulate,
-                        hipStream_t s) {
-    const size_t words = h.n;
-    const bool vec = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
-    const size_t items = vec ? words / 2 : words;
-    const dim3 grid(static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>((items + kRingModThreads - 1) / kRingModThreads, 1024))),
-                    static_cast<unsigned>(families));
-    for_bool(vec, [&](auto v) {
-        for_bool(accumulate, [&](auto acc) {
-            hipLaunchKernelGGL((ring_mod_gram_reduce_kernel<decltype(v)::value, decltype(acc)::value>), grid, dim3(kRingModThreads), 0, s, out, status, sum,
-                               sum + ring_mod_gram_words(), flags, words, words, h.rc, h.prime[1]->mod, h.pq);
-        });
-    });
-}
-
 // The layout of a chunk in one prime's half of the workspace, in polynomials:
 //   [c-hat: r per family, or r once for a shared c][g-hat: group per family][partials: slices per family, when slices > 1][sums: 1 per family]
 // Pairs per group: what P carries (plan.group >= 1: mod_quad_call) and, for a family that does not fit whole, what the workspace
@@ -141,10 +119,8 @@ static void mod_quad_enqueue(const LsrRingMod& h, const ModQuadCall& c, hipStrea
     const bool shared = c.c_rows == 1;
     const size_t c_polys = shared ? 0 : c.r, rest = polys - (shared ? c.r : 0), g_fam = pairs * n, c_fam = c.r * n;
     uint64_t* const ws = h.gram_ws.ptr;
-    uint32_t* const flags = reinterpret_cast<uint32_t*>(ws + 2 * half);
-    auto transforms = [&](uint64_t* data, size_t count, bool inverse) {
-        for (int i = 0; i < 2; ++i) launch_ntt(*h.prime[i], data + i * half, count, inverse, s);
-    };
+    uint32_t* const flags = ring_mod_gram_flags(h);
+    auto transforms = [&](uint64_t* data, size_t count, bool inverse) { ring_mod_gram_transforms(h, data, count, inverse, s); };
     auto per_family = [&](size_t group, size_t sl) { return c_polys + group + (sl > 1 ? sl : 0) + 1; };
 
     size_t group = std::min(pairs, plan.group);
@@ -187,25 +163,14 @@ static void mod_quad_enqueue(const LsrRingMod& h, const ModQuadCall& c, hipStrea
             transforms(ghat, now * gnow, false);
             quad_evaluate<A>(h, sum, part, ghat, ws, c, p0, p0 + gnow, std::min(slices, gnow), shared ? 0 : c_fam, run, now, s);
             transforms(sum, now, true);
-            quad_reduce(h, c.out + j0 * n, c.status + j0, sum, flags, now, p0 > 0, s);
+            ring_mod_gated_reduce(h, c.out + j0 * n, c.status + j0, sum, sum + half, flags, n, now, p0 > 0, s);
         }
     }
 }
 
-// One call on the device (caller validated the arguments): the handle's mutex and event and the Gram workspace as mod_gram_device.
+// One call on the device (caller validated the arguments) in the handle's bracket (ring_mod_call), on its Gram workspace
 static void mod_quad_device(const LsrRingMod& h, const ModQuadCall& c, hipStream_t s) {
-    std::lock_guard<std::mutex> lock(h.mutex);
-    const bool capturing = stream_is_capturing(s);
-    if (!h.gram_ws.ptr) {
-        if (capturing) throw std::runtime_error(kWorkspaceBeforeCapture);
-        h.gram_ws.allocate(2 * ring_mod_gram_words() + kRingModGramFlagWords);
-    }
-    if (h.prime[0]->use_f64 != h.prime[1]->use_f64) throw std::runtime_error("the two prime contexts run different kernel flavours");
-    if (!capturing) h.event.wait(s);
-    if (h.prime[0]->use_f64) mod_quad_enqueue<ArithF64>(h, c, s);
-    else mod_quad_enqueue<ArithU64>(h, c, s);
-    LSR_HIP(hipGetLastError());
-    if (!capturing) h.event.record(s);
+    ring_mod_call(h, s, true, [&] { for_ring_mod_flavour(h, [&](auto a) { mod_quad_enqueue<decltype(a)>(h, c, s); }); });
 }
 
 // host buffers through bounded device chunks of whole families on the first prime context's work stream (a shared c goes up once);
@@ -253,10 +218,7 @@ int mod_quad_call(const char* where, const LsrRingMod* h, const lsr::ModQuadCall
     if (overflow) return lsr::abi_refuse(where, "the sizes of g, c or out overflow size_t (batch, r, c_rows)");
     if (c.offdiag >= h->q)
         return lsr::abi_refuse(where, "offdiag = " + std::to_string(c.offdiag) + " is not a canonical word: the modulus is " + std::to_string(h->q));
-    const uint64_t half = h->q >> 1;
-    if (c.bound_g > half || c.bound_c > half)
-        return lsr::abi_refuse(where, "bound_g = " + std::to_string(c.bound_g) + ", bound_c = " + std::to_string(c.bound_c) + ": a bound is above floor(q / 2) = " +
-                                          std::to_string(half) + " (0 states none)");
+    if (lsr::ring_mod_bounds_check(where, h->q, "bound_g", c.bound_g, "bound_c", c.bound_c) != 0) return -1;
     if (c.batch == 0) return 0;
     return lsr::abi_guarded(where, [&] {
         const size_t poly_bytes = (size_t)h->n * 8;
@@ -282,12 +244,7 @@ int mod_quad_call(const char* where, const LsrRingMod* h, const lsr::ModQuadCall
         if (__builtin_mul_overflow(c.batch, poly_bytes, &out_bytes) || __builtin_mul_overflow(c.batch * pairs, poly_bytes, &g_bytes) ||
             __builtin_mul_overflow(c.c_rows * c.r, poly_bytes, &c_bytes))
             throw std::runtime_error("the sizes of g, c or out overflow size_t at this ring degree");
-        const size_t status_bytes = c.batch * sizeof(int32_t);
-        lsr::require_apart(c.out, out_bytes, c.g, g_bytes, "out overlaps g: the output must not share memory with an operand");
-        lsr::require_apart(c.out, out_bytes, c.c, c_bytes, "out overlaps c: the output must not share memory with an operand");
-        lsr::require_apart(c.status, status_bytes, c.g, g_bytes, "status overlaps g: the output must not share memory with an operand");
-        lsr::require_apart(c.status, status_bytes, c.c, c_bytes, "status overlaps c: the output must not share memory with an operand");
-        lsr::require_apart(c.status, status_bytes, c.out, out_bytes, "status overlaps out: the two outputs must not share memory");
+        lsr::require_outputs_apart({"out", c.out, out_bytes}, {"status", c.status, c.batch * sizeof(int32_t)}, {{"g", c.g, g_bytes}, {"c", c.c, c_bytes}});
         lsr::require_device();
         lsr::DeviceGuard guard(h->device);
         if (device) lsr::mod_quad_device(*h, c, static_cast<hipStream_t>(stream));

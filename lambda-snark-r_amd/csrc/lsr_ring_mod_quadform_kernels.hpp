@@ -25,7 +25,7 @@
 // products (Barrett) and canonical sums.
 #pragma once
 
-#include "lsr_ring_mod_gram_kernels.hpp"
+#include "lsr_ring_mod_kernels.hpp"
 #include "lsr_ring_quadform_kernels.hpp"
 
 namespace lsr {
