@@ -1071,6 +1071,60 @@ int lsr_ring_mod_quadform_batch(const LsrRingMod* h, uint64_t* out, int32_t* sta
 int lsr_ring_mod_quadform_batch_device(const LsrRingMod* h, uint64_t* d_out, int32_t* d_status, const uint64_t* d_g, const uint64_t* d_c, size_t batch,
                                        size_t r, size_t c_rows, uint64_t offdiag, uint64_t bound_g, uint64_t bound_c, void* stream) LSR_NOEXCEPT;
 
+/* ---------------- NTT: responses under any modulus (z = y + sum c s with a verified abort on a ring handle) ---------------- */
+/* The masked response of a Fiat-Shamir-with-aborts protocol — z = y + c s, accepted only where its l-infinity norm stays within
+ * gamma - beta and thrown away otherwise — in Z_q[X]/(X^n + 1) for the q of an LsrRingMod, n <= 4096:
+ *   z[j][c] = y[j][c] + sum_{i < terms} p[j][i] * v[j term_stride + i][c].
+ * Shapes, layouts, term_stride rules and limits are those of lsr_ring_mod_fold_batch above: v [vectors][width][n], p
+ * [outputs][terms][n], out [outputs][width][n], status [outputs]; y is [outputs][width][n] of canonical words, or NULL for no mask.
+ *
+ * Definition.  Let f be what lsr_ring_mod_fold_batch writes for the same v, p, term_stride, bound_v and bound_p.  Then
+ * z[j] = (f[j] + y[j]) mod q word for word, and the status of output j, [outputs] (int32), never NULL and written for every output, is
+ *   -1   some word output j reads — those of the fold and the width n words of y[j] — was >= q;
+ *    0   some such word's centred magnitude exceeded bound_v, bound_p or bound_y;
+ *    2   LSR_RING_RESPOND_REJECTED: the inputs were fine, but the centred magnitude of some word of z[j] exceeds bound_z.  This is
+ *        the abort: the caller restarts that instance;
+ *    1   accepted: out[j] = z[j].
+ * -1 wins over 0, 0 wins over 2, 2 wins over 1.  For every status other than 1 EVERY word of out[j] is 0 when the call completes;
+ * the other outputs are unaffected.  That holds too where the offending word is met in a later group of terms or a later chunk of
+ * components.  (The handle's workspace still holds the residues of the product until the next call on the handle: the promise is
+ * about out.)
+ *
+ * Bounds: l-infinity bounds on centred representatives, inclusive; 0 for any of them states none, which is floor(q/2), so
+ * bound_z == 0 never rejects.  With y == NULL and bound_z == 0 the call equals lsr_ring_mod_fold_batch word for word, status
+ * included.  The norm held against bound_z is that of the representative of z centred mod q, in (-q/2, q/2]: it is the norm of the
+ * INTEGER y + sum c s whenever bound_y + terms n bound_v bound_p < q/2, and a caller that needs the integer norm declares bounds
+ * that say so.
+ *
+ * In place: y may be exactly out (sample the mask into the output buffer, then respond).  Any other overlap of out with y, v or p,
+ * and any overlap of status with anything, is refused.
+ *
+ * Grouping rule: the fold's — terms in groups of at most lsr_ring_mod_capacity_product(q, n, bound_v, bound_p), y added once, with
+ * the first group, and the norm judged on the finished sum alone.
+ *
+ * Range: n <= 4096.  Above it the call is refused and the message names the composed route: the fold's composed route, then an add
+ * mod q and lsr_ntt_ring_linf_batch_device on lsr_ring_mod_coeff_context(h).
+ *
+ * Refusals (-1 and lsr_last_error naming the entry point, before any device work; they read only q and n of the handle), in the
+ * fold's order: (1) NULL handle, out, status, v or p; (2) terms == 0.  (3) Then outputs == 0 or width == 0 is a no-op that returns 0.
+ * Then (4) terms above LSR_RING_DOT_MAX_TERMS; (5) width above LSR_RING_FOLD_MAX_WIDTH; (6) a size that overflows size_t; (7) a NULL y
+ * with bound_y != 0, then any of the four bounds above floor(q/2) — the message names all four; (8) n above 4096; (9) the byte size
+ * of v, p or out overflowing size_t at the handle's n; (10) out overlapping y (unless y == out), v, then p, status overlapping y, v,
+ * p, then out, in address range; (11) no visible device.
+ *
+ * Workspace, ordering and graph capture: the fold's.  The handle's own workspace and flag words, nothing allocated, there is no
+ * _prepare; the _device form enqueues only and captures into a HIP graph as the first call on a fresh handle; calls on one handle are
+ * ordered by its mutex and event, and a captured call is not bracketed.  The plain form takes host buffers through bounded device
+ * chunks of whole outputs within LAMBDA_SNARK_STAGING_MIB, y as one more staged operand (or with out, where it is out), and returns
+ * when out and status are complete. */
+#define LSR_RING_RESPOND_REJECTED 2
+int lsr_ring_mod_respond_batch(const LsrRingMod* h, uint64_t* out, int32_t* status, const uint64_t* y, const uint64_t* v, const uint64_t* p,
+                               size_t outputs, size_t terms, size_t term_stride, size_t width, uint64_t bound_y, uint64_t bound_v,
+                               uint64_t bound_p, uint64_t bound_z) LSR_NOEXCEPT;
+int lsr_ring_mod_respond_batch_device(const LsrRingMod* h, uint64_t* d_out, int32_t* d_status, const uint64_t* d_y, const uint64_t* d_v,
+                                      const uint64_t* d_p, size_t outputs, size_t terms, size_t term_stride, size_t width, uint64_t bound_y,
+                                      uint64_t bound_v, uint64_t bound_p, uint64_t bound_z, void* stream) LSR_NOEXCEPT;
+
 /* ---------------- Gaussian sampler: seeded / device ---------------- */
 /* sample i of object (seed, domain, index) uses ChaCha20 stream word i (low bit: sign; upper 63 bits: the uniform
  * value compared with the CDT table at 63-bit precision);

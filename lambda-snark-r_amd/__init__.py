@@ -27,7 +27,7 @@ __all__ = [
     "NttContext", "LweContext", "Commitment", "Params", "CoreError", "verify_opening_with_context",
     "sample_gaussian", "verify_openings_batch", "verify_openings_words", "PublicParams", "PROFILE_RING_B", "PROFILE_SCALAR_A",
     "CyclicNtt", "QuotientPlan", "R1csProver", "compute_root_of_unity", "NTT_MODULUS", "NTT_PRIMITIVE_ROOT",
-    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PACK_CENTRED", "RING_PACK_RESIDUE", "ring_pack_words", "ring_pack_min_bits", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "RingMod", "ring_mod_primes", "ring_mod_capacity", "ring_mod_capacity_bounded", "ring_mod_capacity_product", "ring_mod_capacity_quadform", "RingModMatrix", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
+    "RING_DOT_F64_RECENTRE_PERIOD", "RING_DOT_MAX_TERMS", "RING_FOLD_MAX_WIDTH", "RING_MATVEC_MAX_ROWS", "RING_MATVEC_MAX_MATRIX_BYTES", "RingMatrix", "ring_gadget_min_digits", "RING_SAMPLE_UNIFORM", "RING_SAMPLE_BOUNDED", "RING_SAMPLE_BALL", "RING_SAMPLE_MAX_WORDS", "ring_sample_key", "RING_OPNORM_MAX_DEGREE", "RING_CHALLENGE_ATTEMPT_WORDS", "RING_CHALLENGE_MAX_TRIES", "ring_opnorm_table", "RING_PACK_CENTRED", "RING_PACK_RESIDUE", "ring_pack_words", "ring_pack_min_bits", "RING_PROJECT_ROWS", "RING_PROJECT_ADJOINT_MAX_SETS", "RING_SCALAR_COMBINE_MAX_SETS", "RING_GRAM_MAX_VECTORS", "ring_gram_index", "RingMod", "ring_mod_primes", "ring_mod_capacity", "ring_mod_capacity_bounded", "ring_mod_capacity_product", "ring_mod_capacity_quadform", "RING_RESPOND_REJECTED", "RingModMatrix", "SimpleProver", "chacha20rng_keys", "random_blinding", "random_blinding_device", "verify_simple_batch", "verify_simple_batch_device",
 ]
 
 
@@ -702,6 +702,8 @@ class _RingScalar:
 
 # the most vectors of one family of a ring Gram matrix (batch.h LSR_RING_GRAM_MAX_VECTORS)
 RING_GRAM_MAX_VECTORS = 64
+# the status of a response whose inputs were fine and whose norm was not (batch.h LSR_RING_RESPOND_REJECTED)
+RING_RESPOND_REJECTED = 2
 
 
 def ring_gram_index(r, i, l):
@@ -1331,6 +1333,44 @@ class RingMod:
         p [outputs][terms][n].  Asynchronous on `stream`; enqueues only."""
         _check(self._lib.lsr_ring_mod_fold_batch_device(self._h, d_out, d_status, d_v, d_p, outputs, terms, term_stride, width, int(bound_v), int(bound_p),
                                                         stream), "lsr_ring_mod_fold_batch_device")
+
+    def respond(self, v, p, y=None, term_stride=0, bound_y=0, bound_v=0, bound_p=0, bound_z=0):
+        """The masked response z[j] = y[j] + sum_i p[j][i] * v[j term_stride + i] mod (X^n + 1, q) with its abort (host arrays,
+        n <= 4096): v and p as ``fold`` takes them, y [outputs, width, n] ([width, n] for a 2-d p) or None for no mask.
+        Returns (out [outputs, width, n], status [outputs]) — ([width, n], status) for a 2-d p.  The bounds are l-infinity bounds on
+        centred words (0: none).  status[j] is 1 where out[j] = z[j] was accepted; 2 (RING_RESPOND_REJECTED) where the inputs were
+        fine but a word of z[j] exceeded bound_z; 0 where a word of v, p or y exceeded its bound; -1 where one was >= q.  For every
+        status other than 1 every word of out[j] is 0."""
+        n = self.n
+        v_in, p_in = _u64_array(v, "v"), _u64_array(p, "p")
+        if v_in.ndim != 3 or v_in.shape[-1] != n:
+            raise ValueError("v must be [vectors, width, n]")
+        if p_in.ndim not in (2, 3) or p_in.shape[-1] != n:
+            raise ValueError("p must be [terms, n] or [outputs, terms, n]")
+        terms, term_stride = p_in.shape[-2], int(term_stride)
+        if terms == 0:
+            raise ValueError("terms must be at least 1")
+        v3, p3 = np.ascontiguousarray(v_in), np.ascontiguousarray(p_in.reshape(-1, terms, n))
+        outputs, width = p3.shape[0], v3.shape[1]
+        if term_stride < 0 or (outputs and v3.shape[0] < (outputs - 1) * term_stride + terms):
+            raise ValueError("v must hold (outputs - 1) * term_stride + terms vectors")
+        y3 = None
+        if y is not None:
+            y3 = np.ascontiguousarray(_u64_array(y, "y"))
+            if y3.shape != ((width, n) if p_in.ndim == 2 else (outputs, width, n)):
+                raise ValueError("y must be [outputs, width, n] ([width, n] for a 2-d p)")
+        out = np.empty((outputs, width, n), dtype=np.uint64)
+        status = np.empty(outputs, dtype=np.int32)
+        _check(self._lib.lsr_ring_mod_respond_batch(self._h, out.ctypes.data, status.ctypes.data, None if y3 is None else y3.ctypes.data, v3.ctypes.data,
+                                                    p3.ctypes.data, outputs, terms, term_stride, width, int(bound_y), int(bound_v), int(bound_p),
+                                                    int(bound_z)), "lsr_ring_mod_respond_batch")
+        return (out[0], status[0]) if p_in.ndim == 2 else (out, status)
+
+    def respond_device(self, d_out, d_status, d_y, d_v, d_p, outputs, terms, term_stride, width, bound_y=0, bound_v=0, bound_p=0, bound_z=0, stream=0):
+        """Device buffers: out [outputs][width][n], status [outputs] int32, y as out (0: no mask; d_out itself: in place), v and p
+        as ``fold_device`` takes them.  Asynchronous on `stream`; enqueues only."""
+        _check(self._lib.lsr_ring_mod_respond_batch_device(self._h, d_out, d_status, d_y or None, d_v, d_p, outputs, terms, term_stride, width, int(bound_y),
+                                                           int(bound_v), int(bound_p), int(bound_z), stream), "lsr_ring_mod_respond_batch_device")
 
     def quadform(self, g, c, offdiag=2, bound_g=0, bound_c=0):
         """out[j] = sum_i g[j][(i, i)] c_i c_i + offdiag * sum_{i < l} g[j][(i, l)] c_i c_l mod (X^n + 1, q) (host arrays, DESIGN.md

@@ -201,6 +201,8 @@ SIGNATURES = {
     "lsr_ring_mod_capacity_quadform": (c_size, [u64, u32, u64, u64]),
     "lsr_ring_mod_quadform_batch": (c_int, [vp, vp, vp, vp, vp, c_size, c_size, c_size, u64, u64, u64]),
     "lsr_ring_mod_quadform_batch_device": (c_int, [vp, vp, vp, vp, vp, c_size, c_size, c_size, u64, u64, u64, vp]),
+    "lsr_ring_mod_respond_batch": (c_int, [vp, vp, vp, vp, vp, vp, c_size, c_size, c_size, c_size, u64, u64, u64, u64]),
+    "lsr_ring_mod_respond_batch_device": (c_int, [vp, vp, vp, vp, vp, vp, c_size, c_size, c_size, c_size, u64, u64, u64, u64, vp]),
     "lsr_sample_gaussian_seeded": (c_int, [vp, c_size, c_double, u64, u32, u64]),
     "lsr_gaussian_cdf": (c_size, [c_double, vp, c_size]),
     "lsr_lwe_context_create_seeded": (vp, [ctypes.POINTER(PublicParams), u64, c_int]),

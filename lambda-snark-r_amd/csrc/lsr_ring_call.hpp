@@ -129,7 +129,7 @@ inline size_t staging_chunk(size_t count, size_t words_per_item) {
 
 // what `run` sees of one chunk: items [first, first + now) of the call, the device buffer of each lane in the order the lanes were
 // declared (an absent lane: NULL), and group_first, the group the group lanes' buffers start at
-constexpr size_t kStagedMaxLanes = 4;
+constexpr size_t kStagedMaxLanes = 5;
 struct StagedChunk {
     size_t first, now, group_first;
     void* buffer[kStagedMaxLanes];

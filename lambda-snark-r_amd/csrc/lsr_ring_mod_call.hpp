@@ -4,6 +4,7 @@
 // flavour of its prime contexts, the views of its two workspaces, the launchers of the checked lift and the gated reduce that every
 // bounded call runs (lsr_ring_mod_kernels.hpp), and the refusals the bounded entry points have in common.  Host code only.
 #pragma once
+#include <functional>
 #include <initializer_list>
 #include <stdexcept>
 #include <string>
@@ -114,6 +115,38 @@ void ring_mod_gated_reduce(const Handle& h, uint64_t* out, int32_t* status, cons
                                flags, words, words, h.rc, h.prime[1]->mod, h.pq);
         });
     });
+}
+
+// A fold on the handle (lsr_ring_mod_fold.hip) and the calls that run its loop with a reduce stage of their own
+// (lsr_ring_mod_respond.hip): the arguments of one call, validated,
+struct ModFoldCall {
+    uint64_t* out;
+    int32_t* status;
+    const uint64_t *v, *p;
+    size_t outputs, terms, ts, width;
+    uint64_t bound_v, bound_p;   // as the caller gave them: 0 = none
+};
+// one group of terms of a chunk of outputs with its sums complete in the workspace: outputs [j0, j0 + now), `words` words of each
+// from component c0 on (whole outputs, or one component range of one output taken alone)
+struct ModFoldPiece {
+    size_t j0, now, c0, words;
+    bool first_group, last_group;
+};
+// and what runs behind the tiles.  reduce: every piece, in the loop's order; finish (may be empty): behind the last reduce of
+// outputs [j0, j0 + now).  flags_first: an output taken alone has its flags completed by storeless check passes before its first
+// reduce, as a reduce that gates its stores needs them.
+struct ModFoldStage {
+    std::function<void(const ModFoldPiece&, const RingModWorkspace&)> reduce;
+    std::function<void(size_t j0, size_t now, const RingModWorkspace&)> finish;
+    bool flags_first;
+};
+void ring_mod_fold_enqueue(const LsrRingMod& h, const ModFoldCall& c, const ModFoldStage& stage, hipStream_t s);   // lsr_ring_mod_fold.hip
+// the outputs a host form stages at a time: whole outputs with the span of vectors they read, each operand within the staging bound
+// where one output's is
+inline size_t ring_mod_fold_staging_chunk(const LsrRingMod& h, const ModFoldCall& c) {
+    const size_t bound = std::max<size_t>(1, staging_bytes() / ((size_t)h.n * 8));          // polynomials per staged operand
+    const size_t fit_v = c.ts == 0 ? c.outputs : (bound / c.width > c.terms ? (bound / c.width - c.terms) / c.ts + 1 : 1);
+    return std::max<size_t>(1, std::min({c.outputs, fit_v, bound / c.terms, bound / c.width}));
 }
 
 // batch.h's refusal of a stated bound above floor(q / 2), naming both bounds of the call (the second counts only where its operand

@@ -35,14 +35,6 @@ static_assert(kRingModBhatMaxRows <= 65535, "the outputs of a chunk are one grid
 // tiles per prime from which a launch counts as filling the device: 1024 workgroups over both primes, four to a compute unit
 constexpr size_t kRingModFoldFillTiles = 512;
 
-struct ModFoldCall {
-    uint64_t* out;
-    int32_t* status;
-    const uint64_t *v, *p;
-    size_t outputs, terms, ts, width;
-    uint64_t bound_v, bound_p;   // as the caller gave them: 0 = none
-};
-
 // Both primes in one launch, the prime as grid z: in this form the check costs no registers over ntt_tile_ring_fold, where a launch
 // per prime with the check as a template argument costs the checking launch 20 to 34 VGPRs in the FP64 flavour and a wave
 // (profiles/r35_ring_mod_fold_resource_usage.txt).
@@ -60,8 +52,9 @@ static void fold_tiles(const LsrRingMod& h, const RingModWorkspace& w, const uin
     });
 }
 
+// The loop of a fold with the stage behind the tiles as `stage` (ModFoldCall, ModFoldStage: lsr_ring_mod_call.hpp)
 template <class A>
-static void mod_fold_enqueue(const LsrRingMod& h, const ModFoldCall& c, hipStream_t s) {
+static void mod_fold_enqueue(const LsrRingMod& h, const ModFoldCall& c, const ModFoldStage& stage, hipStream_t s) {
     const size_t n = h.n, vec = c.width * n;
     const uint64_t half = h.q >> 1, bound_v = c.bound_v ? c.bound_v : half, bound_p = c.bound_p ? c.bound_p : half;
     const size_t capacity = ring_mod_capacity_product(h.q, h.n, bound_v, bound_p);    // >= max_terms >= 1
@@ -82,7 +75,7 @@ static void mod_fold_enqueue(const LsrRingMod& h, const ModFoldCall& c, hipStrea
         const uint64_t* const vj = c.v + j0 * c.ts * vec;
         const uint64_t* const pj = c.p + j0 * c.terms * n;
         zero_words_async(reinterpret_cast<uint64_t*>(w.flags), (now + 1) / 2, s);
-        if (!whole) {   // (now == 1) the output's flags before its first reduce: its term vectors are contiguous in v
+        if (!whole && stage.flags_first) {   // (now == 1) the output's flags before its first reduce: its term vectors are contiguous in v
             ring_mod_check_pass(h, vj, w.flags, c.terms * vec, 1, 0, bound_v, s);
             ring_mod_check_pass(h, pj, w.flags, c.terms * n, 1, 0, bound_p, s);
         }
@@ -95,26 +88,34 @@ static void mod_fold_enqueue(const LsrRingMod& h, const ModFoldCall& c, hipStrea
                 for (int i = 0; i < 2; ++i) launch_ntt(*h.prime[i], w.bhat[i], now * group, false, s);
                 const RingModFoldShape shape{words, (uint32_t)group, vec, c.ts * vec, h.q, bound_v};
                 fold_tiles<A>(h, w, vj + i0 * vec + c0 * n, shape, now, s);
-                // out: [now][words] (one chunk of whole outputs, or one component range of one output)
-                ring_mod_gated_reduce(h, c.out + j0 * vec + c0 * n, c.status + j0, w.sums[0], w.sums[1], w.flags, words, now, i0 > 0, s);
+                stage.reduce({j0, now, c0, words, i0 == 0, i0 + group == c.terms}, w);
             }
         }
+        if (stage.finish) stage.finish(j0, now, w);
     }
+}
+
+void ring_mod_fold_enqueue(const LsrRingMod& h, const ModFoldCall& c, const ModFoldStage& stage, hipStream_t s) {
+    for_ring_mod_flavour(h, [&](auto a) { mod_fold_enqueue<decltype(a)>(h, c, stage, s); });
 }
 
 // One call on the device (caller validated the arguments) in the handle's bracket (ring_mod_call)
 static void mod_fold_device(const LsrRingMod& h, const ModFoldCall& c, hipStream_t s) {
-    ring_mod_call(h, s, false, [&] { for_ring_mod_flavour(h, [&](auto a) { mod_fold_enqueue<decltype(a)>(h, c, s); }); });
+    const size_t n = h.n, vec = c.width * n;
+    // out: [now][words] (one chunk of whole outputs, or one component range of one output), gated by the flags
+    const ModFoldStage gated{[&](const ModFoldPiece& k, const RingModWorkspace& w) {
+                                 ring_mod_gated_reduce(h, c.out + k.j0 * vec + k.c0 * n, c.status + k.j0, w.sums[0], w.sums[1], w.flags, k.words, k.now,
+                                                       !k.first_group, s);
+                             },
+                             nullptr, true};
+    ring_mod_call(h, s, false, [&] { ring_mod_fold_enqueue(h, c, gated, s); });
 }
 
 // host buffers through bounded device chunks on the first prime context's work stream: whole outputs with the span of vectors they
 // read (each operand within the staging bound where one output's is; one output at a time otherwise); status comes back with out
 static void host_mod_fold(const LsrRingMod& h, const ModFoldCall& c) {
     const size_t n = h.n, vec = c.width * n;
-    const size_t bound = std::max<size_t>(1, staging_bytes() / (n * 8));          // polynomials per staged operand
-    const size_t fit_v = c.ts == 0 ? c.outputs : (bound / c.width > c.terms ? (bound / c.width - c.terms) / c.ts + 1 : 1);
-    const size_t chunk = std::max<size_t>(1, std::min({c.outputs, fit_v, bound / c.terms, bound / c.width}));
-    host_staged(*h.prime[0], c.outputs, chunk,
+    host_staged(*h.prime[0], c.outputs, ring_mod_fold_staging_chunk(h, c),
                 {staged_items(c.v, nullptr, c.ts * vec * 8, c.terms * vec * 8), staged_items(c.p, nullptr, c.terms * n * 8),
                  staged_items(nullptr, c.out, vec * 8), staged_items(nullptr, c.status, sizeof(int32_t))},
                 [&](const StagedChunk& k, hipStream_t s) {
